@@ -1,7 +1,19 @@
 #!/usr/bin/env python
 """bench.py -- env-steps/s of the fused PlanEnv.step() path on RandomMiniEnv at 65 536 envs per GPU.
 
-python bench.py --gpus N --steps K --warmup W
+python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: set-up, pre-roll, W warm-up steps, the K timed steps,
+the outputs of the last timed step if --dump-outputs is given, and the JSON line.  --full adds everything else the
+benchmark measures, after the metric: the parked-pose share, the CPU baseline (--no-cpu-baseline skips it), the
+informational legs -- observation, rollout, geometry pools, C2 / C4 -- (--no-aux skips them), and, in a sharded run, the
+second timed region with rounds 1-2's ring.
+
+--dump-outputs DIR: what the last timed step handed its caller (BatchedPlanEnv.step: the observation's pose, robot
+state, target index and iteration counter, the reward and the done mask) as DIR/<name>.npy, float64 (done: float32),
+rank 0's envs -- a fixed sample of DUMP_MAX_ENVS of them when the rank holds more.  The inputs (geometry, actions, noise
+seeds, the number of steps before the last one) depend on the arguments only, so two builds can be compared file for
+file; not with --reps 0, whose number of steps depends on a timing.
 
 N > 1: either started once per rank by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`
 (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment), or -- with WORLD_SIZE unset -- bench.py starts its N
@@ -15,10 +27,11 @@ device (Philox4x32-10), float32 actions ~ U(action_space) pre-staged in HBM, res
 A "step" is one pass of the hot path over all envs of the rank.  With N > 1 ranks the env index space is sharded in
 contiguous blocks (weak scaling); the done masks go into a device-side ring that is all-gathered once per 128-step rollout.
 
-Timed region: barrier + synchronize, then `reps` x `--steps` steps back to back, then every rank drains ITS OWN stream
-and gathers and stops its clock (the closing barrier comes after and is not timed); `reps` is chosen so that the region
-lasts >= 50 ms (one 20-step block is 0.3 ms: shorter than a host synchronisation is exact).  value = envs x reps x steps
-/ MAX over ranks of the wall time; the device time of the same region (HIP events) is printed beside it.
+Timed region: barrier + synchronize, then `--steps` steps back to back, then every rank drains ITS OWN stream and
+gathers and stops its clock (the closing barrier comes after and is not timed).  value = envs x steps / MAX over ranks of
+the wall time, ms_per_step = that wall time / steps; the device time of the same region (HIP events) is printed beside
+it.  `--reps R` repeats the block of steps R times inside the region (timed steps = R x steps); `--reps 0` chooses R so
+that the region lasts >= 50 ms (one 20-step block is 0.3 ms, and a host synchronisation is a visible part of that).
 """
 import argparse
 import glob
@@ -38,7 +51,8 @@ sys.path.insert(0, ROOT)
 ENVS_PER_GPU = 65536
 GATHER_EVERY = 128        # multi-GPU: the done masks of this many steps travel in one all-gather (see run_rank): one
                           # rollout of the reference's PPO runner (StepEnvRoller number_of_steps=128, scripts/rl_runners/ppo_runner.py:70)
-MIN_REGION_MS = 50.0     # the timed region lasts at least this long (see run_rank: reps)
+MIN_REGION_MS = 50.0     # with --reps 0 the timed region lasts at least this long (see run_rank: reps)
+DUMP_MAX_ENVS = 1 << 18  # --dump-outputs: envs written per array at most (84 B per env: <= 22 MB in all)
 # ALGORITHMIC bytes per env-step (DESIGN.md "Bytes"): SoA state in + out (7 f64 robot + min_dist f64 +
 # target_idx i32 + current_iter i32 + robot_collided u8 = 73 B each way) + action 2 x f32 + reward f64 + done u8.
 # The shared costmap / path are LDS- and cache-resident and contribute no compulsory HBM traffic.
@@ -253,6 +267,23 @@ def parked_fraction(env, run, steps):
     before = env.parked_poses()
     run()
     return (env.parked_poses() - before) / float(env.n_envs * steps)
+
+
+def dump_outputs(env, done, out_dir):
+    """--dump-outputs: what BatchedPlanEnv.step returned at the last timed step -- the observation (pose, robot state,
+    target index, iteration counter), the reward and the done mask (`done`: the tensor that step wrote it to) -- as
+    out_dir/<name>.npy, envs along the last axis; a fixed sample of DUMP_MAX_ENVS envs (sorted) when there are more."""
+    import torch
+    torch.cuda.synchronize()
+    obs = env._obs
+    n = env.n_envs
+    idx = np.arange(n) if n <= DUMP_MAX_ENVS else np.sort(np.random.RandomState(0).choice(n, DUMP_MAX_ENVS, replace=False))
+    arrays = {"pose": obs.pose, "robot_state": obs.robot_state, "target_idx": obs.target_idx,
+              "current_iter": obs.current_iter, "reward": env.reward}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy().astype(np.float64)[..., idx])
+    np.save(os.path.join(out_dir, "done.npy"), done.cpu().numpy().astype(np.float32)[idx])
 
 
 def steady_state(env, pool, rng):
@@ -569,8 +600,9 @@ def run_rank(args):
 
     state = {"k0": 0, "pre_rolled": False}
 
-    def measure(gather_every, warmup):
-        """One timed region with the done-mask ring of `gather_every` rows: dict(elapsed, stream_ms, total, reps)."""
+    def measure(gather_every, warmup, reps):
+        """One timed region with the done-mask ring of `gather_every` rows: dict(elapsed, stream_ms, total, reps, done),
+        `done` = the done mask the region's last step returned."""
         ring = torch.zeros(gather_every, n, dtype=torch.uint8, device=torch.device("cuda", device)) if sharded else None
         gather = bdist.DoneGather(gather_every * n, torch.device("cuda", device), packed=True) if sharded else None   # (one bit per env on the links)
         if sharded:
@@ -616,24 +648,26 @@ def run_rank(args):
         for k in range(warmup):
             one_step(k0 + k)
         k0 += warmup
-        # How long is one block of `steps` steps?  (an untimed probe, so that --warmup 0 works too.)  A block shorter
-        # than MIN_REGION_MS is no instrument -- at the driver's --steps 20 it lasts 0.3 ms and one host synchronisation is
-        # 9 % of it -- so the timed region repeats the block `reps` times back to back; `steps` stays what was asked for,
-        # ms_per_step and value are per step.  Every rank uses the same `reps` (MAX of the probes).
+        # The timed region is `reps` blocks of `steps` steps back to back; ms_per_step and value are per step.  reps > 0
+        # is taken as given (1 by default: the region is exactly --steps steps).  reps == 0: how long is one block?  (an
+        # untimed probe, so that --warmup 0 works too.)  The region then repeats the block until it lasts MIN_REGION_MS
+        # -- at --steps 20 one block lasts 0.3 ms and one host synchronisation is 9 % of it.  Every rank uses the same
+        # `reps` (MAX of the probes).
         # (the probe's first block only fills the launch queue -- timed from a standing start it reads up to 20 % slow, and
         #  the region then ends before MIN_REGION_MS --, its second block is the one that is timed; 10 % on top)
-        probe = max(1, min(args.steps, 32))
-        barrier()
-        for k in range(probe):
-            one_step(k0 + k)
-        ev0.record(stream)
-        for k in range(probe):
-            one_step(k0 + probe + k)
-        ev1.record(stream)
-        k0 += 2 * probe
-        drain()
-        probe_ms = max_over_ranks(ev0.elapsed_time(ev1) / probe)
-        reps = args.reps if args.reps > 0 else int(min(8192, max(1, np.ceil(1.1 * MIN_REGION_MS / max(probe_ms * args.steps, 1e-6)))))
+        if reps <= 0:
+            probe = max(1, min(args.steps, 32))
+            barrier()
+            for k in range(probe):
+                one_step(k0 + k)
+            ev0.record(stream)
+            for k in range(probe):
+                one_step(k0 + probe + k)
+            ev1.record(stream)
+            k0 += 2 * probe
+            drain()
+            probe_ms = max_over_ranks(ev0.elapsed_time(ev1) / probe)
+            reps = int(min(8192, max(1, np.ceil(1.1 * MIN_REGION_MS / max(probe_ms * args.steps, 1e-6)))))
         k0 = (k0 + gather_every - 1) // gather_every * gather_every   # (the ring starts the region at row 0)
         total = reps * args.steps
 
@@ -654,13 +688,21 @@ def run_rank(args):
         barrier()
         stream_ms_local = ev0.elapsed_time(ev1)
         state["k0"] = k0 + total
-        return {"elapsed": max_over_ranks(elapsed_local), "stream_ms": max_over_ranks(stream_ms_local), "total": total, "reps": reps}
+        done = env.done if gather is None else ring[(k0 + total - 1) % gather_every]
+        return {"elapsed": max_over_ranks(elapsed_local), "stream_ms": max_over_ranks(stream_ms_local), "total": total,
+                "reps": reps, "done": done}
 
     gather_every = max(1, int(args.gather_every))
-    main_run = measure(gather_every, args.warmup)
-    short_run = measure(8, 0) if sharded and gather_every != 8 else None   # rounds 1-2's ring, for comparison across rounds
+    main_run = measure(gather_every, args.warmup, 1 if args.reps is None else args.reps)
     elapsed, stream_ms, total, reps = main_run["elapsed"], main_run["stream_ms"], main_run["total"], main_run["reps"]
     env.check_errors()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(env, main_run["done"], args.dump_outputs)
+    # rounds 1-2's ring, for comparison across rounds (a region of >= MIN_REGION_MS unless --reps says otherwise)
+    short_run = None
+    if args.full and sharded and gather_every != 8:
+        short_run = measure(8, 0, 0 if args.reps is None else args.reps)
+        env.check_errors()
 
     # The step's launches run back to back on one stream; their combined average duration is measured live with HIP
     # events recorded on the launch stream around the timed region (at N=1 the region holds nothing but these
@@ -710,34 +752,36 @@ def run_rank(args):
                          "traffic_source": traffic_src,
                          "issue": issue_object(),
                          "note": "shared-map config is latency-bound (SURVEY 8d): the HBM fraction is low by "
-                                 "construction; see DESIGN.md.  The HBM-bound config is aux.c4_aisle_private_maps"},
+                                 "construction; see DESIGN.md.  The HBM-bound config is aux.c4_aisle_private_maps (--full)"},
         }
         out["gather_every"] = gather_every if sharded else None
         out["done_masks_packed"] = bool(sharded)
+        out["full"] = bool(args.full)
         if short_run is not None:
             out["gather_every_8"] = {"value": total_envs * short_run["total"] / short_run["elapsed"], "unit": "env-steps/s",
                                      "ms_per_step": short_run["elapsed"] / short_run["total"] * 1e3,
                                      "device_ms_per_step": short_run["stream_ms"] / short_run["total"],
                                      "what": "the same workload with the done-mask ring of rounds 1-2 (one all-gather per 8 steps, "
                                              "bit-packed): a second timed region of this run, NOT the metric"}
-        out["parked_pose_fraction"] = parked_fraction(env, lambda: [env.step(pool[k % 16]) for k in range(64)], 64)
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(g)
-        if world == 1 and not args.no_aux:
-            try:  # informational only: never let it cost the metric line
-                # (the observation legs on the AisleTurn maps come first: measured behind the pool legs -- tens of GB of
-                #  buffers allocated and freed -- the 1.16 GB image buffer of the 133 x 133 window was written 15 x slower,
-                #  3.4 - 4.0 ms per call in three runs against 0.265 - 0.27 ms in every run without that history, whatever
-                #  the kernel version: the mapping of a fresh allocation, not the kernel)
-                aux = aux_ego_aisle(device)
-                aux.update(aux_measurements(env, pool, n))
-                env.close()
-                del env
-                torch.cuda.empty_cache()
-                aux.update(aux_other_configs(device))
-                out["aux"] = aux
-            except Exception as exc:  # noqa: BLE001
-                out["aux"] = {"error": repr(exc)}
+        if args.full:   # everything beside the headline figure
+            out["parked_pose_fraction"] = parked_fraction(env, lambda: [env.step(pool[k % 16]) for k in range(64)], 64)
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(g)
+            if world == 1 and not args.no_aux:
+                try:  # informational only: never let it cost the metric line
+                    # (the observation legs on the AisleTurn maps come first: measured behind the pool legs -- tens of GB of
+                    #  buffers allocated and freed -- the 1.16 GB image buffer of the 133 x 133 window was written 15 x slower,
+                    #  3.4 - 4.0 ms per call in three runs against 0.265 - 0.27 ms in every run without that history, whatever
+                    #  the kernel version: the mapping of a fresh allocation, not the kernel)
+                    aux = aux_ego_aisle(device)
+                    aux.update(aux_measurements(env, pool, n))
+                    env.close()
+                    del env
+                    torch.cuda.empty_cache()
+                    aux.update(aux_other_configs(device))
+                    out["aux"] = aux
+                except Exception as exc:  # noqa: BLE001
+                    out["aux"] = {"error": repr(exc)}
         print(json.dumps(out))
         sys.stdout.flush()
     if sharded:
@@ -751,11 +795,15 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--envs-per-gpu", type=int, default=ENVS_PER_GPU)
-    ap.add_argument("--reps", type=int, default=0, help="repeat the block of --steps steps this many times inside the "
-                    "timed region (default: as many as make the region last %.0f ms)" % MIN_REGION_MS)
+    ap.add_argument("--reps", type=int, default=None, help="repeat the block of --steps steps this many times inside the "
+                    "timed region (default 1; 0: as many as make the region last %.0f ms)" % MIN_REGION_MS)
     ap.add_argument("--gather-every", type=int, default=GATHER_EVERY, help="multi-GPU: steps between two all-gathers of the done-mask ring")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-aux", action="store_true", help="skip the informational legs (observation, pools, C2 / C4)")
+    ap.add_argument("--full", action="store_true", help="after the metric, also measure everything beside it: parked-pose "
+                    "share, CPU baseline, informational legs, the 8-step ring of a sharded run")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-aux", action="store_true", help="with --full: skip the informational legs (observation, pools, C2 / C4)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the outputs of the last timed step to "
+                    "DIR/<name>.npy (rank 0's envs; see the module docstring)")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args))

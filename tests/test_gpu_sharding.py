@@ -216,9 +216,10 @@ def _bench_line(result):
 
 def test_bench_rccl_at_world_size_one(launcher):
     """bench.py itself through the RCCL ring (forced group at N = 1): the line says so, and the timed region obeys its
-    rules -- reps x steps steps, wall time within a few percent of the HIP-event time of the same region."""
+    rules -- with --reps 0: reps x steps steps lasting >= 50 ms, wall time within a few percent of the HIP-event time of
+    the same region."""
     r = launcher.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
-                      "--envs-per-gpu", "16384", "--no-aux", "--no-cpu-baseline"],
+                      "--envs-per-gpu", "16384", "--no-aux", "--no-cpu-baseline", "--reps", "0"],
                      env={"BCP_DIST_FORCE": "1", "BCP_DIST_BACKEND": "nccl", "MASTER_ADDR": "127.0.0.1",
                           "MASTER_PORT": str(_free_port()), "HSA_ENABLE_IPC_MODE_LEGACY": "0"}, timeout=600, cwd=ROOT)
     line = _bench_line(r)

@@ -5,7 +5,7 @@ O=gpurun_out/r4al; mkdir -p $O; rm -f $O/*
 timeout -k 10 600 python -m pytest tests -m gpu -x -q --timeout 300 > $O/tests.log 2>&1; echo "tests rc=$?" > $O/rc.txt
 if grep -q "Memory access fault" $O/tests.log; then echo FAULT; tail -n 20 $O/tests.log; exit 1; fi
 if ! grep -q "rc=0" $O/rc.txt; then tail -n 30 $O/tests.log; exit 1; fi
-python bench.py > $O/bench_default.json 2> $O/bench.err; echo "bench rc=$?" >> $O/rc.txt
+python bench.py --full > $O/bench_default.json 2> $O/bench.err; echo "bench rc=$?" >> $O/rc.txt
 bash tools/step_pmc.sh > $O/step_pmc.log 2>&1; echo "step_pmc rc=$?" >> $O/rc.txt
 bash tools/c4_pmc.sh > $O/c4_pmc.log 2>&1; echo "c4_pmc rc=$?" >> $O/rc.txt
 bash tools/step_alu_pmc.sh > $O/alu_c3.log 2>&1; echo "alu c3 rc=$?" >> $O/rc.txt

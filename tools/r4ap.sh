@@ -8,5 +8,5 @@ for rep in 1 2; do for lib in tools/libbcplan_base.so bc_gym_planning_env_amd/li
   echo "== $lib" >> $O/endless.txt
   BCP_LIB=$lib python tools/bench_endless.py 2>&1 | grep -E "side stream|high-priority|one refresh|status" >> $O/endless.txt
 done; done
-python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?" >> $O/rc.txt
+python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?" >> $O/rc.txt
 cat $O/rc.txt; tail -n 1 $O/tests.log; cat $O/endless.txt; python tools/bench_summary.py $O/bench.json
