@@ -8,7 +8,7 @@ from .api import (Action, Box, ContinuousRewardProviderState, CostMap2D, Diffdri
 
 __all__ = ["Action", "Box", "ContinuousRewardProviderState", "CostMap2D", "DiffdriveRobotState", "EnvParams",
            "INDUSTRIAL_DIFFDRIVE_V1", "INDUSTRIAL_TRICYCLE_V1", "Observation", "RewardParams", "State",
-           "TricycleRobotState", "BatchedPlanEnv", "NativeOps"]
+           "TricycleRobotState", "BatchedPlanEnv", "BatchedRandomAisleTurnEnv", "NativeOps"]
 
 
 def __getattr__(name):
@@ -16,6 +16,9 @@ def __getattr__(name):
     if name in ("BatchedPlanEnv", "BatchedState", "BatchedObservation"):
         from . import batched_env
         return getattr(batched_env, name)
+    if name == "BatchedRandomAisleTurnEnv":
+        from .aisle_env import BatchedRandomAisleTurnEnv
+        return BatchedRandomAisleTurnEnv
     if name == "NativeOps":
         from .ops import NativeOps
         return NativeOps

@@ -57,6 +57,12 @@ class BcpMiniWorldParams(C.Structure):
         "lim_ang_dist", "angular_pose_noise_scale", "resolution", "goal_spat_dist", "goal_ang_dist")]
 
 
+class BcpAisleWorldParams(C.Structure):
+    _fields_ = [(k, C.c_double * 2) for k in (
+        "main_corridor_length", "turn_corridor_length", "turn_corridor_angle", "main_corridor_width",
+        "turn_corridor_width")] + [(k, C.c_double) for k in ("margin", "resolution", "path_delta")]
+
+
 class BcpStepIO(C.Structure):
     _fields_ = [
         ("actions", C.c_void_p), ("noise_z", C.c_void_p), ("noise_z_out", C.c_void_p), ("reward", C.c_void_p),
@@ -118,6 +124,12 @@ SYMBOLS = {
     "bcp_release_mini_worlds": (C.c_int, [_H, C.c_void_p]),
     "bcp_mini_world_paths": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
+    "bcp_sample_aisle_worlds": (C.c_int, [_H, C.POINTER(BcpAisleWorldParams), C.c_void_p, C.c_int64, C.c_int32,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bcp_render_aisle_worlds": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_int32, C.c_int32,
+                                          C.c_void_p, C.c_void_p]),
+    "bcp_aisle_world_paths": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_double, C.c_int32, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p]),
     "bcp_device_normals": (C.c_int, [_H, C.c_int64, C.c_int64, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p]),
     "bcp_step_form": (C.c_int, [_H]),
     "bcp_time_step_kernels": (C.c_int, [_H, C.POINTER(BcpStepIO), C.c_uint32, C.c_int32, C.c_void_p,

@@ -43,13 +43,16 @@ class DeviceGeometryPool(object):
     geometry-pool mode needs, as device tensors.  `costmaps` / `paths` hand out host copies on demand, for the per-env
     views (envs[i].get_state())."""
 
-    def __init__(self, maps, origin, resolution, paths, lens, init):
+    def __init__(self, maps, origin, resolution, paths, lens, init, origins=None, valid_rows=None, valid_cols=None):
         self.maps = maps                  # uint8 [G, rows, cols]
-        self.origin = np.asarray(origin, dtype=np.float64)   # one origin for all entries
+        self.origin = np.asarray(origin, dtype=np.float64) if origin is not None else None   # one origin for all entries
         self.resolution = float(resolution)
         self.path_points = paths          # float64 [G, max_len, 3], already refined
         self.lens = lens                  # int32 [G]
         self.init = init                  # float64 [G, 2] = (min_spat_dist_so_far, target_idx)
+        # optional, for entries of different sizes: float64 [G, 2] origin of every entry, int32 [G] true shape of every
+        # entry (the rest of its [rows, cols] is padding); None = one origin, every entry uses all of [rows, cols]
+        self.origins, self.valid_rows, self.valid_cols = origins, valid_rows, valid_cols
 
     def __len__(self):
         return int(self.maps.shape[0])
@@ -68,7 +71,20 @@ class DeviceGeometryPool(object):
 
     @property
     def costmaps(self):
-        return self._Lazy(len(self), lambda k: CostMap2D(self.maps[k].cpu().numpy(), self.resolution, self.origin))
+        if self.origins is None:
+            return self._Lazy(len(self), lambda k: CostMap2D(self.maps[k].cpu().numpy(), self.resolution, self.origin))
+
+        def fetch(k):   # the entry cropped to its true shape, with its own origin
+            vr = int(self.valid_rows[k]) if self.valid_rows is not None else self.maps.shape[1]
+            vc = int(self.valid_cols[k]) if self.valid_cols is not None else self.maps.shape[2]
+            return CostMap2D(self.maps[k, :vr, :vc].cpu().numpy(), self.resolution, self.origins[k].cpu().numpy())
+        return self._Lazy(len(self), fetch)
+
+    def entry_origins(self, device):
+        """float64 [G, 2] device tensor: the origin of every entry."""
+        if self.origins is not None:
+            return self.origins.to(device).contiguous()
+        return torch.from_numpy(np.tile(self.origin, (len(self), 1))).to(device)
 
     @property
     def paths(self):
@@ -419,9 +435,8 @@ class BatchedPlanEnv(object):
         n, dev = self.n_envs, self.device
         dp = getattr(self, "_device_pool", None)
         if dp is not None:   # everything is on the device already (refined paths included)
-            g_n = len(dp)
             self._costmaps, self._paths, self._shared_path = costmaps, paths, False
-            self.set_costmap_tensors(dp.maps, torch.from_numpy(np.tile(dp.origin, (g_n, 1))).to(dev), dp.resolution)
+            self.set_costmap_tensors(dp.maps, dp.entry_origins(dev), dp.resolution, dp.valid_rows, dp.valid_cols)
             self._keep.update(path=dp.path_points, lens=dp.lens)
             _lib.check(self._lib.bcp_set_paths(self._h, dp.path_points.data_ptr(), dp.lens.data_ptr(),
                                                int(dp.path_points.shape[1]), 0, self._stream()))

@@ -23,6 +23,7 @@
 #include "bcp_step.h"
 #include "bcp_ego.h"
 #include "bcp_sample.h"
+#include "bcp_aisle.h"
 
 using namespace bcp;
 
@@ -2883,6 +2884,68 @@ extern "C" int bcp_mini_world_paths(bcp_handle* h, const double* worlds, int64_t
     const EntrySelect all = {nullptr, nullptr, n_worlds};
     hipLaunchKernelGGL(mini_world_paths_kernel, dim3(stride_grid(n_worlds, 128)), dim3(128), 0, (hipStream_t)stream, worlds, all,
                        path_delta, h->params.spatial_precision, h->params.angular_precision,
+                       (int)(h->params.reward_provider == BCP_REWARD_PURE_PURSUIT), (int)max_len, paths, lens, init, status);
+    HIP_TRY(hipGetLastError());
+    return BCP_OK;
+}
+
+// ---- RandomAisleTurnEnv worlds made on the device ----------------------------------------------------------------
+static bool aisle_resolution_ok(double resolution)
+{
+    return resolution > 0 && (int)(0.05 / resolution) <= 1;   // Wall.render: thickness = max(1, int(width / resolution))
+}
+
+extern "C" int bcp_sample_aisle_worlds(bcp_handle* h, const bcp_aisle_world_params* p, uint32_t* mt_state, int64_t n_chains,
+                                       int32_t episodes, double* worlds, int32_t* shapes, void* stream)
+{
+    if (!h || !p || !mt_state || !worlds || !shapes || n_chains <= 0 || episodes <= 0 || !(p->path_delta > 0))
+        return fail(BCP_E_INVALID, "bcp_sample_aisle_worlds: bad argument");
+    if (!aisle_resolution_ok(p->resolution))
+        return fail(BCP_E_INVALID, "bcp_sample_aisle_worlds: resolution %g: walls thicker than one pixel are not supported",
+                    p->resolution);
+    HIP_TRY(hipSetDevice(h->device));
+    AisleWorldParams ap;
+    for (int k = 0; k < 2; ++k) {
+        ap.main_length[k] = p->main_corridor_length[k];
+        ap.turn_length[k] = p->turn_corridor_length[k];
+        ap.angle[k] = p->turn_corridor_angle[k];
+        ap.main_width[k] = p->main_corridor_width[k];
+        ap.turn_width[k] = p->turn_corridor_width[k];
+    }
+    ap.margin = p->margin;
+    ap.resolution = p->resolution;
+    ap.path_delta = p->path_delta;
+    hipLaunchKernelGGL(aisle_world_draw_kernel, dim3((unsigned)n_chains), dim3(64), 0, (hipStream_t)stream, ap, mt_state,
+                       n_chains, (int)episodes, worlds, shapes);
+    HIP_TRY(hipGetLastError());
+    return BCP_OK;
+}
+
+extern "C" int bcp_render_aisle_worlds(bcp_handle* h, const double* worlds, const int32_t* shapes, int64_t n_worlds,
+                                       double resolution, int32_t rows, int32_t pitch, uint8_t* maps, void* stream)
+{
+    if (!h || !worlds || !shapes || !maps || n_worlds <= 0 || rows <= 0 || pitch <= 0 || (pitch & 15) ||
+        ((uintptr_t)maps & 15))
+        return fail(BCP_E_INVALID, "bcp_render_aisle_worlds: bad argument (pitch and maps must be 16-byte aligned)");
+    if (!aisle_resolution_ok(resolution))
+        return fail(BCP_E_INVALID, "bcp_render_aisle_worlds: resolution %g: walls thicker than one pixel are not supported",
+                    resolution);
+    if (n_worlds > 0x7fffffff) return fail(BCP_E_INVALID, "bcp_render_aisle_worlds: too many worlds");
+    HIP_TRY(hipSetDevice(h->device));
+    hipLaunchKernelGGL(aisle_world_render_kernel, dim3((unsigned)n_worlds), dim3(256), 0, (hipStream_t)stream, worlds, shapes,
+                       (int)rows, (int)pitch, 1.0 / resolution, maps);
+    HIP_TRY(hipGetLastError());
+    return BCP_OK;
+}
+
+extern "C" int bcp_aisle_world_paths(bcp_handle* h, const double* worlds, int64_t n_worlds, double path_delta, int32_t max_len,
+                                     double* paths, int32_t* lens, double* init, int32_t* status, void* stream)
+{
+    if (!h || !worlds || !paths || !lens || !init || !status || n_worlds <= 0 || max_len < 2 || !(path_delta > 0))
+        return fail(BCP_E_INVALID, "bcp_aisle_world_paths: bad argument");
+    HIP_TRY(hipSetDevice(h->device));
+    hipLaunchKernelGGL(aisle_world_paths_kernel, dim3(stride_grid(n_worlds, 128)), dim3(128), 0, (hipStream_t)stream, worlds,
+                       n_worlds, path_delta, h->params.spatial_precision, h->params.angular_precision,
                        (int)(h->params.reward_provider == BCP_REWARD_PURE_PURSUIT), (int)max_len, paths, lens, init, status);
     HIP_TRY(hipGetLastError());
     return BCP_OK;

@@ -452,6 +452,43 @@ int bcp_parked_poses(bcp_handle *h, int64_t *count, void *stream);
 int bcp_device_normals(bcp_handle *h, int64_t first_env, int64_t n_envs, uint64_t first_step, int32_t n_steps, double *out,
                        void *stream);
 
+/* ---- RandomAisleTurnEnv worlds made on the device ---------------------------------------------------------- */
+/* The ranges RandomAisleTurnEnv._draw_random_turn_params draws from (envs/synth_turn_env.py:317-332; low, high each),
+ * TurnParams.margin (:31) and the EnvParams fields the world needs.  host struct. */
+typedef struct bcp_aisle_world_params {
+    double main_corridor_length[2], turn_corridor_length[2], turn_corridor_angle[2];
+    double main_corridor_width[2], turn_corridor_width[2];
+    double margin;
+    double resolution;   /* EnvParams.resolution: below 0.025 m the walls would be 2 px thick -> BCP_E_INVALID */
+    double path_delta;   /* EnvParams.path_delta: only the refined path length of the record depends on it */
+} bcp_aisle_world_params;
+/* _draw_random_turn_params (envs/synth_turn_env.py:317-332) `episodes` times in a row for every stream (mt_state as
+ * bcp_mini_world_seed makes it; the streams continue where they stopped), and what path_and_costmap_from_config
+ * (:110-192) computes before it draws: one wavefront per stream.  World k of stream c is entry c * episodes + k.
+ * Outputs (device):
+ *   worlds  double [n_chains * episodes][44]: [0, 8) turn params (main / turn corridor length, turn angle, main / turn
+ *           corridor width, flip_arnd_oy, flip_arnd_ox as 0 / 1, rot_theta), [8, 10) world origin, [10, 30) corners
+ *           A .. J (:42-79), [30, 42) oriented way points B, K, L, F (:82-97) after rotation and flips, [42] the length
+ *           of the refined path (utilities/path_tools.py:178-240), [43] 0
+ *   shapes  int32  [n_chains * episodes][2] = (rows, cols) of the world's map (CostMap2D.create_empty,
+ *           utilities/costmap_2d.py:58-69)
+ * There is no rejection: the reference tests nothing.  Transcendentals are the device's: a coordinate can differ from
+ * numpy's in its last bit. */
+int bcp_sample_aisle_worlds(bcp_handle *h, const bcp_aisle_world_params *p /*host*/, uint32_t *mt_state, int64_t n_chains,
+                            int32_t episodes, double *worlds, int32_t *shapes, void *stream);
+/* The five 1-px walls of every world (:174-190, Wall.render -> cv2.line, envs/base/maps.py:28-44) into padded pool
+ * entries, one workgroup per world: maps uint8 [n_worlds][rows][pitch] (device, 16-byte aligned) is zeroed entry by
+ * entry and each world is drawn into its own shapes[g] = (rows_g, cols_g) corner; the padding stays 0.  pitch must be a
+ * multiple of 16, and rows / pitch at least every world's rows / cols: a world that does not fit is left empty. */
+int bcp_render_aisle_worlds(bcp_handle *h, const double *worlds, const int32_t *shapes, int64_t n_worlds,
+                            double resolution, int32_t rows, int32_t pitch, uint8_t *maps, void *stream);
+/* make_initial_state (envs/base/env.py:179-214) for aisle worlds: refine_path of the coarse path B K L F
+ * (utilities/path_tools.py:178-240: np.linspace arithmetic, inserted points carry their segment's first heading) and the
+ * initial state of this handle's reward provider (reward.py:261-288 / :355-371).  paths / lens / init / status as
+ * bcp_mini_world_paths (max_len: at least the largest record[42]). */
+int bcp_aisle_world_paths(bcp_handle *h, const double *worlds, int64_t n_worlds, double path_delta, int32_t max_len,
+                          double *paths, int32_t *lens, double *init, int32_t *status, void *stream);
+
 /* ---- measurement -------------------------------------------------------------------------------------- */
 /* Which kernels a bcp_step() of this handle launches, as configured now: 0 = step_kernel alone (no distance field, or a
  * forced mode), 1 = step_fast_pair_kernel alone (every undecided pose settled in place), 2 = step_fast_pair_kernel +
