@@ -12,6 +12,7 @@ MODEL_TRICYCLE, MODEL_DIFFDRIVE = 0, 1
 REWARD_CONTINUOUS, REWARD_PURE_PURSUIT = 0, 1
 STEP_AUTO_RESET, STEP_ACTIONS_F32 = 1, 2
 ERR_ANGLE_JUMP, ERR_TIME_ORDER, ERR_INTERNAL = 1, 2, 4
+DONE_GOAL, DONE_TIMEOUT, DONE_COLLIDED = 1, 2, 4
 TUNE_EXACT_MODE, TUNE_DENSE_THRESHOLD, TUNE_CULL, TUNE_DEFER, TUNE_EDT_LDS, TUNE_FUSED, TUNE_EGO_SPARSE, TUNE_NEAR_DILATE = 0, 1, 2, 3, 4, 5, 6, 7
 TUNE_LOCAL_PAIRS, TUNE_EGO_LIST_STRIDE, TUNE_NEAR_SHIFT = 8, 9, 10
 E_NO_DEVICE = -2
@@ -67,6 +68,13 @@ class BcpStepIO(C.Structure):
     _fields_ = [
         ("actions", C.c_void_p), ("noise_z", C.c_void_p), ("noise_z_out", C.c_void_p), ("reward", C.c_void_p),
         ("done", C.c_void_p), ("collided_now", C.c_void_p), ("err", C.c_void_p),
+    ]
+
+
+class BcpEpisodeRecord(C.Structure):
+    _fields_ = [
+        ("capacity", C.c_int64), ("reason", C.c_void_p), ("ret", C.c_void_p), ("count", C.c_void_p),
+        ("env_id", C.c_void_p), ("geom", C.c_void_p), ("final_ret", C.c_void_p), ("final", BcpState),
     ]
 
 
@@ -135,6 +143,11 @@ SYMBOLS = {
     "bcp_time_step_kernels": (C.c_int, [_H, C.POINTER(BcpStepIO), C.c_uint32, C.c_int32, C.c_void_p,
                                         C.POINTER(C.c_float)]),
     "bcp_time_steps": (C.c_int, [_H, C.POINTER(BcpStepIO), C.c_uint32, C.c_int32, C.c_void_p, C.POINTER(C.c_float)]),
+    "bcp_bind_episode_record": (C.c_int, [_H, C.POINTER(BcpEpisodeRecord)]),
+    "bcp_episode_record_overflows": (C.c_int, [_H, C.POINTER(C.c_int64), C.c_void_p]),
+    "bcp_final_egocentric_costmaps": (C.c_int, [_H, _f64p, _f64p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "bcp_final_goal_n_state": (C.c_int, [_H, _f64p, C.c_void_p, C.c_void_p]),
+    "bcp_final_goal_direction_state": (C.c_int, [_H, _f64p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

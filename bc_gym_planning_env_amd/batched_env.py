@@ -258,6 +258,124 @@ class _EnvViews(object):
         return EnvView(self._env, i % self._env.n_envs)
 
 
+class EpisodeEnds(object):
+    """The episodes that ended in the last step (libbcplan's episode record, bcp_bind_episode_record): what a caller of the
+    reference's PlanEnv sees from step() before it calls reset() (envs/base/env.py:334-361, 293-303), kept although the
+    step has already auto-reset the env.  Device tensors, filled by the step kernel itself (no sync, no extra launch):
+
+      reason        uint8 [N]          BCP_DONE_* bits of every env (GOAL | TIMEOUT | COLLIDED, env.py:400-419), 0 = not done
+      count         int32 [1]          envs that ended in the last step (may exceed `capacity`: overflow)
+      env_ids       int32 [capacity]   slot j < count: which env ended (order unspecified)
+      geom          int32 [capacity]   the geometry-pool entry the episode ran on (-1 without a pool)
+      final_state   BatchedState over the slots: the state the env held after its last step, before the reset
+                    (robot, reward-provider state, current_iter = episode length, robot_collided; the seen pose / robot
+                    state with delays; no queues)
+      final_return  float64 [capacity] the episode's return, the float64 sum of its rewards in step order
+      ret           float64 [N]        every env's running return (zeroed by every reset; set_state / fan_out leave it)
+
+    The running returns start at 0 when the record is bound: bound in the middle of episodes, each env's first
+    final_return covers only the steps since then (bind right after a reset() for whole-episode returns).
+    """
+
+    GOAL, TIMEOUT, COLLIDED = _lib.DONE_GOAL, _lib.DONE_TIMEOUT, _lib.DONE_COLLIDED
+
+    def __init__(self, env, capacity):
+        n, dev, cap = env.n_envs, env.device, int(capacity)
+        if cap < 1:
+            raise ValueError("capacity must be positive")
+        self._env, self.capacity = env, cap
+
+        def zeros(*shape, dtype=torch.float64):
+            return torch.zeros(*shape, dtype=dtype, device=dev)
+
+        self.reason = zeros(n, dtype=torch.uint8)
+        self.ret = zeros(n)
+        self.count = zeros(1, dtype=torch.int32)
+        self.env_ids = zeros(cap, dtype=torch.int32)
+        self.geom = torch.full((cap,), -1, dtype=torch.int32, device=dev)
+        self.final_return = zeros(cap)
+        pd, sd = int(env.params.pose_delay), int(env.params.state_delay)
+        self.final_state = BatchedState(zeros(7, cap), zeros(cap), zeros(cap, dtype=torch.int32),
+                                        zeros(cap, dtype=torch.int32), zeros(cap, dtype=torch.uint8),
+                                        pose_seen=zeros(3, cap) if pd else None,
+                                        robot_state_seen=zeros(7, cap) if sd else None)
+
+    def _c_struct(self):
+        rec = _lib.BcpEpisodeRecord()
+        rec.capacity = self.capacity
+        rec.reason, rec.ret, rec.count = self.reason.data_ptr(), self.ret.data_ptr(), self.count.data_ptr()
+        rec.env_id, rec.geom, rec.final_ret = self.env_ids.data_ptr(), self.geom.data_ptr(), self.final_return.data_ptr()
+        f = self.final_state
+        for k, name in enumerate(_STATE_FIELDS):
+            setattr(rec.final, name, f.robot[k].data_ptr())
+        rec.final.min_spat_dist_so_far = f.min_spat_dist_so_far.data_ptr()
+        rec.final.target_idx = f.target_idx.data_ptr()
+        rec.final.current_iter = f.current_iter.data_ptr()
+        rec.final.robot_collided = f.robot_collided.data_ptr()
+        rec.final.pose_seen = f.pose_seen.data_ptr() if f.pose_seen is not None else None
+        rec.final.robot_state_seen = f.robot_state_seen.data_ptr() if f.robot_state_seen is not None else None
+        return rec
+
+    @property
+    def length(self):
+        """int32 [capacity]: the episodes' lengths in steps (final_state.current_iter)."""
+        return self.final_state.current_iter
+
+    def terminated(self):
+        """bool [N]: the episode ended in a terminal state -- goal reached or collided (a time-out together with one
+        of them counts as terminal)."""
+        return (self.reason & (self.GOAL | self.COLLIDED)) != 0
+
+    def truncated(self):
+        """bool [N]: the episode was cut by the time limit alone (gymnasium's `truncated`, SB3's TimeLimit.truncated):
+        bootstrap V(final observation) there."""
+        return self.reason == self.TIMEOUT
+
+    def overflowed(self):
+        """True if more envs ended in the last step than there are slots (synchronises)."""
+        return int(self.count[0]) > self.capacity
+
+    def slots(self):
+        """Number of filled slots of the last step, min(count, capacity) (synchronises)."""
+        return min(int(self.count[0]), self.capacity)
+
+    def to_host(self):
+        """The last step's episode ends as a list of (env id, reference State, reason bits, return, length); the States
+        hold no delay queues.  Synchronises -- for debugging and tests."""
+        e = self._env
+        m = self.slots()
+        ids = self.env_ids[:m].cpu().numpy()
+        geom = self.geom[:m].cpu().numpy()
+        reason = self.reason.cpu().numpy()
+        ret = self.final_return[:m].cpu().numpy()
+        f = self.final_state
+        robot = f.robot[:, :m].cpu().numpy()
+        md = f.min_spat_dist_so_far[:m].cpu().numpy()
+        ti = f.target_idx[:m].cpu().numpy()
+        it = f.current_iter[:m].cpu().numpy()
+        col = f.robot_collided[:m].cpu().numpy()
+        ps = f.pose_seen[:, :m].cpu().numpy() if f.pose_seen is not None else None
+        rs = f.robot_state_seen[:, :m].cpu().numpy() if f.robot_state_seen is not None else None
+        view = EnvView(e, 0)
+        cls = (ContinuousRewardPurePursuitProviderState if e.params.reward_provider_name == CONTINUOUS_REWARD_PURE_PURSUIT
+               else ContinuousRewardProviderState)
+        out = []
+        for j in range(m):
+            i, g = int(ids[j]), int(geom[j])
+            path = e._paths[g] if g >= 0 else e.path_of(i)
+            costmap = e._costmaps[g] if g >= 0 else e.costmap_of(i)
+            rps = cls(min_spat_dist_so_far=float(md[j]), path=path, target_idx=int(ti[j]))
+            n_it = int(it[j])
+            st = State(reward_provider_state=rps, path=rps.current_path(), original_path=np.copy(path), costmap=costmap,
+                       iter_timeout=e.params.iteration_timeout,
+                       current_time=float(e.time_of(f.current_iter[j:j + 1])[0]), current_iter=n_it,
+                       robot_collided=bool(col[j]), poses_queue=[], robot_state_queue=[], control_queue=[],
+                       pose=ps[:, j].copy() if ps is not None else robot[:3, j].copy(),
+                       robot_state=view._robot_state(rs[:, j] if rs is not None else robot[:, j]))
+            out.append((i, st, int(reason[i]), float(ret[j]), n_it))
+        return out
+
+
 class BatchedPlanEnv(object):
     """N planning envs on one MI355X.
 
@@ -374,6 +492,7 @@ class BatchedPlanEnv(object):
         self._flags_f32 = self._flags_f64 | _lib.STEP_ACTIONS_F32
         self._obs = BatchedObservation(self)
         self._info = {}
+        self.episode_ends = None   # enable_episode_record()
         self.seed(seed)
         self.reset()
 
@@ -696,7 +815,8 @@ class BatchedPlanEnv(object):
         noise_z: optional [N,3] float64 standard normals (slot order) replacing the on-device RNG.
         done_out: optional uint8 [N] device tensor that receives the done mask instead of `self.done` (e.g. a row of
         a ring buffer that is all-gathered every few steps).
-        Returns (BatchedObservation, reward float64[N], done uint8[N], {}) -- device tensors, no sync."""
+        Returns (BatchedObservation, reward float64[N], done uint8[N], info) -- device tensors, no sync; info is {} or,
+        with enable_episode_record(), {"episode_ends": EpisodeEnds}."""
         # fast path: a device tensor of the right shape and dtype goes straight to the library
         if not (isinstance(actions, torch.Tensor) and actions.device == self.device and actions.is_contiguous()
                 and actions.dtype in (torch.float32, torch.float64) and tuple(actions.shape) == (self.n_envs, 2)):
@@ -776,9 +896,36 @@ class BatchedPlanEnv(object):
         self._last_inputs = tuple(keep)
         return reward, done
 
+    def enable_episode_record(self, capacity=None):
+        """Keep what every episode end leaves behind (bcp_bind_episode_record): from now on step() returns
+        info = {"episode_ends": EpisodeEnds} -- why each env's episode ended, its final state before the auto-reset, its
+        return and length, as device tensors the step kernel fills (no sync, no extra launch).  capacity: slots for envs
+        that end in one step (default n_envs: never overflows).  Binding synchronises the device.  The running returns
+        start at 0 here: bound in the middle of episodes, the first return of each env covers only the steps since.
+        Returns the EpisodeEnds."""
+        ends = EpisodeEnds(self, self.n_envs if capacity is None else capacity)
+        rec = ends._c_struct()
+        _lib.check(self._lib.bcp_bind_episode_record(self._h, C.byref(rec)))
+        self.episode_ends = ends
+        self._info = {"episode_ends": ends}
+        return ends
+
+    def disable_episode_record(self):
+        """Unbind the episode record: step() returns info = {} again."""
+        _lib.check(self._lib.bcp_bind_episode_record(self._h, None))
+        self.episode_ends = None
+        self._info = {}
+
     def check_errors(self):
         """Raise what the reference would have raised during the last step (synchronises); and a RuntimeError if a
-        wait inside the step kernel ever gave up (bcp_expired_waits: a defect of the library, not of the data)."""
+        wait inside the step kernel ever gave up (bcp_expired_waits: a defect of the library, not of the data), or if the
+        episode record had more episode ends in one step than slots since the last call."""
+        if self.episode_ends is not None:
+            steps = C.c_int64()
+            _lib.check(self._lib.bcp_episode_record_overflows(self._h, C.byref(steps), self._stream()))
+            if steps.value:
+                raise RuntimeError("episode record: %d step(s) ended more episodes than its %d slots hold"
+                                   % (steps.value, self.episode_ends.capacity))
         gave_up = C.c_int64()
         _lib.check(self._lib.bcp_expired_waits(self._h, C.byref(gave_up), self._stream()))
         if gave_up.value:

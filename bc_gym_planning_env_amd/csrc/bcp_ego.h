@@ -45,7 +45,14 @@ struct EgoArgs {
     int64_t n_images;
     int32_t win_lds_bytes;       // ego_costmap_window_kernel: LDS bytes for the visible part of the map (+ ring)
     uint8_t* out;                // [n][drows][dcols]
+    const int32_t* live;         // optional device count: only images < min(n_images, *live) are drawn (the final
+                                 // observations of an episode record, bcp_final_egocentric_costmaps); the rest stay untouched
 };
+
+__device__ __forceinline__ int64_t ego_images(const EgoArgs& a)
+{
+    return a.live ? min(a.n_images, (int64_t)max(*a.live, 0)) : a.n_images;
+}
 
 __device__ __forceinline__ int sat_int(double v)   // cv::saturate_cast<int>(double): nearest-even, saturating
 {
@@ -544,12 +551,13 @@ __global__ void __launch_bounds__(64 * kEgoWaves) ego_costmap_kernel(const EgoAr
     const int cg = lane % kGroups, rl = lane / kGroups;
     const int64_t P = (int64_t)a.drows * a.dcols;
     const int64_t first = (int64_t)blockIdx.x * waves + wave, stride = (int64_t)gridDim.x * waves;
-    for (int64_t base = first; base < a.n_images; base += 64 * stride) {
+    const int64_t n_img = ego_images(a);   // (a.live: an episode record's count)
+    for (int64_t base = first; base < n_img; base += 64 * stride) {
         EgoXform T;
         memset(&T, 0, sizeof(T));
         const int64_t mine = base + lane * stride;   // lane l: transform of the wave's l-th image of this batch
-        if (mine < a.n_images) T = ego_transform(a, mine);
-        const int64_t left = (a.n_images - base + stride - 1) / stride;
+        if (mine < n_img) T = ego_transform(a, mine);
+        const int64_t left = (n_img - base + stride - 1) / stride;
         const int count = (int)(left < 64 ? left : 64);
         for (int k = 0; k < count; ++k) {            // the wave's images, one at a time
             const int64_t img = base + k * stride;
@@ -585,8 +593,9 @@ __global__ void __launch_bounds__(256) ego_costmap_binned_kernel(const EgoArgs a
     constexpr int kGroups = 128 / PX, kRows = 64 / kGroups;
     const int cg = lane % kGroups, rl = lane / kGroups;
     const int64_t P = (int64_t)a.drows * a.dcols;
-    const int64_t chunk = (a.n_images + gridDim.x - 1) / gridDim.x;
-    const int64_t lo = blockIdx.x * chunk, hi = min(lo + chunk, a.n_images);
+    const int64_t n_img = ego_images(a);   // (a.live: an episode record's count)
+    const int64_t chunk = (n_img + gridDim.x - 1) / gridDim.x;
+    const int64_t lo = blockIdx.x * chunk, hi = min(lo + chunk, n_img);
     for (int64_t pos = lo; pos < hi;) {
         const int64_t me = (int64_t)order[pos] % a.n_envs;
         const int64_t g = a.geom_of_env ? (int64_t)a.geom_of_env[me] : me;
@@ -657,12 +666,13 @@ __global__ void __launch_bounds__(256) ego_costmap_window_kernel(const EgoArgs a
     const int cg = lane % kGroups, rl = lane / kGroups;
     const int64_t P = (int64_t)a.drows * a.dcols;
     const int64_t first = blockIdx.x, stride = gridDim.x;
-    for (int64_t base = first; base < a.n_images; base += 64 * stride) {
+    const int64_t n_img = ego_images(a);   // (a.live: an episode record's count)
+    for (int64_t base = first; base < n_img; base += 64 * stride) {
         EgoXform T;
         memset(&T, 0, sizeof(T));
         const int64_t mine = base + lane * stride;   // lane l: transform of the workgroup's l-th image of this batch
-        if (mine < a.n_images) T = ego_transform(a, mine);
-        const int64_t left = (a.n_images - base + stride - 1) / stride;
+        if (mine < n_img) T = ego_transform(a, mine);
+        const int64_t left = (n_img - base + stride - 1) / stride;
         const int count = (int)(left < 64 ? left : 64);
         for (int k = 0; k < count; ++k) {
             const int64_t img = base + k * stride;
@@ -878,12 +888,13 @@ __global__ void __launch_bounds__(64 * kEgoWaves) ego_sparse_kernel(const EgoArg
     const LdsI32x2 col_tab = (LdsI32x2)((__attribute__((address_space(3))) uint32_t*)ego_lds + wave * per_wave_words);
     const LdsI32x2 row_tab = col_tab + a.dcols;
     __attribute__((address_space(3))) uint32_t* const mine_cells = (__attribute__((address_space(3))) uint32_t*)(row_tab + a.drows);
-    for (int64_t base = first; base < a.n_images; base += 64 * stride) {
+    const int64_t n_img = ego_images(a);   // (a.live: an episode record's count)
+    for (int64_t base = first; base < n_img; base += 64 * stride) {
         EgoXform T;
         memset(&T, 0, sizeof(T));
         const int64_t mine = base + lane * stride;   // lane l: transform of the wave's l-th image of this batch
-        if (mine < a.n_images) T = ego_transform(a, mine);
-        const int64_t left = (a.n_images - base + stride - 1) / stride;
+        if (mine < n_img) T = ego_transform(a, mine);
+        const int64_t left = (n_img - base + stride - 1) / stride;
         const int count = (int)(left < 64 ? left : 64);
         for (int k = 0; k < count; ++k) {            // the wave's images, one at a time
             const int64_t img = base + k * stride;
@@ -987,10 +998,10 @@ __global__ void __launch_bounds__(64 * kEgoWaves) ego_sparse_kernel(const EgoArg
 
 // ---- grouping images by map entry: count -> exclusive scan -> scatter ------------------------------------------
 __global__ void ego_bin_count_kernel(const int32_t* __restrict__ geom_of_env, int64_t n_envs, int64_t n_images,
-                                     int32_t* __restrict__ bin_count, int32_t* __restrict__ rank)
+                                     int32_t* __restrict__ bin_count, int32_t* __restrict__ rank, const int32_t* __restrict__ live)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_images) return;
+    if (i >= n_images || (live && i >= *live)) return;
     const int64_t me = i % n_envs;
     const int64_t g = geom_of_env ? (int64_t)geom_of_env[me] : me;
     rank[i] = atomicAdd(bin_count + g, 1);
@@ -1024,10 +1035,10 @@ __global__ void __launch_bounds__(1024) ego_bin_scan_kernel(const int32_t* __res
 
 __global__ void ego_bin_scatter_kernel(const int32_t* __restrict__ geom_of_env, int64_t n_envs, int64_t n_images,
                                        const int32_t* __restrict__ bin_start, const int32_t* __restrict__ rank,
-                                       int32_t* __restrict__ order)
+                                       int32_t* __restrict__ order, const int32_t* __restrict__ live)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_images) return;
+    if (i >= n_images || (live && i >= *live)) return;
     const int64_t me = i % n_envs;
     const int64_t g = geom_of_env ? (int64_t)geom_of_env[me] : me;
     order[bin_start[g] + rank[i]] = (int32_t)i;

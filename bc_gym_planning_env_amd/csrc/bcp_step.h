@@ -48,6 +48,36 @@ struct PathDesc {
 
 struct Pending;
 
+// The episode record (bcp_bind_episode_record): where the step kernels leave each env whose episode ends.  It lies at the END
+// of StepStatic and is NOT part of what step_local_kernel stages in LDS (kStaticChunks): the kernels read it through the
+// global block a.S, behind the internal flag kStepRecord, and only where an env is finished.
+// Two-launch step with a record: what kernel 2's redo of a parked env needs from kernel 1, one per parking slot
+struct RecPark {
+    double ret_before;      // the env's return before this step
+    int32_t slot, pad;      // the record slot kernel 1 gave the env (-1: none)
+};
+
+// How finalize_env_from finishes an env: first time (on = false), or kernel 2 redoing an env kernel 1 finished optimistically
+struct RecRedo {
+    double ret_before;
+    int32_t slot;
+    bool on;
+};
+
+struct EpisodeRec {
+    uint8_t* reason;        // [N] BCP_DONE_* bits of the last step
+    double* ret;            // [N] running return of the episode, or nullptr
+    int32_t* count;         // [1] envs that ended in the last step (published by the last party of the step)
+    int32_t* env_id;        // [capacity]
+    int32_t* geom;          // [capacity] pool entry the episode ran on (-1 without a pool)
+    double* final_ret;      // [capacity] (with ret)
+    DevState fin;           // [capacity] final states: x .. collided, pose_seen / state_seen with delays, queues nullptr
+    int64_t capacity;
+    uint32_t* work;         // library-owned [3]: slots taken so far in this step, ticket of the publishing parties, steps
+                            // whose count exceeded the capacity (bcp_episode_record_overflows)
+    RecPark* park;          // library-owned [kShards][pending_cap] (two-launch form), indexed like StepStatic::pending
+};
+
 // Everything a step needs that only changes when the caller re-binds something.  It lives in DEVICE memory (uploaded
 // when dirty) and the kernels get a pointer: kernel arguments sit in host memory on this platform, and a kernel that
 // takes kilobytes of arguments by value pays a PCIe-latency scalar load every time it touches a new field.
@@ -67,6 +97,7 @@ struct StepStatic {
     // state arrays; a reset moves it to next_geom[entry].  nullptr: env i uses entry i.
     int32_t* geom_of_env;
     const int32_t* next_geom;
+    EpisodeRec rec;            // (last: not staged in LDS, see EpisodeRec)
 };
 
 // What a wave needs before anything else -- where its state, its path and (kernel 2) its parked poses are -- travels
@@ -151,6 +182,26 @@ constexpr int kTickWords = 16;
 constexpr int kTickLocalTicket = 8;   // step_local_kernel's ticket: not on the line the prologues read the counter and the seed from
 
 constexpr uint32_t kStepAdvances = 1u << 24;   // internal flag: this launch is the last kernel of its step
+constexpr uint32_t kStepRecord = 1u << 25;     // internal flag: an episode record is bound (StepStatic::rec)
+
+// The step's count of ended envs, by the last party of the step (every slot has been taken): published, counter re-armed
+__device__ __forceinline__ void record_store_count(const EpisodeRec& R)
+{
+    const uint32_t taken = atomicExch(R.work, 0u);
+    *R.count = (int32_t)taken;
+    if ((int64_t)taken > R.capacity) atomicAdd(R.work + 2, 1u);
+}
+
+// The last of `parties` to get here (each after its own slots were taken) publishes the count.  One lane per party.
+__device__ __forceinline__ void record_publish(const StepStatic* S, unsigned int parties)
+{
+    uint32_t* work = S->rec.work;
+    __threadfence();
+    if (atomicAdd(work + 1, 1u) == parties - 1) {
+        work[1] = 0u;
+        record_store_count(S->rec);
+    }
+}
 
 // which: 0 = kernel 1 / single-kernel step, 1 = kernel 2
 __device__ __forceinline__ StepArgs resolve_step(const StepArgs& in, int which)
@@ -179,6 +230,8 @@ __device__ __forceinline__ void advance_step_by_ticket(const StepArgs& a)
     if (atomicAdd(ticket, 1u) == gridDim.x - 1) {
         *ticket = 0u;
         a.tick[0] = a.step_counter + 1;
+        // (every workgroup finished its envs -- in the wave that drew its ticket -- before it drew)
+        if (a.flags & kStepRecord) record_store_count(a.S->rec);
     }
 }
 
@@ -1000,12 +1053,15 @@ __device__ __forceinline__ int64_t slot_of(SP S, int64_t i, const Pending& q)
 // PLAIN = true (no delays, continuous reward provider -- see step_is_plain) compiles the delay queues and the
 // pure-pursuit branch out.
 // (A: StepArgs by value, or by reference into the kernel-argument segment -- only a.S, the output pointers and a.flags are used)
+// Returns the episode-record slot the env took (-1: none, or no record bound).
 template <bool PLAIN, typename A, typename SP>
-__device__ __forceinline__ void finalize_env_from(const A& a, SP S, int64_t i, Pending& q, bool hit, LdsF64 lds_path = nullptr,
+__device__ __forceinline__ int finalize_env_from(const A& a, SP S, int64_t i, Pending& q, bool hit, LdsF64 lds_path = nullptr,
                                              const PathWindow* free_window = nullptr, bool have_score = false,
                                              ScoredFree score = ScoredFree(), int known_len = -1, bool score_fits_hit = false,
-                                             int64_t out_base = 0)
-{   // (the score travels by value: a pointer to a local made the compiler keep it in scratch memory;
+                                             int64_t out_base = 0, RecRedo redo = RecRedo{0.0, -1, false})
+{   // (redo.on: step_pending_kernel finishes again an env that step_fast_pair_kernel finished optimistically as free -- the
+    //  record keeps the slot kernel 1 gave it, redo.slot, and the return starts from redo.ret_before;
+    //  the score travels by value: a pointer to a local made the compiler keep it in scratch memory;
     //  out_base: element offset of this step's rows in the output arrays -- step k of a rollout writes row k, bcp_rollout --;
     //  known_len >= 0: the caller already holds the length of this env's path;
     //  score_fits_hit: `score` was computed for the rolled-back pose of a colliding env -- continuous provider only)
@@ -1064,7 +1120,8 @@ __device__ __forceinline__ void finalize_env_from(const A& a, SP S, int64_t i, P
         }
         goal = target > m - 1;
     }
-    const bool done = goal || (iter >= P.iteration_timeout) || collided;
+    const bool timeout = iter >= P.iteration_timeout;
+    const bool done = goal || timeout || collided;   // env.py:400-419
 
     const int64_t o = out_base + i;
     as_global(a.reward)[o] = rew;
@@ -1078,7 +1135,9 @@ __device__ __forceinline__ void finalize_env_from(const A& a, SP S, int64_t i, P
         as_global(a.noise_z_out)[3 * o + 2] = (q.drawn & 4) ? q.z[2] : nan;
     }
 
-    if (done && (a.flags & BCP_STEP_AUTO_RESET)) {  // PlanEnv.reset(): set_state(initial_state) (env.py:293-303)
+    const bool reset = done && (a.flags & BCP_STEP_AUTO_RESET);
+    InitAhead ahead = InitAhead();   // (initialised: left undefined outside the branch, it was kept in scratch memory)
+    if (reset) {  // PlanEnv.reset(): set_state(initial_state) (env.py:293-303)
         int64_t k = i;
         if (S->geom_of_env) {  // RandomMiniEnv.reset(): the env moves on to its next geometry (mini_env.py:469-481).
             // Computed from the entry the step started with, so kernel 2 redoing an env that kernel 1 already reset
@@ -1086,7 +1145,62 @@ __device__ __forceinline__ void finalize_env_from(const A& a, SP S, int64_t i, P
             k = S->next_geom ? as_global(S->next_geom)[g] : g;
             as_global(S->geom_of_env)[i] = (int32_t)k;
         }
-        const InitAhead ahead = fetch_init_ahead(S, k, tri);
+        ahead = fetch_init_ahead(S, k, tri);
+    }
+    // Episode record (bcp_bind_episode_record), one wave-uniform test of the launch flags when none is bound.  The state the
+    // env holds after its last step goes to a slot while the initial-state loads above are in flight.
+    int rec_slot = -1;
+    if (a.flags & kStepRecord) {
+        const EpisodeRec& R = a.S->rec;   // (the global block: step_local_kernel's LDS copy ends before the record)
+        double ret_sum = 0.0;             // the episode's return, summed in step order (reward.py:66-69, :144-153)
+        if (R.ret) ret_sum = (redo.on ? redo.ret_before : as_global(R.ret)[i]) + rew;
+        as_global(R.reason)[i] = done ? (uint8_t)((goal ? BCP_DONE_GOAL : 0) | (timeout ? BCP_DONE_TIMEOUT : 0) |
+                                                  (collided ? BCP_DONE_COLLIDED : 0))
+                                      : (uint8_t)0;
+        // one ballot and one atomic per wave hand out the slots (kernel 2's redo keeps the slot kernel 1 gave the env)
+        const bool keeps = redo.on && redo.slot >= 0;
+        const bool take = done && !keeps;
+        const uint64_t takers = __ballot(take);
+        if (takers) {
+            const int first = (int)__ffsll((unsigned long long)takers) - 1;
+            const int lane = lane_id();
+            int base = 0;
+            if (lane == first) base = (int)atomicAdd(R.work, (uint32_t)__popcll(takers));
+            base = bcast_i(base, first);
+            if (take) rec_slot = base + (int)__popcll(takers & ((1ull << lane) - 1ull));
+        }
+        if (keeps) rec_slot = redo.slot;
+        if (done && rec_slot < R.capacity) {   // (beyond: overflow, only counted)
+            const int64_t j = rec_slot, c = R.capacity;
+            as_global(R.env_id)[j] = (int32_t)i;
+            as_global(R.geom)[j] = S->geom_of_env ? (int32_t)g : -1;
+            if (R.ret) as_global(R.final_ret)[j] = ret_sum;
+            as_global(R.fin.x)[j] = r.p.x;
+            as_global(R.fin.y)[j] = r.p.y;
+            as_global(R.fin.angle)[j] = r.p.th;
+            as_global(R.fin.v)[j] = r.v;
+            as_global(R.fin.w)[j] = r.w;
+            if (tri) {
+                as_global(R.fin.steer)[j] = r.steer;
+                as_global(R.fin.wheel)[j] = r.wheel;
+            }
+            as_global(R.fin.min_dist)[j] = min_dist;
+            as_global(R.fin.target_idx)[j] = target;
+            as_global(R.fin.cur_iter)[j] = iter;
+            as_global(R.fin.collided)[j] = (uint8_t)collided;
+            if (pose_delay) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) R.fin.pose_seen[k * c + j] = seen[k];
+            }
+            if (state_delay) {
+#pragma unroll
+                for (int k = 0; k < 7; ++k) R.fin.state_seen[k * c + j] = seen_rs[k];
+            }
+        }
+        if (!done) rec_slot = -1;
+        if (R.ret) as_global(R.ret)[i] = reset ? 0.0 : ret_sum;
+    }
+    if (reset) {
         r.p.x = ahead.x;
         r.p.y = ahead.y;
         r.p.th = ahead.th;
@@ -1134,15 +1248,18 @@ __device__ __forceinline__ void finalize_env_from(const A& a, SP S, int64_t i, P
 #pragma unroll
         for (int c = 0; c < 7; ++c) S->st.state_seen[c * n + i] = seen_rs[c];
     }
+    return rec_slot;
 }
 
 // (the parameter block where the launch arguments point to: the two-launch and the general step kernels)
 template <bool PLAIN, typename A>
-__device__ __forceinline__ void finalize_env(const A& a, int64_t i, Pending& q, bool hit, LdsF64 lds_path = nullptr,
-                                             const PathWindow* free_window = nullptr, bool have_score = false,
-                                             ScoredFree score = ScoredFree(), int known_len = -1, bool score_fits_hit = false)
+__device__ __forceinline__ int finalize_env(const A& a, int64_t i, Pending& q, bool hit, LdsF64 lds_path = nullptr,
+                                            const PathWindow* free_window = nullptr, bool have_score = false,
+                                            ScoredFree score = ScoredFree(), int known_len = -1, bool score_fits_hit = false,
+                                            RecRedo redo = RecRedo{0.0, -1, false})
 {
-    finalize_env_from<PLAIN>(a, a.S, i, q, hit, lds_path, free_window, have_score, score, known_len, score_fits_hit);
+    return finalize_env_from<PLAIN>(a, a.S, i, q, hit, lds_path, free_window, have_score, score, known_len, score_fits_hit, 0,
+                                    redo);
 }
 
 // ---- loads shared by the step kernels ------------------------------------------------------------------------
@@ -1334,6 +1451,8 @@ __global__ void __launch_bounds__(2 * kBlock) step_fast_pair_kernel(const StepAr
     __syncthreads();
 
     bool hit = false;
+    int64_t parked_at = -1;   // the env's parking slot (episode record: kernel 1 leaves the env's record slot there)
+    double park_ret = 0.0;
     if (mover) {
         // (3a) collision: distance-field classification, then parking or in-place settling
         const int64_t g = slot_of(a.S, i, q);
@@ -1379,7 +1498,10 @@ __global__ void __launch_bounds__(2 * kBlock) step_fast_pair_kernel(const StepAr
             q.py = py;
             q.env_lo = (int32_t)(uint32_t)i;
             q.env_hi = (int32_t)(i >> 32);
-            a.S->pending[(int64_t)slot * kShards + shard] = q;  // interleaved: the used slots stay in a few pages
+            parked_at = (int64_t)slot * kShards + shard;
+            a.S->pending[parked_at] = q;  // interleaved: the used slots stay in a few pages
+            // (episode record: kernel 2's redo starts the return from where this step found it)
+            if ((a.flags & kStepRecord) && a.S->rec.ret) park_ret = a.S->rec.ret[i];
         }
     } else if (!ABLATED(a, kAblateNoReward)) {
         // (3b) scorer: ContinuousRewardProvider.reward for the pose as it stands if nothing collides
@@ -1414,7 +1536,14 @@ __global__ void __launch_bounds__(2 * kBlock) step_fast_pair_kernel(const StepAr
         sc.rew = hand_score[lane];
         sc.min_dist = hand_score[kBlock + lane];
         sc.target = (int)hand_score[2 * kBlock + lane];
-        finalize_env<PLAIN>(a, i, q, hit, lds_path, nullptr, !ABLATED(a, kAblateNoReward), sc);
+        const int rec_slot = finalize_env<PLAIN>(a, i, q, hit, lds_path, nullptr, !ABLATED(a, kAblateNoReward), sc);
+        if ((a.flags & kStepRecord) && parked_at >= 0) {
+            RecPark p;
+            p.ret_before = park_ret;
+            p.slot = rec_slot;
+            p.pad = 0;
+            a.S->rec.park[parked_at] = p;
+        }
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) a.tick[1] = a.step_counter;   // for kernel 2 (see StepArgs::tick)
     advance_step_by_ticket(a);   // (only when no kernel 2 follows)
@@ -1430,6 +1559,18 @@ constexpr int kPendingWaves = 4;  // wave = 2 * (row-chunk slot) + (edge slot)
 // aisle config, tens of thousands of undecided poses per step: 0.076 ms parked, 0.086 ms in place, 0.102 ms with the
 // former limit of 8192); the in-place path remains for far denser cases and as BCP_TUNE_DENSE_THRESHOLD.
 constexpr int kParkCapacity = 1 << 20;
+
+// kernel 2's redo of the env in parking slot `at`: with a record, the return and slot kernel 1 left for it
+__device__ __forceinline__ RecRedo redo_of(const StepArgs& a, int64_t at)
+{
+    RecRedo r{0.0, -1, true};
+    if (a.flags & kStepRecord) {
+        const RecPark p = a.S->rec.park[at];
+        r.ret_before = p.ret_before;
+        r.slot = p.slot;
+    }
+    return r;
+}
 
 template <bool WIDE, bool PLAIN>
 __global__ void __launch_bounds__(kBlock * kPendingWaves) step_pending_kernel(const StepArgs launch_args)
@@ -1467,8 +1608,13 @@ __global__ void __launch_bounds__(kBlock * kPendingWaves) step_pending_kernel(co
                                           a.hot.map_wpr);
             if (hit && lane == 0) {
                 Pending q = *e;
-                finalize_env<PLAIN>(a, i, q, true);
+                finalize_env<PLAIN>(a, i, q, true, nullptr, nullptr, false, ScoredFree(), -1, false,
+                                    redo_of(a, (int64_t)idx * kShards + shard));
             }
+        }
+        if (a.flags & kStepRecord) {   // (the last workgroup publishes the step's count of ended envs)
+            __syncthreads();
+            if (threadIdx.x == 0) record_publish(a.S, gridDim.x);
         }
         return;
     }
@@ -1494,8 +1640,13 @@ __global__ void __launch_bounds__(kBlock * kPendingWaves) step_pending_kernel(co
         // kernel 1 already finished this env as "free"; only a collision changes anything
         if (hit && threadIdx.x == 0) {
             Pending q = *e;
-            finalize_env<PLAIN>(a, i, q, true);
+            finalize_env<PLAIN>(a, i, q, true, nullptr, nullptr, false, ScoredFree(), -1, false,
+                                redo_of(a, (int64_t)idx * kShards + shard));
         }
+    }
+    if (a.flags & kStepRecord) {
+        __syncthreads();
+        if (threadIdx.x == 0) record_publish(a.S, gridDim.x);
     }
 }
 
@@ -1540,14 +1691,14 @@ constexpr int kHandDoubles = 8;   // per pair and env: pose [3], score / noise [
 constexpr int kLocalMapWords = 4096;   // a shared lethal bitmap of up to 16 KB is staged in LDS for the exact tests
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-constexpr int kStaticChunks = (int)((sizeof(StepStatic) + 15) / 16);   // *S in 16-byte pieces
+constexpr int kStaticChunks = (int)((offsetof(StepStatic, rec) + 15) / 16);   // *S in 16-byte pieces, up to the record
 
 static size_t local_step_lds_bytes(int n_verts, int lds_path_doubles, int staged_map_words, bool plain = true, int pairs = kLocalPairsMax)
 {
     const int kLocalPairs = pairs, kLocalWaves = 4 * pairs, kLocalEnvs = pairs * kBlock;
     size_t bytes = ((size_t)2 * n_verts + lds_path_doubles + (size_t)kLocalPairs * kHandDoubles * kBlock + 8) * sizeof(double);
     bytes += 2 * kBlock * sizeof(uint32_t);          // bucket index of the shared path
-    bytes += 16 * sizeof(int32_t);                   // parked count, ticket counter, movers parked, -, scans done per pair [4], scan lists ready per pair [4], - [4]
+    bytes += 16 * sizeof(int32_t);                   // parked count, ticket counter, movers parked, movers finished (episode record), scans done per pair [4], scan lists ready per pair [4], - [4]
     bytes = (bytes + 15) & ~(size_t)15;
     bytes += (size_t)kLocalEnvs * sizeof(ParkedPose);
     bytes += (size_t)kLocalWaves * kSparseLdsWords * sizeof(uint32_t);   // a cell list per wave (coop_collides_sparse)
@@ -2325,6 +2476,19 @@ __device__ __forceinline__ void step_local_body(KernArgPtr kernarg, const int rs
             }
             finalize_env_from<PLAIN>(a, SL, i, q, hit_now, lds_path, nullptr, !ABLATED(a, kAblateNoReward), sc, my_len, fits, out_base);
         }
+        // Episode record: the step's count can only be published once every mover has taken its slots, so with a record the
+        // last mover of the workgroup (ctl[3], an LDS count) draws the step's ticket in place of the wave below -- one
+        // global atomic per workgroup, as without a record; the last workgroup moves the counter on and publishes the count.
+        if ((a.flags & kStepRecord) && lane == 0 &&
+            __hip_atomic_fetch_add(&ctl[3], 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP) == kLocalPairs - 1) {
+            __threadfence();
+            unsigned int* ticket = reinterpret_cast<unsigned int*>(a.tick + kTickLocalTicket);
+            if (atomicAdd(ticket, 1u) == gridDim.x - 1) {
+                *ticket = 0u;
+                a.tick[0] = a.tick[0] + 1;   // (every workgroup read the counter before it drew; movers never hold it)
+                record_store_count(a.S->rec);
+            }
+        }
     }
     DIAG_STAMP(13);            // mover: out of tickets
     DIAG_STAMP_W(kWHelper1, 14);       // helper: out of tickets
@@ -2343,7 +2507,7 @@ __device__ __forceinline__ void step_local_body(KernArgPtr kernarg, const int rs
     // ticket's line (the parked-pose count, first form): 14.3 us.  The parked poses are counted in a word per workgroup instead.
     if ((a.flags & kStepAdvances) && tid == (kLocalWaves - 1) * kBlock) {
         if (n_parked) a.parked_slots[blockIdx.x] += (uint64_t)n_parked;   // (this workgroup's word: no atomic; bcp_parked_poses adds them up)
-        if (!ROLL || rs == a.rollout_steps - 1) {
+        if ((!ROLL || rs == a.rollout_steps - 1) && !(a.flags & kStepRecord)) {   // (with a record: the movers draw, above)
             const unsigned int ticket_drawn =
                 __hip_atomic_fetch_add((GlobalPtr<unsigned int>)(a.tick + kTickLocalTicket), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (ticket_drawn == gridDim.x - 1) {

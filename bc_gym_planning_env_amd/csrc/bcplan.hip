@@ -146,6 +146,12 @@ struct bcp_handle {
     int32_t* edt_stale_list;  // owned: [entries] + [1] count, scratch of ensure_fields
     int64_t edt_stale_cap;
     bool edt_lazy;            // a refresh has left stale fields behind since the last full build
+    // episode record (bcp_bind_episode_record): the caller's arrays, and the library's two words of the step's count
+    bool have_rec;
+    EpisodeRec rec;
+    RecPark* rec_park;        // owned: [kShards][pending_cap] (two-launch form with a record)
+    uint32_t* rec_work;       // owned: [3] slots taken in the running step, ticket of the parties that publish the count,
+                              // steps that overflowed the capacity since bcp_episode_record_overflows last looked
 };
 
 // number of entries of a non-shared map / path / initial-state array
@@ -188,11 +194,12 @@ static int check_state(const bcp_state* s, int tricycle, const bcp_params* p = n
 
 // ------------------------------------------------------------------------------------------------ kernels (one-time, operator seams)
 __global__ void reset_kernel(DevState st, DevState init, const uint8_t* __restrict__ mask, int64_t n, int tri,
-                             int32_t* __restrict__ geom_of_env, const int32_t* __restrict__ next_geom)
+                             int32_t* __restrict__ geom_of_env, const int32_t* __restrict__ next_geom, double* __restrict__ ret)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     if (mask && !mask[i]) return;
+    if (ret) ret[i] = 0.0;   // (episode record: a new episode's return)
     int64_t k = i;
     if (geom_of_env) {  // geometry pool: a reset draws the env's next geometry (mini_env.py:469-481)
         k = geom_of_env[i];
@@ -710,28 +717,38 @@ __global__ void world_to_pixel_kernel(const double* __restrict__ xy, int64_t n, 
     out[2 * i + 1] = (int64_t)rint((xy[2 * i + 1] - oy) * inv_res);
 }
 
+// The rows an observation kernel reads: the bound state (n = n_envs, env i on entry geom_of_env[i] or i), or the final
+// states of an episode record (n = capacity, row j on entry `entry[j]`, only rows j < *live).
+struct ObsRows {
+    DevState st;
+    int64_t n;
+    const int32_t* entry;
+    const int32_t* live;
+};
+
 // EgocentricCostmap.observation's goal_n_state (envs/egocentric.py:140-160), one thread per env
-__global__ void goal_n_state_kernel(const StepStatic* __restrict__ S, double wsx, double wsy, int n_state,
+__global__ void goal_n_state_kernel(const StepStatic* __restrict__ S, ObsRows R, double wsx, double wsy, int n_state,
                                     float* __restrict__ out)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= S->n) return;
-    const int64_t g = S->geom_of_env ? (int64_t)S->geom_of_env[i] : i;
+    if (i >= R.n || (R.live && i >= *R.live)) return;
+    const DevState& rs = R.st;
+    const int64_t g = R.entry ? (int64_t)R.entry[i] : (S->geom_of_env ? (int64_t)S->geom_of_env[i] : i);
     const int m = S->path.shared ? S->path.max_len : S->path.lens[g];
     // Observation.path: the way points still ahead, path[target_idx:] (reward.py:59-64) -- or, for the pure-pursuit
     // provider, path[:target_idx + 1] (reward.py:118-123), whose first row is always way point 0
-    const int target = S->P.reward_provider == BCP_REWARD_PURE_PURSUIT ? 0 : S->st.target_idx[i];
+    const int target = S->P.reward_provider == BCP_REWARD_PURE_PURSUIT ? 0 : rs.target_idx[i];
     float* o = out + i * (3 + n_state);
     if (target > m - 1) {   // nothing left of the path: zeros (egocentric.py:142-150)
         for (int k = 0; k < 3 + n_state; ++k) o[k] = 0.0f;
         return;
     }
     const double* wp = S->path.pts + ((S->path.shared ? 0 : g * (int64_t)S->path.max_len) + target) * 5;
-    const int64_t n = S->n;
+    const int64_t n = R.n;
     // Observation.pose / .robot_state are the delayed ones when delays are configured
     const bool dp = S->P.pose_delay > 0, ds = S->P.state_delay > 0;
-    const double x = dp ? S->st.pose_seen[i] : S->st.x[i], y = dp ? S->st.pose_seen[n + i] : S->st.y[i];
-    const double th = dp ? S->st.pose_seen[2 * n + i] : S->st.angle[i];
+    const double x = dp ? rs.pose_seen[i] : rs.x[i], y = dp ? rs.pose_seen[n + i] : rs.y[i];
+    const double th = dp ? rs.pose_seen[2 * n + i] : rs.angle[i];
     // inverse_transform (coordinate_transformations.py:57-84), then project_poses (:310-328)
     const double c = cos(th), s = sin(th);
     const double tx = -x * c - y * s, ty = x * s - y * c, tt = normalize_angle(-th);
@@ -743,24 +760,26 @@ __global__ void goal_n_state_kernel(const StepStatic* __restrict__ S, double wsx
     o[1] = (float)fmin(fmax(ey / wsy, -1.0), 1.0);
     o[2] = (float)eth;
     // robot_state.to_numpy_array(): x, y, angle, v, w (, wheel_angle)
-    o[3] = (float)(ds ? S->st.state_seen[i] : S->st.x[i]);
-    o[4] = (float)(ds ? S->st.state_seen[n + i] : S->st.y[i]);
-    o[5] = (float)(ds ? S->st.state_seen[2 * n + i] : S->st.angle[i]);
-    o[6] = (float)(ds ? S->st.state_seen[3 * n + i] : S->st.v[i]);
-    o[7] = (float)(ds ? S->st.state_seen[4 * n + i] : S->st.w[i]);
-    if (n_state > 5) o[8] = (float)(ds ? S->st.state_seen[6 * n + i] : S->st.wheel[i]);
+    o[3] = (float)(ds ? rs.state_seen[i] : rs.x[i]);
+    o[4] = (float)(ds ? rs.state_seen[n + i] : rs.y[i]);
+    o[5] = (float)(ds ? rs.state_seen[2 * n + i] : rs.angle[i]);
+    o[6] = (float)(ds ? rs.state_seen[3 * n + i] : rs.v[i]);
+    o[7] = (float)(ds ? rs.state_seen[4 * n + i] : rs.w[i]);
+    if (n_state > 5) o[8] = (float)(ds ? rs.state_seen[6 * n + i] : rs.wheel[i]);
 }
 
 // ColoredEgoCostmapRandomAisleTurnEnv's `goal` vector (envs/synth_turn_env.py:412-420), one thread per env: the LAST way
 // point in the robot frame over the window's world size, normalised to unit length, then (v, w, wheel_angle)
-__global__ void goal_direction_state_kernel(const StepStatic* __restrict__ S, double wsx, double wsy, double* __restrict__ out)
+__global__ void goal_direction_state_kernel(const StepStatic* __restrict__ S, ObsRows R, double wsx, double wsy,
+                                            double* __restrict__ out)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= S->n) return;
-    const int64_t g = S->geom_of_env ? (int64_t)S->geom_of_env[i] : i;
+    if (i >= R.n || (R.live && i >= *R.live)) return;
+    const DevState& rs = R.st;
+    const int64_t g = R.entry ? (int64_t)R.entry[i] : (S->geom_of_env ? (int64_t)S->geom_of_env[i] : i);
     const int m = S->path.shared ? S->path.max_len : S->path.lens[g];
     const double* wp = S->path.pts + ((S->path.shared ? 0 : g * (int64_t)S->path.max_len) + (m - 1)) * 5;
-    const double x = S->st.x[i], y = S->st.y[i], th = S->st.angle[i];   // the robot's own pose (not the delayed one)
+    const double x = rs.x[i], y = rs.y[i], th = rs.angle[i];   // the robot's own pose (not the delayed one)
     const double c = cos(th), s = sin(th);
     const double tx = -x * c - y * s, ty = x * s - y * c, tt = normalize_angle(-th);
     const double ct = cos(tt), st = sin(tt);
@@ -769,9 +788,9 @@ __global__ void goal_direction_state_kernel(const StepStatic* __restrict__ S, do
     double* o = out + 5 * i;
     o[0] = gx / norm;
     o[1] = gy / norm;
-    o[2] = S->st.v[i];
-    o[3] = S->st.w[i];
-    o[4] = S->P.model == BCP_MODEL_TRICYCLE ? S->st.wheel[i] : 0.0;
+    o[2] = rs.v[i];
+    o[3] = rs.w[i];
+    o[4] = S->P.model == BCP_MODEL_TRICYCLE ? rs.wheel[i] : 0.0;
 }
 
 
@@ -1131,6 +1150,8 @@ extern "C" int bcp_destroy(bcp_handle* h)
     if (h->edt_stale_list) (void)hipFree(h->edt_stale_list);
     if (h->pending) (void)hipFree(h->pending);
     if (h->tick) (void)hipFree(h->tick);
+    if (h->rec_work) (void)hipFree(h->rec_work);
+    if (h->rec_park) (void)hipFree(h->rec_park);
     if (h->pending_count) (void)hipFree(h->pending_count);
     if (h->adapt) (void)hipFree(h->adapt);
     if (h->dev_static) (void)hipFree(h->dev_static);
@@ -1702,7 +1723,8 @@ extern "C" int bcp_reset_masked(bcp_handle* h, const uint8_t* mask, void* stream
     const int threads = 256;
     const int blocks = (int)((h->n + threads - 1) / threads);
     hipLaunchKernelGGL(reset_kernel, dim3(blocks), dim3(threads), 0, (hipStream_t)stream, h->st, h->init, mask, h->n,
-                       (int)(h->params.model == BCP_MODEL_TRICYCLE), h->geom_of_env, h->next_geom);
+                       (int)(h->params.model == BCP_MODEL_TRICYCLE), h->geom_of_env, h->next_geom,
+                       h->have_rec ? h->rec.ret : nullptr);
     HIP_TRY(hipGetLastError());
     return BCP_OK;
 }
@@ -1756,6 +1778,14 @@ static int upload_step_static(bcp_handle* h, hipStream_t s)
     S.next_geom = h->n_geoms > 0 ? h->next_geom : nullptr;
     S.lds_path_doubles =
         (defer && h->path.shared && h->path.max_len * 5 * sizeof(double) <= 24 * 1024) ? h->path.max_len * 5 : 0;
+    if (h->have_rec) {
+        if (defer && !h->rec_park)   // (the parking slots are sized once, when they are first allocated)
+            HIP_TRY(hipMalloc((void**)&h->rec_park, (size_t)kShards * h->pending_cap * sizeof(RecPark)));
+        h->rec.park = defer ? h->rec_park : nullptr;
+        S.rec = h->rec;
+    } else {
+        memset(&S.rec, 0, sizeof(S.rec));
+    }
     if (!h->dev_static) HIP_TRY(hipMalloc((void**)&h->dev_static, sizeof(StepStatic)));
     // pageable source: the copy is staged before the call returns, so host_static may change afterwards
     HIP_TRY(hipMemcpyAsync(h->dev_static, &S, sizeof(StepStatic), hipMemcpyHostToDevice, s));
@@ -1871,6 +1901,7 @@ static int launch_step(bcp_handle* h, const bcp_step_io* io, uint32_t flags, hip
     a.collided_now = io->collided_now;
     a.err = io->err;
     a.flags = flags;
+    if (h->have_rec) a.flags |= kStepRecord;   // (the kernels look at the record only with this flag)
     // the step counter and the noise seed are read on the device (StepArgs::tick); the kernels resolve these themselves
     a.seed = a.step_counter = 0;
     a.pending_count = a.pending_next = nullptr;
@@ -2048,6 +2079,7 @@ extern "C" int bcp_rollout(bcp_handle* h, const bcp_step_io* io, int32_t n_steps
     int rc = check_step(h, io, flags, "bcp_rollout");
     if (rc != BCP_OK) return rc;
     if (n_steps <= 0) return fail(BCP_E_INVALID, "bcp_rollout: n_steps must be positive");
+    if (h->have_rec) return fail(BCP_E_STATE, "bcp_rollout: an episode record is bound (rows over K steps are not kept)");
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
     if (h->static_dirty) {
@@ -2203,6 +2235,8 @@ extern "C" int bcp_time_step_kernels(bcp_handle* h, const bcp_step_io* io, uint3
     int rc = check_step(h, io, flags, "bcp_time_step_kernels");
     if (rc != BCP_OK) return rc;
     if (steps <= 0 || !kernel_ms) return fail(BCP_E_INVALID, "bcp_time_step_kernels: bad steps / output");
+    if (h->have_rec)   // (its kernel-1-only loop would take record slots that no launch publishes)
+        return fail(BCP_E_STATE, "bcp_time_step_kernels: an episode record is bound");
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
     // full steps first (the state advances), then the same number of kernel-1-only launches on the reached state:
@@ -2462,13 +2496,16 @@ extern "C" int bcp_egocentric_route(bcp_handle* h, int32_t* info4)
     return BCP_OK;
 }
 
-extern "C" int bcp_egocentric_costmaps(bcp_handle* h, const double* poses, int64_t n, const double* window_origin,
-                                       const double* window_size, uint8_t border_value, uint8_t* out, void* stream)
+// rec != nullptr: the final observations of an episode record (bcp_final_egocentric_costmaps) -- image j from final state j
+// on entry rec->geom[j] (private maps without a pool: env rec->env_id[j]), n = capacity, only the first *count drawn
+static int egocentric_costmaps(bcp_handle* h, const double* poses, int64_t n, const double* window_origin,
+                               const double* window_size, uint8_t border_value, uint8_t* out, void* stream,
+                               const EpisodeRec* rec)
 {
     if (!h || !out) return fail(BCP_E_INVALID, "bcp_egocentric_costmaps: null argument");
     if (!h->have_map) return fail(BCP_E_STATE, "bcp_egocentric_costmaps: costmaps not set");
     if (!poses && !h->have_state) return fail(BCP_E_STATE, "bcp_egocentric_costmaps: no poses given and no state bound");
-    if (n <= 0 || (!poses && n != h->n)) return fail(BCP_E_INVALID, "bcp_egocentric_costmaps: n must be n_envs without poses");
+    if (n <= 0 || (!poses && !rec && n != h->n)) return fail(BCP_E_INVALID, "bcp_egocentric_costmaps: n must be n_envs without poses");
     if ((window_origin == nullptr) != (window_size == nullptr))
         return fail(BCP_E_INVALID, "bcp_egocentric_costmaps: window origin and size go together");
     EgoArgs a;
@@ -2498,6 +2535,21 @@ extern "C" int bcp_egocentric_costmaps(bcp_handle* h, const double* poses, int64
         a.sth = h->st.pose_seen + 2 * h->n;
     }
     a.geom_of_env = h->n_geoms > 0 ? h->geom_of_env : nullptr;
+    a.n_envs = h->n;
+    if (rec) {   // the record's rows: its final poses (State.pose: the delayed one with a pose delay), entries, count
+        const int64_t c = rec->capacity;
+        a.sx = rec->fin.x;
+        a.sy = rec->fin.y;
+        a.sth = rec->fin.angle;
+        if (h->params.pose_delay > 0 && rec->fin.pose_seen) {
+            a.sx = rec->fin.pose_seen;
+            a.sy = rec->fin.pose_seen + c;
+            a.sth = rec->fin.pose_seen + 2 * c;
+        }
+        a.geom_of_env = h->n_geoms > 0 ? rec->geom : (h->map.shared ? nullptr : rec->env_id);
+        a.n_envs = c;
+        a.live = rec->count;
+    }
     a.has_window = window_origin != nullptr;
     if (window_origin) {
         a.win_ox = window_origin[0];
@@ -2507,7 +2559,6 @@ extern "C" int bcp_egocentric_costmaps(bcp_handle* h, const double* poses, int64
     const size_t row_bytes = ((size_t)a.drows * 2 + kEgoBoundInts) * sizeof(int32_t);   // one table: row terms, row bounds
     a.border = border_value;
     a.out = out;
-    a.n_envs = h->n;
     a.n_images = n;
     a.cols_magic = (uint32_t)(((uint64_t)1 << 32) / (uint64_t)a.cols) + 1;   // (staged maps are < 64 KB: exact)
     if (a.dcols < 4) return fail(BCP_E_INVALID, "bcp_egocentric_costmaps: windows narrower than 4 px are not supported");
@@ -2623,9 +2674,10 @@ extern "C" int bcp_egocentric_costmaps(bcp_handle* h, const double* poses, int64
         int32_t* order = h->ego_order + h->ego_order_cap;
         HIP_TRY(hipMemsetAsync(bin_count, 0, (size_t)n_bins * sizeof(int32_t), st));
         const dim3 per_image((unsigned)((n + 255) / 256));
-        hipLaunchKernelGGL(ego_bin_count_kernel, per_image, block, 0, st, a.geom_of_env, a.n_envs, n, bin_count, rank);
+        hipLaunchKernelGGL(ego_bin_count_kernel, per_image, block, 0, st, a.geom_of_env, a.n_envs, n, bin_count, rank, a.live);
         hipLaunchKernelGGL(ego_bin_scan_kernel, dim3(1), dim3(1024), 0, st, bin_count, n_bins, bin_start);
-        hipLaunchKernelGGL(ego_bin_scatter_kernel, per_image, block, 0, st, a.geom_of_env, a.n_envs, n, bin_start, rank, order);
+        hipLaunchKernelGGL(ego_bin_scatter_kernel, per_image, block, 0, st, a.geom_of_env, a.n_envs, n, bin_start, rank, order,
+                           a.live);
         const size_t lds = map_bytes + 4 * row_bytes;
         const void* fn = px8 ? (const void*)ego_costmap_binned_kernel<8> : (const void*)ego_costmap_binned_kernel<4>;
         if (lds > 64 * 1024)
@@ -2682,10 +2734,28 @@ extern "C" int bcp_egocentric_costmaps(bcp_handle* h, const double* poses, int64
     return BCP_OK;
 }
 
-extern "C" int bcp_goal_n_state(bcp_handle* h, const double* world_size, float* out, void* stream)
+// the bound state's rows, or (rec) the record's final states
+static ObsRows obs_rows(const bcp_handle* h, const EpisodeRec* rec)
 {
-    if (!h || !world_size || !out) return fail(BCP_E_INVALID, "bcp_goal_n_state: null argument");
-    if (!h->have_path || !h->have_state) return fail(BCP_E_STATE, "bcp_goal_n_state: paths and state must be set first");
+    ObsRows R;
+    if (rec) {
+        R.st = rec->fin;
+        R.n = rec->capacity;
+        R.entry = h->n_geoms > 0 ? rec->geom : rec->env_id;
+        R.live = rec->count;
+    } else {
+        R.st = h->st;
+        R.n = h->n;
+        R.entry = nullptr;
+        R.live = nullptr;
+    }
+    return R;
+}
+
+static int goal_n_state(bcp_handle* h, const double* world_size, float* out, void* stream, const EpisodeRec* rec, const char* who)
+{
+    if (!h || !world_size || !out) return fail(BCP_E_INVALID, "%s: null argument", who);
+    if (!h->have_path || !h->have_state) return fail(BCP_E_STATE, "%s: paths and state must be set first", who);
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
     if (h->static_dirty) {
@@ -2693,27 +2763,128 @@ extern "C" int bcp_goal_n_state(bcp_handle* h, const double* world_size, float* 
         if (rc != BCP_OK) return rc;
     }
     const int n_state = h->params.model == BCP_MODEL_TRICYCLE ? 6 : 5;
-    hipLaunchKernelGGL(goal_n_state_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, s, h->dev_static,
+    const ObsRows R = obs_rows(h, rec);
+    hipLaunchKernelGGL(goal_n_state_kernel, dim3((unsigned)((R.n + 255) / 256)), dim3(256), 0, s, h->dev_static, R,
                        world_size[0], world_size[1], n_state, out);
     HIP_TRY(hipGetLastError());
     return BCP_OK;
 }
 
-extern "C" int bcp_goal_direction_state(bcp_handle* h, const double* world_size, double* out, void* stream)
+static int goal_direction_state(bcp_handle* h, const double* world_size, double* out, void* stream, const EpisodeRec* rec,
+                                const char* who)
 {
-    if (!h || !world_size || !out) return fail(BCP_E_INVALID, "bcp_goal_direction_state: null argument");
-    if (!h->have_path || !h->have_state)
-        return fail(BCP_E_STATE, "bcp_goal_direction_state: paths and state must be set first");
+    if (!h || !world_size || !out) return fail(BCP_E_INVALID, "%s: null argument", who);
+    if (!h->have_path || !h->have_state) return fail(BCP_E_STATE, "%s: paths and state must be set first", who);
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
     if (h->static_dirty) {
         const int rc = upload_step_static(h, s);
         if (rc != BCP_OK) return rc;
     }
-    hipLaunchKernelGGL(goal_direction_state_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, s, h->dev_static,
+    const ObsRows R = obs_rows(h, rec);
+    hipLaunchKernelGGL(goal_direction_state_kernel, dim3((unsigned)((R.n + 255) / 256)), dim3(256), 0, s, h->dev_static, R,
                        world_size[0], world_size[1], out);
     HIP_TRY(hipGetLastError());
     return BCP_OK;
+}
+
+extern "C" int bcp_egocentric_costmaps(bcp_handle* h, const double* poses, int64_t n, const double* window_origin,
+                                       const double* window_size, uint8_t border_value, uint8_t* out, void* stream)
+{
+    return egocentric_costmaps(h, poses, n, window_origin, window_size, border_value, out, stream, nullptr);
+}
+
+extern "C" int bcp_goal_n_state(bcp_handle* h, const double* world_size, float* out, void* stream)
+{
+    return goal_n_state(h, world_size, out, stream, nullptr, "bcp_goal_n_state");
+}
+
+extern "C" int bcp_goal_direction_state(bcp_handle* h, const double* world_size, double* out, void* stream)
+{
+    return goal_direction_state(h, world_size, out, stream, nullptr, "bcp_goal_direction_state");
+}
+
+// ---- episode ends under auto-reset (bcp_episode_record) ----------------------------------------------------------
+extern "C" int bcp_bind_episode_record(bcp_handle* h, const bcp_episode_record* rec)
+{
+    if (!h) return fail(BCP_E_INVALID, "bcp_bind_episode_record: null handle");
+    HIP_TRY(hipSetDevice(h->device));
+    if (!rec) {
+        h->have_rec = false;
+        memset(&h->rec, 0, sizeof(h->rec));
+        h->static_dirty = true;
+        return BCP_OK;
+    }
+    const bcp_params& p = h->params;
+    const bcp_state& f = rec->final;
+    if (rec->capacity <= 0 || rec->capacity > ((int64_t)1 << 31) - 1)
+        return fail(BCP_E_INVALID, "bcp_bind_episode_record: capacity must be in [1, 2^31)");
+    if (!rec->reason || !rec->count || !rec->env_id || !rec->geom || (rec->ret && !rec->final_ret))
+        return fail(BCP_E_INVALID, "bcp_bind_episode_record: reason, count, env_id, geom (and final_ret with ret) are required");
+    if (!f.x || !f.y || !f.angle || !f.v || !f.w || !f.min_spat_dist_so_far || !f.target_idx || !f.current_iter ||
+        !f.robot_collided || (p.model == BCP_MODEL_TRICYCLE && (!f.steering_motor_command || !f.wheel_angle)))
+        return fail(BCP_E_INVALID, "bcp_bind_episode_record: missing final-state array");
+    if ((p.pose_delay > 0 && !f.pose_seen) || (p.state_delay > 0 && !f.robot_state_seen))
+        return fail(BCP_E_INVALID, "bcp_bind_episode_record: delays > 0 need the final pose_seen / robot_state_seen");
+    if (f.control_queue || f.poses_queue || f.robot_state_queue)
+        return fail(BCP_E_INVALID, "bcp_bind_episode_record: the final state keeps no queues (their pointers must be NULL)");
+    if (!h->rec_work) {
+        HIP_TRY(hipMalloc((void**)&h->rec_work, 3 * sizeof(uint32_t)));
+    }
+    // (no stream to order this on: every step still in flight on any stream finishes first)
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemset(h->rec_work, 0, 3 * sizeof(uint32_t)));
+    EpisodeRec& R = h->rec;
+    R.reason = rec->reason;
+    R.ret = rec->ret;
+    R.count = rec->count;
+    R.env_id = rec->env_id;
+    R.geom = rec->geom;
+    R.final_ret = rec->final_ret;
+    R.fin = to_dev_state(&f);
+    R.fin.pose_seen = p.pose_delay > 0 ? f.pose_seen : nullptr;
+    R.fin.state_seen = p.state_delay > 0 ? f.robot_state_seen : nullptr;
+    R.capacity = rec->capacity;
+    R.work = h->rec_work;
+    h->have_rec = true;
+    h->static_dirty = true;
+    return BCP_OK;
+}
+
+extern "C" int bcp_episode_record_overflows(bcp_handle* h, int64_t* steps, void* stream)
+{
+    if (!h || !steps) return fail(BCP_E_INVALID, "bcp_episode_record_overflows: null argument");
+    *steps = 0;
+    if (!h->rec_work) return BCP_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    uint32_t v = 0;
+    HIP_TRY(hipMemcpyAsync(&v, h->rec_work + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIP_TRY(hipMemsetAsync(h->rec_work + 2, 0, sizeof(uint32_t), (hipStream_t)stream));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    *steps = (int64_t)v;
+    return BCP_OK;
+}
+
+extern "C" int bcp_final_egocentric_costmaps(bcp_handle* h, const double* window_origin, const double* window_size,
+                                             int32_t border_value, uint8_t* out, void* stream)
+{
+    if (!h) return fail(BCP_E_INVALID, "bcp_final_egocentric_costmaps: null handle");
+    if (!h->have_rec) return fail(BCP_E_STATE, "bcp_final_egocentric_costmaps: no episode record bound");
+    if (border_value < 0 || border_value > 255) return fail(BCP_E_INVALID, "bcp_final_egocentric_costmaps: border value");
+    return egocentric_costmaps(h, nullptr, h->rec.capacity, window_origin, window_size, (uint8_t)border_value, out, stream,
+                               &h->rec);
+}
+
+extern "C" int bcp_final_goal_n_state(bcp_handle* h, const double* world_size, float* out, void* stream)
+{
+    if (h && !h->have_rec) return fail(BCP_E_STATE, "bcp_final_goal_n_state: no episode record bound");
+    return goal_n_state(h, world_size, out, stream, h ? &h->rec : nullptr, "bcp_final_goal_n_state");
+}
+
+extern "C" int bcp_final_goal_direction_state(bcp_handle* h, const double* world_size, double* out, void* stream)
+{
+    if (h && !h->have_rec) return fail(BCP_E_STATE, "bcp_final_goal_direction_state: no episode record bound");
+    return goal_direction_state(h, world_size, out, stream, h ? &h->rec : nullptr, "bcp_final_goal_direction_state");
 }
 
 // ---- RandomMiniEnv worlds sampled on the device ----------------------------------------------------------------

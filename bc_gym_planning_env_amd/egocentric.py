@@ -20,9 +20,13 @@ def _f64x2(v):
 class BatchedEgocentricCostmap(object):
     """Observation wrapper around a BatchedPlanEnv (or BatchedRandomMiniEnv): step() / reset() return
     OrderedDict(env=uint8 [N, H, W, 1], goal_n_state=float32 [N, 9, 1]) device tensors (8 rows for a diff-drive robot).
-    The window defaults are the reference's: 0.5 m behind to 3 m ahead of the robot, 2 m to each side."""
+    The window defaults are the reference's: 0.5 m behind to 3 m ahead of the robot, 2 m to each side.
+    final_observation=True: the env's episode record is enabled (env.enable_episode_record) and step() adds
+    info["final_observation"], the observation of every episode that ended in the step, drawn from its final state
+    before the auto-reset (SB3's terminal_observation, gymnasium's final_obs): the same keys with leading dimension
+    `capacity`, row j belongs to env info["episode_ends"].env_ids[j] for j < count."""
 
-    def __init__(self, env, x_bounds=(-0.5, 3.), y_bounds=(-2., 2.), border_value=0):
+    def __init__(self, env, x_bounds=(-0.5, 3.), y_bounds=(-2., 2.), border_value=0, final_observation=False):
         self.env = env
         self.action_space = env.action_space
         self._origin = _f64x2([x_bounds[0], y_bounds[0]])
@@ -41,6 +45,10 @@ class BatchedEgocentricCostmap(object):
         self.images = torch.zeros((n,) + self.image_shape + (1,), dtype=torch.uint8, device=dev)
         self.goal_n_state = torch.zeros((n, 3 + self.n_state, 1), dtype=torch.float32, device=dev)
         self._obs = OrderedDict((('env', self.images), ('goal_n_state', self.goal_n_state)))
+        self._final = None
+        if final_observation:
+            ends = env.episode_ends if env.episode_ends is not None else env.enable_episode_record()
+            self._alloc_final(ends.capacity)
 
     def unwrapped(self):
         return self.env
@@ -71,8 +79,43 @@ class BatchedEgocentricCostmap(object):
         return {"kernel": _lib.EGO_KERNELS.get(int(info[0]), "?"), "max_cells": int(info[1]), "list_stride": int(info[2]),
                 "limit": int(info[3])}
 
+    # the final observation's keys and vector, [capacity] rows (BatchedColoredEgoCostmap has its own)
+    _FINAL_KEYS = ('env', 'goal_n_state')
+
+    def _final_vector(self, cap):
+        return torch.zeros((cap, 3 + self.n_state, 1), dtype=torch.float32, device=self.env.device)
+
+    def _alloc_final(self, cap):
+        self.final_images = torch.zeros((cap,) + self.image_shape + (1,), dtype=torch.uint8, device=self.env.device)
+        self.final_vector = self._final_vector(cap)
+        self._final = OrderedDict(zip(self._FINAL_KEYS, (self.final_images, self.final_vector)))
+
+    def _final_buffers(self):
+        """The buffers follow the env's record: a record bound again with another capacity gets buffers of that size."""
+        ends = self.env.episode_ends
+        if ends is None:
+            raise RuntimeError("final_observation=True needs the env's episode record (env.disable_episode_record() "
+                               "was called)")
+        if self.final_images.shape[0] != ends.capacity:
+            self._alloc_final(ends.capacity)
+        return self._final
+
+    def _final_observation(self, stream):
+        """The final observations of the record's slots (bcp_final_egocentric_costmaps / bcp_final_goal_n_state)."""
+        e = self.env
+        _lib.check(self._lib.bcp_final_egocentric_costmaps(
+            e._h, self._origin.ctypes.data_as(_lib._f64p), self._size.ctypes.data_as(_lib._f64p), self._border,
+            self.final_images.data_ptr(), stream))
+        _lib.check(self._lib.bcp_final_goal_n_state(e._h, self._world.ctypes.data_as(_lib._f64p),
+                                                    self.final_vector.data_ptr(), stream))
+
     def step(self, actions, **kw):
         _o, reward, done, info = self.env.step(actions, **kw)
+        if self._final is not None:
+            # drawn now, on the step's stream: a pool refresh after this step may release the worlds the envs just left
+            final = self._final_buffers()
+            self._final_observation(C.c_void_p(torch.cuda.current_stream(self.env.device).cuda_stream))
+            info = dict(info, final_observation=final)   # (a copy: the env's own info dict stays as the env keeps it)
         return self.observation(), reward, done, info
 
     def reset(self, mask=None):
@@ -100,10 +143,23 @@ class BatchedColoredEgoCostmap(BatchedEgocentricCostmap):
     OrderedDict(environment=uint8 [N, 133, 133, 1], goal=float64 [N, 5, 1]) -- the egocentric costmap 0.5 m behind to
     3.5 m ahead of the robot, and (unit direction to the final way point, v, w, wheel_angle)."""
 
-    def __init__(self, env, x_bounds=(-0.5, 3.5), y_bounds=(-2., 2.), border_value=0):
-        super(BatchedColoredEgoCostmap, self).__init__(env, x_bounds, y_bounds, border_value)
+    def __init__(self, env, x_bounds=(-0.5, 3.5), y_bounds=(-2., 2.), border_value=0, final_observation=False):
+        super(BatchedColoredEgoCostmap, self).__init__(env, x_bounds, y_bounds, border_value, final_observation)
         self.goal = torch.zeros((env.n_envs, 5, 1), dtype=torch.float64, device=env.device)
         self._obs = OrderedDict((('environment', self.images), ('goal', self.goal)))
+
+    _FINAL_KEYS = ('environment', 'goal')
+
+    def _final_vector(self, cap):
+        return torch.zeros((cap, 5, 1), dtype=torch.float64, device=self.env.device)
+
+    def _final_observation(self, stream):
+        e = self.env
+        _lib.check(self._lib.bcp_final_egocentric_costmaps(
+            e._h, self._origin.ctypes.data_as(_lib._f64p), self._size.ctypes.data_as(_lib._f64p), self._border,
+            self.final_images.data_ptr(), stream))
+        _lib.check(self._lib.bcp_final_goal_direction_state(e._h, self._world.ctypes.data_as(_lib._f64p),
+                                                            self.final_vector.data_ptr(), stream))
 
     def observation(self, _observation=None):
         stream = self._refresh_images()

@@ -489,6 +489,51 @@ int bcp_render_aisle_worlds(bcp_handle *h, const double *worlds, const int32_t *
 int bcp_aisle_world_paths(bcp_handle *h, const double *worlds, int64_t n_worlds, double path_delta, int32_t max_len,
                           double *paths, int32_t *lens, double *init, int32_t *status, void *stream);
 
+/* ---- episode ends under auto-reset ---------------------------------------------------------------------- */
+/* Why an env's episode ended: the three terms of PlanEnv's done (envs/base/env.py:400-419 -- goal reached, current_iter >=
+ * iteration_timeout, robot_collided); several may be set at once.  A time-out alone is a truncation (the episode was cut,
+ * its last state is not terminal: a learner bootstraps V(s_T) there); goal and collision are terminal. */
+enum { BCP_DONE_GOAL = 1, BCP_DONE_TIMEOUT = 2, BCP_DONE_COLLIDED = 4 };
+
+/* Where the step leaves every env whose episode ends (done = 1), before BCP_STEP_AUTO_RESET restores its initial state:
+ * what the reference's caller sees from step() before it calls reset() (env.py:334-361, 293-303).  Host struct of device
+ * pointers, caller-owned; N = n_envs. */
+typedef struct bcp_episode_record {
+    int64_t capacity;      /* slots in the [capacity] arrays */
+    uint8_t *reason;       /* [N] BCP_DONE_* bits of the last step, 0 where done = 0 (written for every env) */
+    double *ret;           /* [N] running float64 sum of this episode's rewards in step order (the rewards of
+                              reward.py:66-69 / :144-153), or NULL = not kept.  Zeroed by every reset (auto-reset,
+                              bcp_reset_masked); bcp_broadcast_state and writes of the state arrays leave it alone */
+    int32_t *count;        /* [1] envs that ended in the last step (may exceed capacity: overflow) */
+    int32_t *env_id;       /* [capacity] which env ended, one slot per ended env, order unspecified */
+    int32_t *geom;         /* [capacity] pool entry the episode ran on (-1 without a geometry pool) */
+    double *final_ret;     /* [capacity] the episode's return (needs ret) */
+    bcp_state final;       /* [capacity] each: the State the env held after its last step, BEFORE the reset -- x ..
+                              robot_collided (current_iter = episode length); pose_seen [3][capacity] / robot_state_seen
+                              [7][capacity] when pose_delay / state_delay > 0; the queue pointers must be NULL */
+} bcp_episode_record;
+
+/* Binds (rec != NULL) or unbinds (NULL) the episode record.  From then on every step -- every step form, with and without
+ * BCP_STEP_AUTO_RESET -- gives each env with done = 1 exactly one slot (without auto-reset an env that is not reset ends
+ * again on every step, as the reference's done stays true), and its final state is bit for bit the state a handle without
+ * auto-reset holds after the same step.  *count is published on the device by the step itself: no host synchronisation,
+ * no extra launch, the same launch arguments from step to step (captured steps replay).  Without a record the step kernels
+ * do not look at one.  bcp_rollout refuses to run with a record bound (BCP_E_STATE).  Binding synchronises the device (it
+ * re-arms the library's counters, which steps still in flight on any stream may be using) and does not touch `ret`: the
+ * caller zeroes it, and a record bound in the middle of episodes returns partial sums for them. */
+int bcp_bind_episode_record(bcp_handle *h, const bcp_episode_record *rec /*host struct of device pointers; NULL = unbind*/);
+/* Steps whose count exceeded the capacity since the last call (or the bind): *steps, host pointer; synchronises `stream`.
+ * Slots beyond the capacity are counted but not written. */
+int bcp_episode_record_overflows(bcp_handle *h, int64_t *steps /*host*/, void *stream);
+/* The observations of the episodes that ended in the last step (SB3's terminal_observation, gymnasium's final_obs), drawn
+ * from the record on the device: slot j < min(*count, capacity) from final state j on pool entry geom[j] (private maps
+ * without a pool: env_id[j]); slots beyond are left untouched.  No host synchronisation.  Same outputs as
+ * bcp_egocentric_costmaps / bcp_goal_n_state / bcp_goal_direction_state with [capacity] rows. */
+int bcp_final_egocentric_costmaps(bcp_handle *h, const double *window_origin /*host*/, const double *window_size /*host*/,
+                                  int32_t border_value, uint8_t *out /*[capacity][H][W]*/, void *stream);
+int bcp_final_goal_n_state(bcp_handle *h, const double *world_size /*host*/, float *out, void *stream);
+int bcp_final_goal_direction_state(bcp_handle *h, const double *world_size /*host*/, double *out, void *stream);
+
 /* ---- measurement -------------------------------------------------------------------------------------- */
 /* Which kernels a bcp_step() of this handle launches, as configured now: 0 = step_kernel alone (no distance field, or a
  * forced mode), 1 = step_fast_pair_kernel alone (every undecided pose settled in place), 2 = step_fast_pair_kernel +
