@@ -11,6 +11,7 @@ MAX_VERTS = 32
 MODEL_TRICYCLE, MODEL_DIFFDRIVE = 0, 1
 REWARD_CONTINUOUS, REWARD_PURE_PURSUIT = 0, 1
 STEP_AUTO_RESET, STEP_ACTIONS_F32 = 1, 2
+LOOKAHEAD_PER_ENV = 1 << 8
 ERR_ANGLE_JUMP, ERR_TIME_ORDER, ERR_INTERNAL = 1, 2, 4
 DONE_GOAL, DONE_TIMEOUT, DONE_COLLIDED = 1, 2, 4
 TUNE_EXACT_MODE, TUNE_DENSE_THRESHOLD, TUNE_CULL, TUNE_DEFER, TUNE_EDT_LDS, TUNE_FUSED, TUNE_EGO_SPARSE, TUNE_NEAR_DILATE = 0, 1, 2, 3, 4, 5, 6, 7
@@ -78,6 +79,15 @@ class BcpEpisodeRecord(C.Structure):
     ]
 
 
+class BcpLookaheadIO(C.Structure):
+    _fields_ = [
+        ("actions", C.c_void_p), ("noise_z", C.c_void_p), ("mask", C.c_void_p),
+        ("horizon", C.c_int32), ("n_candidates", C.c_int32),
+        ("ret", C.c_void_p), ("steps", C.c_void_p), ("reason", C.c_void_p), ("final_pose", C.c_void_p),
+        ("final_target_idx", C.c_void_p), ("err", C.c_void_p), ("best", C.c_void_p), ("best_action", C.c_void_p),
+    ]
+
+
 # every symbol include/bcplan.h declares: (restype, argtypes)
 _H = C.c_void_p
 SYMBOLS = {
@@ -97,6 +107,7 @@ SYMBOLS = {
     "bcp_broadcast_state": (C.c_int, [_H, C.c_int64, C.c_void_p, C.c_void_p]),
     "bcp_step": (C.c_int, [_H, C.POINTER(BcpStepIO), C.c_uint32, C.c_void_p]),
     "bcp_rollout": (C.c_int, [_H, C.POINTER(BcpStepIO), C.c_int32, C.c_uint32, C.c_void_p]),
+    "bcp_lookahead": (C.c_int, [_H, C.POINTER(BcpLookaheadIO), C.c_uint32, C.c_void_p]),
     "bcp_expired_waits": (C.c_int, [_H, C.POINTER(C.c_int64), C.c_void_p]),
     "bcp_parked_poses": (C.c_int, [_H, C.POINTER(C.c_int64), C.c_void_p]),
     "bcp_side_stream": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_void_p)]),

@@ -376,6 +376,30 @@ class EpisodeEnds(object):
         return out
 
 
+class Lookahead(object):
+    """What BatchedPlanEnv.lookahead() returns: device tensors over [N, K] candidates (no sync).  `ret` float64 return of
+    the steps taken, `steps` int32, `reason` uint8 DONE_* bits (0: not done within the horizon); optional, None unless
+    asked for: `final_pose` [N, K, 3], `final_target_idx`, `err`, `best` int32 [N], `best_action` [N, 2].  The tensors
+    are the env's cached buffers for this (H, K): the next lookahead() with the same shape overwrites them."""
+
+    FIELDS = ("ret", "steps", "reason", "final_pose", "final_target_idx", "err", "best", "best_action")
+
+    def __init__(self, horizon, n_candidates, **tensors):
+        self.horizon, self.n_candidates = horizon, n_candidates
+        for name in self.FIELDS:
+            setattr(self, name, tensors.get(name))
+
+    def collided(self):
+        """bool [N, K]: the candidate ends in a collision"""
+        return (self.reason & _lib.DONE_COLLIDED) != 0
+
+    def timed_out(self):
+        return (self.reason & _lib.DONE_TIMEOUT) != 0
+
+    def reached_goal(self):
+        return (self.reason & _lib.DONE_GOAL) != 0
+
+
 class BatchedPlanEnv(object):
     """N planning envs on one MI355X.
 
@@ -895,6 +919,70 @@ class BatchedPlanEnv(object):
             self.err.copy_(err_out[-1])
         self._last_inputs = tuple(keep)
         return reward, done
+
+    def lookahead(self, actions, noise_z=None, mask=None, want=("final_pose", "best")):
+        """Score K candidate action sequences for every env over the next H steps WITHOUT stepping it (bcp_lookahead):
+        nothing of the env changes -- state, pool entries, noise stream, episode record.  actions: [H, K, 2] = one
+        candidate library shared by all envs, or [H, N, K, 2] = candidates per env; float32 or float64.  noise_z: None =
+        the noise-free forward model (whatever the env's noise setting), or [H, N, K, 3] standard normals.  mask:
+        optional [N]; rows of envs with mask 0 keep what the cached buffers held.  want: optional outputs to compute, from
+        "final_pose", "final_target_idx", "err", "best", "best_action" ("best_action" implies "best").  Each candidate
+        stops after its first done step (no auto-reset).  Returns a Lookahead of device tensors, no sync; the buffers are
+        cached per (H, K), so a planner that calls this every tick allocates nothing.  Delays > 0 are refused."""
+        if not isinstance(actions, torch.Tensor):
+            actions = torch.from_numpy(np.ascontiguousarray(actions))
+        if actions.dtype not in (torch.float32, torch.float64):
+            actions = actions.to(torch.float64)
+        actions = actions.to(self.device).contiguous()
+        n = self.n_envs
+        if actions.dim() == 3 and actions.shape[2] == 2:
+            flags = 0
+        elif actions.dim() == 4 and actions.shape[1] == n and actions.shape[3] == 2:
+            flags = _lib.LOOKAHEAD_PER_ENV
+        else:
+            raise ValueError("actions must have shape (H, K, 2) or (H, %d, K, 2), got %s" % (n, tuple(actions.shape)))
+        h, k = int(actions.shape[0]), int(actions.shape[-2])
+        if actions.dtype == torch.float32:
+            flags |= _lib.STEP_ACTIONS_F32
+        want = set(want)
+        unknown = want - set(Lookahead.FIELDS[3:])
+        if unknown:
+            raise ValueError("lookahead: unknown outputs %s" % sorted(unknown))
+        if "best_action" in want:
+            want.add("best")
+        cache = self.__dict__.setdefault("_lookahead_buffers", {})
+        buf = cache.setdefault((h, k), {})
+        shapes = {"ret": ((n, k), torch.float64), "steps": ((n, k), torch.int32), "reason": ((n, k), torch.uint8),
+                  "final_pose": ((n, k, 3), torch.float64), "final_target_idx": ((n, k), torch.int32),
+                  "err": ((n, k), torch.int32), "best": ((n,), torch.int32), "best_action": ((n, 2), actions.dtype)}
+        io = _lib.BcpLookaheadIO()
+        io.actions, io.horizon, io.n_candidates = actions.data_ptr(), h, k
+        keep = [actions]
+        if noise_z is not None:
+            z = noise_z if isinstance(noise_z, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(noise_z))
+            z = z.to(self.device, torch.float64).contiguous()
+            assert tuple(z.shape) == (h, n, k, 3)
+            io.noise_z = z.data_ptr()
+            keep.append(z)
+        if mask is not None:
+            mask = mask if isinstance(mask, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(mask))
+            mask = mask.to(self.device).to(torch.uint8).contiguous()
+            assert tuple(mask.shape) == (n,)
+            io.mask = mask.data_ptr()
+            keep.append(mask)
+        out = {}
+        for name in Lookahead.FIELDS:
+            if name not in want and name not in Lookahead.FIELDS[:3]:
+                continue
+            shape, dtype = shapes[name]
+            key = (name, dtype)
+            if key not in buf:
+                buf[key] = torch.zeros(shape, dtype=dtype, device=self.device)
+            out[name] = buf[key]
+            setattr(io, name, buf[key].data_ptr())
+        _lib.check(self._lib.bcp_lookahead(self._h, C.byref(io), flags, self._stream()))
+        self._last_lookahead_inputs = tuple(keep)   # alive until the stream has consumed them
+        return Lookahead(h, k, **out)
 
     def enable_episode_record(self, capacity=None):
         """Keep what every episode end leaves behind (bcp_bind_episode_record): from now on step() returns

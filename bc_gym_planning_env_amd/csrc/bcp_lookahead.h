@@ -1,0 +1,207 @@
+// bcp_lookahead.h -- bcp_lookahead(): K candidate action sequences per env, each stepped up to H times on a private copy of
+// the env's state that lives in registers.  Nothing of the handle is written; the only global stores are the outputs.
+// Included by bcplan.hip after bcp_step.h, whose device functions (robot model, collides_wave, reward providers) it is
+// built from -- none of the step kernels' hand-off machinery (tickets, parking, alternating counters) is involved.
+#pragma once
+
+#include "bcp_step.h"
+
+// Launch arguments: the handle's parameter block and the caller's pointers (bcp_lookahead_io), nothing that changes from
+// call to call -- a captured call replays.
+struct LookaheadArgs {
+    const StepStatic* S;
+    const void* actions;       // [H][K][2] or [H][N][K][2]
+    const double* noise_z;     // nullptr or [H][N][K][3]
+    const uint8_t* mask;       // nullptr or [N]
+    double* ret;               // [N][K]
+    int32_t* steps;
+    uint8_t* reason;
+    double* final_pose;        // optional [N][K][3]
+    int32_t* final_target;     // optional
+    int32_t* err;              // optional
+    int32_t* best;             // optional [N]
+    void* best_action;         // optional [N][2]
+    int64_t n, total;          // N, N * K
+    int32_t horizon, k;
+    uint32_t flags;            // BCP_STEP_ACTIONS_F32 | BCP_LOOKAHEAD_PER_ENV
+};
+
+// step t of candidate k of env i, float32 or float64, widened like load_env does
+__device__ __forceinline__ void lookahead_action(const LookaheadArgs& a, int64_t row, double& cmd0, double& cmd1)
+{
+    if (a.flags & BCP_STEP_ACTIONS_F32) {
+        const GlobalPtr<const float> p = as_global(reinterpret_cast<const float*>(a.actions)) + 2 * row;
+        cmd0 = (double)p[0];
+        cmd1 = (double)p[1];
+    } else {
+        const GlobalPtr<const double> p = as_global(reinterpret_cast<const double*>(a.actions)) + 2 * row;
+        cmd0 = p[0];
+        cmd1 = p[1];
+    }
+}
+
+// One lane per (env, candidate), candidates of an env adjacent: lane c of the grid holds candidate c % K of env c / K, so
+// with K >= 64 a wave is 64 candidates of ONE env (its state is one broadcast load; map tiles, path window and footprint
+// are the same lines for the whole wave) and with K < 64 a wave holds 64 / K envs.  One wavefront per workgroup, like
+// step_kernel: collides_wave settles ambiguous poses with the whole wave and owns the workgroup's dynamic LDS.
+// PLAIN: continuous reward provider and the noise-free forward model (no noise_z) -- the pure-pursuit branch and
+// kinematic_step_noise are compiled out.
+// A step is PlanEnv.step without the stores: robot, collision, roll-back (env.py:458-459), iter + 1, reward (:352), done
+// (:407-419) -- the order and the laws of finalize_env_from, minus delay queues (refused by the host), reset and record.
+template <bool PLAIN>
+__global__ void __launch_bounds__(kBlock) lookahead_kernel(const LookaheadArgs a)
+{
+    const StepStatic* S = a.S;
+    const DevParams& P = S->P;
+    const int tid = threadIdx.x;
+    const int64_t gc = (int64_t)blockIdx.x * kBlock + tid;
+    const bool in_range = gc < a.total;
+    const int64_t c = in_range ? gc : a.total - 1;   // lanes past N * K shadow the last candidate and never store
+    const int64_t i = c / a.k;
+    const int k = (int)(c - i * a.k);
+    const bool live = in_range && (!a.mask || as_global(a.mask)[i] != 0);
+
+    const CollisionLds L = collision_lds_setup(P, S->map, tid);
+
+    // ---- the env's state, once (lanes of one env read the same addresses)
+    const bool tri = P.model == BCP_MODEL_TRICYCLE;
+    const bool pure_pursuit = !PLAIN && P.reward_provider == BCP_REWARD_PURE_PURSUIT;
+    const bool noisy_model = !PLAIN && a.noise_z != nullptr;
+    const bool per_env = (a.flags & BCP_LOOKAHEAD_PER_ENV) != 0;
+    Robot r;
+    r.p.x = as_global(S->st.x)[i];
+    r.p.y = as_global(S->st.y)[i];
+    r.p.th = as_global(S->st.angle)[i];
+    r.v = as_global(S->st.v)[i];
+    r.w = as_global(S->st.w)[i];
+    r.steer = tri ? as_global(S->st.steer)[i] : 0.0;
+    r.wheel = tri ? as_global(S->st.wheel)[i] : 0.0;
+    double min_dist = as_global(S->st.min_dist)[i];
+    int target = as_global(S->st.target_idx)[i];
+    int iter = as_global(S->st.cur_iter)[i];
+    bool collided = as_global(S->st.collided)[i] != 0;
+    const int64_t g = S->geom_of_env ? (int64_t)as_global(S->geom_of_env)[i] : i;   // slot_of
+    const double* pts = S->path.pts + (S->path.shared ? 0 : g * (int64_t)S->path.max_len * 5);
+    const int m = S->path.shared ? S->path.max_len : S->path.lens[g];
+
+    double ret = 0.0;
+    int steps = 0, reason = 0, errs = 0;
+    bool finished = !live;
+    // Every lane stays in the loop until the whole wave is through (collides_wave is a wave-wide call); a lane that is
+    // finished, masked out or past N * K passes active = false and keeps its results as they are.
+    for (int t = 0; t < a.horizon; ++t) {
+        if (__ballot(!finished) == 0) break;   // wave-uniform
+        const bool active = !finished;
+        const int64_t wide_row = ((int64_t)t * a.n + i) * a.k + k;
+        double cmd0, cmd1;
+        lookahead_action(a, per_env ? wide_row : (int64_t)t * a.k + k, cmd0, cmd1);
+        double z[3] = {0.0, 0.0, 0.0};
+        if (noisy_model) {
+            z[0] = as_global(a.noise_z)[3 * wide_row + 0];
+            z[1] = as_global(a.noise_z)[3 * wide_row + 1];
+            z[2] = as_global(a.noise_z)[3 * wide_row + 2];
+        }
+        // ---- _env_step (envs/base/env.py:442-461)
+        Robot nr = r;
+        int drawn = 0;
+        RobotDrive d = robot_step_begin(P, nr, cmd0, cmd1);
+        if (!noisy_model) d.noisy = false;   // the noise-free forward model, whatever the handle's noise_on
+        const int e = robot_step_end(P, nr, d, z, drawn);
+        const bool hit = collides_wave(P, S->map, S->cull, L, S->exact_mode, S->dense_threshold, S->wide != 0, active, g,
+                                       nr.p.x, nr.p.y, nr.p.th);
+        if (active) {
+            if (hit) {   // robot.set_pose(*old_position): pose restored, v = w = 0 (tricycle_model.py:471-476)
+                nr.p = r.p;
+                nr.v = 0.0;
+                nr.w = 0.0;
+            }
+            r = nr;
+            iter += 1;
+            collided = collided || hit;
+            double rew;
+            bool goal;
+            if (pure_pursuit) {
+                rew = reward_pure_pursuit(pts, m, r.p.x, r.p.y, collided, min_dist, target);
+                goal = hypot(pts[5 * (m - 1)] - r.p.x, pts[5 * (m - 1) + 1] - r.p.y) < 1.0;   // done(), reward.py:141-150
+            } else {
+                const PathWindow w = path_window_of(P, S->path.shared != 0, S->path.bbox, S->path.index, g, r.p.x, r.p.y);
+                rew = reward_step<4>(P, pts, w, m, r.p.x, r.p.y, r.p.th, min_dist, target);
+                goal = target > m - 1;
+            }
+            const bool timeout = iter >= P.iteration_timeout;
+            ret += rew;
+            steps = t + 1;
+            errs |= e;
+            if (goal || timeout || collided) {   // env.py:400-419
+                reason = (goal ? BCP_DONE_GOAL : 0) | (timeout ? BCP_DONE_TIMEOUT : 0) | (collided ? BCP_DONE_COLLIDED : 0);
+                finished = true;
+            }
+        }
+    }
+    if (!live) return;
+    as_global(a.ret)[c] = ret;
+    as_global(a.steps)[c] = steps;
+    as_global(a.reason)[c] = (uint8_t)reason;
+    if (a.final_pose) {
+        as_global(a.final_pose)[3 * c + 0] = r.p.x;
+        as_global(a.final_pose)[3 * c + 1] = r.p.y;
+        as_global(a.final_pose)[3 * c + 2] = r.p.th;
+    }
+    if (a.final_target) as_global(a.final_target)[c] = target;
+    if (a.err) as_global(a.err)[c] = errs;
+}
+
+// best / best_action: the candidate of each env with the largest key (free before collided, then ret), lowest k on ties.
+// `group` lanes (a power of two <= 64, chosen by the host from K) share an env: each scans k = lane, lane + group, .. in
+// ascending order, then the group reduces with shuffles.  Keys are compared, never added: the result does not depend on
+// the order of the reduction.  Every lane takes part in every shuffle (an env past N or masked out holds "none").
+struct BestKey {
+    int k, free_;
+    double ret;
+};
+
+__device__ __forceinline__ bool best_key_before(const BestKey& x, const BestKey& y)   // x wins over y
+{
+    if (x.k < 0) return false;
+    if (y.k < 0) return true;
+    if (x.free_ != y.free_) return x.free_ > y.free_;
+    if (x.ret != y.ret) return x.ret > y.ret;
+    return x.k < y.k;
+}
+
+__global__ void __launch_bounds__(256) lookahead_best_kernel(const LookaheadArgs a, int group)
+{
+    const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t i = gid / group;
+    const int sub = (int)(gid - i * group);
+    const bool live = i < a.n && (!a.mask || as_global(a.mask)[i] != 0);
+    BestKey b = {-1, 0, 0.0};
+    if (live) {
+        for (int k = sub; k < a.k; k += group) {
+            const int64_t c = i * a.k + k;
+            const BestKey x = {k, (as_global(a.reason)[c] & BCP_DONE_COLLIDED) ? 0 : 1, as_global(a.ret)[c]};
+            if (best_key_before(x, b)) b = x;
+        }
+    }
+    for (int off = group >> 1; off > 0; off >>= 1) {
+        BestKey o;
+        o.k = __shfl_xor(b.k, off);
+        o.free_ = __shfl_xor(b.free_, off);
+        o.ret = __shfl_xor(b.ret, off);
+        if (best_key_before(o, b)) b = o;
+    }
+    if (!live || sub != 0) return;
+    as_global(a.best)[i] = b.k;
+    if (a.best_action) {   // step 0 of the winner, in the dtype of `actions`
+        const int64_t row = (a.flags & BCP_LOOKAHEAD_PER_ENV) ? i * a.k + b.k : (int64_t)b.k;
+        if (a.flags & BCP_STEP_ACTIONS_F32) {
+            const GlobalPtr<const float> p = as_global(reinterpret_cast<const float*>(a.actions)) + 2 * row;
+            as_global(reinterpret_cast<float*>(a.best_action))[2 * i + 0] = p[0];
+            as_global(reinterpret_cast<float*>(a.best_action))[2 * i + 1] = p[1];
+        } else {
+            const GlobalPtr<const double> p = as_global(reinterpret_cast<const double*>(a.actions)) + 2 * row;
+            as_global(reinterpret_cast<double*>(a.best_action))[2 * i + 0] = p[0];
+            as_global(reinterpret_cast<double*>(a.best_action))[2 * i + 1] = p[1];
+        }
+    }
+}

@@ -21,6 +21,7 @@
 #include "bcp_raster.h"
 #include "bcp_coop.h"
 #include "bcp_step.h"
+#include "bcp_lookahead.h"
 #include "bcp_ego.h"
 #include "bcp_sample.h"
 #include "bcp_aisle.h"
@@ -2107,6 +2108,77 @@ extern "C" int bcp_rollout(bcp_handle* h, const bcp_step_io* io, int32_t n_steps
         if (io->err) row.err = io->err + (size_t)k * n;
         rc = launch_step(h, &row, flags, s);
         if (rc != BCP_OK) return rc;
+    }
+    HIP_TRY(hipGetLastError());
+    return BCP_OK;
+}
+
+// K candidate plans per env, scored on private copies of the env's state (bcp_lookahead.h).  Reads the handle, writes only
+// the caller's outputs: no step counter, ticket, parking counter, record or watchdog word is touched, so the steps before
+// and after the call are the steps of a handle that never looked ahead.
+extern "C" int bcp_lookahead(bcp_handle* h, const bcp_lookahead_io* io, uint32_t flags, void* stream)
+{
+    if (!h || !io) return fail(BCP_E_INVALID, "bcp_lookahead: null argument");
+    constexpr uint32_t allowed = BCP_STEP_ACTIONS_F32 | BCP_LOOKAHEAD_PER_ENV;
+    if (flags & ~allowed) return fail(BCP_E_INVALID, "bcp_lookahead: undefined flag bits 0x%x", flags & ~allowed);
+    if (!h->have_map || !h->have_path || !h->have_state)
+        return fail(BCP_E_STATE, "bcp_lookahead: costmaps, paths and state must be set first");
+    const bcp_params& p = h->params;
+    if (p.control_delay > 0 || p.pose_delay > 0 || p.state_delay > 0)
+        return fail(BCP_E_INVALID, "bcp_lookahead: control_delay / pose_delay / state_delay > 0 are not supported (every "
+                                   "candidate would need delay queues of its own)");
+    if (io->horizon < 1 || io->n_candidates < 1)
+        return fail(BCP_E_INVALID, "bcp_lookahead: horizon and n_candidates must be at least 1");
+    if (!io->actions || !io->ret || !io->steps || !io->reason)
+        return fail(BCP_E_INVALID, "bcp_lookahead: actions / ret / steps / reason are required");
+    if (io->noise_z && !p.noise_on)
+        return fail(BCP_E_INVALID, "bcp_lookahead: noise_z given, but the handle was created without noise (noise_on = 0)");
+    if (io->best_action && !io->best) return fail(BCP_E_INVALID, "bcp_lookahead: best_action needs best");
+    // element offsets are int64: the largest is 3 * H * N * K (noise_z); the grid has N * K / 64 workgroups
+    const int64_t limit = (int64_t)1 << 62;
+    const int64_t nk_max = limit / 3 / io->horizon;
+    if (h->n > nk_max / io->n_candidates)
+        return fail(BCP_E_INVALID, "bcp_lookahead: n_envs * n_candidates * horizon is too large for 64-bit element offsets");
+    const int64_t total = h->n * io->n_candidates;
+    const int64_t blocks = (total + kBlock - 1) / kBlock;
+    if (blocks > 0x7FFFFFFF) return fail(BCP_E_INVALID, "bcp_lookahead: n_envs * n_candidates exceeds the largest grid (2^37 lanes)");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (h->static_dirty) {
+        const int rc = upload_step_static(h, s);
+        if (rc != BCP_OK) return rc;
+    }
+    if (h->edt_lazy) {   // collides_wave classifies with the uint8 field
+        const int rc = ensure_fields(h, s);
+        if (rc != BCP_OK) return rc;
+    }
+    LookaheadArgs a;
+    a.S = h->dev_static;
+    a.actions = io->actions;
+    a.noise_z = io->noise_z;
+    a.mask = io->mask;
+    a.ret = io->ret;
+    a.steps = io->steps;
+    a.reason = io->reason;
+    a.final_pose = io->final_pose;
+    a.final_target = io->final_target_idx;
+    a.err = io->err;
+    a.best = io->best;
+    a.best_action = io->best_action;
+    a.n = h->n;
+    a.total = total;
+    a.horizon = io->horizon;
+    a.k = io->n_candidates;
+    a.flags = flags;
+    const size_t lds = collision_lds_bytes(p.n_verts, h->map.in_lds, h->map.rows, h->map.wpr);
+    const bool plain = p.reward_provider == BCP_REWARD_CONTINUOUS && !io->noise_z;
+    if (plain) hipLaunchKernelGGL(lookahead_kernel<true>, dim3((unsigned)blocks), dim3(kBlock), lds, s, a);
+    else hipLaunchKernelGGL(lookahead_kernel<false>, dim3((unsigned)blocks), dim3(kBlock), lds, s, a);
+    if (io->best) {
+        int group = 1;
+        while (group < 64 && group < io->n_candidates) group <<= 1;
+        const int64_t lanes = h->n * group;
+        hipLaunchKernelGGL(lookahead_best_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, s, a, group);
     }
     HIP_TRY(hipGetLastError());
     return BCP_OK;

@@ -125,6 +125,9 @@ class BatchedEgocentricCostmap(object):
     def seed(self, seed=None):
         self.env.seed(seed)
 
+    def lookahead(self, actions, **kw):
+        return self.env.lookahead(actions, **kw)
+
     def get_state(self):
         return self.env.get_state()
 

@@ -534,6 +534,53 @@ int bcp_final_egocentric_costmaps(bcp_handle *h, const double *window_origin /*h
 int bcp_final_goal_n_state(bcp_handle *h, const double *world_size /*host*/, float *out, void *stream);
 int bcp_final_goal_direction_state(bcp_handle *h, const double *world_size /*host*/, double *out, void *stream);
 
+/* ---- look-ahead: score K candidate plans per env without stepping it ------------------------------------- */
+/* bcp_lookahead flags (it also takes BCP_STEP_ACTIONS_F32) */
+enum {
+    BCP_LOOKAHEAD_PER_ENV = 1 << 8 /* actions are [H][N][K][2]: every env has candidates of its own; otherwise [H][K][2],
+                                      one candidate library shared by all envs */
+};
+
+/* Inputs / outputs of bcp_lookahead.  Host struct of device pointers, caller-owned; N = n_envs, H = horizon,
+ * K = n_candidates.  No counterpart struct in the reference: it is what a planner's `.act(obs)` (README "motion planning
+ * challenge", bc_gym_planning_env/run_the_challange.py) works out with get_state / set_state and H x K calls of PlanEnv.step. */
+typedef struct bcp_lookahead_io {
+    const void *actions;       /* [H][K][2], or [H][N][K][2] with BCP_LOOKAHEAD_PER_ENV: step t of candidate k; float64, or
+                                  float32 with BCP_STEP_ACTIONS_F32, widened before any arithmetic as in bcp_step */
+    const double *noise_z;     /* NULL: the noise-free forward model (the arithmetic of a handle created with noise_on = 0,
+                                  whatever this handle's setting), or [H][N][K][3] standard normals in slot order, consumed
+                                  as bcp_step_io.noise_z is (needs params.noise_on).  The on-device Philox stream is never
+                                  used and never advanced */
+    const uint8_t *mask;       /* optional [N]: rows of envs with mask[i] == 0 are left untouched in every output */
+    int32_t horizon;           /* H >= 1 */
+    int32_t n_candidates;      /* K >= 1; N * K * H * 3 must stay below 2^62 (the element offsets are 64-bit) */
+    double *ret;               /* [N][K] float64 sum of the rewards of the steps taken, added in step order from 0.0 (the rule
+                                  of bcp_episode_record.ret; rewards of reward.py:66-69 / :144-153) */
+    int32_t *steps;            /* [N][K] steps taken: index of the first step with done = 1 (env.py:407-419) plus one, else H */
+    uint8_t *reason;           /* [N][K] BCP_DONE_* bits of that done step (as bcp_episode_record.reason), 0 if none was done */
+    double *final_pose;        /* optional [N][K][3]: State.pose after the last step taken (after the roll-back of
+                                  env.py:458-459 where it collided) */
+    int32_t *final_target_idx; /* optional [N][K]: the reward provider's target_idx after the last step taken */
+    int32_t *err;              /* optional [N][K]: OR of the BCP_ERR_* bits of the steps taken */
+    int32_t *best;             /* optional [N]: the candidate with the largest key (reason & BCP_DONE_COLLIDED ? 0 : 1, ret),
+                                  compared lexicographically; ties go to the lowest k */
+    void *best_action;         /* optional [N][2], dtype of `actions` (needs best): step 0 of candidate best[i] for env i --
+                                  can be passed to bcp_step as it is */
+} bcp_lookahead_io;
+
+/* For every env i and candidate k: a private copy of env i's state (x .. robot_collided, its map / path / pool entry) is
+ * stepped `horizon` times with the candidate's actions, WITHOUT auto-reset, stopping after the first step whose done is 1
+ * -- PlanEnv.step (envs/base/env.py:334-361) H times on a copy made with get_state / set_state (env.py:305-330).  An env
+ * that is already done takes its first step, which is done, like the reference's.  Nothing of the handle changes: no state
+ * array, not geom_of_env, not the step counter or the noise stream, not a bound episode record.  Asynchronous on `stream`,
+ * no allocation, no synchronisation; the launch arguments depend only on the pointers given, so a call can be captured into
+ * a HIP graph (on a pool whose maps are refreshed by bcp_refresh_mini_worlds, capture after the refresh: the call settles
+ * stale distance fields on its stream like bcp_pose_collides).
+ * Refused with BCP_E_INVALID: control_delay, pose_delay or state_delay > 0 (every candidate would need private delay
+ * queues), horizon < 1, n_candidates < 1, noise_z on a handle without noise_on, best_action without best.  There is no
+ * other limit on H or K: a candidate is one lane, K may be smaller or larger than a wavefront. */
+int bcp_lookahead(bcp_handle *h, const bcp_lookahead_io *io, uint32_t flags, void *stream);
+
 /* ---- measurement -------------------------------------------------------------------------------------- */
 /* Which kernels a bcp_step() of this handle launches, as configured now: 0 = step_kernel alone (no distance field, or a
  * forced mode), 1 = step_fast_pair_kernel alone (every undecided pose settled in place), 2 = step_fast_pair_kernel +
