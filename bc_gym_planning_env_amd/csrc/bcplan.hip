@@ -958,7 +958,9 @@ static void build_cull_geometry(const bcp_params& p, double res, CullDesc* C)
     // by n_out discs: a disc row of spacing h covers the capsule of radius rho when its radius is sqrt(rho^2+(h/2)^2)
     double rho = 0;
     for (int k = 0; k < K; ++k) rho = std::max(rho, seg_dist(p.verts[k][0], p.verts[k][1], a0, ay, a1, ay));
-    const int n_out = a1 > a0 ? std::min(kMaxSamples, std::max(2, (int)std::ceil((a1 - a0) / (0.5 * rho)) + 1)) : 1;
+    // (compared as doubles: a footprint that lies ON its axis has rho == 0, and an infinite quotient must not reach an int)
+    const double want_out = a1 > a0 ? std::ceil((a1 - a0) / (0.5 * rho)) + 1 : 1;
+    const int n_out = a1 > a0 ? (want_out >= kMaxSamples ? kMaxSamples : std::max(2, (int)want_out)) : 1;
     const double h = n_out > 1 ? (a1 - a0) / (n_out - 1) : 0.0;
     const double r_out = std::sqrt(rho * rho + 0.25 * h * h) / res + kSlackOuter;
     C->n_out = n_out;
@@ -1067,6 +1069,9 @@ extern "C" int bcp_create(const bcp_params* params, int64_t n_envs, int device, 
     if (n_envs <= 0) return fail(BCP_E_INVALID, "bcp_create: n_envs must be positive");
     if (params->n_verts < 3 || params->n_verts > BCP_MAX_VERTS)
         return fail(BCP_E_INVALID, "bcp_create: n_verts %d outside [3, %d]", params->n_verts, BCP_MAX_VERTS);
+    for (int k = 0; k < params->n_verts; ++k)
+        if (!std::isfinite(params->verts[k][0]) || !std::isfinite(params->verts[k][1]))
+            return fail(BCP_E_INVALID, "bcp_create: footprint vertex %d is not finite", k);
     if (params->model != BCP_MODEL_TRICYCLE && params->model != BCP_MODEL_DIFFDRIVE)
         return fail(BCP_E_INVALID, "bcp_create: unknown robot model %d", params->model);
     if (!(params->dt > 0)) return fail(BCP_E_INVALID, "bcp_create: dt must be > 0 (path_tools.py:307)");

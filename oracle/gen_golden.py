@@ -14,6 +14,8 @@ Fixture list:
   g8_traj_*.npz             full PlanEnv.step trajectories (RandomMiniEnv seeds, AisleTurnEnv variants)
   g9 .. g12                 RandomMiniEnv worlds, egocentric observations, delays / pure pursuit, coloured ego costmap
   g13_serialized_*.npz      PlanEnv.serialize() records taken mid-episode + the next 100 steps of the live env
+  g15_footprint_zoo.npz     the footprint zoo of tests/footprints.py: pre-fill polygons, scaled stock footprints and
+                            pose_collides verdicts on the g6 maps   (python oracle/gen_golden.py footprint_zoo)
 """
 import os
 import sys
@@ -253,6 +255,72 @@ def gen_footprints():
         save("g5_footprint_vertices.npz", **out)
     finally:
         cv2.fillPoly = orig_fill
+
+
+class _FootprintOnly(object):
+    """All that pose_collides asks of a robot"""
+
+    def __init__(self, footprint):
+        self._footprint = np.array(footprint, dtype=np.float64)
+
+    def get_footprint(self):
+        return self._footprint
+
+
+def gen_footprint_zoo():
+    """The zoo of tests/footprints.py (the shapes are imported from there, nothing is restated here) through the genuine
+    get_pixel_footprint (what it hands to cv2.fillPoly), create_standard_robot(..., footprint_scale=s).get_footprint()
+    and envs.base.env.pose_collides on the maps of g6."""
+    import cv2  # the harness stub
+    from bc_gym_planning_env.envs.base.env import pose_collides
+    from bc_gym_planning_env.robot_models.robot_examples_factory import create_standard_robot
+    from bc_gym_planning_env.utilities.costmap_2d import CostMap2D
+    from bc_gym_planning_env.utilities.path_tools import get_pixel_footprint
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import footprints as F
+    g6 = np.load(os.path.join(OUT, "g6_pose_collides.npz"))
+    rng = np.random.RandomState(115)
+    captured = {}
+    orig_fill = cv2.fillPoly
+
+    def capture(img, pts, color, *a, **k):
+        captured["shape"] = img.shape
+        captured["pts"] = np.array(pts[0], dtype=np.int32)
+        return orig_fill(img, pts, color, *a, **k)
+    out = {"names": np.array(sorted(F.ZOO))}
+    for stock, (robot_name, _) in sorted(F.STOCK.items()):
+        for s in F.SCALES:
+            out["scaled_%s_x%g" % (stock, s)] = np.array(create_standard_robot(robot_name, footprint_scale=s).get_footprint())
+    cv2.fillPoly = capture
+    try:
+        for name in sorted(F.ZOO):
+            fp = F.ZOO[name]
+            rs = F.resolutions(name)
+            out[name + "_res"] = np.array(rs)
+            for ri, res in enumerate(rs):
+                angles = np.concatenate([rng.uniform(-np.pi, np.pi, 24), F.angle_set(0, 0)])
+                pts = np.zeros((len(angles), len(fp), 2), dtype=np.int32)
+                shapes = np.zeros((len(angles), 2), dtype=np.int32)
+                for i, a in enumerate(angles):
+                    get_pixel_footprint(a, fp, res)
+                    pts[i], shapes[i] = captured["pts"], captured["shape"]
+                key = "%s_r%d" % (name, ri)
+                out[key + "_angles"], out[key + "_pts"], out[key + "_shape"] = angles, pts, shapes
+    finally:
+        cv2.fillPoly = orig_fill
+    n = 1500
+    for tag in ("mini0", "mini3", "mini64"):
+        res = float(g6[tag + "_res"])
+        costmap = CostMap2D(g6[tag + "_map"].copy(), res, g6[tag + "_origin"].copy())
+        # the same poses for every footprint; the rim lets an image lie partly or wholly off the map
+        poses = np.stack([rng.uniform(-4.6, 4.6, n), rng.uniform(-4.6, 4.6, n), rng.uniform(-np.pi, np.pi, n)], axis=1)
+        out[tag + "_poses"] = poses
+        for name in sorted(F.ZOO):
+            robot = _FootprintOnly(F.ZOO[name])
+            verdict = np.array([pose_collides(p[0], p[1], p[2], robot, costmap) for p in poses], dtype=np.uint8)
+            out["%s_%s_collides" % (name, tag)] = np.packbits(verdict)
+            print("   %-16s %s: %d/%d collide" % (name, tag, verdict.sum(), n))
+    save("g15_footprint_zoo.npz", **out)
 
 
 def make_mini_env(seed, resolution=0.03, robot_name=None):
@@ -676,6 +744,9 @@ def main():
     os.makedirs(OUT, exist_ok=True)
     O.build()
     H.load()
+    if sys.argv[1:] == ["footprint_zoo"]:   # (added after the others: writes its own file only)
+        gen_footprint_zoo()
+        return
     gen_robot_steps()
     gen_scalar_utils()
     gen_footprints()
@@ -689,6 +760,7 @@ def main():
     gen_serialized_records()
     gen_diffdrive_trajectories()
     gen_trajectories()
+    gen_footprint_zoo()
 
 
 if __name__ == "__main__":

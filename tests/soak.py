@@ -1,6 +1,8 @@
 """Long randomised parity run: the HIP step against the oracle, every step, every env, several configurations.
 Not collected by pytest (minutes of CPU oracle time); it lives under tests/ because it drives the oracle.
-Usage: python tests/soak.py [steps] [n_envs] [seed]   (from the repository root)"""
+Usage: python tests/soak.py [steps] [n_envs] [seed] [footprint]   (from the repository root)
+`footprint` (off by default) names a member of the zoo in tests/footprints.py, e.g. U: one more configuration then runs
+that footprint at its wide resolution (8-word row masks, general even-odd contour) on a tricycle model."""
 import sys, os, time, numpy as np, torch
 sys.path.insert(0, '.')
 import oracle as O
@@ -9,6 +11,7 @@ from bc_gym_planning_env_amd import BatchedPlanEnv, CostMap2D, EnvParams, mini_e
 steps = int(sys.argv[1]) if len(sys.argv) > 1 else 600
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 8192
 seed = int(sys.argv[3]) if len(sys.argv) > 3 else 0
+zoo_member = sys.argv[4] if len(sys.argv) > 4 else None
 G = os.path.join('tests', 'golden')
 ATOL = 1e-9
 O.build()
@@ -105,6 +108,27 @@ p = O.make_params("diffdrive", noise=None, spatial_precision=0.2, angular_precis
 ref = O.OracleBatch(p, n, gd["costmap"], gd["origin"], res, gd["path"])
 ref.reset_from_paths()
 run("diff-drive 64x64", env, ref, scale=(1.0, 1.0))
+del env
+
+# 4b. optional: a footprint of the zoo at its wide resolution, tricycle model + noise, speckle world
+if zoo_member is not None:
+    sys.path.insert(0, 'tests')
+    import footprints as F
+    from bc_gym_planning_env_amd import robots
+    verts = F.ZOO[zoo_member]
+    res = F.wide_resolution(verts)
+    assert res is not None and F.footprint_is_wide(verts, res) and F.check_kernel_size(verts, res), zoo_member
+    cm, origin, path = F.speckle_world(O, verts, res, seed=seed)
+    params = EnvParams(goal_spat_dist=0.2, goal_ang_dist=np.pi / 8, resolution=res, refine_path=False, iteration_timeout=100)
+    with F.registered(F.registered_name(zoo_member), verts, model=0) as robot:
+        env = BatchedPlanEnv(CostMap2D(cm, res, origin), path, params, n_envs=n, robot_name=robot,
+                             noise_parameters=dict(robots.PLANENV_NOISE), auto_reset=True, seed=seed)
+        p = O.make_params("tricycle", noise=O.PLANENV_NOISE, spatial_precision=0.2, angular_precision=np.pi / 8,
+                          iteration_timeout=100, footprint=verts)
+        ref = O.OracleBatch(p, n, cm, origin, res, path)
+        ref.reset_from_paths()
+        run("zoo %s @%.4f (wide)" % (zoo_member, res), env, ref, scale=(3.0, 1.0))
+        del env
 print("soak ok")
 
 # 5. egocentric views: thousands of random poses on random-byte costmaps, shared and private, against the oracle

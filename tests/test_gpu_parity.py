@@ -152,11 +152,8 @@ def test_kat_collision_table(torch_cuda):
     from bc_gym_planning_env_amd import NativeOps
     from bc_gym_planning_env_amd import EnvParams
     g = load("kat_collision_map.npz")
-    rect = np.array([[-0.77, -0.385], [-0.77, 0.385], [0.67, 0.385], [0.67, -0.385]])
-    from bc_gym_planning_env_amd import robots
-    robots.FOOTPRINTS["kat_rect"] = rect
-    robots.MODELS["kat_rect"] = 1
-    try:
+    from footprints import ZOO, registered
+    with registered("kat_rect", ZOO["kat_rect"]):
         ops = NativeOps("kat_rect")
         ops.set_costmap(g["costmap"], g["origin"], float(g["resolution"]))
         poses = [(x, 0., 0.2) for x in range(7)] + [(x, 1.2, np.pi / 2 + 0.4) for x in range(7)]
@@ -168,8 +165,6 @@ def test_kat_collision_table(torch_cuda):
         np.testing.assert_array_equal(got * inside, expected)
         masks, shapes = ops.get_pixel_footprint(np.array([0.]), 0.05)
         assert int((masks[0] > 0).sum()) == 493  # test_path_tools.py:465-468
-    finally:
-        del robots.FOOTPRINTS["kat_rect"], robots.MODELS["kat_rect"]
 
 
 @pytest.mark.parametrize("path", TRAJ, ids=[os.path.basename(p)[8:-4] for p in TRAJ])

@@ -87,6 +87,40 @@ def test_g6_pose_collides(oracle, golden_dir):
         np.testing.assert_array_equal(np.array(got, dtype=np.uint8), g[tag + "_collides"])
 
 
+def test_g15_footprint_zoo(oracle, golden_dir):
+    """The zoo of tests/footprints.py as the genuine reference sees it: the integer polygon and image shape
+    get_pixel_footprint hands to cv2.fillPoly, the scaled stock footprints of create_standard_robot, and the verdicts of
+    envs.base.env.pose_collides on the g6 maps -- all equal to the oracle's, exactly."""
+    import footprints as F
+    g = load(golden_dir, "g15_footprint_zoo.npz")
+    g6 = load(golden_dir, "g6_pose_collides.npz")
+    assert list(g["names"]) == sorted(F.ZOO)
+    for stock, (_, fp) in F.STOCK.items():
+        for s in F.SCALES:
+            want = g["scaled_%s_x%g" % (stock, s)]
+            np.testing.assert_array_equal(F.ZOO["%s_x%g" % (stock, s)], want)
+            model = "tricycle" if stock == "tricycle" else "diffdrive"
+            np.testing.assert_array_equal(oracle.footprint_of(oracle.make_params(model, footprint_scale=s)), want)
+    n_polys = 0
+    for name in sorted(F.ZOO):
+        np.testing.assert_array_equal(g[name + "_res"], F.resolutions(name))
+        for ri, res in enumerate(F.resolutions(name)):
+            key = "%s_r%d" % (name, ri)
+            for a, pts, shape in zip(g[key + "_angles"], g[key + "_pts"], g[key + "_shape"]):
+                v, half = oracle.footprint_vertices(a, F.ZOO[name], res)
+                np.testing.assert_array_equal(v, pts, err_msg="%s at %g, angle %r" % (name, res, a))
+                assert (2 * half[1] + 1, 2 * half[0] + 1) == tuple(shape)
+                n_polys += 1
+    assert n_polys > 2500
+    for tag in ("mini0", "mini3", "mini64"):
+        cm, origin, res, poses = g6[tag + "_map"], g6[tag + "_origin"], float(g6[tag + "_res"]), g[tag + "_poses"]
+        for name in sorted(F.ZOO):
+            want = np.unpackbits(g["%s_%s_collides" % (name, tag)])[:len(poses)]
+            got = np.array([oracle.pose_collides(p[0], p[1], p[2], F.ZOO[name], cm, origin, res) for p in poses], dtype=np.uint8)
+            np.testing.assert_array_equal(got, want, err_msg="%s on %s" % (name, tag))
+            assert want.any() and not want.all()
+
+
 @pytest.mark.parametrize("tag", ["a", "b", "c"])
 def test_g7_reward(oracle, golden_dir, tag):
     g = load(golden_dir, "g7_reward.npz")
