@@ -88,6 +88,22 @@ class BcpLookaheadIO(C.Structure):
     ]
 
 
+class BcpMppiParams(C.Structure):
+    _fields_ = [
+        ("horizon", C.c_int32), ("n_candidates", C.c_int32), ("iterations", C.c_int32),
+        ("sigma", C.c_double * 2), ("low", C.c_double * 2), ("high", C.c_double * 2),
+        ("lambda_", C.c_double), ("collision_penalty", C.c_double), ("seed", C.c_uint64), ("draw_index", C.c_uint64),
+    ]
+
+
+class BcpMppiIO(C.Structure):
+    _fields_ = [
+        ("mean", C.c_void_p), ("action", C.c_void_p), ("mask", C.c_void_p), ("eps_in", C.c_void_p), ("eps_out", C.c_void_p),
+        ("draw_index", C.c_void_p), ("iter_mean", C.c_void_p), ("iter_ret", C.c_void_p), ("iter_reason", C.c_void_p),
+        ("err", C.c_void_p),
+    ]
+
+
 # every symbol include/bcplan.h declares: (restype, argtypes)
 _H = C.c_void_p
 SYMBOLS = {
@@ -108,6 +124,7 @@ SYMBOLS = {
     "bcp_step": (C.c_int, [_H, C.POINTER(BcpStepIO), C.c_uint32, C.c_void_p]),
     "bcp_rollout": (C.c_int, [_H, C.POINTER(BcpStepIO), C.c_int32, C.c_uint32, C.c_void_p]),
     "bcp_lookahead": (C.c_int, [_H, C.POINTER(BcpLookaheadIO), C.c_uint32, C.c_void_p]),
+    "bcp_mppi": (C.c_int, [_H, C.POINTER(BcpMppiParams), C.POINTER(BcpMppiIO), C.c_uint32, C.c_void_p]),
     "bcp_expired_waits": (C.c_int, [_H, C.POINTER(C.c_int64), C.c_void_p]),
     "bcp_parked_poses": (C.c_int, [_H, C.POINTER(C.c_int64), C.c_void_p]),
     "bcp_side_stream": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_void_p)]),

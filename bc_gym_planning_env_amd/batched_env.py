@@ -400,6 +400,21 @@ class Lookahead(object):
         return (self.reason & _lib.DONE_GOAL) != 0
 
 
+class Mppi(object):
+    """What BatchedPlanEnv.mppi() returns (device tensors, no sync): `mean` [N, H, 2] float64, the refined plan; `action`
+    [N, 2] = mean[:, 0], ready for step(); optional, None unless asked for: `eps` [I, N, K, H, 2] float32 (the
+    perturbations used), `iter_mean` [I, N, H, 2] (the mean going into each iteration), `iter_ret` / `iter_reason`
+    [I, N, K], `err` int32 [N].  Everything but `mean` is a cached buffer of the env for this (H, K, I)."""
+
+    FIELDS = ("eps", "iter_mean", "iter_ret", "iter_reason", "err")
+
+    def __init__(self, horizon, n_candidates, iterations, mean, action, **tensors):
+        self.horizon, self.n_candidates, self.iterations = horizon, n_candidates, iterations
+        self.mean, self.action = mean, action
+        for name in self.FIELDS:
+            setattr(self, name, tensors.get(name))
+
+
 class BatchedPlanEnv(object):
     """N planning envs on one MI355X.
 
@@ -983,6 +998,81 @@ class BatchedPlanEnv(object):
         _lib.check(self._lib.bcp_lookahead(self._h, C.byref(io), flags, self._stream()))
         self._last_lookahead_inputs = tuple(keep)   # alive until the stream has consumed them
         return Lookahead(h, k, **out)
+
+    def mppi(self, mean, sigma, iterations, n_candidates, lam, collision_penalty, seed=0, draw_index=0, mask=None, eps=None,
+             want=(), action_dtype=None):
+        """Refine one plan per env by sampling around it (bcp_mppi, one kernel launch, nothing of the env changes): for each
+        of `iterations` rounds, n_candidates plans u = clip(mean + sigma * eps, action box) -- candidate 0 is the mean itself
+        -- are rolled out with the noise-free forward model as lookahead() rolls them out, scored ret - collision_penalty *
+        collided, and the mean becomes their average under the weights softmax(score / lam).
+        mean: [N, H, 2]; a contiguous float64 tensor on the env's device is refined IN PLACE (and returned), anything else
+        is copied first.  sigma: two standard deviations (v, w).  n_candidates: a power of two in [8, 1024].  seed,
+        draw_index: the perturbation stream (the env's own noise stream is not involved); draw_index may be a one-element
+        int64 / uint64 tensor on the device, read by the kernel -- a captured call then draws afresh on every replay once the
+        word was changed.  eps: optional [I, N, K, H, 2] float32 perturbations to use instead (replay).  mask: optional [N];
+        rows of envs with mask 0 are left untouched.  want: from "eps", "iter_mean", "iter_ret", "iter_reason", "err".
+        action_dtype: torch.float64 (default) or torch.float32.  Returns an Mppi; buffers are cached per (H, K, I).  Delays
+        > 0 are refused."""
+        n = self.n_envs
+        if not isinstance(mean, torch.Tensor):
+            mean = torch.from_numpy(np.ascontiguousarray(mean))
+        if mean.dim() != 3 or mean.shape[0] != n or mean.shape[2] != 2:
+            raise ValueError("mean must have shape (%d, H, 2), got %s" % (n, tuple(mean.shape)))
+        mean = mean.to(self.device, torch.float64).contiguous()
+        h, k, it = int(mean.shape[1]), int(n_candidates), int(iterations)
+        want = set(want)
+        unknown = want - set(Mppi.FIELDS)
+        if unknown:
+            raise ValueError("mppi: unknown outputs %s" % sorted(unknown))
+        action_dtype = torch.float64 if action_dtype is None else action_dtype
+        if action_dtype not in (torch.float32, torch.float64):
+            raise ValueError("action_dtype must be torch.float32 or torch.float64")
+        p = _lib.BcpMppiParams()
+        p.horizon, p.n_candidates, p.iterations = h, k, it
+        sigma = np.asarray(sigma, dtype=np.float64).reshape(2)
+        low, high = (np.asarray(b, dtype=np.float64).reshape(2) for b in (self.action_space.low, self.action_space.high))
+        for d in range(2):
+            p.sigma[d], p.low[d], p.high[d] = sigma[d], low[d], high[d]
+        p.lambda_, p.collision_penalty, p.seed = float(lam), float(collision_penalty), int(seed) & (2 ** 64 - 1)
+        io = _lib.BcpMppiIO()
+        io.mean = mean.data_ptr()
+        keep = [mean]
+        if isinstance(draw_index, torch.Tensor):
+            assert draw_index.numel() == 1 and draw_index.dtype in (torch.int64, torch.uint64) and draw_index.is_cuda
+            io.draw_index = draw_index.data_ptr()
+            keep.append(draw_index)
+        else:
+            p.draw_index = int(draw_index) & (2 ** 64 - 1)
+        if mask is not None:
+            mask = mask if isinstance(mask, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(mask))
+            mask = mask.to(self.device).to(torch.uint8).contiguous()
+            assert tuple(mask.shape) == (n,)
+            io.mask = mask.data_ptr()
+            keep.append(mask)
+        if eps is not None:
+            eps = eps if isinstance(eps, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(eps))
+            eps = eps.to(self.device, torch.float32).contiguous()
+            if tuple(eps.shape) != (it, n, k, h, 2):
+                raise ValueError("eps must have shape %s, got %s" % ((it, n, k, h, 2), tuple(eps.shape)))
+            io.eps_in = eps.data_ptr()
+            keep.append(eps)
+        buf = self.__dict__.setdefault("_mppi_buffers", {}).setdefault((h, k, it), {})
+        shapes = {"action": ((n, 2), action_dtype), "eps": ((it, n, k, h, 2), torch.float32),
+                  "iter_mean": ((it, n, h, 2), torch.float64), "iter_ret": ((it, n, k), torch.float64),
+                  "iter_reason": ((it, n, k), torch.uint8), "err": ((n,), torch.int32)}
+        out = {}
+        for name in ("action",) + Mppi.FIELDS:
+            if name != "action" and name not in want:
+                continue
+            shape, dtype = shapes[name]
+            if (name, dtype) not in buf:
+                buf[(name, dtype)] = torch.zeros(shape, dtype=dtype, device=self.device)
+            out[name] = buf[(name, dtype)]
+            setattr(io, "eps_out" if name == "eps" else name, out[name].data_ptr())
+        flags = _lib.STEP_ACTIONS_F32 if action_dtype == torch.float32 else 0
+        _lib.check(self._lib.bcp_mppi(self._h, C.byref(p), C.byref(io), flags, self._stream()))
+        self._last_mppi_inputs = tuple(keep)   # alive until the stream has consumed them
+        return Mppi(h, k, it, mean, **out)
 
     def enable_episode_record(self, capacity=None):
         """Keep what every episode end leaves behind (bcp_bind_episode_record): from now on step() returns

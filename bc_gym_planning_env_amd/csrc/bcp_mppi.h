@@ -1,0 +1,253 @@
+// bcp_mppi.h -- bcp_mppi(): sampling-based refinement of one plan per env (MPPI), I iterations of sample -> roll out ->
+// weight -> update inside ONE launch.  Included by bcplan.hip after bcp_lookahead.h.  The trip body is lookahead_kernel's,
+// restated (as that kernel restates finalize_env_from) so that neither it nor the step kernels compile to anything else;
+// candidate actions are not read from memory but made in registers: mean + sigma * eps, clipped to the action box.
+// Nothing of the handle is written; the only global stores are the caller's outputs (bcp_mppi_io).
+#pragma once
+
+#include "bcp_lookahead.h"
+
+// Launch arguments: the handle's parameter block, the caller's pointers and bcp_mppi_params by value -- nothing that the
+// library changes from call to call, so a captured call replays (fresh perturbations come from *draw_index).
+struct MppiArgs {
+    const StepStatic* S;
+    bcp_mppi_params p;
+    double* mean;                // [N][H][2], in / out
+    void* action;                // [N][2]
+    const uint8_t* mask;         // nullptr or [N]
+    const float* eps_in;         // nullptr or [I][N][K][H][2]
+    float* eps_out;              // nullptr or same
+    const uint64_t* draw_index;  // nullptr or one device word
+    double* iter_mean;           // nullptr or [I][N][H][2]
+    double* iter_ret;            // nullptr or [I][N][K]
+    uint8_t* iter_reason;        // nullptr or [I][N][K]
+    int32_t* err;                // nullptr or [N]
+    int64_t n;
+    int32_t score_word;          // where the score area starts in the dynamic LDS (32-bit words, even), behind collides_wave's
+    uint32_t flags;              // BCP_STEP_ACTIONS_F32
+};
+
+// The two perturbations of (env, draw, iteration j, candidate k, step t): Philox4x32-10 keyed by the seed on the counter
+//   c0 = env (low word), c1 = k | env (high bits) << 10 | draw (bits 32..51) << 12, c2 = j * H + t, c3 = draw (low word)
+// (distinct for draws below 2^52 and I * H <= 2^32), then ONE float32 Box-Muller pair on the top 24 bits of two words:
+// u = (m + 1/2) 2^-24 in (0, 1], r = sqrt(-2 ln u) <= 5.89, angle 2 pi m' 2^-24 through sincospi.  A function of its
+// arguments alone: the update pass calls it again for the values the roll-out pass used instead of keeping K * H of them.
+__device__ __forceinline__ void mppi_draw(uint64_t seed, uint64_t env, uint64_t draw, uint32_t jt, int k, float& e0, float& e1)
+{
+    uint32_t c[4] = {(uint32_t)env, (uint32_t)k | ((uint32_t)(env >> 32) << 10) | ((uint32_t)(draw >> 32) << 12), jt,
+                     (uint32_t)draw};
+    philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+    const float u = ((float)(c[0] >> 8) + 0.5f) * 5.9604644775390625e-08f;   // 2^-24
+    const float r = sqrtf(-2.0f * logf(u));
+    float sn, cs;
+    sincospif(2.0f * ((float)(c[1] >> 8) * 5.9604644775390625e-08f), &sn, &cs);
+    e0 = r * cs;
+    e1 = r * sn;
+}
+
+// u = min(max(mean + sigma * eps, low), high): one product, one sum, two comparisons, each rounded on its own
+__device__ __forceinline__ double mppi_command(double mean, double sigma, float eps, double low, double high)
+{
+    double u = mean + sigma * (double)eps;
+    u = u < low ? low : u;
+    return u > high ? high : u;
+}
+
+// One wavefront per workgroup (collides_wave is wave-wide and owns the dynamic LDS up to score_word).  With K >= 64 the
+// workgroup is ONE env: its K / 64 chunks of candidates are rolled out one after another by the same lanes (lane l holds
+// k = chunk * 64 + l), so the env's state is loaded once and everything the update needs stays in the wave.  With K < 64
+// the wave holds 64 / K envs, and the reductions run over groups of K adjacent lanes (xor shuffles: every lane of a group
+// ends with the same bits, whatever its position).
+// The mean lives in the caller's `mean` array, not in LDS: the rows of an env are read and written by the one wave that
+// owns the env, a lane's row is one broadcast load per trip (all lanes of an env read the same 16 bytes, L1-resident:
+// H * 16 bytes per env), and an LDS copy of 64 / K envs x H rows would sit on top of the ~14 KB collision area that already
+// bounds the waves per CU.  Row t is replaced in place as soon as its weighted sum is known (nothing reads the old row t
+// afterwards); a workgroup barrier -- one wave: a fence -- orders an iteration's stores before the next one's loads.
+// Scores: one double per (lane, chunk) in LDS behind the collision area (K >= 64: K * 8 bytes; K < 64: 512), written
+// and read by the same lane; they turn into the weights in place.  The update needs every u[t] again after the weights
+// are known: the perturbation is drawn again from its counter (or read again from eps_in).
+// Loops are bounded by I, H and K / 64; no atomics, no waits on other workgroups.
+template <bool PLAIN>
+__global__ void __launch_bounds__(kBlock) mppi_kernel(const MppiArgs a)
+{
+    typedef __attribute__((address_space(3))) double* LdsScore;
+    const StepStatic* S = a.S;
+    const DevParams& P = S->P;
+    const int tid = threadIdx.x;
+    const int K = a.p.n_candidates, H = a.p.horizon;
+    const int group = K < kBlock ? K : kBlock;    // lanes that share an env (a power of two, the host checked K)
+    const int chunks = K / group;
+    const int64_t i_raw = (int64_t)blockIdx.x * (kBlock / group) + tid / group;
+    const bool in_range = i_raw < a.n;
+    const int64_t i = in_range ? i_raw : a.n - 1;   // lanes past N shadow the last env and never store
+    const int kl = tid & (group - 1);
+    const bool live = in_range && (!a.mask || as_global(a.mask)[i] != 0);
+
+    const CollisionLds L = collision_lds_setup(P, S->map, tid);
+    const LdsScore score = (LdsScore)(lds_dyn + a.score_word) + tid;   // chunk ch at score[ch * kBlock]
+
+    // ---- the env's state, once for all iterations and chunks
+    const bool tri = P.model == BCP_MODEL_TRICYCLE;
+    const bool pure_pursuit = !PLAIN && P.reward_provider == BCP_REWARD_PURE_PURSUIT;
+    Robot r0;
+    r0.p.x = as_global(S->st.x)[i];
+    r0.p.y = as_global(S->st.y)[i];
+    r0.p.th = as_global(S->st.angle)[i];
+    r0.v = as_global(S->st.v)[i];
+    r0.w = as_global(S->st.w)[i];
+    r0.steer = tri ? as_global(S->st.steer)[i] : 0.0;
+    r0.wheel = tri ? as_global(S->st.wheel)[i] : 0.0;
+    const double min_dist0 = as_global(S->st.min_dist)[i];
+    const int target0 = as_global(S->st.target_idx)[i];
+    const int iter0 = as_global(S->st.cur_iter)[i];
+    const bool collided0 = as_global(S->st.collided)[i] != 0;
+    const int64_t g = S->geom_of_env ? (int64_t)as_global(S->geom_of_env)[i] : i;   // slot_of
+    const double* pts = S->path.pts + (S->path.shared ? 0 : g * (int64_t)S->path.max_len * 5);
+    const int m = S->path.shared ? S->path.max_len : S->path.lens[g];
+
+    const uint64_t draw = a.draw_index ? *as_global(a.draw_index) : a.p.draw_index;
+    const GlobalPtr<double> mean = as_global(a.mean) + i * H * 2;
+    const double zero3[3] = {0.0, 0.0, 0.0};
+    int errs = 0;
+    double first0 = 0.0, first1 = 0.0;   // row 0 of the newest mean
+
+    for (int j = 0; j < a.p.iterations; ++j) {
+        if (a.iter_mean && live)
+            for (int e = kl; e < 2 * H; e += group) as_global(a.iter_mean)[((int64_t)j * a.n + i) * H * 2 + e] = mean[e];
+        // ---- roll-outs: the trip body of lookahead_kernel on a copy of the state, one chunk of candidates at a time
+        double best = -INFINITY;
+        for (int ch = 0; ch < chunks; ++ch) {
+            const int k = ch * kBlock + kl;
+            const int64_t c = ((int64_t)j * a.n + i) * K + k;   // [I][N][K]
+            Robot r = r0;
+            double min_dist = min_dist0;
+            int target = target0, iter = iter0;
+            bool collided = collided0;
+            double ret = 0.0;
+            int reason = 0;
+            bool finished = !live;
+            for (int t = 0; t < H; ++t) {
+                // the perturbations are made (and written to eps_out) for every step, taken or not: the update uses them all
+                float e0 = 0.0f, e1 = 0.0f;
+                if (a.eps_in) {
+                    if (k != 0) {
+                        e0 = as_global(a.eps_in)[(c * H + t) * 2 + 0];
+                        e1 = as_global(a.eps_in)[(c * H + t) * 2 + 1];
+                    }
+                } else if (k != 0) {
+                    mppi_draw(a.p.seed, (uint64_t)i, draw, (uint32_t)j * (uint32_t)H + (uint32_t)t, k, e0, e1);
+                }
+                if (a.eps_out && live) {
+                    as_global(a.eps_out)[(c * H + t) * 2 + 0] = e0;
+                    as_global(a.eps_out)[(c * H + t) * 2 + 1] = e1;
+                }
+                if (__ballot(!finished) == 0) {   // wave-uniform
+                    if (a.eps_out) continue;
+                    break;
+                }
+                const bool active = !finished;
+                const double cmd0 = mppi_command(mean[2 * t + 0], a.p.sigma[0], e0, a.p.low[0], a.p.high[0]);
+                const double cmd1 = mppi_command(mean[2 * t + 1], a.p.sigma[1], e1, a.p.low[1], a.p.high[1]);
+                // ---- _env_step (envs/base/env.py:442-461)
+                Robot nr = r;
+                int drawn = 0;
+                RobotDrive d = robot_step_begin(P, nr, cmd0, cmd1);
+                d.noisy = false;   // the noise-free forward model, whatever the handle's noise_on
+                const int e = robot_step_end(P, nr, d, zero3, drawn);
+                const bool hit = collides_wave(P, S->map, S->cull, L, S->exact_mode, S->dense_threshold, S->wide != 0, active,
+                                               g, nr.p.x, nr.p.y, nr.p.th);
+                if (active) {
+                    if (hit) {   // robot.set_pose(*old_position): pose restored, v = w = 0 (tricycle_model.py:471-476)
+                        nr.p = r.p;
+                        nr.v = 0.0;
+                        nr.w = 0.0;
+                    }
+                    r = nr;
+                    iter += 1;
+                    collided = collided || hit;
+                    double rew;
+                    bool goal;
+                    if (pure_pursuit) {
+                        rew = reward_pure_pursuit(pts, m, r.p.x, r.p.y, collided, min_dist, target);
+                        goal = hypot(pts[5 * (m - 1)] - r.p.x, pts[5 * (m - 1) + 1] - r.p.y) < 1.0;   // done(), reward.py:141-150
+                    } else {
+                        const PathWindow w = path_window_of(P, S->path.shared != 0, S->path.bbox, S->path.index, g, r.p.x, r.p.y);
+                        rew = reward_step<4>(P, pts, w, m, r.p.x, r.p.y, r.p.th, min_dist, target);
+                        goal = target > m - 1;
+                    }
+                    const bool timeout = iter >= P.iteration_timeout;
+                    ret += rew;
+                    errs |= e;
+                    if (goal || timeout || collided) {   // env.py:400-419
+                        reason = (goal ? BCP_DONE_GOAL : 0) | (timeout ? BCP_DONE_TIMEOUT : 0) | (collided ? BCP_DONE_COLLIDED : 0);
+                        finished = true;
+                    }
+                }
+            }
+            if (live) {
+                if (a.iter_ret) as_global(a.iter_ret)[c] = ret;
+                if (a.iter_reason) as_global(a.iter_reason)[c] = (uint8_t)reason;
+            }
+            const double s = (reason & BCP_DONE_COLLIDED) ? ret - a.p.collision_penalty : ret;
+            score[ch * kBlock] = s;
+            best = s > best ? s : best;
+        }
+        // ---- weights: w_k = exp((s_k - max s) / lambda) / sum, over the lane's chunks and then the group's lanes
+        for (int off = group >> 1; off > 0; off >>= 1) {
+            const double o = __shfl_xor(best, off);
+            best = o > best ? o : best;
+        }
+        double total = 0.0;
+        for (int ch = 0; ch < chunks; ++ch) {
+            const double w = exp((score[ch * kBlock] - best) / a.p.lambda_);
+            score[ch * kBlock] = w;
+            total += w;
+        }
+        for (int off = group >> 1; off > 0; off >>= 1) total += __shfl_xor(total, off);
+        for (int ch = 0; ch < chunks; ++ch) score[ch * kBlock] = score[ch * kBlock] / total;
+        // ---- update: mean[t] = sum_k w_k u_k[t], the commands made again from their counters
+        for (int t = 0; t < H; ++t) {
+            const double m0 = mean[2 * t + 0], m1 = mean[2 * t + 1];
+            double acc0 = 0.0, acc1 = 0.0;
+            for (int ch = 0; ch < chunks; ++ch) {
+                const int k = ch * kBlock + kl;
+                float e0 = 0.0f, e1 = 0.0f;
+                if (a.eps_in) {
+                    if (k != 0) {
+                        const int64_t c = ((int64_t)j * a.n + i) * K + k;
+                        e0 = as_global(a.eps_in)[(c * H + t) * 2 + 0];
+                        e1 = as_global(a.eps_in)[(c * H + t) * 2 + 1];
+                    }
+                } else if (k != 0) {
+                    mppi_draw(a.p.seed, (uint64_t)i, draw, (uint32_t)j * (uint32_t)H + (uint32_t)t, k, e0, e1);
+                }
+                const double w = score[ch * kBlock];
+                acc0 += w * mppi_command(m0, a.p.sigma[0], e0, a.p.low[0], a.p.high[0]);
+                acc1 += w * mppi_command(m1, a.p.sigma[1], e1, a.p.low[1], a.p.high[1]);
+            }
+            for (int off = group >> 1; off > 0; off >>= 1) {
+                acc0 += __shfl_xor(acc0, off);
+                acc1 += __shfl_xor(acc1, off);
+            }
+            if (live && kl == 0) {
+                mean[2 * t + 0] = acc0;
+                mean[2 * t + 1] = acc1;
+            }
+            if (t == 0) {
+                first0 = acc0;
+                first1 = acc1;
+            }
+        }
+        __syncthreads();   // this iteration's rows before the next one's loads (one wave per workgroup)
+    }
+    for (int off = group >> 1; off > 0; off >>= 1) errs |= __shfl_xor(errs, off);
+    if (!live || kl != 0) return;
+    if (a.flags & BCP_STEP_ACTIONS_F32) {
+        as_global(reinterpret_cast<float*>(a.action))[2 * i + 0] = (float)first0;
+        as_global(reinterpret_cast<float*>(a.action))[2 * i + 1] = (float)first1;
+    } else {
+        as_global(reinterpret_cast<double*>(a.action))[2 * i + 0] = first0;
+        as_global(reinterpret_cast<double*>(a.action))[2 * i + 1] = first1;
+    }
+    if (a.err) as_global(a.err)[i] = errs;
+}

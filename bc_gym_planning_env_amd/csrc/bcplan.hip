@@ -22,6 +22,7 @@
 #include "bcp_coop.h"
 #include "bcp_step.h"
 #include "bcp_lookahead.h"
+#include "bcp_mppi.h"
 #include "bcp_ego.h"
 #include "bcp_sample.h"
 #include "bcp_aisle.h"
@@ -2185,6 +2186,85 @@ extern "C" int bcp_lookahead(bcp_handle* h, const bcp_lookahead_io* io, uint32_t
         const int64_t lanes = h->n * group;
         hipLaunchKernelGGL(lookahead_best_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, s, a, group);
     }
+    HIP_TRY(hipGetLastError());
+    return BCP_OK;
+}
+
+// Sampling-based refinement of one plan per env (bcp_mppi.h): I iterations of sample, roll out, weight and update in one
+// launch.  Like bcp_lookahead it reads the handle and writes only the caller's arrays.
+extern "C" int bcp_mppi(bcp_handle* h, const bcp_mppi_params* p, const bcp_mppi_io* io, uint32_t flags, void* stream)
+{
+    if (!h || !p || !io) return fail(BCP_E_INVALID, "bcp_mppi: null argument");
+    if (flags & ~(uint32_t)BCP_STEP_ACTIONS_F32) return fail(BCP_E_INVALID, "bcp_mppi: undefined flag bits 0x%x", flags & ~(uint32_t)BCP_STEP_ACTIONS_F32);
+    if (!h->have_map || !h->have_path || !h->have_state)
+        return fail(BCP_E_STATE, "bcp_mppi: costmaps, paths and state must be set first");
+    const bcp_params& hp = h->params;
+    if (hp.control_delay > 0 || hp.pose_delay > 0 || hp.state_delay > 0)
+        return fail(BCP_E_INVALID, "bcp_mppi: control_delay / pose_delay / state_delay > 0 are not supported (every "
+                                   "candidate would need delay queues of its own)");
+    if (p->horizon < 1 || p->iterations < 1) return fail(BCP_E_INVALID, "bcp_mppi: horizon and iterations must be at least 1");
+    const int32_t K = p->n_candidates;
+    if (K < 8 || K > 1024 || (K & (K - 1)) != 0)
+        return fail(BCP_E_INVALID, "bcp_mppi: n_candidates must be a power of two in [8, 1024], got %d", K);
+    if (!(p->lambda_ > 0.0) || !std::isfinite(p->lambda_)) return fail(BCP_E_INVALID, "bcp_mppi: lambda_ must be positive and finite");
+    if (!std::isfinite(p->collision_penalty)) return fail(BCP_E_INVALID, "bcp_mppi: collision_penalty must be finite");
+    for (int d = 0; d < 2; ++d) {
+        if (!(p->sigma[d] >= 0.0) || !std::isfinite(p->sigma[d]))
+            return fail(BCP_E_INVALID, "bcp_mppi: sigma[%d] must be finite and not negative", d);
+        if (!std::isfinite(p->low[d]) || !std::isfinite(p->high[d])) return fail(BCP_E_INVALID, "bcp_mppi: the action box must be finite");
+        if (p->low[d] > p->high[d]) return fail(BCP_E_INVALID, "bcp_mppi: low[%d] > high[%d]", d, d);
+    }
+    if (!io->mean || !io->action) return fail(BCP_E_INVALID, "bcp_mppi: mean and action are required");
+    // element offsets are int64: the largest is 2 * I * N * K * H (eps); the bound leaves the room the header promises
+    const int64_t limit = (int64_t)1 << 62;
+    if (h->n > limit / 5 / p->iterations / K / p->horizon)
+        return fail(BCP_E_INVALID, "bcp_mppi: iterations * n_envs * n_candidates * horizon is too large for 64-bit element offsets");
+    const int group = K < kBlock ? K : kBlock;
+    const int64_t blocks = (h->n * group + kBlock - 1) / kBlock;
+    if (blocks > 0x7FFFFFFF) return fail(BCP_E_INVALID, "bcp_mppi: n_envs exceeds the largest grid");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (h->static_dirty) {
+        const int rc = upload_step_static(h, s);
+        if (rc != BCP_OK) return rc;
+    }
+    if (h->edt_lazy) {   // collides_wave classifies with the uint8 field
+        const int rc = ensure_fields(h, s);
+        if (rc != BCP_OK) return rc;
+    }
+    MppiArgs a;
+    a.S = h->dev_static;
+    a.p = *p;
+    a.mean = io->mean;
+    a.action = io->action;
+    a.mask = io->mask;
+    a.eps_in = io->eps_in;
+    a.eps_out = io->eps_out;
+    a.draw_index = io->draw_index;
+    a.iter_mean = io->iter_mean;
+    a.iter_ret = io->iter_ret;
+    a.iter_reason = io->iter_reason;
+    a.err = io->err;
+    a.n = h->n;
+    a.flags = flags;
+    // the scores of a lane's chunks of candidates sit behind the collision area: 8 bytes per (lane, chunk)
+    const size_t collision = (collision_lds_bytes(hp.n_verts, h->map.in_lds, h->map.rows, h->map.wpr) + 7) & ~(size_t)7;
+    a.score_word = (int32_t)(collision / sizeof(uint32_t));
+    const size_t lds = collision + (size_t)(K / group) * kBlock * sizeof(double);
+    const bool plain = hp.reward_provider == BCP_REWARD_CONTINUOUS;
+    const void* fn = plain ? reinterpret_cast<const void*>(mppi_kernel<true>) : reinterpret_cast<const void*>(mppi_kernel<false>);
+    if (lds > 64 * 1024) {   // (a staged map of nearly 64 KiB plus the scores; the attribute belongs to the function on a device)
+        static std::mutex lds_mutex;
+        static int32_t lds_max[64][2];
+        std::lock_guard<std::mutex> lock(lds_mutex);
+        int32_t& cur = lds_max[h->device & 63][plain ? 1 : 0];
+        if ((int32_t)lds > cur) {
+            HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            cur = (int32_t)lds;
+        }
+    }
+    if (plain) hipLaunchKernelGGL(mppi_kernel<true>, dim3((unsigned)blocks), dim3(kBlock), lds, s, a);
+    else hipLaunchKernelGGL(mppi_kernel<false>, dim3((unsigned)blocks), dim3(kBlock), lds, s, a);
     HIP_TRY(hipGetLastError());
     return BCP_OK;
 }

@@ -128,6 +128,9 @@ class BatchedEgocentricCostmap(object):
     def lookahead(self, actions, **kw):
         return self.env.lookahead(actions, **kw)
 
+    def mppi(self, mean, *args, **kw):
+        return self.env.mppi(mean, *args, **kw)
+
     def get_state(self):
         return self.env.get_state()
 

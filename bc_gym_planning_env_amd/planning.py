@@ -1,7 +1,9 @@
-"""A shooting planner on top of BatchedPlanEnv.lookahead(): the `.act(obs) -> Action` of the reference's motion planning
-challenge (README, bc_gym_planning_env/run_the_challange.py), for N envs at once.  A worked example, not a planning framework: every
-tick each env scores a fixed library of candidate plans with the noise-free forward model and takes the first action of
-the best one (no collision within the horizon first, then the largest return)."""
+"""Planners on top of BatchedPlanEnv: the `.act(obs) -> Action` of the reference's motion planning challenge (README,
+bc_gym_planning_env/run_the_challange.py), for N envs at once.  Worked examples, not a planning framework.
+ShootingPlanner: every tick each env scores a fixed library of candidate plans with the noise-free forward model
+(lookahead()) and takes the first action of the best one (no collision within the horizon first, then the largest return).
+MPPIPlanner: every tick each env refines its own plan by sampling around it (mppi(), one kernel launch) and takes the
+plan's first action; the rest of the plan is the next tick's warm start."""
 import numpy as np
 import torch
 
@@ -46,3 +48,54 @@ class ShootingPlanner(object):
         forward model of the robot")."""
         self.last = self.env.lookahead(self.library, want=("best", "best_action"))
         return self.last.best_action
+
+
+class MPPIPlanner(object):
+    """Model-predictive path integral control per env on BatchedPlanEnv.mppi(): a receding-horizon plan `mean` [N, H, 2]
+    (float64, on the device) refined every tick and shifted by one step afterwards.
+
+    :param env: a BatchedPlanEnv (or a wrapper that forwards mppi); delays must be 0
+    :param horizon: steps H of the plan
+    :param n_candidates: samples K per iteration, a power of two in [8, 1024] (candidate 0 is the plan itself)
+    :param iterations: refinement rounds I per tick
+    :param sigma: standard deviations (v, w) of the perturbations
+    :param lam: temperature of the weights softmax(score / lam)
+    :param collision_penalty: subtracted from the return of a candidate that collides within the horizon
+    :param seed: of the perturbation stream (tick j uses draw index j; the env's noise stream is not involved)
+
+    A new plan -- at the start, and for the envs named by reset_plans() -- holds the centre of the action box,
+    (low + high) / 2, at every step."""
+
+    def __init__(self, env, horizon, n_candidates, iterations, sigma, lam, collision_penalty, seed=0):
+        self.env = env
+        base = env
+        while not hasattr(base, "n_envs"):   # wrappers forward mppi(); the sizes and the device are the batched env's
+            base = base.unwrapped() if callable(base.unwrapped) else base.unwrapped
+        device = base.device
+        self.horizon, self.n_candidates, self.iterations = int(horizon), int(n_candidates), int(iterations)
+        self.sigma, self.lam, self.collision_penalty, self.seed = tuple(sigma), float(lam), float(collision_penalty), int(seed)
+        space = base.action_space
+        centre = 0.5 * (np.asarray(space.low, np.float64) + np.asarray(space.high, np.float64))
+        self.default = torch.from_numpy(centre).to(device)
+        self.mean = self.default.expand(base.n_envs, self.horizon, 2).contiguous()
+        self.draw_index = 0
+        self._fresh = True    # nothing to shift yet
+        self.last = None      # the Mppi of the latest act()
+
+    def reset_plans(self, mask):
+        """Call after env.step() with its done mask ([N], non-zero = the env's episode ended and, under auto-reset, it
+        starts anew): those envs' plans go back to the default."""
+        mask = mask if isinstance(mask, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(mask))
+        mask = mask.to(self.mean.device) != 0
+        self.mean.copy_(torch.where(mask[:, None, None], self.default, self.mean))
+
+    def act(self, observation=None):
+        """actions [N, 2] (float64 device tensor) for env.step().  The observation is not needed (as for ShootingPlanner):
+        the roll-outs start from the env's own state."""
+        if not self._fresh:   # receding horizon: drop the step just taken, repeat the last row
+            self.mean.copy_(torch.cat([self.mean[:, 1:], self.mean[:, -1:]], dim=1))
+        self._fresh = False
+        self.last = self.env.mppi(self.mean, self.sigma, self.iterations, self.n_candidates, self.lam, self.collision_penalty,
+                                  seed=self.seed, draw_index=self.draw_index)
+        self.draw_index += 1
+        return self.last.action

@@ -581,6 +581,61 @@ typedef struct bcp_lookahead_io {
  * other limit on H or K: a candidate is one lane, K may be smaller or larger than a wavefront. */
 int bcp_lookahead(bcp_handle *h, const bcp_lookahead_io *io, uint32_t flags, void *stream);
 
+/* ---- plan refinement by sampling (MPPI): sample, roll out, weight, update -- I times in one launch -------- */
+/* Parameters of bcp_mppi, passed to the kernel by value. */
+typedef struct bcp_mppi_params {
+    int32_t horizon, n_candidates, iterations;   /* H, K, I */
+    double  sigma[2];           /* std of the perturbation per action component, >= 0 */
+    double  low[2], high[2];    /* the action box (action_space.low / high widened to float64) */
+    double  lambda_;            /* temperature, > 0 */
+    double  collision_penalty;  /* subtracted from the score of a candidate whose reason has BCP_DONE_COLLIDED */
+    uint64_t seed, draw_index;  /* perturbation stream; draw_index is used when io.draw_index is NULL */
+} bcp_mppi_params;
+
+/* Host struct of device pointers, caller-owned; N = n_envs. */
+typedef struct bcp_mppi_io {
+    double *mean;               /* [N][H][2] in: the plan to refine (warm start); out: after I iterations */
+    void   *action;             /* [N][2]: step 0 of the refined mean, float64, or float32 with BCP_STEP_ACTIONS_F32 */
+    const uint8_t *mask;        /* optional [N]; mask 0: mean / action rows (and every optional output's) untouched */
+    const float *eps_in;        /* optional [I][N][K][H][2]: parity mode, the perturbations to use (candidate 0's are ignored) */
+    float  *eps_out;            /* optional, same shape: the perturbations used (replay) */
+    const uint64_t *draw_index; /* optional device word: read by the kernel instead of params.draw_index */
+    double *iter_mean;          /* optional [I][N][H][2]: the mean going INTO iteration j */
+    double *iter_ret;           /* optional [I][N][K] */
+    uint8_t *iter_reason;       /* optional [I][N][K] */
+    int32_t *err;               /* optional [N]: OR of the candidates' err bits */
+} bcp_mppi_io;
+
+/* Refines one plan per env by model-predictive path integral control.  All arithmetic is float64, each product and sum
+ * rounded on its own.  For iteration j, env i, candidate k, step t, component d:
+ *     u = min(max(mean_j[i][t][d] + sigma[d] * (double)eps_j[i][k][t][d], low[d]), high[d])
+ * Candidate 0 is the unperturbed mean (eps = 0, written as 0 to eps_out).  Every candidate is rolled out exactly as
+ * bcp_lookahead with noise_z = NULL rolls out per-env float64 actions u: a private copy of env i's state, the noise-free
+ * forward model, no auto-reset, stop after the first done step, ret added in step order from 0.0.  Then
+ *     s_k = ret_k - collision_penalty * [reason_k & BCP_DONE_COLLIDED]
+ *     w_k = exp((s_k - max_k s) / lambda_) / sum_k exp((s_k - max_k s) / lambda_)
+ *     mean_{j+1}[i][t][d] = sum_k w_k * u_k[t][d]        (steps after a candidate's done step count with their u)
+ * After the last iteration `mean` holds mean_I and action[i] = mean_I[i][0] (rounded to float32 under the flag): it can be
+ * passed to bcp_step as it is.  The order of the sum over k is unspecified (partial sums per lane, then a butterfly).
+ * Perturbations: read from eps_in, or drawn on the device -- Philox4x32-10 keyed by `seed` on a counter made of (env index,
+ * draw_index, j, k, t), one float32 Box-Muller pair for the two components: deterministic, |eps| <= 5.89, the same values
+ * for the same (seed, draw_index); distinct streams for draw_index < 2^52 and I * H <= 2^32.  The step's own noise stream
+ * is never read or advanced.
+ * Nothing of the handle changes (as for bcp_lookahead): no step kernel runs, no state array, step counter, noise stream or
+ * episode record is touched.  One kernel launch, asynchronous on `stream`, no allocation, no synchronisation; the launch
+ * arguments are the caller's pointers and *p by value, so a call can be captured into a HIP graph, and with io->draw_index
+ * successive replays draw fresh perturbations once the caller has changed that word.
+ * Refused with BCP_E_INVALID:
+ *   - control_delay, pose_delay or state_delay > 0 (every candidate would need private delay queues);
+ *   - horizon < 1 or iterations < 1;
+ *   - n_candidates not a power of two in [8, 1024] (the K candidates of an env share a wavefront, or K / 64 passes of one);
+ *   - lambda_ not > 0 (or not finite);
+ *   - a negative or non-finite sigma;
+ *   - low[d] > high[d]; a non-finite low, high or collision_penalty;
+ *   - 5 * I * N * K * H >= 2^62 (the element offsets are 64-bit);
+ *   - flag bits other than BCP_STEP_ACTIONS_F32; mean or action NULL. */
+int bcp_mppi(bcp_handle *h, const bcp_mppi_params *p, const bcp_mppi_io *io, uint32_t flags, void *stream);
+
 /* ---- measurement -------------------------------------------------------------------------------------- */
 /* Which kernels a bcp_step() of this handle launches, as configured now: 0 = step_kernel alone (no distance field, or a
  * forced mode), 1 = step_fast_pair_kernel alone (every undecided pose settled in place), 2 = step_fast_pair_kernel +

@@ -1,0 +1,560 @@
+"""bcp_mppi on the GPU: I iterations of sample -> roll out -> weight -> update per env in one launch.  Every check is per
+iteration and teacher-forced: iteration j is judged from the mean the kernel itself took into it (iter_mean[j]) and the
+perturbations it used (eps), so a last-bit difference in one weight cannot cascade into another trajectory.
+
+Roll-outs: u_j is rebuilt in numpy (exact IEEE operations, tests/mppi_ref.candidates); env.lookahead(u_j) must give
+iter_ret[j] and iter_reason[j] bit for bit (the same arithmetic), and the CPU oracle the same reasons and ret within 1e-9.
+
+Update: the next mean is compared with the restatement (weights in np.longdouble) applied to the kernel's own iter_ret[j],
+iter_reason[j] and u_j, within  4 (K + 16) 2^-53 max(|low|, |high|).  Derivation: with U = max(|low|, |high|) >= |u| and
+eps = 2^-53, x_k = (s_k - max s) / lambda carries two roundings, which exp turns into an absolute error of at most
+2 eps |x_k| exp(x_k) <= eps (|x| e^-|x| <= 1 / e); exp itself is within 1 ulp (ocml's documented bound for the float64 exp),
+so every e_k <= 1 is off by at most 3 eps.  The sum Z >= 1 of K such terms has a relative error of at most (K - 1) eps from
+its additions plus 3 K eps / Z from its terms, the quotient w_k = e_k / Z one rounding more, and the K-term sum of the
+products w_k u_k at most (K - 1) eps sum |w_k u_k| <= (K - 1) eps U plus one rounding per product: in all less than
+(2 K + 3 K / Z + 8) eps U <= 4 (K + 16) eps U in whatever order the sums are taken (Z >= 1 is the worst case only when a
+single candidate holds all the weight, where the other terms vanish)."""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+
+import lookahead_ref as LR
+import mppi_ref as MR
+from util import GOLDEN, env_from_traj
+
+pytestmark = pytest.mark.gpu
+
+ALL = ("eps", "iter_mean", "iter_ret", "iter_reason", "err")
+OUT = ("mean", "action") + ALL
+
+
+def _set_start(torch, env, start):
+    env.state.robot.copy_(torch.from_numpy(start.robot))
+    env.state.min_spat_dist_so_far.copy_(torch.from_numpy(start.min_dist))
+    env.state.target_idx.copy_(torch.from_numpy(start.target_idx))
+    env.state.current_iter.copy_(torch.from_numpy(start.cur_iter))
+    env.state.robot_collided.copy_(torch.from_numpy(start.collided))
+    if start.geom is not None:
+        env.geom_of_env.copy_(torch.from_numpy(start.geom))
+
+
+def _read_start(env):
+    s = env.state
+    return LR.StartState(s.robot.cpu().numpy(), s.min_spat_dist_so_far.cpu().numpy(), s.target_idx.cpu().numpy(),
+                         s.current_iter.cpu().numpy(), s.robot_collided.cpu().numpy(),
+                         None if env.geom_of_env is None else env.geom_of_env.cpu().numpy())
+
+
+def _box(env):
+    return np.asarray(env.action_space.low, np.float64), np.asarray(env.action_space.high, np.float64)
+
+
+def _tolerance(env, k):
+    low, high = _box(env)
+    return 4.0 * (k + 16) * 2.0 ** -53 * max(np.abs(low).max(), np.abs(high).max())
+
+
+def _random_mean(env, rng, n, h):
+    """a plan that is not constant over the horizon, inside the box"""
+    low, high = _box(env)
+    return np.ascontiguousarray(rng.uniform(low, high, (n, h, 2)))
+
+
+def _snapshot(res):
+    return {f: getattr(res, f).clone() for f in OUT if getattr(res, f) is not None}
+
+
+def _teacher_forced(torch, env, res, sigma, lam, penalty, oracle_args=None, rows=None, tag=""):
+    """res: Mppi with all optional outputs.  oracle_args: (oracle, params, world, start) or None.  rows: envs to compare"""
+    low, high = _box(env)
+    it, n, k = res.iter_ret.shape
+    sel = slice(None) if rows is None else rows
+    tsel = slice(None) if rows is None else torch.from_numpy(np.asarray(rows)).cuda()
+    tol = _tolerance(env, k)
+    worst_update, worst_ret, hits = 0.0, 0.0, 0
+    for j in range(it):
+        mean_j = res.iter_mean[j].cpu().numpy()
+        eps_j = res.eps[j].cpu().numpy()
+        assert (eps_j[sel][:, 0] == 0).all(), "candidate 0 is the unperturbed mean"
+        u = MR.candidates(mean_j, sigma, eps_j, low, high)
+        la = env.lookahead(torch.from_numpy(MR.as_lookahead_actions(u)).cuda(), want=())
+        ret, reason = res.iter_ret[j].cpu().numpy(), res.iter_reason[j].cpu().numpy()
+        assert torch.equal(la.ret[tsel], res.iter_ret[j][tsel]), "%s iteration %d: ret differs from lookahead's by %g" % (
+            tag, j, (la.ret[tsel] - res.iter_ret[j][tsel]).abs().max())
+        assert torch.equal(la.reason[tsel], res.iter_reason[j][tsel]), "%s iteration %d: reason" % (tag, j)
+        if oracle_args is not None:
+            oracle, params, world, start = oracle_args
+            exp = LR.oracle_lookahead(oracle, params, world, start, MR.as_lookahead_actions(u), threads=16)
+            np.testing.assert_array_equal(reason[sel], exp["reason"][sel], err_msg="%s iteration %d reason" % (tag, j))
+            worst_ret = max(worst_ret, np.abs(ret[sel] - exp["ret"][sel]).max())
+        want, _ = MR.update(u, ret, reason, lam, penalty)
+        got = (res.iter_mean[j + 1] if j + 1 < it else res.mean).cpu().numpy()
+        worst_update = max(worst_update, np.abs(got[sel] - want[sel]).max())
+        hits += int(((reason[sel] & LR.DONE_COLLIDED) != 0).sum())
+    print("%s: max |mean - restatement| = %.3g (bound %.3g), max |ret - oracle| = %.3g, %d collided candidates"
+          % (tag, worst_update, tol, worst_ret, hits))
+    assert worst_ret <= 1e-9, tag
+    assert worst_update <= tol, tag
+    assert torch.equal(res.action[tsel], res.mean[:, 0][tsel]), tag
+    return hits
+
+
+def _scenario_env(torch, kind, n):
+    """'scatter' / 'goal' on a handle that has noise on (the refinement must not care), 'aisle' as recorded"""
+    g, name, start = MR.scenario_world(kind, n)
+    env = env_from_traj(g, "mini_with_noise" if "mini" in name else name, n_envs=n)
+    assert env.noise_parameters is not None
+    low, high = _box(env)
+    np.testing.assert_array_equal(low, MR.ACTION_LOW)
+    np.testing.assert_array_equal(high, MR.ACTION_HIGH)
+    _set_start(torch, env, start)
+    return g, name, start, env
+
+
+# ---------------------------------------------------------------------------------------------- 1. scenarios and shapes
+@pytest.mark.parametrize("kind", ["scatter", "goal", "aisle"])
+def test_scenarios_teacher_forced(torch_cuda, oracle, kind):
+    """the scenarios tests/test_mppi_host.py shows to be non-vacuous, with its perturbations (parity mode) and I = 4"""
+    torch = torch_cuda
+    (n, k, h), _, sigma, lam, penalty = MR.SCENARIOS[kind]
+    g, name, start, env = _scenario_env(torch, kind, n)
+    eps = MR.host_eps(MR.EPS_SEED, 5, n, k, h)[:4]
+    res = env.mppi(MR.initial_mean(kind, n, h), sigma, 4, k, lam, penalty, eps=eps, want=ALL)
+    assert torch.equal(res.eps, torch.from_numpy(eps).cuda()), "parity mode: the perturbations used are the ones given"
+    hits = _teacher_forced(torch, env, res, sigma, lam, penalty,
+                           (oracle, MR.scenario_oracle_params(oracle, name), LR.shared_world(g), start), tag=kind)
+    assert (res.err == 0).all()
+    if kind != "goal":
+        assert hits >= 100
+    # the first iteration is the restatement's, reasons exactly and returns within the oracle's 1e-9
+    u0 = MR.candidates(MR.initial_mean(kind, n, h), sigma, eps[0], *_box(env))
+    exp = LR.oracle_lookahead(oracle, MR.scenario_oracle_params(oracle, name), LR.shared_world(g), start,
+                              MR.as_lookahead_actions(u0), threads=16)
+    np.testing.assert_array_equal(res.iter_reason[0].cpu().numpy(), exp["reason"])
+    np.testing.assert_allclose(res.iter_ret[0].cpu().numpy(), exp["ret"], rtol=0, atol=1e-9)
+
+
+@pytest.mark.parametrize("kind,n,k,h,it", [("scatter", 64, 64, 16, 4), ("scatter", 2048, 16, 8, 2), ("scatter", 32, 8, 32, 3),
+                                           ("aisle", 16, 256, 16, 2), ("aisle", 8, 1024, 8, 1)])
+def test_shapes_teacher_forced_with_device_perturbations(torch_cuda, oracle, kind, n, k, h, it):
+    """K below, at and above a wavefront (groups of K lanes; one chunk; 4 and 16 chunks), the perturbations drawn on the
+    device; the inputs of the 'scatter' and 'aisle' scenarios at other shapes"""
+    torch = torch_cuda
+    _, _, sigma, lam, penalty = MR.SCENARIOS[kind]
+    g, name, start, env = _scenario_env(torch, kind, n)
+    res = env.mppi(MR.initial_mean(kind, n, h), sigma, it, k, lam, penalty, seed=7, draw_index=3, want=ALL)
+    _teacher_forced(torch, env, res, sigma, lam, penalty,
+                    (oracle, MR.scenario_oracle_params(oracle, name), LR.shared_world(g), start), tag="%dx%dx%dx%d" % (n, k, h, it))
+    assert (res.eps[:, :, 1:] != 0).any() and bool(torch.isfinite(res.eps).all())
+
+
+def test_odd_env_count_and_mask(torch_cuda, oracle):
+    """N = 37 with K = 16: the last wave holds one env and three shadows; rows of envs with mask 0 keep every output"""
+    torch = torch_cuda
+    n, k, h, it = 37, 16, 12, 2
+    _, _, sigma, lam, penalty = MR.SCENARIOS["scatter"]
+    g, name, start, env = _scenario_env(torch, "scatter", n)
+    rng = np.random.RandomState(1)
+    mean0 = _random_mean(env, rng, n, h)
+    res = env.mppi(mean0, sigma, it, k, lam, penalty, seed=1, want=ALL)
+    args = (oracle, MR.scenario_oracle_params(oracle, name), LR.shared_world(g), start)
+    _teacher_forced(torch, env, res, sigma, lam, penalty, args, tag="N=37")
+    first = _snapshot(res)
+    mask = (np.arange(n) % 3 != 1).astype(np.uint8)
+    off = torch.from_numpy(mask == 0).cuda()
+    mean1 = torch.from_numpy(_random_mean(env, rng, n, h)).cuda()
+    before = mean1.clone()
+    res2 = env.mppi(mean1, sigma, it, k, lam, penalty, seed=2, mask=mask, want=ALL)
+    assert res2.mean.data_ptr() == mean1.data_ptr(), "a float64 device tensor is refined in place"
+    assert torch.equal(res2.mean[off], before[off])
+    for f in ("action", "err", "eps", "iter_mean", "iter_ret", "iter_reason"):
+        a, b = getattr(res2, f), first[f]
+        assert torch.equal(a[off] if a.shape[0] == n else a[:, off], b[off] if b.shape[0] == n else b[:, off]), f
+    _teacher_forced(torch, env, res2, sigma, lam, penalty, args, rows=np.nonzero(mask)[0], tag="masked")
+    assert not torch.equal(res2.mean[~off], before[~off])
+
+
+# ---------------------------------------------------------------------------------------------- 2. configurations
+def _drive(env, rng, steps, gain):
+    for _ in range(steps):
+        a = env.action_space.sample_batch(env.n_envs, rng)
+        a[:, 0] *= gain
+        env.step(a)
+
+
+def _configuration(torch, oracle, env, params, world, k, h, it, tag, sigma=(0.2, 0.8), lam=0.3, penalty=2.0, min_hits=0):
+    rng = np.random.RandomState(17)
+    start = _read_start(env)
+    res = env.mppi(_random_mean(env, rng, env.n_envs, h), sigma, it, k, lam, penalty, seed=11, draw_index=5, want=ALL)
+    hits = _teacher_forced(torch, env, res, sigma, lam, penalty, (oracle, params, world, start), tag=tag)
+    assert hits >= min_hits, tag
+    after = _read_start(env)
+    for f in ("robot", "min_dist", "target_idx", "cur_iter", "collided"):
+        np.testing.assert_array_equal(getattr(start, f), getattr(after, f))
+
+
+def test_diffdrive(torch_cuda, oracle):
+    torch = torch_cuda
+    from bc_gym_planning_env_amd import BatchedPlanEnv, CostMap2D, EnvParams
+    g = np.load(os.path.join(GOLDEN, "g8dd_traj_mini64_00.npz"))
+    res, n = float(g["resolution"]), 64
+    params = EnvParams(goal_spat_dist=0.2, goal_ang_dist=np.pi / 8, resolution=res, refine_path=False,
+                       robot_name='industrial_diffdrive_v1')
+    env = BatchedPlanEnv(CostMap2D(g["costmap"], res, g["origin"]), g["path"], params, n_envs=n, noise_parameters=None)
+    rng = np.random.RandomState(3)
+    robot = np.zeros((7, n))
+    robot[:] = g["start_state"][:, None]
+    robot[0:3] += np.concatenate([rng.normal(0, 0.05, (2, n)), rng.normal(0, 0.4, (1, n))])
+    _set_start(torch, env, LR.StartState(robot, np.full(n, float(g["init_min_dist"])), np.full(n, int(g["init_target_idx"])),
+                                         np.zeros(n)))
+    p = oracle.make_params("diffdrive", noise=None, spatial_precision=0.2, angular_precision=np.pi / 8)
+    _configuration(torch, oracle, env, p, LR.shared_world(g), 32, 24, 2, "diffdrive")
+
+
+def test_pure_pursuit(torch_cuda, oracle):
+    torch = torch_cuda
+    from bc_gym_planning_env_amd import BatchedPlanEnv, CostMap2D, EnvParams
+    g = np.load(os.path.join(GOLDEN, "g8_traj_aisle_default.npz"))
+    res, n = float(g["resolution"]), 64
+    params = EnvParams(resolution=res, refine_path=False, reward_provider_name='continuous_reward_pure_pursuit')
+    env = BatchedPlanEnv(CostMap2D(g["costmap"], res, g["origin"]), g["path"], params, n_envs=n)
+    _drive(env, np.random.RandomState(4), 30, 2.0)
+    p = oracle.make_params("tricycle", noise=None, reward_provider=oracle.REWARD_PURE_PURSUIT)
+    _configuration(torch, oracle, env, p, LR.shared_world(g), 64, 24, 2, "pure pursuit", lam=0.05)
+
+
+def test_private_maps_and_paths(torch_cuda, oracle):
+    """every env with its own (padded) costmap and its own path of its own length"""
+    torch = torch_cuda
+    from bc_gym_planning_env_amd import BatchedPlanEnv, CostMap2D, EnvParams
+    names = ["g8_traj_aisle_c4_00.npz", "g8_traj_aisle_c4_10.npz", "g8_traj_aisle_c4_01.npz", "g8_traj_aisle_c4_11.npz"]
+    gs = [np.load(os.path.join(GOLDEN, nm)) for nm in names]
+    n = 96
+    res = float(gs[0]["resolution"])
+    costmaps = [CostMap2D(gs[i % 4]["costmap"], res, gs[i % 4]["origin"]) for i in range(n)]
+    paths = [gs[i % 4]["path"][:len(gs[i % 4]["path"]) - (i % 3)] for i in range(n)]
+    env = BatchedPlanEnv(costmaps, paths, EnvParams(resolution=res, refine_path=False), n_envs=n, seed=5)
+    rows = max(c.get_data().shape[0] for c in costmaps)
+    cols = max(c.get_data().shape[1] for c in costmaps)
+    maps = np.full((n, rows, cols), 254, dtype=np.uint8)   # (poisoned padding: never read as in-map)
+    vr, vc = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    for i, c in enumerate(costmaps):
+        d = c.get_data()
+        maps[i, :d.shape[0], :d.shape[1]] = d
+        vr[i], vc[i] = d.shape
+    origins = np.stack([c.get_origin() for c in costmaps])
+    pbuf = np.zeros((n, max(len(p) for p in paths), 3))
+    for i, p_ in enumerate(paths):
+        pbuf[i, :len(p_)] = p_
+    env.set_costmap_tensors(torch.from_numpy(maps).cuda(), torch.from_numpy(origins).cuda(), res,
+                            torch.from_numpy(vr).cuda(), torch.from_numpy(vc).cuda())
+    _drive(env, np.random.RandomState(9), 25, 2.0)
+    world = dict(costmaps=maps, origins=origins, resolution=res, paths=pbuf, lens=np.array([len(p_) for p_ in paths]),
+                 rows=vr, cols=vc)
+    _configuration(torch, oracle, env, oracle.make_params("tricycle", noise=None), world, 16, 24, 2, "private maps")
+
+
+def _mini_pool_env(n, **kw):
+    from bc_gym_planning_env_amd import EnvParams, mini_env
+    params = mini_env.RandomMiniEnvParams(env_params=EnvParams(goal_ang_dist=np.pi / 8., goal_spat_dist=0.2,
+                                                               iteration_timeout=60))
+    pool = mini_env.sample_pool(params, list(range(100, 107)), 3)
+    env = mini_env.BatchedRandomMiniEnv(n, params, pool=pool, seed=11, noise_parameters="planenv", **kw)
+    paths = env._paths
+    pbuf = np.zeros((len(paths), max(len(p) for p in paths), 3))
+    for j, p in enumerate(paths):
+        pbuf[j, :len(p)] = p
+    world = dict(costmaps=np.stack([c.get_data() for c in pool.costmaps]), origins=np.stack([c.get_origin() for c in pool.costmaps]),
+                 resolution=params.env_params.resolution, paths=pbuf, lens=np.array([len(q) for q in paths]))
+    return env, world
+
+
+def test_mini_pool_with_envs_on_different_entries(torch_cuda, oracle):
+    torch = torch_cuda
+    n = 96
+    env, world = _mini_pool_env(n, auto_reset=True)
+    _drive(env, np.random.RandomState(4), 75, 3.0)
+    assert len(np.unique(env.geom_of_env.cpu().numpy())) >= 16
+    p = oracle.make_params("tricycle", noise=None, spatial_precision=0.2, angular_precision=np.pi / 8, iteration_timeout=60)
+    _configuration(torch, oracle, env, p, world, 32, 32, 2, "mini pool")
+
+
+def test_aisle_pool_with_envs_on_different_entries(torch_cuda, oracle):
+    torch = torch_cuda
+    from bc_gym_planning_env_amd import EnvParams, aisle_env
+    ep = EnvParams(iteration_timeout=60)
+    n = 64
+    env = aisle_env.BatchedRandomAisleTurnEnv(n, ep, seeds=list(range(16)), episodes=4, sampler="device_resident",
+                                              auto_reset=True, seed=5)
+    dp = env.pool
+    rows, cols = [int(v) for v in dp.shapes.cpu().numpy().max(0)]
+    padded = dp.maps.cpu().numpy()
+    vr, vc = dp.valid_rows.cpu().numpy(), dp.valid_cols.cpu().numpy()
+    maps = np.zeros((len(dp), rows, cols), dtype=np.uint8)   # the oracle reads entry g as vr[g] rows of vc[g] cells
+    for g_ in range(len(dp)):
+        maps[g_].reshape(-1)[:vr[g_] * vc[g_]] = padded[g_, :vr[g_], :vc[g_]].ravel()
+    world = dict(costmaps=maps, origins=dp.origins.cpu().numpy(), resolution=ep.resolution,
+                 paths=dp.path_points.cpu().numpy(), lens=dp.lens.cpu().numpy(), rows=vr, cols=vc)
+    _drive(env, np.random.RandomState(21), 90, 3.0)
+    assert len(np.unique(env.geom_of_env.cpu().numpy())) >= 16
+    p = oracle.make_params("tricycle", noise=None, spatial_precision=ep.goal_spat_dist, angular_precision=ep.goal_ang_dist,
+                           iteration_timeout=60)
+    _configuration(torch, oracle, env, p, world, 32, 24, 2, "aisle pool")
+
+
+# ---------------------------------------------------------------------------------------------- 3. the exact limit
+def test_one_hot_limit_is_bit_exact(torch_cuda):
+    """lambda = 1 / 1024 and whole-number returns: wherever the best score is unique, the runner-up is >= 1024 lambda
+    below it, every other weight is exp(<= -1024) = 0 and the best one 1 / 1 -- the new mean IS the best candidate's u"""
+    torch = torch_cuda
+    n, k, h = 64, 8, 32
+    _, _, sigma, _, penalty = MR.SCENARIOS["scatter"]
+    lam = 1.0 / 1024
+    g, name, start, env = _scenario_env(torch, "scatter", n)
+    res = env.mppi(MR.initial_mean("scatter", n, h), sigma, 1, k, lam, penalty, seed=5, want=ALL)
+    score = MR.scores(res.iter_ret[0].cpu().numpy(), res.iter_reason[0].cpu().numpy(), penalty)
+    order = np.sort(score, axis=1)
+    unique = np.nonzero(order[:, -1] - order[:, -2] >= 800 * lam)[0]
+    print("%d of %d envs have a unique best candidate" % (len(unique), n))
+    assert len(unique) >= 4
+    u = MR.candidates(res.iter_mean[0].cpu().numpy(), sigma, res.eps[0].cpu().numpy(), *_box(env))
+    best = score.argmax(axis=1)
+    assert len(set(best[unique].tolist())) >= 2
+    np.testing.assert_array_equal(res.mean.cpu().numpy()[unique], u[unique, best[unique]])
+
+
+# ---------------------------------------------------------------------------------------------- 4. the device stream
+def test_device_stream_replays_and_is_standard_normal(torch_cuda):
+    torch = torch_cuda
+    n, k, h, it = 256, 64, 16, 2
+    _, _, sigma, lam, penalty = MR.SCENARIOS["goal"]
+    g, name, start, env = _scenario_env(torch, "goal", n)
+    mean0 = MR.initial_mean("goal", n, h)
+
+    def call(**kw):
+        return _snapshot(env.mppi(mean0, sigma, it, k, lam, penalty, want=ALL, **kw))
+
+    a = call(seed=9, draw_index=4)
+    replay = call(eps=a["eps"])
+    again = call(seed=9, draw_index=4)
+    for f in OUT:
+        assert torch.equal(a[f], replay[f]), "eps_out fed back as eps_in: " + f
+        assert torch.equal(a[f], again[f]), "the same (seed, draw_index) twice: " + f
+    word = torch.tensor([4], dtype=torch.int64, device="cuda")
+    assert torch.equal(call(seed=9, draw_index=word)["eps"], a["eps"]), "the device word is read like the host value"
+    eps = a["eps"]
+    assert not torch.equal(call(seed=9, draw_index=5)["eps"], eps) and not torch.equal(call(seed=10, draw_index=4)["eps"], eps)
+    assert not torch.equal(call(seed=9, draw_index=1 << 32 | 4)["eps"], eps)
+    e = eps.cpu().numpy()
+    assert (e[:, :, 0] == 0).all(), "candidate 0"
+    assert (e[0] != e[1])[:, 1:].mean() > 0.99, "iterations"
+    assert (e[:, 0] != e[:, 1])[:, 1:].mean() > 0.99 and (e[:, :, 1] != e[:, :, 2]).mean() > 0.99, "envs, candidates"
+    assert (e[:, :, 1:, 0] != e[:, :, 1:, 1]).mean() > 0.99 and (e[..., 0] != e[..., 1])[:, :, 1:].mean() > 0.99, "steps, components"
+    z = e[:, :, 1:].astype(np.float64).ravel()
+    m = z.size
+    assert m >= 10 ** 6 and np.isfinite(z).all()
+    mu, var = z.mean(), z.var()
+    print("M = %d: sample mean %.5f (bound %.5f), sample variance %.5f (bound 1 +- %.5f), max |eps| %.3f"
+          % (m, mu, 5 / np.sqrt(m), var, 5 * np.sqrt(2.0 / m), np.abs(z).max()))
+    assert abs(mu) <= 5 / np.sqrt(m) and abs(var - 1) <= 5 * np.sqrt(2.0 / m)
+    # the two components of a pair are uncorrelated, neighbouring steps too (same tolerance as the mean: products of
+    # independent standard normals have variance 1)
+    pairs = e[:, :, 1:].astype(np.float64)
+    assert abs((pairs[..., 0] * pairs[..., 1]).mean()) <= 5 / np.sqrt(m / 2)
+    assert abs((pairs[:, :, :, :-1] * pairs[:, :, :, 1:]).mean()) <= 5 / np.sqrt(m * (h - 1) / h)
+
+
+# ---------------------------------------------------------------------------------------------- 5. nothing moved
+def _state_tensors(env):
+    s = env.state
+    return [s.robot, s.min_spat_dist_so_far, s.target_idx, s.current_iter, s.robot_collided, env.geom_of_env]
+
+
+def test_mppi_leaves_the_handle_untouched(torch_cuda):
+    """on-device noise, a pool, auto-reset and a bound episode record: state, geom_of_env and the record are bit-identical
+    after each of 50 calls, and the steps in between -- rewards, dones, drawn normals (the tick words key them), episode
+    ends -- equal those of a twin that never called it"""
+    torch = torch_cuda
+    n, k, h = 256, 32, 12
+    rng = np.random.RandomState(2)
+    envs = []
+    for _ in range(2):
+        env, _w = _mini_pool_env(n, auto_reset=True)
+        envs.append((env, env.enable_episode_record()))
+    (env, ends), (twin, twin_ends) = envs
+    zout, zout_twin = (torch.zeros(n, 3, dtype=torch.float64, device="cuda") for _ in range(2))
+    mean = torch.from_numpy(_random_mean(env, rng, n, h)).cuda()
+    n_ends = 0
+    for t in range(60):
+        a = env.action_space.sample_batch(n, rng)
+        a[:, 0] *= 3.0
+        if t >= 10:
+            before = [x.clone() for x in _state_tensors(env)] + [ends.ret.clone(), ends.count.clone(), ends.reason.clone()]
+            res = env.mppi(mean, (0.2, 0.6), 2, k, 0.3, 2.0, seed=1, draw_index=t, want=ALL)
+            after = _state_tensors(env) + [ends.ret, ends.count, ends.reason]
+            for b, x in zip(before, after):
+                assert torch.equal(b, x), "step %d" % t
+            assert bool(torch.isfinite(res.mean).all())
+        _, r1, d1, _ = env.step(a, noise_z_out=zout)
+        _, r2, d2, _ = twin.step(a, noise_z_out=zout_twin)
+        assert torch.equal(r1, r2) and torch.equal(d1, d2), t
+        assert torch.equal(torch.nan_to_num(zout, nan=7.0), torch.nan_to_num(zout_twin, nan=7.0)), t
+        for x, y in zip(_state_tensors(env), _state_tensors(twin)):
+            assert torch.equal(x, y), t
+        m = int(ends.count[0])
+        assert m == int(twin_ends.count[0]) and m <= n and torch.equal(ends.reason, twin_ends.reason), t
+        o1, o2 = torch.argsort(ends.env_ids[:m]), torch.argsort(twin_ends.env_ids[:m])
+        for x, y in ((ends.env_ids, twin_ends.env_ids), (ends.geom, twin_ends.geom), (ends.final_return, twin_ends.final_return),
+                     (ends.length, twin_ends.length), (ends.final_state.robot.T, twin_ends.final_state.robot.T)):
+            assert torch.equal(x[:m][o1], y[:m][o2]), "episode ends, step %d" % t
+        assert torch.equal(ends.ret, twin_ends.ret), t
+        n_ends += m
+    assert n_ends > n
+    env.check_errors()
+    twin.check_errors()
+
+
+# ---------------------------------------------------------------------------------------------- 6. action, refusals, capture
+def test_action_is_step_zero_of_the_mean_and_steps(torch_cuda):
+    torch = torch_cuda
+    n, k, h = 64, 16, 8
+    _, _, sigma, lam, penalty = MR.SCENARIOS["goal"]
+    g, name, start, env = _scenario_env(torch, "goal", n)
+    r64 = _snapshot(env.mppi(MR.initial_mean("goal", n, h), sigma, 2, k, lam, penalty, seed=3))
+    r32 = _snapshot(env.mppi(MR.initial_mean("goal", n, h), sigma, 2, k, lam, penalty, seed=3, action_dtype=torch.float32))
+    assert r64["action"].dtype == torch.float64 and torch.equal(r64["action"], r64["mean"][:, 0])
+    assert r32["action"].dtype == torch.float32 and torch.equal(r32["mean"], r64["mean"])
+    assert torch.equal(r32["action"], r64["mean"][:, 0].to(torch.float32))
+    low, high = _box(env)
+    a = r64["action"].cpu().numpy()
+    assert (a >= low).all() and (a <= high).all() and len(np.unique(a[:, 1])) > n // 2
+    _, rew, done, _ = env.step(r32["action"])
+    _set_start(torch, env, start)
+    _, rew64, _, _ = env.step(r64["action"])
+    env.check_errors()
+    assert bool(torch.isfinite(rew).all()) and bool(torch.isfinite(rew64).all())
+
+
+def _raw(env, mean, action, **over):
+    from bc_gym_planning_env_amd import _lib
+    low, high = _box(env)
+    p, io = _lib.BcpMppiParams(), _lib.BcpMppiIO()
+    p.horizon, p.n_candidates, p.iterations = int(mean.shape[1]), 16, 1
+    for d in range(2):
+        p.sigma[d], p.low[d], p.high[d] = 0.1, low[d], high[d]
+    p.lambda_, p.collision_penalty = 0.5, 1.0
+    io.mean, io.action = mean.data_ptr(), action.data_ptr()
+    flags = over.pop("flags", 0)
+    for name, v in over.items():
+        if isinstance(v, tuple):
+            getattr(p, name)[v[0]] = v[1]
+        else:
+            setattr(p, name, v)
+    return env._lib.bcp_mppi(env._h, C.byref(p), C.byref(io), flags, None), env._lib.bcp_last_error()
+
+
+def test_refusals(torch_cuda):
+    torch = torch_cuda
+    from bc_gym_planning_env_amd import BatchedPlanEnv, CostMap2D, EnvParams, _lib
+    g = LR.mini_fixture()
+    res = float(g["resolution"])
+    mean = torch.zeros(8, 4, 2, dtype=torch.float64, device="cuda") + 0.3
+    action = torch.zeros(8, 2, dtype=torch.float64, device="cuda")
+    for delays in (dict(control_delay=1), dict(pose_delay=2), dict(state_delay=1)):
+        params = EnvParams(goal_spat_dist=0.2, goal_ang_dist=np.pi / 8, resolution=res, refine_path=False, **delays)
+        env = BatchedPlanEnv(CostMap2D(g["costmap"], res, g["origin"]), g["path"], params, n_envs=8)
+        with pytest.raises(_lib.BcpError, match="error -1: .*delay"):
+            env.mppi(mean, (0.1, 0.1), 1, 16, 0.5, 1.0)
+    env = env_from_traj(g, "mini_nonoise", n_envs=8)
+    assert _raw(env, mean, action)[0] == 0
+    torch.cuda.synchronize()
+    inf, nan = float("inf"), float("nan")
+    bad = [dict(horizon=0), dict(horizon=-3), dict(iterations=0), dict(iterations=-1)]
+    bad += [dict(n_candidates=v) for v in (0, 1, 4, 7, 12, 24, 100, 1023, 2048, -8)]
+    bad += [dict(lambda_=v) for v in (0.0, -1.0, nan, inf)]
+    bad += [dict(sigma=(d, v)) for d in (0, 1) for v in (-0.1, nan, inf)]
+    bad += [dict(low=(d, v)) for d in (0, 1) for v in (2.0, nan, -inf)]      # (2.0 > high)
+    bad += [dict(high=(d, v)) for d in (0, 1) for v in (-2.0, nan, inf)]     # (-2.0 < low)
+    bad += [dict(collision_penalty=v) for v in (nan, inf, -inf)]
+    bad += [dict(horizon=2 ** 31 - 1, iterations=2 ** 31 - 1, n_candidates=1024), dict(flags=1), dict(flags=1 << 8), dict(flags=4)]
+    for over in bad:
+        rc, msg = _raw(env, mean, action, **over)
+        assert rc == -1 and msg.startswith(b"bcp_mppi"), (over, rc, msg)
+    assert b"too large" in _raw(env, mean, action, horizon=2 ** 31 - 1, iterations=2 ** 31 - 1, n_candidates=1024)[1]
+    for ok in (dict(n_candidates=8), dict(n_candidates=1024), dict(sigma=(0, 0.0)), dict(low=(0, float(_box(env)[1][0])))):
+        assert _raw(env, mean, action, **ok)[0] == 0, ok
+    torch.cuda.synchronize()
+    with pytest.raises(ValueError):
+        env.mppi(torch.zeros(8, 4, 3), (0.1, 0.1), 1, 16, 0.5, 1.0)
+    with pytest.raises(ValueError):
+        env.mppi(mean, (0.1, 0.1), 1, 16, 0.5, 1.0, want=("esp",))
+    with pytest.raises(ValueError):
+        env.mppi(mean, (0.1, 0.1), 1, 16, 0.5, 1.0, eps=torch.zeros(1, 8, 16, 5, 2))
+
+
+def test_captured_call_draws_afresh_from_a_device_word(torch_cuda):
+    """captured with draw_index on the device, replayed three times with the word incremented in between == three direct
+    calls with draw_index 0, 1, 2 (each refining, in place, the mean the one before left)"""
+    torch = torch_cuda
+    n, k, h, it = 128, 32, 12, 2
+    _, _, sigma, lam, penalty = MR.SCENARIOS["goal"]
+    g, name, start, env = _scenario_env(torch, "goal", n)
+    mean0 = torch.from_numpy(MR.initial_mean("goal", n, h)).cuda()
+    direct = []
+    mean = mean0.clone()
+    for d in range(3):
+        direct.append(_snapshot(env.mppi(mean, sigma, it, k, lam, penalty, seed=4, draw_index=d, want=ALL)))
+    assert not torch.equal(direct[0]["eps"], direct[1]["eps"]) and not torch.equal(direct[0]["mean"], direct[1]["mean"])
+    word = torch.zeros(1, dtype=torch.int64, device="cuda")
+    mean = mean0.clone()
+    stream = torch.cuda.Stream()
+    stream.wait_stream(torch.cuda.current_stream())
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.stream(stream):
+        env.mppi(mean, sigma, it, k, lam, penalty, seed=4, draw_index=word, want=ALL)
+        torch.cuda.synchronize()
+        with torch.cuda.graph(graph, stream=stream):
+            res = env.mppi(mean, sigma, it, k, lam, penalty, seed=4, draw_index=word, want=ALL)
+    torch.cuda.synchronize()
+    mean.copy_(mean0)
+    for d in range(3):
+        for f in ALL + ("action",):
+            getattr(res, f).zero_()
+        graph.replay()
+        torch.cuda.synchronize()
+        for f in OUT:
+            assert torch.equal(getattr(res, f), direct[d][f]), "replay %d: %s" % (d, f)
+        word += 1
+
+
+# ---------------------------------------------------------------------------------------------- 7. closed loop
+def test_mppi_planner_beats_random_actions(torch_cuda):
+    """256 RandomMiniEnv envs, 200 ticks, the seeds of the ShootingPlanner test: the planner's mean return is strictly
+    larger than that of action_space.sample_batch actions (ShootingPlanner's is printed beside them)"""
+    torch = torch_cuda
+    from bc_gym_planning_env_amd import MPPIPlanner, ShootingPlanner, constant_command_library, mini_env
+    n, ticks = 256, 200
+
+    def run(which):
+        env = mini_env.BatchedRandomMiniEnv(n, n_chains=64, episodes=4, auto_reset=True, seed=3)
+        if which == "mppi":
+            planner = MPPIPlanner(env, horizon=16, n_candidates=64, iterations=2, sigma=(0.2, 0.6), lam=0.3,
+                                  collision_penalty=2.0, seed=0)
+        else:
+            planner = ShootingPlanner(env, constant_command_library(env.action_space, 4, 9, 16))
+        rng = np.random.RandomState(0)
+        total = torch.zeros(n, dtype=torch.float64, device="cuda")
+        for _ in range(ticks):
+            a = env.action_space.sample_batch(n, rng)
+            _, rew, done, _ = env.step(a if which == "random" else planner.act())
+            if which == "mppi":
+                planner.reset_plans(done)
+            total += rew
+        env.check_errors()
+        return float(total.mean())
+
+    mppi, shooting, random_ = run("mppi"), run("shooting"), run("random")
+    print("mean return over %d ticks: MPPIPlanner %.4f, ShootingPlanner %.4f, random actions %.4f" % (ticks, mppi, shooting, random_))
+    assert mppi > random_
