@@ -887,6 +887,29 @@ class BatchedPlanEnv(object):
         self._last_inputs = (actions, z, done)  # keep inputs alive until the stream has consumed them
         return self._obs, self.reward, done, self._info
 
+    def _device_tensor(self, x, dtype=None, shape=None):
+        """A tensor, or anything numpy can wrap, on the env's device and contiguous.  dtype None keeps float32 / float64
+        and widens everything else to float64; a shape, if given, is asserted."""
+        if not isinstance(x, torch.Tensor):
+            x = torch.from_numpy(np.ascontiguousarray(x))
+        if dtype is None:
+            dtype = x.dtype if x.dtype in (torch.float32, torch.float64) else torch.float64
+        x = x.to(self.device).to(dtype).contiguous()
+        assert shape is None or tuple(x.shape) == shape
+        return x
+
+    def _cached_outputs(self, cache_name, key, shapes, names):
+        """{name: zero-initialised device buffer of shapes[name] = (shape, dtype)}, made on first use and cached in
+        self.<cache_name>[key] -- a planner that calls every tick allocates nothing."""
+        buf = self.__dict__.setdefault(cache_name, {}).setdefault(key, {})
+        out = {}
+        for name in names:
+            shape, dtype = shapes[name]
+            if (name, dtype) not in buf:
+                buf[(name, dtype)] = torch.zeros(shape, dtype=dtype, device=self.device)
+            out[name] = buf[(name, dtype)]
+        return out
+
     def rollout(self, actions, noise_z=None, noise_z_out=None, collided_out=None, err_out=None):
         """K ticks for every env in one library call (bcp_rollout): actions [K, N, 2] float32 / float64 on the device (or
         anything torch can put there).  Returns (reward float64 [K, N], done uint8 [K, N]) device tensors, no sync; the
@@ -895,11 +918,7 @@ class BatchedPlanEnv(object):
         [K, N] (without them only the last step's collided_now / err are kept).  With the single-launch step form the K
         steps are ONE kernel launch -- open-loop Monte-Carlo rollouts from one state (the reference's README) pay launch,
         argument fetch and staging once, and no workgroup waits for the chip's slowest one between steps."""
-        if not isinstance(actions, torch.Tensor):
-            actions = torch.from_numpy(np.ascontiguousarray(actions))
-        if actions.dtype not in (torch.float32, torch.float64):
-            actions = actions.to(torch.float64)
-        actions = actions.to(self.device).contiguous()
+        actions = self._device_tensor(actions)
         k, n = int(actions.shape[0]), self.n_envs
         assert tuple(actions.shape) == (k, n, 2) and k >= 1
         io = _lib.BcpStepIO()
@@ -907,9 +926,7 @@ class BatchedPlanEnv(object):
         flags = self._flags_f32 if actions.dtype == torch.float32 else self._flags_f64
         keep = [actions]
         if noise_z is not None:
-            z = noise_z if isinstance(noise_z, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(noise_z))
-            z = z.to(self.device, torch.float64).contiguous()
-            assert tuple(z.shape) == (k, n, 3)
+            z = self._device_tensor(noise_z, torch.float64, (k, n, 3))
             io.noise_z = z.data_ptr()
             keep.append(z)
         if noise_z_out is not None:
@@ -944,11 +961,7 @@ class BatchedPlanEnv(object):
         "final_pose", "final_target_idx", "err", "best", "best_action" ("best_action" implies "best").  Each candidate
         stops after its first done step (no auto-reset).  Returns a Lookahead of device tensors, no sync; the buffers are
         cached per (H, K), so a planner that calls this every tick allocates nothing.  Delays > 0 are refused."""
-        if not isinstance(actions, torch.Tensor):
-            actions = torch.from_numpy(np.ascontiguousarray(actions))
-        if actions.dtype not in (torch.float32, torch.float64):
-            actions = actions.to(torch.float64)
-        actions = actions.to(self.device).contiguous()
+        actions = self._device_tensor(actions)
         n = self.n_envs
         if actions.dim() == 3 and actions.shape[2] == 2:
             flags = 0
@@ -965,8 +978,6 @@ class BatchedPlanEnv(object):
             raise ValueError("lookahead: unknown outputs %s" % sorted(unknown))
         if "best_action" in want:
             want.add("best")
-        cache = self.__dict__.setdefault("_lookahead_buffers", {})
-        buf = cache.setdefault((h, k), {})
         shapes = {"ret": ((n, k), torch.float64), "steps": ((n, k), torch.int32), "reason": ((n, k), torch.uint8),
                   "final_pose": ((n, k, 3), torch.float64), "final_target_idx": ((n, k), torch.int32),
                   "err": ((n, k), torch.int32), "best": ((n,), torch.int32), "best_action": ((n, 2), actions.dtype)}
@@ -974,27 +985,17 @@ class BatchedPlanEnv(object):
         io.actions, io.horizon, io.n_candidates = actions.data_ptr(), h, k
         keep = [actions]
         if noise_z is not None:
-            z = noise_z if isinstance(noise_z, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(noise_z))
-            z = z.to(self.device, torch.float64).contiguous()
-            assert tuple(z.shape) == (h, n, k, 3)
+            z = self._device_tensor(noise_z, torch.float64, (h, n, k, 3))
             io.noise_z = z.data_ptr()
             keep.append(z)
         if mask is not None:
-            mask = mask if isinstance(mask, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(mask))
-            mask = mask.to(self.device).to(torch.uint8).contiguous()
-            assert tuple(mask.shape) == (n,)
+            mask = self._device_tensor(mask, torch.uint8, (n,))
             io.mask = mask.data_ptr()
             keep.append(mask)
-        out = {}
-        for name in Lookahead.FIELDS:
-            if name not in want and name not in Lookahead.FIELDS[:3]:
-                continue
-            shape, dtype = shapes[name]
-            key = (name, dtype)
-            if key not in buf:
-                buf[key] = torch.zeros(shape, dtype=dtype, device=self.device)
-            out[name] = buf[key]
-            setattr(io, name, buf[key].data_ptr())
+        out = self._cached_outputs("_lookahead_buffers", (h, k), shapes,
+                                   [name for name in Lookahead.FIELDS if name in want or name in Lookahead.FIELDS[:3]])
+        for name, t in out.items():
+            setattr(io, name, t.data_ptr())
         _lib.check(self._lib.bcp_lookahead(self._h, C.byref(io), flags, self._stream()))
         self._last_lookahead_inputs = tuple(keep)   # alive until the stream has consumed them
         return Lookahead(h, k, **out)
@@ -1014,11 +1015,9 @@ class BatchedPlanEnv(object):
         action_dtype: torch.float64 (default) or torch.float32.  Returns an Mppi; buffers are cached per (H, K, I).  Delays
         > 0 are refused."""
         n = self.n_envs
-        if not isinstance(mean, torch.Tensor):
-            mean = torch.from_numpy(np.ascontiguousarray(mean))
+        mean = self._device_tensor(mean, torch.float64)   # (a contiguous float64 tensor on the device: itself)
         if mean.dim() != 3 or mean.shape[0] != n or mean.shape[2] != 2:
             raise ValueError("mean must have shape (%d, H, 2), got %s" % (n, tuple(mean.shape)))
-        mean = mean.to(self.device, torch.float64).contiguous()
         h, k, it = int(mean.shape[1]), int(n_candidates), int(iterations)
         want = set(want)
         unknown = want - set(Mppi.FIELDS)
@@ -1044,31 +1043,22 @@ class BatchedPlanEnv(object):
         else:
             p.draw_index = int(draw_index) & (2 ** 64 - 1)
         if mask is not None:
-            mask = mask if isinstance(mask, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(mask))
-            mask = mask.to(self.device).to(torch.uint8).contiguous()
-            assert tuple(mask.shape) == (n,)
+            mask = self._device_tensor(mask, torch.uint8, (n,))
             io.mask = mask.data_ptr()
             keep.append(mask)
         if eps is not None:
-            eps = eps if isinstance(eps, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(eps))
-            eps = eps.to(self.device, torch.float32).contiguous()
+            eps = self._device_tensor(eps, torch.float32)
             if tuple(eps.shape) != (it, n, k, h, 2):
                 raise ValueError("eps must have shape %s, got %s" % ((it, n, k, h, 2), tuple(eps.shape)))
             io.eps_in = eps.data_ptr()
             keep.append(eps)
-        buf = self.__dict__.setdefault("_mppi_buffers", {}).setdefault((h, k, it), {})
         shapes = {"action": ((n, 2), action_dtype), "eps": ((it, n, k, h, 2), torch.float32),
                   "iter_mean": ((it, n, h, 2), torch.float64), "iter_ret": ((it, n, k), torch.float64),
                   "iter_reason": ((it, n, k), torch.uint8), "err": ((n,), torch.int32)}
-        out = {}
-        for name in ("action",) + Mppi.FIELDS:
-            if name != "action" and name not in want:
-                continue
-            shape, dtype = shapes[name]
-            if (name, dtype) not in buf:
-                buf[(name, dtype)] = torch.zeros(shape, dtype=dtype, device=self.device)
-            out[name] = buf[(name, dtype)]
-            setattr(io, "eps_out" if name == "eps" else name, out[name].data_ptr())
+        out = self._cached_outputs("_mppi_buffers", (h, k, it), shapes,
+                                   ["action"] + [name for name in Mppi.FIELDS if name in want])
+        for name, t in out.items():
+            setattr(io, "eps_out" if name == "eps" else name, t.data_ptr())
         flags = _lib.STEP_ACTIONS_F32 if action_dtype == torch.float32 else 0
         _lib.check(self._lib.bcp_mppi(self._h, C.byref(p), C.byref(io), flags, self._stream()))
         self._last_mppi_inputs = tuple(keep)   # alive until the stream has consumed them

@@ -1,10 +1,94 @@
-// bcp_lookahead.h -- bcp_lookahead(): K candidate action sequences per env, each stepped up to H times on a private copy of
-// the env's state that lives in registers.  Nothing of the handle is written; the only global stores are the outputs.
+// bcp_lookahead.h -- the roll-out core of the planning kernels (PlanState, plan_load, plan_trip: one PlanEnv.step on a
+// private copy of an env's state that lives in registers), and bcp_lookahead(): K candidate action sequences per env, each
+// taking up to H such trips.  Nothing of the handle is written; the only global stores are the outputs.
 // Included by bcplan.hip after bcp_step.h, whose device functions (robot model, collides_wave, reward providers) it is
 // built from -- none of the step kernels' hand-off machinery (tickets, parking, alternating counters) is involved.
+// bcp_mppi.h rolls its candidates out with the same core.
 #pragma once
 
 #include "bcp_step.h"
+
+// ---- the roll-out core -----------------------------------------------------------------------------------------------
+// What a trip advances: the part of an env's state that PlanEnv.step changes when no delay queue exists.
+struct PlanState {
+    Robot r;
+    double min_dist;
+    int target, iter;
+    bool collided;
+};
+
+// Env i's state as it is bound to the handle, its slot g (map / path / pool entry), its way points and their count.  The
+// lanes of one env read the same addresses: a broadcast load each.
+__device__ __forceinline__ void plan_load(const StepStatic* S, int64_t i, PlanState& st, int64_t& g, const double*& pts, int& m)
+{
+    const bool tri = S->P.model == BCP_MODEL_TRICYCLE;
+    st.r.p.x = as_global(S->st.x)[i];
+    st.r.p.y = as_global(S->st.y)[i];
+    st.r.p.th = as_global(S->st.angle)[i];
+    st.r.v = as_global(S->st.v)[i];
+    st.r.w = as_global(S->st.w)[i];
+    st.r.steer = tri ? as_global(S->st.steer)[i] : 0.0;
+    st.r.wheel = tri ? as_global(S->st.wheel)[i] : 0.0;
+    st.min_dist = as_global(S->st.min_dist)[i];
+    st.target = as_global(S->st.target_idx)[i];
+    st.iter = as_global(S->st.cur_iter)[i];
+    st.collided = as_global(S->st.collided)[i] != 0;
+    g = S->geom_of_env ? (int64_t)as_global(S->geom_of_env)[i] : i;   // slot_of
+    pts = S->path.pts + (S->path.shared ? 0 : g * (int64_t)S->path.max_len * 5);
+    m = S->path.shared ? S->path.max_len : S->path.lens[g];
+}
+
+// One trip: PlanEnv.step without the stores -- _env_step (envs/base/env.py:442-461: robot, collision, roll-back), iter + 1,
+// reward (:352), done (:400-419) -- in the order and by the laws of finalize_env_from, minus delay queues (refused by the
+// host), reset and record.  This is the one statement of that sequence outside the step kernels, which stay as they are
+// (bcp_step.h); test_bitwise_equal_to_the_step_on_a_twin_handle holds it to them bit for bit.
+// Wave-uniform: every lane of the wave calls it, because collides_wave settles ambiguous poses with the whole wave; a lane
+// with active = false (finished, masked out, past the end of the grid) keeps st, ret, errs, reason and finished as they are.
+// PLAIN: continuous reward provider and no noise_z -- the pure-pursuit branch and kinematic_step_noise are compiled out.
+// noisy_model false is the noise-free forward model, whatever the handle's noise_on; z is then not read.
+template <bool PLAIN>
+__device__ __forceinline__ void plan_trip(const StepStatic* S, const CollisionLds& L, int64_t g, const double* pts, int m,
+                                          double cmd0, double cmd1, const double z[3], bool noisy_model, bool active,
+                                          PlanState& st, double& ret, int& errs, int& reason, bool& finished)
+{
+    const DevParams& P = S->P;
+    const bool pure_pursuit = !PLAIN && P.reward_provider == BCP_REWARD_PURE_PURSUIT;
+    Robot nr = st.r;
+    int drawn = 0;
+    RobotDrive d = robot_step_begin(P, nr, cmd0, cmd1);
+    if (!noisy_model) d.noisy = false;   // kinematic_step, not kinematic_step_noise fed with zeros
+    const int e = robot_step_end(P, nr, d, z, drawn);
+    const bool hit = collides_wave(P, S->map, S->cull, L, S->exact_mode, S->dense_threshold, S->wide != 0, active, g,
+                                   nr.p.x, nr.p.y, nr.p.th);
+    if (!active) return;
+    if (hit) {   // robot.set_pose(*old_position): pose restored, v = w = 0 (tricycle_model.py:471-476)
+        nr.p = st.r.p;
+        nr.v = 0.0;
+        nr.w = 0.0;
+    }
+    st.r = nr;
+    st.iter += 1;
+    st.collided = st.collided || hit;
+    double rew;
+    bool goal;
+    if (pure_pursuit) {
+        rew = reward_pure_pursuit(pts, m, nr.p.x, nr.p.y, st.collided, st.min_dist, st.target);
+        goal = hypot(pts[5 * (m - 1)] - nr.p.x, pts[5 * (m - 1) + 1] - nr.p.y) < 1.0;   // done(), reward.py:141-150
+    } else {
+        const PathWindow w = path_window_of(P, S->path.shared != 0, S->path.bbox, S->path.index, g, nr.p.x, nr.p.y);
+        rew = reward_step<4>(P, pts, w, m, nr.p.x, nr.p.y, nr.p.th, st.min_dist, st.target);
+        goal = st.target > m - 1;
+    }
+    const bool timeout = st.iter >= P.iteration_timeout;
+    ret += rew;
+    errs |= e;
+    if (goal || timeout || st.collided) {
+        reason = (goal ? BCP_DONE_GOAL : 0) | (timeout ? BCP_DONE_TIMEOUT : 0) | (st.collided ? BCP_DONE_COLLIDED : 0);
+        finished = true;
+    }
+}
+
+// ---- bcp_lookahead ---------------------------------------------------------------------------------------------------
 
 // Launch arguments: the handle's parameter block and the caller's pointers (bcp_lookahead_io), nothing that changes from
 // call to call -- a captured call replays.
@@ -44,10 +128,7 @@ __device__ __forceinline__ void lookahead_action(const LookaheadArgs& a, int64_t
 // with K >= 64 a wave is 64 candidates of ONE env (its state is one broadcast load; map tiles, path window and footprint
 // are the same lines for the whole wave) and with K < 64 a wave holds 64 / K envs.  One wavefront per workgroup, like
 // step_kernel: collides_wave settles ambiguous poses with the whole wave and owns the workgroup's dynamic LDS.
-// PLAIN: continuous reward provider and the noise-free forward model (no noise_z) -- the pure-pursuit branch and
-// kinematic_step_noise are compiled out.
-// A step is PlanEnv.step without the stores: robot, collision, roll-back (env.py:458-459), iter + 1, reward (:352), done
-// (:407-419) -- the order and the laws of finalize_env_from, minus delay queues (refused by the host), reset and record.
+// PLAIN: plan_trip's -- the host picks it when the provider is the continuous one and no noise_z is given.
 template <bool PLAIN>
 __global__ void __launch_bounds__(kBlock) lookahead_kernel(const LookaheadArgs a)
 {
@@ -63,31 +144,18 @@ __global__ void __launch_bounds__(kBlock) lookahead_kernel(const LookaheadArgs a
 
     const CollisionLds L = collision_lds_setup(P, S->map, tid);
 
-    // ---- the env's state, once (lanes of one env read the same addresses)
-    const bool tri = P.model == BCP_MODEL_TRICYCLE;
-    const bool pure_pursuit = !PLAIN && P.reward_provider == BCP_REWARD_PURE_PURSUIT;
     const bool noisy_model = !PLAIN && a.noise_z != nullptr;
     const bool per_env = (a.flags & BCP_LOOKAHEAD_PER_ENV) != 0;
-    Robot r;
-    r.p.x = as_global(S->st.x)[i];
-    r.p.y = as_global(S->st.y)[i];
-    r.p.th = as_global(S->st.angle)[i];
-    r.v = as_global(S->st.v)[i];
-    r.w = as_global(S->st.w)[i];
-    r.steer = tri ? as_global(S->st.steer)[i] : 0.0;
-    r.wheel = tri ? as_global(S->st.wheel)[i] : 0.0;
-    double min_dist = as_global(S->st.min_dist)[i];
-    int target = as_global(S->st.target_idx)[i];
-    int iter = as_global(S->st.cur_iter)[i];
-    bool collided = as_global(S->st.collided)[i] != 0;
-    const int64_t g = S->geom_of_env ? (int64_t)as_global(S->geom_of_env)[i] : i;   // slot_of
-    const double* pts = S->path.pts + (S->path.shared ? 0 : g * (int64_t)S->path.max_len * 5);
-    const int m = S->path.shared ? S->path.max_len : S->path.lens[g];
+    PlanState st;   // the env's state, once
+    int64_t g;
+    const double* pts;
+    int m;
+    plan_load(S, i, st, g, pts, m);
 
     double ret = 0.0;
     int steps = 0, reason = 0, errs = 0;
     bool finished = !live;
-    // Every lane stays in the loop until the whole wave is through (collides_wave is a wave-wide call); a lane that is
+    // Every lane stays in the loop until the whole wave is through (plan_trip is a wave-wide call); a lane that is
     // finished, masked out or past N * K passes active = false and keeps its results as they are.
     for (int t = 0; t < a.horizon; ++t) {
         if (__ballot(!finished) == 0) break;   // wave-uniform
@@ -101,53 +169,19 @@ __global__ void __launch_bounds__(kBlock) lookahead_kernel(const LookaheadArgs a
             z[1] = as_global(a.noise_z)[3 * wide_row + 1];
             z[2] = as_global(a.noise_z)[3 * wide_row + 2];
         }
-        // ---- _env_step (envs/base/env.py:442-461)
-        Robot nr = r;
-        int drawn = 0;
-        RobotDrive d = robot_step_begin(P, nr, cmd0, cmd1);
-        if (!noisy_model) d.noisy = false;   // the noise-free forward model, whatever the handle's noise_on
-        const int e = robot_step_end(P, nr, d, z, drawn);
-        const bool hit = collides_wave(P, S->map, S->cull, L, S->exact_mode, S->dense_threshold, S->wide != 0, active, g,
-                                       nr.p.x, nr.p.y, nr.p.th);
-        if (active) {
-            if (hit) {   // robot.set_pose(*old_position): pose restored, v = w = 0 (tricycle_model.py:471-476)
-                nr.p = r.p;
-                nr.v = 0.0;
-                nr.w = 0.0;
-            }
-            r = nr;
-            iter += 1;
-            collided = collided || hit;
-            double rew;
-            bool goal;
-            if (pure_pursuit) {
-                rew = reward_pure_pursuit(pts, m, r.p.x, r.p.y, collided, min_dist, target);
-                goal = hypot(pts[5 * (m - 1)] - r.p.x, pts[5 * (m - 1) + 1] - r.p.y) < 1.0;   // done(), reward.py:141-150
-            } else {
-                const PathWindow w = path_window_of(P, S->path.shared != 0, S->path.bbox, S->path.index, g, r.p.x, r.p.y);
-                rew = reward_step<4>(P, pts, w, m, r.p.x, r.p.y, r.p.th, min_dist, target);
-                goal = target > m - 1;
-            }
-            const bool timeout = iter >= P.iteration_timeout;
-            ret += rew;
-            steps = t + 1;
-            errs |= e;
-            if (goal || timeout || collided) {   // env.py:400-419
-                reason = (goal ? BCP_DONE_GOAL : 0) | (timeout ? BCP_DONE_TIMEOUT : 0) | (collided ? BCP_DONE_COLLIDED : 0);
-                finished = true;
-            }
-        }
+        plan_trip<PLAIN>(S, L, g, pts, m, cmd0, cmd1, z, noisy_model, active, st, ret, errs, reason, finished);
+        if (active) steps = t + 1;
     }
     if (!live) return;
     as_global(a.ret)[c] = ret;
     as_global(a.steps)[c] = steps;
     as_global(a.reason)[c] = (uint8_t)reason;
     if (a.final_pose) {
-        as_global(a.final_pose)[3 * c + 0] = r.p.x;
-        as_global(a.final_pose)[3 * c + 1] = r.p.y;
-        as_global(a.final_pose)[3 * c + 2] = r.p.th;
+        as_global(a.final_pose)[3 * c + 0] = st.r.p.x;
+        as_global(a.final_pose)[3 * c + 1] = st.r.p.y;
+        as_global(a.final_pose)[3 * c + 2] = st.r.p.th;
     }
-    if (a.final_target) as_global(a.final_target)[c] = target;
+    if (a.final_target) as_global(a.final_target)[c] = st.target;
     if (a.err) as_global(a.err)[c] = errs;
 }
 

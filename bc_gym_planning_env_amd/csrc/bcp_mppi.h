@@ -1,7 +1,7 @@
 // bcp_mppi.h -- bcp_mppi(): sampling-based refinement of one plan per env (MPPI), I iterations of sample -> roll out ->
-// weight -> update inside ONE launch.  Included by bcplan.hip after bcp_lookahead.h.  The trip body is lookahead_kernel's,
-// restated (as that kernel restates finalize_env_from) so that neither it nor the step kernels compile to anything else;
-// candidate actions are not read from memory but made in registers: mean + sigma * eps, clipped to the action box.
+// weight -> update inside ONE launch.  Included by bcplan.hip after bcp_lookahead.h, whose roll-out core (plan_load,
+// plan_trip) takes the trips: a candidate is rolled out by the very code lookahead_kernel runs.  Candidate actions are not
+// read from memory but made in registers: mean + sigma * eps, clipped to the action box.
 // Nothing of the handle is written; the only global stores are the caller's outputs (bcp_mppi_io).
 #pragma once
 
@@ -86,24 +86,11 @@ __global__ void __launch_bounds__(kBlock) mppi_kernel(const MppiArgs a)
     const CollisionLds L = collision_lds_setup(P, S->map, tid);
     const LdsScore score = (LdsScore)(lds_dyn + a.score_word) + tid;   // chunk ch at score[ch * kBlock]
 
-    // ---- the env's state, once for all iterations and chunks
-    const bool tri = P.model == BCP_MODEL_TRICYCLE;
-    const bool pure_pursuit = !PLAIN && P.reward_provider == BCP_REWARD_PURE_PURSUIT;
-    Robot r0;
-    r0.p.x = as_global(S->st.x)[i];
-    r0.p.y = as_global(S->st.y)[i];
-    r0.p.th = as_global(S->st.angle)[i];
-    r0.v = as_global(S->st.v)[i];
-    r0.w = as_global(S->st.w)[i];
-    r0.steer = tri ? as_global(S->st.steer)[i] : 0.0;
-    r0.wheel = tri ? as_global(S->st.wheel)[i] : 0.0;
-    const double min_dist0 = as_global(S->st.min_dist)[i];
-    const int target0 = as_global(S->st.target_idx)[i];
-    const int iter0 = as_global(S->st.cur_iter)[i];
-    const bool collided0 = as_global(S->st.collided)[i] != 0;
-    const int64_t g = S->geom_of_env ? (int64_t)as_global(S->geom_of_env)[i] : i;   // slot_of
-    const double* pts = S->path.pts + (S->path.shared ? 0 : g * (int64_t)S->path.max_len * 5);
-    const int m = S->path.shared ? S->path.max_len : S->path.lens[g];
+    PlanState st0;   // the env's state, once for all iterations and chunks
+    int64_t g;
+    const double* pts;
+    int m;
+    plan_load(S, i, st0, g, pts, m);
 
     const uint64_t draw = a.draw_index ? *as_global(a.draw_index) : a.p.draw_index;
     const GlobalPtr<double> mean = as_global(a.mean) + i * H * 2;
@@ -114,15 +101,12 @@ __global__ void __launch_bounds__(kBlock) mppi_kernel(const MppiArgs a)
     for (int j = 0; j < a.p.iterations; ++j) {
         if (a.iter_mean && live)
             for (int e = kl; e < 2 * H; e += group) as_global(a.iter_mean)[((int64_t)j * a.n + i) * H * 2 + e] = mean[e];
-        // ---- roll-outs: the trip body of lookahead_kernel on a copy of the state, one chunk of candidates at a time
+        // ---- roll-outs: plan_trip on a copy of the state, one chunk of candidates at a time
         double best = -INFINITY;
         for (int ch = 0; ch < chunks; ++ch) {
             const int k = ch * kBlock + kl;
             const int64_t c = ((int64_t)j * a.n + i) * K + k;   // [I][N][K]
-            Robot r = r0;
-            double min_dist = min_dist0;
-            int target = target0, iter = iter0;
-            bool collided = collided0;
+            PlanState st = st0;
             double ret = 0.0;
             int reason = 0;
             bool finished = !live;
@@ -148,41 +132,7 @@ __global__ void __launch_bounds__(kBlock) mppi_kernel(const MppiArgs a)
                 const bool active = !finished;
                 const double cmd0 = mppi_command(mean[2 * t + 0], a.p.sigma[0], e0, a.p.low[0], a.p.high[0]);
                 const double cmd1 = mppi_command(mean[2 * t + 1], a.p.sigma[1], e1, a.p.low[1], a.p.high[1]);
-                // ---- _env_step (envs/base/env.py:442-461)
-                Robot nr = r;
-                int drawn = 0;
-                RobotDrive d = robot_step_begin(P, nr, cmd0, cmd1);
-                d.noisy = false;   // the noise-free forward model, whatever the handle's noise_on
-                const int e = robot_step_end(P, nr, d, zero3, drawn);
-                const bool hit = collides_wave(P, S->map, S->cull, L, S->exact_mode, S->dense_threshold, S->wide != 0, active,
-                                               g, nr.p.x, nr.p.y, nr.p.th);
-                if (active) {
-                    if (hit) {   // robot.set_pose(*old_position): pose restored, v = w = 0 (tricycle_model.py:471-476)
-                        nr.p = r.p;
-                        nr.v = 0.0;
-                        nr.w = 0.0;
-                    }
-                    r = nr;
-                    iter += 1;
-                    collided = collided || hit;
-                    double rew;
-                    bool goal;
-                    if (pure_pursuit) {
-                        rew = reward_pure_pursuit(pts, m, r.p.x, r.p.y, collided, min_dist, target);
-                        goal = hypot(pts[5 * (m - 1)] - r.p.x, pts[5 * (m - 1) + 1] - r.p.y) < 1.0;   // done(), reward.py:141-150
-                    } else {
-                        const PathWindow w = path_window_of(P, S->path.shared != 0, S->path.bbox, S->path.index, g, r.p.x, r.p.y);
-                        rew = reward_step<4>(P, pts, w, m, r.p.x, r.p.y, r.p.th, min_dist, target);
-                        goal = target > m - 1;
-                    }
-                    const bool timeout = iter >= P.iteration_timeout;
-                    ret += rew;
-                    errs |= e;
-                    if (goal || timeout || collided) {   // env.py:400-419
-                        reason = (goal ? BCP_DONE_GOAL : 0) | (timeout ? BCP_DONE_TIMEOUT : 0) | (collided ? BCP_DONE_COLLIDED : 0);
-                        finished = true;
-                    }
-                }
+                plan_trip<PLAIN>(S, L, g, pts, m, cmd0, cmd1, zero3, false, active, st, ret, errs, reason, finished);
             }
             if (live) {
                 if (a.iter_ret) as_global(a.iter_ret)[c] = ret;

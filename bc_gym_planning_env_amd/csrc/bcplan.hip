@@ -14,7 +14,9 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <new>
+#include <utility>
 #include <vector>
 
 #include "bcp_device.h"
@@ -137,7 +139,7 @@ struct bcp_handle {
     int32_t ring_episodes;    // of the last bcp_plan_mini_worlds
     bool ring_planned, ring_refreshed;   // plan -> refresh -> release, in that order
     int32_t edt_in_lds;       // distance transform of maps that fit: the LDS-resident kernel (BCP_TUNE_EDT_LDS)
-    int32_t last_step_form;   // 0 none yet, 1 single-kernel step, 2 two-kernel step (parking counters in use)
+    int32_t last_step_form;   // step_form() of the last step launched, -1: none yet
     int32_t fused;            // settle parked poses inside the step launch (step_local_kernel) instead of a second launch
     uint64_t* parked_slots;   // owned: a word per workgroup of step_local_kernel, its parked poses so far (bcp_parked_poses)
     int64_t parked_cap;
@@ -1117,6 +1119,7 @@ extern "C" int bcp_create(const bcp_params* params, int64_t n_envs, int device, 
     h->cull_enabled = 1;
     h->defer = 1;
     h->fused = 1;
+    h->last_step_form = -1;
     h->ego_sparse = 1;
     h->ego_cells_max = -1;
     h->static_dirty = true;
@@ -1764,6 +1767,34 @@ static bool step_uses_deferral(const bcp_handle* h)
     return h->defer && h->cull.on && h->exact_mode == 0 && h->pending != nullptr;
 }
 
+// Which kernels a step of this handle launches as it is configured now -- the numbers bcp_step_form documents: 0 step_kernel,
+// 1 step_fast_pair_kernel alone, 2 that + step_pending_kernel, 3 step_local_kernel (the single-launch form).  Once
+// upload_step_static has run, S.pending != nullptr says the same as step_uses_deferral.
+// (an explicit BCP_TUNE_DENSE_THRESHOLD asks for poses to be settled inside the stepping wave: the two-launch form has that
+// path, and bcp_set_tuning clears `adaptive` with it -- form 3 never meets a negative threshold)
+static int step_form(const bcp_handle* h)
+{
+    if (!step_uses_deferral(h)) return 0;
+    if (h->dense_threshold < 0) return 1;
+    return (h->fused && h->adaptive) ? 3 : 2;
+}
+
+// Lets `fn` be launched with `bytes` of dynamic LDS on `device`.  The attribute belongs to the FUNCTION on a device, not to
+// a handle, so it is only ever raised: the largest size any handle of this process has asked for stays set (two live handles
+// with different staging sizes would otherwise lower it under each other).
+static int raise_dynamic_lds(const void* fn, int device, size_t bytes)
+{
+    static std::mutex mutex;
+    static std::map<std::pair<const void*, int>, size_t> raised;   // (function, device) -> the attribute as it stands
+    std::lock_guard<std::mutex> lock(mutex);
+    size_t& cur = raised[std::make_pair(fn, device)];
+    if (bytes > cur) {
+        HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+        cur = bytes;
+    }
+    return BCP_OK;
+}
+
 static int upload_step_static(bcp_handle* h, hipStream_t s)
 {
     StepStatic& S = h->host_static;
@@ -1852,20 +1883,17 @@ static int launch_step(bcp_handle* h, const bcp_step_io* io, uint32_t flags, hip
         if (rc != BCP_OK) return rc;
     }
     const StepStatic& S = h->host_static;
-    // (an explicit BCP_TUNE_DENSE_THRESHOLD asks for poses to be settled inside the stepping wave: the two-launch form has that path)
-    const bool fused = S.pending && h->fused && h->adaptive;
-    const int32_t form = fused ? 3 : (S.pending ? 2 : 1);
+    const int form = step_form(h);
+    const bool fused = form == 3;
     if (!fused && h->edt_lazy) {   // these forms read the uint8 field
         const int rc = ensure_fields(h, s);
         if (rc != BCP_OK) return rc;
     }
-    if (form != h->last_step_form) {
-        if (form == 2 && h->last_step_form != 0) {
-            const int rc = rearm_parking(h, s);
-            if (rc != BCP_OK) return rc;
-        }
-        h->last_step_form = form;
+    if ((form == 1 || form == 2) && (h->last_step_form == 0 || h->last_step_form == 3)) {   // parking resumes after another form
+        const int rc = rearm_parking(h, s);
+        if (rc != BCP_OK) return rc;
     }
+    h->last_step_form = form;
     StepArgs a;
     a.S = h->dev_static;
     StepHot& hot = a.hot;
@@ -1928,25 +1956,13 @@ static int launch_step(bcp_handle* h, const bcp_step_io* io, uint32_t flags, hip
         const int variant = (S.wide ? 2 : 0) | (step_is_plain(h) ? 1 : 0);
         const bool roll = rollout_steps > 1;
         const int pairs = roll ? 4 : local_pairs(h);
-        const int pslot = roll ? 3 : (pairs == 4 ? 2 : (pairs == 2 ? 1 : 0));
         const void* fn = local_step_fn(variant, pairs, roll);
         a.rollout_steps = rollout_steps;
         const int64_t bitmap_words = (int64_t)S.map.rows * S.map.wpr;
         const size_t lds = local_step_lds_bytes(h->params.n_verts, S.lds_path_doubles,
                                                 (S.map.shared && bitmap_words <= kLocalMapWords) ? (int)bitmap_words : 0,
                                                 step_is_plain(h), pairs);
-        // The attribute belongs to the FUNCTION on a device, not to a handle: the largest size any handle of this process
-        // has asked for stays set (two live handles with different staging sizes would otherwise lower it under each other).
-        {
-            static std::mutex lds_mutex;
-            static int32_t lds_max[64][4][4];   // [device][variant][workgroup size | rollout form], zero-initialised
-            std::lock_guard<std::mutex> lock(lds_mutex);
-            int32_t& cur = lds_max[h->device & 63][variant][pslot];
-            if ((int32_t)lds > cur) {
-                HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                cur = (int32_t)lds;
-            }
-        }
+        { const int rc = raise_dynamic_lds(fn, h->device, lds); if (rc != BCP_OK) return rc; }
         a.flags |= kStepAdvances;
         hot.io_flags = a.flags;   // (the prologue's copies, next to the rest of what it fetches)
         hot.io_actions = a.actions;
@@ -1964,7 +1980,7 @@ static int launch_step(bcp_handle* h, const bcp_step_io* io, uint32_t flags, hip
         HIP_TRY(hipLaunchKernel(fn, grid, block, kargs, lds, s));
     } else if (rollout_steps > 1) {
         return fail(BCP_E_STATE, "launch_step: only the single-launch step form takes several steps per launch");
-    } else if (S.pending) {
+    } else if (form != 0) {
         // kernel 1 settles every env the distance field decides; kernel 2 rasterises the parked rest
         const size_t lds1 = ((size_t)h->params.n_verts * 2 + S.lds_path_doubles) * sizeof(double);
         const size_t lds2 = (size_t)2 * 4 * (S.wide ? 8 : 3) * 64 * sizeof(uint32_t);
@@ -2030,7 +2046,7 @@ constexpr uint32_t kWatchdogSteps = 256;
 
 static int step_watchdog(bcp_handle* h, hipStream_t s)
 {
-    if (h->last_step_form != 3) return BCP_OK;   // (only step_local_kernel has such waits)
+    if (step_form(h) != 3) return BCP_OK;   // (only step_local_kernel has such waits)
     if (h->waits_in_flight) {
         const hipError_t q = hipEventQuery(h->waits_event);
         if (q == hipSuccess) {
@@ -2089,13 +2105,7 @@ extern "C" int bcp_rollout(bcp_handle* h, const bcp_step_io* io, int32_t n_steps
     if (h->have_rec) return fail(BCP_E_STATE, "bcp_rollout: an episode record is bound (rows over K steps are not kept)");
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
-    if (h->static_dirty) {
-        rc = upload_step_static(h, s);
-        if (rc != BCP_OK) return rc;
-    }
-    const StepStatic& S = h->host_static;
-    const bool fused = S.pending && h->fused && h->adaptive;
-    if (fused && n_steps > 1) {
+    if (step_form(h) == 3 && n_steps > 1) {
         rc = launch_step(h, io, flags, s, false, n_steps);
         if (rc != BCP_OK) return rc;
         HIP_TRY(hipGetLastError());
@@ -2119,6 +2129,24 @@ extern "C" int bcp_rollout(bcp_handle* h, const bcp_step_io* io, int32_t n_steps
     return BCP_OK;
 }
 
+// What bcp_lookahead and bcp_mppi (`who`) need of the handle before their kernels read it: complete, without delay queues,
+// its parameter block on the device and no stale uint8 field (collides_wave classifies with it).
+static int plan_ready(bcp_handle* h, const char* who, hipStream_t s)
+{
+    if (!h->have_map || !h->have_path || !h->have_state)
+        return fail(BCP_E_STATE, "%s: costmaps, paths and state must be set first", who);
+    const bcp_params& p = h->params;
+    if (p.control_delay > 0 || p.pose_delay > 0 || p.state_delay > 0)
+        return fail(BCP_E_INVALID, "%s: control_delay / pose_delay / state_delay > 0 are not supported (every "
+                                   "candidate would need delay queues of its own)", who);
+    HIP_TRY(hipSetDevice(h->device));
+    if (h->static_dirty) {
+        const int rc = upload_step_static(h, s);
+        if (rc != BCP_OK) return rc;
+    }
+    return h->edt_lazy ? ensure_fields(h, s) : BCP_OK;
+}
+
 // K candidate plans per env, scored on private copies of the env's state (bcp_lookahead.h).  Reads the handle, writes only
 // the caller's outputs: no step counter, ticket, parking counter, record or watchdog word is touched, so the steps before
 // and after the call are the steps of a handle that never looked ahead.
@@ -2127,12 +2155,9 @@ extern "C" int bcp_lookahead(bcp_handle* h, const bcp_lookahead_io* io, uint32_t
     if (!h || !io) return fail(BCP_E_INVALID, "bcp_lookahead: null argument");
     constexpr uint32_t allowed = BCP_STEP_ACTIONS_F32 | BCP_LOOKAHEAD_PER_ENV;
     if (flags & ~allowed) return fail(BCP_E_INVALID, "bcp_lookahead: undefined flag bits 0x%x", flags & ~allowed);
-    if (!h->have_map || !h->have_path || !h->have_state)
-        return fail(BCP_E_STATE, "bcp_lookahead: costmaps, paths and state must be set first");
+    hipStream_t s = (hipStream_t)stream;
+    { const int rc = plan_ready(h, "bcp_lookahead", s); if (rc != BCP_OK) return rc; }
     const bcp_params& p = h->params;
-    if (p.control_delay > 0 || p.pose_delay > 0 || p.state_delay > 0)
-        return fail(BCP_E_INVALID, "bcp_lookahead: control_delay / pose_delay / state_delay > 0 are not supported (every "
-                                   "candidate would need delay queues of its own)");
     if (io->horizon < 1 || io->n_candidates < 1)
         return fail(BCP_E_INVALID, "bcp_lookahead: horizon and n_candidates must be at least 1");
     if (!io->actions || !io->ret || !io->steps || !io->reason)
@@ -2148,16 +2173,6 @@ extern "C" int bcp_lookahead(bcp_handle* h, const bcp_lookahead_io* io, uint32_t
     const int64_t total = h->n * io->n_candidates;
     const int64_t blocks = (total + kBlock - 1) / kBlock;
     if (blocks > 0x7FFFFFFF) return fail(BCP_E_INVALID, "bcp_lookahead: n_envs * n_candidates exceeds the largest grid (2^37 lanes)");
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    if (h->static_dirty) {
-        const int rc = upload_step_static(h, s);
-        if (rc != BCP_OK) return rc;
-    }
-    if (h->edt_lazy) {   // collides_wave classifies with the uint8 field
-        const int rc = ensure_fields(h, s);
-        if (rc != BCP_OK) return rc;
-    }
     LookaheadArgs a;
     a.S = h->dev_static;
     a.actions = io->actions;
@@ -2196,12 +2211,9 @@ extern "C" int bcp_mppi(bcp_handle* h, const bcp_mppi_params* p, const bcp_mppi_
 {
     if (!h || !p || !io) return fail(BCP_E_INVALID, "bcp_mppi: null argument");
     if (flags & ~(uint32_t)BCP_STEP_ACTIONS_F32) return fail(BCP_E_INVALID, "bcp_mppi: undefined flag bits 0x%x", flags & ~(uint32_t)BCP_STEP_ACTIONS_F32);
-    if (!h->have_map || !h->have_path || !h->have_state)
-        return fail(BCP_E_STATE, "bcp_mppi: costmaps, paths and state must be set first");
+    hipStream_t s = (hipStream_t)stream;
+    { const int rc = plan_ready(h, "bcp_mppi", s); if (rc != BCP_OK) return rc; }
     const bcp_params& hp = h->params;
-    if (hp.control_delay > 0 || hp.pose_delay > 0 || hp.state_delay > 0)
-        return fail(BCP_E_INVALID, "bcp_mppi: control_delay / pose_delay / state_delay > 0 are not supported (every "
-                                   "candidate would need delay queues of its own)");
     if (p->horizon < 1 || p->iterations < 1) return fail(BCP_E_INVALID, "bcp_mppi: horizon and iterations must be at least 1");
     const int32_t K = p->n_candidates;
     if (K < 8 || K > 1024 || (K & (K - 1)) != 0)
@@ -2222,16 +2234,6 @@ extern "C" int bcp_mppi(bcp_handle* h, const bcp_mppi_params* p, const bcp_mppi_
     const int group = K < kBlock ? K : kBlock;
     const int64_t blocks = (h->n * group + kBlock - 1) / kBlock;
     if (blocks > 0x7FFFFFFF) return fail(BCP_E_INVALID, "bcp_mppi: n_envs exceeds the largest grid");
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    if (h->static_dirty) {
-        const int rc = upload_step_static(h, s);
-        if (rc != BCP_OK) return rc;
-    }
-    if (h->edt_lazy) {   // collides_wave classifies with the uint8 field
-        const int rc = ensure_fields(h, s);
-        if (rc != BCP_OK) return rc;
-    }
     MppiArgs a;
     a.S = h->dev_static;
     a.p = *p;
@@ -2253,15 +2255,9 @@ extern "C" int bcp_mppi(bcp_handle* h, const bcp_mppi_params* p, const bcp_mppi_
     const size_t lds = collision + (size_t)(K / group) * kBlock * sizeof(double);
     const bool plain = hp.reward_provider == BCP_REWARD_CONTINUOUS;
     const void* fn = plain ? reinterpret_cast<const void*>(mppi_kernel<true>) : reinterpret_cast<const void*>(mppi_kernel<false>);
-    if (lds > 64 * 1024) {   // (a staged map of nearly 64 KiB plus the scores; the attribute belongs to the function on a device)
-        static std::mutex lds_mutex;
-        static int32_t lds_max[64][2];
-        std::lock_guard<std::mutex> lock(lds_mutex);
-        int32_t& cur = lds_max[h->device & 63][plain ? 1 : 0];
-        if ((int32_t)lds > cur) {
-            HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            cur = (int32_t)lds;
-        }
+    if (lds > 64 * 1024) {   // (a staged map of nearly 64 KiB plus the scores)
+        const int rc = raise_dynamic_lds(fn, h->device, lds);
+        if (rc != BCP_OK) return rc;
     }
     if (plain) hipLaunchKernelGGL(mppi_kernel<true>, dim3((unsigned)blocks), dim3(kBlock), lds, s, a);
     else hipLaunchKernelGGL(mppi_kernel<false>, dim3((unsigned)blocks), dim3(kBlock), lds, s, a);
@@ -2335,9 +2331,7 @@ extern "C" int bcp_step_form(bcp_handle* h)
 {
     if (!h) return fail(BCP_E_INVALID, "bcp_step_form: null handle");
     if (!h->have_map || !h->have_path || !h->have_state) return fail(BCP_E_STATE, "bcp_step_form: costmaps, paths and state must be set first");
-    if (!step_uses_deferral(h)) return 0;
-    if (h->dense_threshold < 0) return 1;
-    return (h->fused && h->adaptive) ? 3 : 2;
+    return step_form(h);
 }
 
 extern "C" int bcp_time_steps(bcp_handle* h, const bcp_step_io* io, uint32_t flags, int32_t steps, void* stream,
@@ -2837,8 +2831,10 @@ static int egocentric_costmaps(bcp_handle* h, const double* poses, int64_t n, co
                            a.live);
         const size_t lds = map_bytes + 4 * row_bytes;
         const void* fn = px8 ? (const void*)ego_costmap_binned_kernel<8> : (const void*)ego_costmap_binned_kernel<4>;
-        if (lds > 64 * 1024)
-            HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        if (lds > 64 * 1024) {
+            const int rc = raise_dynamic_lds(fn, h->device, lds);
+            if (rc != BCP_OK) return rc;
+        }
         int per_cu = 0;
         HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, lds));
         const dim3 grid((unsigned)std::min<int64_t>(n, (int64_t)std::max(per_cu, 1) * cus));
@@ -2873,8 +2869,10 @@ static int egocentric_costmaps(bcp_handle* h, const double* poses, int64_t n, co
         const size_t lds = waves * row_bytes + (a.stage_map ? map_bytes : 0);
         const void* fn = a.stage_map ? (px8 ? (const void*)ego_costmap_kernel<true, 8> : (const void*)ego_costmap_kernel<true, 4>)
                                      : (px8 ? (const void*)ego_costmap_kernel<false, 8> : (const void*)ego_costmap_kernel<false, 4>);
-        if (lds > 64 * 1024)
-            HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        if (lds > 64 * 1024) {
+            const int rc = raise_dynamic_lds(fn, h->device, lds);
+            if (rc != BCP_OK) return rc;
+        }
         int per_cu = 0;
         HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64 * waves, lds));
         const dim3 grid((unsigned)std::min<int64_t>((n + waves - 1) / waves, (int64_t)std::max(per_cu, 1) * cus));
