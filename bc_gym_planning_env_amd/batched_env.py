@@ -439,12 +439,14 @@ class BatchedPlanEnv(object):
     :param next_geom: optional int array [G], successor of every pool entry; None = stay on the same entry
     :param map_storage: optional (rows, cols): private costmaps are stored with at least this (padded) shape, e.g.
         (256, 256) for BASELINE's "per-env 256x256 costmap"; the true shapes still bound the collision test
+    :param robot_constants: optional dict replacing any of robots.ROBOT_CONSTANTS (wheel base, steering and
+        acceleration limits, front-column P gain) for a robot of other dimensions than the stock ones
     """
 
     def __init__(self, costmap, path, params=None, n_envs=1, device=0, robot_name=None, noise_parameters='planenv',
                  auto_reset=False, env_id_base=0, seed=0, footprint_scale=1.0, dynamic_model=True,
                  model_front_column_pid=True, template_of_env=None, geom_of_env=None, next_geom=None, map_storage=None,
-                 unpinned_diffdrive_noise=False):
+                 unpinned_diffdrive_noise=False, robot_constants=None):
         params = EnvParams() if params is None else params
         self.params = params
         self._pure_pursuit = params.reward_provider_name == CONTINUOUS_REWARD_PURE_PURSUIT
@@ -460,7 +462,8 @@ class BatchedPlanEnv(object):
         if not torch.cuda.is_available():
             raise RuntimeError("BatchedPlanEnv needs a GPU (libbcplan has no CPU path)")
         self._bcp_params = robots.make_bcp_params(params, self.robot_name, noise_parameters, footprint_scale,
-                                                  dynamic_model, model_front_column_pid, unpinned_diffdrive_noise)
+                                                  dynamic_model, model_front_column_pid, unpinned_diffdrive_noise,
+                                                  robot_constants)
         self._h = C.c_void_p()
         dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
         _lib.check(self._lib.bcp_create(C.byref(self._bcp_params), self.n_envs, dev_index, int(env_id_base),

@@ -87,8 +87,11 @@ __device__ __forceinline__ double py_mod_two_pi(double a)
 // quotient estimate, its exact residual (one fma) and the correction (one fma) -- Markstein's sequence, which returns the
 // correctly rounded quotient, i.e. the very double x / d is (for every divisor whose significand is not all ones: the host
 // refuses such a dt / L; 3 x 10^6 random and swept dividends per divisor checked against exact rational arithmetic, and the
-// reference trajectories are the standing check).  Three instructions instead of the ~28 of a float64 division, six times on
-// the movers' chain of step_local_kernel.
+// reference trajectories are the standing check; tests/test_offstock_host.py repeats the exact-rational check for every dt and
+// wheel base the suite runs with, and pi).  Three instructions instead of the ~28 of a float64 division, six times on the
+// movers' chain of step_local_kernel.
+// One known exception: x = -0.0 returns +0.0 where -0.0 / d is -0.0 (the residual fma(-q, d, x) is (+0.0) + (-0.0) = +0.0, and
+// q + 0.0 * rd loses the sign).  The two compare equal, and no output of the reference shows the difference.
 __device__ __forceinline__ double div_by_const(double x, double d, double rd)
 {
     const double q = x * rd;

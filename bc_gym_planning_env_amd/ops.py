@@ -23,14 +23,14 @@ class NativeOps(object):
     """A libbcplan handle used only for the stand-alone operators (no env state bound)."""
 
     def __init__(self, robot_name=INDUSTRIAL_TRICYCLE_V1, device=0, noise_parameters=None, params=None,
-                 footprint_scale=1.0, dynamic_model=True, model_front_column_pid=True):
+                 footprint_scale=1.0, dynamic_model=True, model_front_column_pid=True, robot_constants=None):
         self._lib = _lib.load()
         if not torch.cuda.is_available():
             raise RuntimeError("NativeOps needs a GPU (libbcplan has no CPU path)")
         self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
         self.params = EnvParams() if params is None else params
         self._p = robots.make_bcp_params(self.params, robot_name, noise_parameters, footprint_scale, dynamic_model,
-                                         model_front_column_pid)
+                                         model_front_column_pid, robot_constants=robot_constants)
         self._h = C.c_void_p()
         self._n_maps = 1
         _lib.check(self._lib.bcp_create(C.byref(self._p), 1, self.device.index or 0, 0, C.byref(self._h)))

@@ -42,9 +42,18 @@ def get_footprint(robot_name, footprint_scale=1.0):
     return FOOTPRINTS[robot_name] * footprint_scale
 
 
+ROBOT_CONSTANTS = dict(front_wheel_from_axis=FRONT_WHEEL_FROM_AXIS, max_front_wheel_angle=MAX_FRONT_WHEEL_ANGLE,
+                       max_front_wheel_speed=MAX_FRONT_WHEEL_SPEED, max_linear_acceleration=MAX_LINEAR_ACCELERATION,
+                       max_angular_acceleration=MAX_ANGULAR_ACCELERATION, front_column_p_gain=FRONT_COLUMN_P_GAIN)
+
+
 def make_bcp_params(env_params, robot_name, noise_parameters, footprint_scale=1.0, dynamic_model=True,
-                    model_front_column_pid=True, unpinned_diffdrive_noise=False):
-    """EnvParams + robot -> bcp_params (include/bcplan.h)."""
+                    model_front_column_pid=True, unpinned_diffdrive_noise=False, robot_constants=None):
+    """EnvParams + robot -> bcp_params (include/bcplan.h).  `robot_constants`: optional dict replacing any of the six
+    constants of ROBOT_CONSTANTS (a robot of other dimensions than the stock examples); unknown keys raise."""
+    unknown = sorted(set(robot_constants or ()) - set(ROBOT_CONSTANTS))
+    if unknown:
+        raise KeyError("Unknown robot constants {}. Should be among {}".format(unknown, sorted(ROBOT_CONSTANTS)))
     p = _lib.BcpParams()
     p.abi_version = _lib.ABI_VERSION
     p.model = MODELS[robot_name]
@@ -71,6 +80,8 @@ def make_bcp_params(env_params, robot_name, noise_parameters, footprint_scale=1.
     p.max_linear_acceleration = MAX_LINEAR_ACCELERATION
     p.max_angular_acceleration = MAX_ANGULAR_ACCELERATION
     p.front_column_p_gain = FRONT_COLUMN_P_GAIN
+    for key, value in (robot_constants or {}).items():
+        setattr(p, key, float(value))
     rp = env_params.reward_provider_params
     p.spatial_precision = float(rp.spatial_precision)
     p.angular_precision = float(rp.angular_precision)

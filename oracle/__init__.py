@@ -164,7 +164,9 @@ PLANENV_NOISE = (0.0, 0.0, 1.e-2, 1.e-2, 1.e-3, 1.e-3)  # envs/base/env.py:228-2
 def make_params(model="tricycle", dt=0.05, noise=None, iteration_timeout=1200, spatial_precision=1.0,
                 angular_precision=np.pi / 2, spatial_progress_multiplier=0.0, footprint=None, footprint_scale=1.0,
                 dynamic_model=True, model_front_column_pid=True, reward_provider=REWARD_CONTINUOUS, control_delay=0,
-                pose_delay=0, state_delay=0):
+                pose_delay=0, state_delay=0, front_wheel_from_axis=0.964,
+                max_front_wheel_angle=0.5 * 170 * np.pi / 180., max_front_wheel_speed=60. * np.pi / 180.,
+                max_linear_acceleration=1. / 2.5, max_angular_acceleration=1. / 2., front_column_p_gain=0.16):
     p = Params()
     p.reward_provider = reward_provider
     p.control_delay, p.pose_delay, p.state_delay = control_delay, pose_delay, state_delay
@@ -177,12 +179,12 @@ def make_params(model="tricycle", dt=0.05, noise=None, iteration_timeout=1200, s
         p.verts[i][0] = x
         p.verts[i][1] = y
     p.dt = dt
-    p.front_wheel_from_axis = 0.964
-    p.max_front_wheel_angle = 0.5 * 170 * np.pi / 180.
-    p.max_front_wheel_speed = 60. * np.pi / 180.
-    p.max_linear_acceleration = 1. / 2.5
-    p.max_angular_acceleration = 1. / 2.
-    p.front_column_p_gain = 0.16
+    p.front_wheel_from_axis = front_wheel_from_axis
+    p.max_front_wheel_angle = max_front_wheel_angle
+    p.max_front_wheel_speed = max_front_wheel_speed
+    p.max_linear_acceleration = max_linear_acceleration
+    p.max_angular_acceleration = max_angular_acceleration
+    p.front_column_p_gain = front_column_p_gain
     p.dynamic_model = int(dynamic_model)
     p.model_front_column_pid = int(model_front_column_pid)
     p.noise_on = int(noise is not None)

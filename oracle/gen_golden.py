@@ -14,6 +14,8 @@ Fixture list:
   g8_traj_*.npz             full PlanEnv.step trajectories (RandomMiniEnv seeds, AisleTurnEnv variants)
   g9 .. g12                 RandomMiniEnv worlds, egocentric observations, delays / pure pursuit, coloured ego costmap
   g13_serialized_*.npz      PlanEnv.serialize() records taken mid-episode + the next 100 steps of the live env
+  g16_robot_step_params.npz, g16_traj_*.npz   robot steps and PlanEnv trajectories away from the stock parameters: other dt,
+                            other tricycle dimensions, other alphas, other reward parameters, a short time-out
   g15_footprint_zoo.npz     the footprint zoo of tests/footprints.py: pre-fill polygons, scaled stock footprints and
                             pose_collides verdicts on the g6 maps   (python oracle/gen_golden.py footprint_zoo)
 """
@@ -740,12 +742,127 @@ def gen_egocentric():
              window_origin=np.array([-0.5, -2.0]), window_size=np.array([3.5, 4.0]))
 
 
+# ---- G16: away from the stock parameters ------------------------------------------------------------------------
+ROBOT_CONSTANT_KEYS = ("front_wheel_from_axis", "max_front_wheel_angle", "max_front_wheel_speed",
+                       "max_linear_acceleration", "max_angular_acceleration", "front_column_p_gain")
+OFFSTOCK_ROBOTS = dict(
+    short=(0.5, 1.0, 2.0, 1.5, 2.0, 0.5),       # short and twitchy
+    long=(1.7, 0.6, 0.3, 0.1, 0.15, 0.05))      # long and sluggish
+OFFSTOCK_DTS = (0.02, 1. / 30., 0.1, 0.25)
+OFFSTOCK_ALPHAS = dict(all_six=(0.02, 0.005, 0.01, 0.02, 0.003, 0.004), first_two=(0.03, 0.01, 0.0, 0.0, 0.0, 0.0))
+# tag -> (RandomMiniEnv seed, steps, EnvParams keywords, (sp, ap, multiplier) or None = EnvParams' own)
+OFFSTOCK_TRAJ = [
+    ("dt0100", 2, 200, dict(dt=0.1), None),
+    ("dt0020", 1, 250, dict(dt=0.02), None),
+    ("dt0033", 4, 400, dict(dt=1. / 30.), None),
+    ("reach_mid", 2, 200, dict(dt=0.1), (0.35, np.pi / 3, 0.5)),
+    ("reach_ap_pi", 3, 150, dict(dt=0.1), (0.1, 3.2, 2.0)),
+    ("timeout7", 1, 150, dict(iteration_timeout=7), None),
+]
+
+
+def gen_offstock():
+    """G16: TricycleRobot.step / DiffDriveRobot.step at four dt, with two tricycles of other dimensions than the stock one,
+    with and without the dynamic model and the front-column PID, and with two other alpha sets; and six PlanEnv
+    trajectories at other dt, reward parameters and time-out.  Every constant used is stored next to the arrays."""
+    from bc_gym_planning_env.robot_models import differential_drive as dd
+    from bc_gym_planning_env.robot_models.tricycle_model import TricycleRobot, TricycleRobotState
+    from bc_gym_planning_env.robot_models.differential_drive import DiffDriveRobot, DiffdriveRobotState
+    from bc_gym_planning_env.robot_models.robot_dimensions_examples import get_dimensions_example
+    from bc_gym_planning_env.envs.base.action import Action
+    from bc_gym_planning_env.envs.base.params import EnvParams
+    from bc_gym_planning_env.envs.base.reward import RewardParams
+    from bc_gym_planning_env.envs.mini_env import RandomMiniEnv, RandomMiniEnvParams
+    stock = get_dimensions_example('industrial_tricycle_v1')
+    method_of = dict(zip(ROBOT_CONSTANT_KEYS, ROBOT_CONSTANT_KEYS[:5] + ("front_column_model_p_gain",)))
+
+    def dimensions(values):
+        members = dict((method_of[k], staticmethod(lambda v=v: v)) for k, v in zip(ROBOT_CONSTANT_KEYS, values))
+        return type("OffstockTricycleDimensions", (stock,), members)
+    robots = [("stock", stock)] + [(name, dimensions(v)) for name, v in sorted(OFFSTOCK_ROBOTS.items())]
+    n = 256
+    tri_st, tri_cmd, tri_f32 = random_robot_inputs(np.random.RandomState(161), n, True)
+    dd_st, dd_cmd, _ = random_robot_inputs(np.random.RandomState(162), n, False)
+    dd_st[:, 5:] = 0.0
+    meta = dict(model=[], dt=[], constants=[], dynamic_model=[], pid=[], noise_on=[], alpha=[], name=[])
+    outs, zs = [], []
+
+    def tricycle(name, dims, dt, dyn, pid, alpha_name):
+        alpha = OFFSTOCK_ALPHAS[alpha_name] if alpha_name else None
+        noise = dict(("alpha%d" % (k + 1), alpha[k]) for k in range(6)) if alpha else None
+        robot = TricycleRobot(dimensions=dims, noise_parameters=noise, dynamic_model=dyn, model_front_column_pid=pid)
+        out, z = np.zeros((n, 7)), np.full((n, 3), np.nan)
+        with SlotTap(dd, 1600 + len(outs)) as tap:
+            for i in range(n):
+                robot.set_state(TricycleRobotState(
+                    x=tri_st[i, 0], y=tri_st[i, 1], angle=tri_st[i, 2], v=tri_st[i, 3], w=tri_st[i, 4],
+                    steering_motor_command=tri_st[i, 5], wheel_angle=tri_st[i, 6]))
+                # (without the PID a float32 command stays float32 through the model, see gen_robot_steps: float64 there)
+                c = tri_cmd[i].astype(np.float32) if tri_f32[i] and pid else tri_cmd[i]
+                robot.step(dt, Action(command=c))
+                out[i] = tri_state_vec(robot.get_state())
+                z[i] = tap.take()
+        meta["model"].append(0); meta["dt"].append(dt); meta["dynamic_model"].append(int(dyn)); meta["pid"].append(int(pid))
+        meta["constants"].append([getattr(dims, method_of[k])() for k in ROBOT_CONSTANT_KEYS])
+        meta["noise_on"].append(int(alpha is not None)); meta["alpha"].append(alpha or (0.,) * 6)
+        meta["name"].append("tri-%s-dt%.4f-dyn%d-pid%d%s" % (name, dt, dyn, pid, "-" + alpha_name if alpha_name else ""))
+        outs.append(out); zs.append(z)
+    for name, dims in robots:
+        for dt in OFFSTOCK_DTS:
+            for dyn in (True, False):
+                for pid in (True, False):
+                    tricycle(name, dims, dt, dyn, pid, None)
+    for alpha_name in sorted(OFFSTOCK_ALPHAS):
+        for (name, dims), dt in zip(robots + robots[:1], OFFSTOCK_DTS):
+            tricycle(name, dims, dt, True, True, alpha_name)
+    n_drawn = (~np.isnan(np.stack(zs))).reshape(len(zs), -1, 3).sum(axis=(0, 1))
+    assert (n_drawn > 500).all(), n_drawn          # (every slot, the first included, is drawn by these alphas)
+    for dt in OFFSTOCK_DTS:
+        robot = DiffDriveRobot(dimensions=get_dimensions_example('industrial_diffdrive_v1'), noise_parameters=None)
+        out = np.zeros((n, 7))
+        for i in range(n):
+            robot.set_state(DiffdriveRobotState(x=dd_st[i, 0], y=dd_st[i, 1], angle=dd_st[i, 2], v=dd_st[i, 3], w=dd_st[i, 4]))
+            robot.step(dt, Action(command=dd_cmd[i]))      # (float64 commands: see gen_robot_steps)
+            out[i] = dd_state_vec(robot.get_state())
+        meta["model"].append(1); meta["dt"].append(dt); meta["dynamic_model"].append(1); meta["pid"].append(1)
+        meta["constants"].append([getattr(stock, method_of[k])() for k in ROBOT_CONSTANT_KEYS])
+        meta["noise_on"].append(0); meta["alpha"].append((0.,) * 6)
+        meta["name"].append("dd-dt%.4f" % dt)
+        outs.append(out); zs.append(np.full((n, 3), np.nan))
+    save("g16_robot_step_params.npz", tri_state=tri_st, tri_cmd=tri_cmd, dd_state=dd_st, dd_cmd=dd_cmd,
+         constant_keys=np.array(ROBOT_CONSTANT_KEYS), names=np.array(meta["name"]),
+         model=np.array(meta["model"], dtype=np.int32), dt=np.array(meta["dt"]), constants=np.array(meta["constants"]),
+         dynamic_model=np.array(meta["dynamic_model"], dtype=np.int32), pid=np.array(meta["pid"], dtype=np.int32),
+         noise_on=np.array(meta["noise_on"], dtype=np.int32), alpha=np.array(meta["alpha"]),
+         out=np.stack(outs), z=np.stack(zs))
+
+    n_collide = 0
+    for tag, seed, steps, kw, reach in OFFSTOCK_TRAJ:
+        defaults = EnvParams()
+        sp, ap, mult = reach if reach else (defaults.goal_spat_dist, defaults.goal_ang_dist, 0.0)
+        ep = EnvParams(goal_spat_dist=sp, goal_ang_dist=ap, reward_provider_params=RewardParams(
+            spatial_precision=sp, angular_precision=ap, spatial_progress_multiplier=mult), **kw)
+        env = RandomMiniEnv(params=RandomMiniEnvParams(env_params=ep), rng=np.random.RandomState(seed),
+                            draw_new_turn_on_reset=False)
+        assert 150 <= steps <= 400
+        rec = record_trajectory(env, env._env, steps, action_seed=1600 + seed, noise_seed=2600 + seed)
+        assert rec["done"].any(), tag
+        n_collide += int(rec["collided"].any())
+        rec.update(dt=np.float64(ep.dt), iteration_timeout=np.int32(ep.iteration_timeout), spatial_precision=np.float64(sp),
+                   angular_precision=np.float64(ap), spatial_progress_multiplier=np.float64(mult))
+        save("g16_traj_%s.npz" % tag, **rec)
+    assert n_collide >= 2, n_collide
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     O.build()
     H.load()
     if sys.argv[1:] == ["footprint_zoo"]:   # (added after the others: writes its own file only)
         gen_footprint_zoo()
+        return
+    if sys.argv[1:] == ["offstock"]:
+        gen_offstock()
         return
     gen_robot_steps()
     gen_scalar_utils()
@@ -761,6 +878,7 @@ def main():
     gen_diffdrive_trajectories()
     gen_trajectories()
     gen_footprint_zoo()
+    gen_offstock()
 
 
 if __name__ == "__main__":

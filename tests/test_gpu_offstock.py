@@ -1,0 +1,262 @@
+"""The HIP path away from the stock parameters: other dt, tricycles of other dimensions, all six alphas, other (spatial
+precision, angular precision, progress multiplier), short time-outs -- against fixtures made with the genuine reference
+(tests/golden/g16_*) and against the CPU oracle, which tests/test_oracle_golden.py pins to those fixtures first.  The batches
+are the ones of tests/offstock.py: 600 envs (two full 256-env workgroups and a tail of 88), shown to be non-vacuous on the
+oracle alone by tests/test_offstock_host.py; every run asserts the same floors on what it saw itself.
+Flags, target_idx and current_iter are compared exactly, state / reward / min_dist within ATOL; no env is left out."""
+import glob
+import os
+
+import numpy as np
+import pytest
+
+import lookahead_ref as LR
+import mppi_ref as MR
+import offstock as OS
+from util import ATOL, GOLDEN, z_in
+
+pytestmark = pytest.mark.gpu
+
+FORMS = [dict(), dict(fused=0), dict(defer=0), dict(local_pairs=2)]
+
+
+def _form_id(m):
+    return "-".join("%s%d" % (k[:5], v) for k, v in sorted(m.items())) or "default"
+
+
+# ---------------------------------------------------------------------------------------------- a. single robot steps
+def _g16():
+    return OS._golden("g16_robot_step_params.npz")
+
+
+@pytest.mark.parametrize("group", ["tri-stock-", "tri-short-", "tri-long-", "noise", "dd-"])
+def test_robot_step_vs_reference_at_other_parameters(torch_cuda, group):
+    """bcp_robot_step on every combination of g16_robot_step_params (dt x dimensions x dynamic model x PID, two alpha sets with
+    the normals by slot, the diff-drive robot at every dt), constants read from the fixture"""
+    from bc_gym_planning_env_amd import EnvParams, NativeOps
+    g = _g16()
+    keys = [str(k) for k in g["constant_keys"]]
+    names = [str(nm) for nm in g["names"]]
+    if group == "noise":
+        combos = [c for c in range(len(names)) if g["noise_on"][c]]
+    else:
+        combos = [c for c in range(len(names)) if names[c].startswith(group) and not g["noise_on"][c]]
+    assert len(combos) == {"noise": 8, "dd-": 4}.get(group, 16)
+    for c in combos:
+        tri = int(g["model"][c]) == 0
+        noise = dict(("alpha%d" % (k + 1), float(g["alpha"][c][k])) for k in range(6)) if g["noise_on"][c] else None
+        ops = NativeOps('industrial_tricycle_v1' if tri else 'industrial_diffdrive_v1', noise_parameters=noise,
+                        params=EnvParams(dt=float(g["dt"][c])), dynamic_model=bool(g["dynamic_model"][c]),
+                        model_front_column_pid=bool(g["pid"][c]),
+                        robot_constants=dict(zip(keys, g["constants"][c].tolist())) if tri else None)
+        st, cmd = (g["tri_state"], g["tri_cmd"]) if tri else (g["dd_state"], g["dd_cmd"])
+        out, err = ops.robot_step(st, cmd, z_in(g["z"][c])) if noise else ops.robot_step(st, cmd)
+        worst = np.abs(out.cpu().numpy() - g["out"][c]).max()
+        print("%-44s max |out - reference| = %.3g" % (names[c], worst))
+        np.testing.assert_allclose(out.cpu().numpy(), g["out"][c], rtol=0, atol=ATOL, err_msg=names[c])
+        assert int(err.sum()) == 0, names[c]
+
+
+# ---------------------------------------------------------------------------------------------- b. recorded trajectories
+G16_TRAJ = sorted(glob.glob(os.path.join(GOLDEN, "g16_traj_*.npz")))
+
+
+@pytest.mark.parametrize("form", FORMS[:3], ids=_form_id)
+@pytest.mark.parametrize("path", G16_TRAJ, ids=[os.path.basename(p)[9:-4] for p in G16_TRAJ])
+def test_recorded_trajectories_at_other_parameters(torch_cuda, path, form):
+    """PlanEnv.step at another dt / reward parameters / time-out, replayed on three replicas with the recorded actions and
+    normals: the assertions of test_full_step_trajectories_vs_reference, `time` (dt accumulated step by step) exact, and the
+    replicas bit-identical to each other"""
+    torch = torch_cuda
+    from bc_gym_planning_env_amd import BatchedPlanEnv, CostMap2D, EnvParams, RewardParams
+    g = dict(np.load(path))
+    res, dt = float(g["resolution"]), float(g["dt"])
+    sp, ap, mult = float(g["spatial_precision"]), float(g["angular_precision"]), float(g["spatial_progress_multiplier"])
+    params = EnvParams(dt=dt, goal_spat_dist=sp, goal_ang_dist=ap, iteration_timeout=int(g["iteration_timeout"]), resolution=res,
+                       refine_path=False, reward_provider_params=RewardParams(sp, ap, mult))
+    n = 3
+    env = BatchedPlanEnv(CostMap2D(g["costmap"], res, g["origin"]), g["path"], params, n_envs=n)
+    env.set_tuning(**form)
+    assert int(env.state.target_idx[0]) == int(g["init_target_idx"])
+    assert float(env.state.min_spat_dist_so_far[0]) == float(g["init_min_dist"])
+    T = len(g["actions"])
+    actions = torch.from_numpy(np.repeat(g["actions"].astype(np.float32)[:, None], n, axis=1)).cuda()
+    z = torch.from_numpy(np.repeat(z_in(g["z"])[:, None], n, axis=1)).cuda()
+    states = torch.zeros(T, 7, n, dtype=torch.float64, device="cuda")
+    rew = torch.zeros(T, n, dtype=torch.float64, device="cuda")
+    done = torch.zeros(T, n, dtype=torch.uint8, device="cuda")
+    coll = torch.zeros(T, n, dtype=torch.uint8, device="cuda")
+    tidx = torch.zeros(T, n, dtype=torch.int32, device="cuda")
+    mind = torch.zeros(T, n, dtype=torch.float64, device="cuda")
+    tm = torch.zeros(T, n, dtype=torch.float64, device="cuda")
+    for t in range(T):
+        obs, r, d, info = env.step(actions[t], z[t])
+        states[t], rew[t], done[t], coll[t] = env.state.robot, r, d, env.state.robot_collided
+        tidx[t], mind[t], tm[t] = env.state.target_idx, env.state.min_spat_dist_so_far, obs.time
+        assert info == {}
+    env.check_errors()
+    for name, a in (("states", states), ("reward", rew), ("done", done), ("collided", coll), ("target_idx", tidx),
+                    ("min_dist", mind), ("time", tm)):
+        for k in range(1, n):
+            assert torch.equal(a[..., k], a[..., 0]), "replica %d differs from replica 0 in %s" % (k, name)
+    np.testing.assert_array_equal(done.cpu().numpy()[:, 0], g["done"])
+    np.testing.assert_array_equal(coll.cpu().numpy()[:, 0], g["collided"])
+    np.testing.assert_array_equal(tidx.cpu().numpy()[:, 0], g["target_idx"])
+    np.testing.assert_array_equal(tm.cpu().numpy()[:, 0], g["time"])
+    np.testing.assert_allclose(states.cpu().numpy()[:, :, 0], g["states"], rtol=0, atol=ATOL)
+    np.testing.assert_allclose(rew.cpu().numpy()[:, 0], g["reward"], rtol=0, atol=ATOL)
+    np.testing.assert_allclose(mind.cpu().numpy()[:, 0], g["min_dist"], rtol=0, atol=ATOL)
+    assert g["done"].any()
+    o = obs[0]
+    assert o.path.shape[0] == max(len(g["path"]) - int(g["target_idx"][-1]), 0)
+    assert o.time == g["time"][-1] and o.dt == dt
+    s = env.envs[0].get_state()
+    assert s.current_iter == T and s.robot_collided == bool(g["collided"][-1])
+
+
+# ---------------------------------------------------------------------------------------------- c, d. batches against the oracle
+def _make_env(b, form=None, seed=123, auto_reset=True):
+    from bc_gym_planning_env_amd import BatchedPlanEnv, CostMap2D
+    params, kw = b.cfg.env_params(b.res), b.cfg.env_kwargs()
+    if b.world == "aisle":
+        cms = [CostMap2D(x["costmap"], b.res, x["origin"]) for x in b.templates]
+        env = BatchedPlanEnv(cms, [x["path"] for x in b.templates], params, n_envs=b.n, auto_reset=auto_reset, seed=seed,
+                             template_of_env=np.arange(b.n) % 4, map_storage=(256, 256), **kw)
+    else:
+        env = BatchedPlanEnv(CostMap2D(b.maps, b.res, b.origins), b.paths, params, n_envs=b.n, auto_reset=auto_reset, seed=seed, **kw)
+    if form:
+        env.set_tuning(**form)
+    np.testing.assert_array_equal(env.action_space.low, b.box.low)
+    np.testing.assert_array_equal(env.action_space.high, b.box.high)
+    return env
+
+
+def _put_start(torch, env, b):
+    st, md, tgt, it = b.start
+    env.state.robot.copy_(torch.from_numpy(st))
+    env.state.min_spat_dist_so_far.copy_(torch.from_numpy(md))
+    env.state.target_idx.copy_(torch.from_numpy(tgt))
+    env.state.current_iter.copy_(torch.from_numpy(it))
+
+
+def _run_against_oracle(torch, oracle, world, row, form):
+    b = OS.Batch(oracle, world, row)
+    env = _make_env(b, form)
+    ref, n = b.ref, b.n
+    if world != "mini":    # (both sides made their initial state from the path on their own)
+        np.testing.assert_array_equal(env.state.target_idx.cpu().numpy(), ref.init_target_idx)
+        np.testing.assert_array_equal(env.state.min_spat_dist_so_far.cpu().numpy(), ref.init_min_dist)
+    _put_start(torch, env, b)
+    noisy = b.cfg.alpha is not None
+    zout = torch.zeros(n, 3, dtype=torch.float64, device="cuda") if noisy else None
+    worst = 0.0
+    for t in range(OS.STEPS):
+        a = b.next_actions()
+        before_state, before_target = np.stack(ref.st), ref.target_idx.copy()
+        if noisy:
+            env.step(a, noise_z_out=zout)
+        else:
+            env.step(a)
+        z = zout.cpu().numpy() if noisy else None
+        b.step_oracle(a, z)
+        gpu_state = env.state.robot.cpu().numpy()
+        flags = [("done", env.done, ref.done), ("collided_now", env.collided_now, ref.collided_now),
+                 ("target_idx", env.state.target_idx, ref.target_idx), ("current_iter", env.state.current_iter, ref.cur_iter),
+                 ("robot_collided", env.state.robot_collided, ref.collided)]
+        bad = set()
+        for name, got, want in flags:
+            bad |= set(np.nonzero(got.cpu().numpy() != want)[0].tolist())
+        if bad:    # a finding: say where the oracle itself stands relative to the limits the flags sit on
+            lines = [", ".join("%s %d / %d" % (name, int(got[i]), int(want[i])) for name, got, want in flags) + " (GPU / oracle): " +
+                     OS.describe_flag_difference(b, i, before_state, before_target, a, z, gpu_state) for i in sorted(bad)[:8]]
+            pytest.fail("%s row %d %s, step %d: %d envs differ in a flag\n%s" % (world, row, form, t, len(bad), "\n".join(lines)))
+        np.testing.assert_allclose(gpu_state, np.stack(ref.st), rtol=0, atol=ATOL, err_msg="step %d" % t)
+        np.testing.assert_allclose(env.reward.cpu().numpy(), ref.reward, rtol=0, atol=ATOL, err_msg="step %d" % t)
+        np.testing.assert_allclose(env.state.min_spat_dist_so_far.cpu().numpy(), ref.min_dist, rtol=0, atol=ATOL, err_msg="step %d" % t)
+        worst = max(worst, np.abs(gpu_state - np.stack(ref.st)).max())
+    env.check_errors()
+    print("%s row %d %s: max |state - oracle| = %.3g, %s" % (world, row, form, worst, b.counts))
+    b.assert_floors()
+
+
+SHARED = ([(row, FORMS[0]) for row in range(1, 11)] + [(row, form) for row in (11, 12) for form in FORMS] +
+          [(row, FORMS[0]) for row in (13, 14)])
+
+
+@pytest.mark.parametrize("row,form", SHARED, ids=["row%d-%s" % (r, _form_id(f)) for r, f in SHARED])
+def test_shared_map_grid_vs_oracle(torch_cuda, oracle, row, form):
+    """shared map and path of g8_traj_mini_00, auto-reset, on-device noise read back and replayed in the oracle, a third of the
+    robots next to lethal cells: one grid row per parameter moved, rows 11 and 12 with everything moved at once and under
+    every step form, rows 13 and 14 with alpha1 / alpha2 alone (only the first noise slot is ever drawn)"""
+    _run_against_oracle(torch_cuda, oracle, "mini", row, form)
+
+
+@pytest.mark.parametrize("row", [1, 7])
+def test_diffdrive_grid_vs_oracle(torch_cuda, oracle, row):
+    """the diff-drive robot on the shared 64 x 64 map, noise off, at dt 0.1 and at (0.35, pi / 3, 0.5)"""
+    _run_against_oracle(torch_cuda, oracle, "dd64", row, None)
+
+
+PRIVATE = [(row, form) for row in (7, 8, 9, 11) for form in (FORMS[0], FORMS[2])]
+
+
+@pytest.mark.parametrize("row,form", PRIVATE, ids=["row%d-%s" % (r, _form_id(f)) for r, f in PRIVATE])
+def test_private_maps_and_paths_grid_vs_oracle(torch_cuda, oracle, row, form):
+    """the four g8_traj_aisle_c4 templates as private 256 x 256 maps and private paths: other sp and ap through the bucket tables
+    and the quantised prefilter records (tight in both, and ap >= pi)"""
+    _run_against_oracle(torch_cuda, oracle, "aisle", row, form)
+
+
+# ---------------------------------------------------------------------------------------------- e. bcp_rollout
+def test_rollout_with_everything_moved(torch_cuda):
+    """row 11 (dt 0.1, short robot, six alphas, (0.35, pi / 3, 0.5)): K = 7 steps per launch, 2 rounds, bit for bit against a
+    twin batch stepped launch by launch"""
+    from test_gpu_rollout import _roll_and_compare
+    from bc_gym_planning_env_amd import BatchedPlanEnv, CostMap2D
+    g = LR.mini_fixture()
+    cfg = OS.Config(11, (0.2, np.pi / 8, 0.0))
+    res = float(g["resolution"])
+    make = lambda: BatchedPlanEnv(CostMap2D(g["costmap"], res, g["origin"]), g["path"], cfg.env_params(res), n_envs=OS.N_ENVS,
+                                  auto_reset=True, seed=77, **cfg.env_kwargs())
+    hits, dones = _roll_and_compare(torch_cuda, make, 7, rounds=2, scale=2.0, scatter=0.5)
+    assert hits > 20 and dones > 20, (hits, dones)
+
+
+# ---------------------------------------------------------------------------------------------- f. bcp_lookahead, bcp_mppi
+def _planning_case(torch, oracle):
+    """row 11 on 64 envs (a third next to lethal cells), the noise-free forward model on a handle that has noise on"""
+    b = OS.Batch(oracle, "mini", 11, n=64)
+    env = _make_env(b, auto_reset=False)
+    _put_start(torch, env, b)
+    st, md, tgt, it = b.start
+    start = LR.StartState(st, md, tgt, it)
+    world = dict(costmaps=b.maps, origins=b.origins, resolution=b.res, paths=b.paths)
+    return b, env, start, world, b.cfg.oracle_params(oracle, noise=False)
+
+
+def test_lookahead_with_everything_moved(torch_cuda, oracle):
+    from test_gpu_lookahead import ALL, _check, _check_best_action
+    torch = torch_cuda
+    k, horizon = 16, 8
+    b, env, start, world, p = _planning_case(torch, oracle)
+    library = LR.random_library(np.random.RandomState(11), k, horizon)
+    exp = LR.oracle_lookahead(oracle, p, world, start, library, threads=16)
+    lib = torch.from_numpy(library).cuda()
+    la = env.lookahead(lib, want=ALL)
+    got = _check(la, exp, horizon, tag="row 11 64x16")
+    _check_best_action(la, lib)
+    assert (la.err.cpu().numpy() == 0).all()
+    assert ((got["reason"] & LR.DONE_COLLIDED) != 0).sum() >= 50 and (exp["ret"] > 0).sum() >= 50
+
+
+def test_mppi_with_everything_moved(torch_cuda, oracle):
+    from test_gpu_mppi import ALL, _teacher_forced
+    torch = torch_cuda
+    k, horizon, sigma, lam, penalty = 16, 8, (0.2, 0.8), 0.3, 2.0
+    b, env, start, world, p = _planning_case(torch, oracle)
+    eps = MR.host_eps(MR.EPS_SEED, 2, b.n, k, horizon)
+    mean = np.ascontiguousarray(np.broadcast_to(np.array((0.4, 0.0)), (b.n, horizon, 2)))
+    res = env.mppi(mean, sigma, 2, k, lam, penalty, eps=eps, want=ALL)
+    assert torch.equal(res.eps, torch.from_numpy(eps).cuda())
+    hits = _teacher_forced(torch, env, res, sigma, lam, penalty, (oracle, p, world, start), tag="row 11")
+    assert (res.err == 0).all() and hits >= 50

@@ -260,3 +260,67 @@ def test_g12_colored_ego_observation(oracle, golden_dir):
         assert img.shape == (rows, cols) and ((img == 254) == want).all(), t
         vec = oracle.goal_direction_state(st[:3], g["path"][-1], world, [st[3], st[4], st[6]])
         np.testing.assert_allclose(vec, g["goal"][t], rtol=0, atol=1e-12)
+
+
+# ---- G16: away from the stock parameters (other dt, tricycle dimensions, alphas, reward parameters, time-out) ----
+def test_g16_robot_step_params(oracle, golden_dir):
+    """Every combination of g16_robot_step_params: the constants come from the fixture, nothing is restated here."""
+    g = dict(load(golden_dir, "g16_robot_step_params.npz"))      # (read every array once)
+    keys = [str(k) for k in g["constant_keys"]]
+    assert len(g["names"]) == len(g["out"]) >= 60
+    n_drawn = np.zeros(3, dtype=np.int64)
+    for c, name in enumerate(g["names"]):
+        tri = int(g["model"][c]) == 0
+        p = oracle.make_params("tricycle" if tri else "diffdrive", dt=float(g["dt"][c]),
+                               noise=g["alpha"][c] if g["noise_on"][c] else None, dynamic_model=int(g["dynamic_model"][c]),
+                               model_front_column_pid=int(g["pid"][c]), **dict(zip(keys, g["constants"][c].tolist())))
+        st, cmd = (g["tri_state"], g["tri_cmd"]) if tri else (g["dd_state"], g["dd_cmd"])
+        for i in range(len(st)):
+            z = g["z"][c, i]
+            out, err, drawn = oracle.robot_step(p, st[i], cmd[i], np.where(np.isnan(z), 1e300, z) if g["noise_on"][c] else None)
+            assert err == 0 and drawn == sum(1 << k for k in range(3) if not np.isnan(z[k])), (name, i)
+            n_drawn += ~np.isnan(z)
+            np.testing.assert_array_equal(out, g["out"][c, i], err_msg="%s row %d" % (name, i))
+    assert (n_drawn > 500).all(), n_drawn
+    # the fixture moves what it claims to move
+    assert len(set(g["dt"].tolist())) == 4 and 0.05 not in g["dt"]
+    assert len(set(map(tuple, g["constants"].tolist()))) == 3
+
+
+G16_TRAJ = sorted(glob.glob(os.path.join(os.path.dirname(__file__), "golden", "g16_traj_*.npz")))
+
+
+@pytest.mark.parametrize("path", G16_TRAJ, ids=[os.path.basename(p)[9:-4] for p in G16_TRAJ])
+def test_g16_trajectories(oracle, path):
+    g = dict(np.load(path))
+    p = oracle.make_params("tricycle", dt=float(g["dt"]), noise=oracle.PLANENV_NOISE,
+                           iteration_timeout=int(g["iteration_timeout"]), spatial_precision=float(g["spatial_precision"]),
+                           angular_precision=float(g["angular_precision"]),
+                           spatial_progress_multiplier=float(g["spatial_progress_multiplier"]))
+    env = oracle.OracleBatch(p, 1, g["costmap"], g["origin"], float(g["resolution"]), g["path"])
+    env.reset_from_paths()
+    assert env.target_idx[0] == int(g["init_target_idx"]) and env.min_dist[0] == float(g["init_min_dist"])
+    np.testing.assert_array_equal([env.st[f][0] for f in range(7)], g["init_state"])
+    assert g["done"].any()
+    for t in range(len(g["actions"])):
+        z = np.where(np.isnan(g["z"][t]), 1e300, g["z"][t])[None]
+        env.step(g["actions"][t][None], z)
+        np.testing.assert_array_equal([env.st[f][0] for f in range(7)], g["states"][t], err_msg="step %d" % t)
+        assert env.reward[0] == g["reward"][t], t
+        assert env.done[0] == g["done"][t], t
+        assert env.collided[0] == g["collided"][t], t
+        assert env.target_idx[0] == g["target_idx"][t], t
+        assert env.min_dist[0] == g["min_dist"][t], t
+        assert env.cur_time[0] == g["time"][t], t
+        assert len(g["path"]) - env.target_idx[0] == g["obs_path_len"][t] or env.target_idx[0] >= len(g["path"])
+    assert env.err[0] == 0
+
+
+def test_g16_covers_the_parameter_points():
+    assert len(G16_TRAJ) == 6
+    gs = [np.load(p) for p in G16_TRAJ]
+    assert sum(int(g["collided"].any()) for g in gs) >= 2
+    assert set(round(float(g["dt"]), 6) for g in gs) >= {0.1, 0.02, round(1. / 30., 6)}
+    assert any(float(g["angular_precision"]) >= np.pi for g in gs) and any(int(g["iteration_timeout"]) == 7 for g in gs)
+    g = [g for g in gs if float(g["dt"]) == 0.1][0]     # time is dt accumulated, which is not iter * dt
+    assert not np.array_equal(g["time"], (np.arange(len(g["time"])) + 1) * 0.1)

@@ -38,3 +38,31 @@ def oracle_params_for(oracle, name, **kw):
 def z_in(z):
     """NaN (= slot not drawn in the reference) -> a poison value that must never be consumed."""
     return np.where(np.isnan(z), 1e300, z)
+
+
+def random_batch(oracle, rng, n, g, name, timeout=1200, xy_sigma=0.15, th_sigma=0.3):
+    """n envs on the recorded map/path, started from random poses near the path (many collide or progress), at a random
+    iteration below `timeout` (the first eight one step before it).  -> state [7, n], min_dist, target_idx, current_iter"""
+    path = g["path"]
+    idx = rng.randint(0, len(path), n)
+    st = np.zeros((7, n))
+    st[0] = path[idx, 0] + rng.normal(0, xy_sigma, n)
+    st[1] = path[idx, 1] + rng.normal(0, xy_sigma, n)
+    st[2] = path[idx, 2] + rng.normal(0, th_sigma, n)
+    st[3] = rng.uniform(0, 0.5, n)
+    st[4] = rng.uniform(-0.5, 0.5, n)
+    st[6] = rng.uniform(-1.0, 1.0, n)
+    # a third of the robots start next to a lethal cell, so that collisions (and rollbacks) really happen
+    ly, lx = np.nonzero(g["costmap"] == 254)
+    near = rng.rand(n) < 0.33
+    pick = rng.randint(0, len(ly), n)
+    res = float(g["resolution"])
+    ang = rng.uniform(-np.pi, np.pi, n)
+    rad = rng.uniform(0.3, 1.0, n)
+    st[0] = np.where(near, g["origin"][0] + lx[pick] * res + rad * np.cos(ang), st[0])
+    st[1] = np.where(near, g["origin"][1] + ly[pick] * res + rad * np.sin(ang), st[1])
+    tgt = np.clip(idx + rng.randint(-3, 4, n), 1, len(path) - 1).astype(np.int32)
+    md = np.hypot(path[tgt, 0] - st[0], path[tgt, 1] - st[1]) + rng.uniform(-0.01, 0.05, n)
+    it = rng.randint(0, timeout, n).astype(np.int32)
+    it[:8] = timeout - 1  # timeout on this very step
+    return st, md, tgt, it
