@@ -3,8 +3,10 @@ import os
 import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "csrc", "bcplan.hip")
-DEPS = [SRC] + [os.path.join(HERE, "csrc", f) for f in ("bcp_device.h", "bcp_raster.h", "bcp_coop.h", "bcp_step.h", "bcp_lookahead.h", "bcp_mppi.h", "bcp_ego.h", "bcp_sample.h", "bcp_aisle.h")] + \
+CSRC = os.path.join(HERE, "csrc")
+SRC = os.path.join(CSRC, "bcplan.hip")
+# every header and source of csrc/ (one translation unit includes them all) and the C ABI: found by listing the directory
+DEPS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hip"))) + \
        [os.path.join(os.path.dirname(HERE), "include", "bcplan.h")]
 OUT = os.path.join(HERE, "libbcplan.so")
 

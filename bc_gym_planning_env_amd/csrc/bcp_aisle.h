@@ -6,7 +6,7 @@
 //   aisle_world_draw_kernel    one wavefront per stream: the MT19937 window of bcp_sample.h, lane 0 draws and computes
 //   aisle_world_render_kernel  one workgroup per world: zero-fill of the padded entry, then the walls
 //   aisle_world_paths_kernel   one thread per world: refine_path over the three segments, initial reward state
-// Included by bcplan.hip (entry points bcp_sample_aisle_worlds, bcp_render_aisle_worlds, bcp_aisle_world_paths).
+// Included by bcplan.hip (entry points bcp_sample_aisle_worlds, bcp_render_aisle_worlds, bcp_aisle_world_paths: bcp_worlds_host.h).
 #pragma once
 
 #include <hip/hip_runtime.h>

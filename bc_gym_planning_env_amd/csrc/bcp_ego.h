@@ -1,7 +1,7 @@
 // bcp_ego.h -- device code of the egocentric observation: extract_egocentric_costmap
 // (utilities/costmap_utils.py:25-75 = cv2.getRotationMatrix2D + cv2.warpAffine with INTER_NEAREST) for every env at
-// once, plus the kernels that group images by map entry for private / pooled maps.  Included by bcplan.hip, which holds
-// the host entry points (bcp_egocentric_costmaps, bcp_goal_n_state).
+// once, plus the kernels that group images by map entry for private / pooled maps.  Included by bcplan.hip; the host
+// entry points (bcp_egocentric_costmaps, bcp_goal_n_state) are in bcp_ego_host.h.
 #pragma once
 
 #include <hip/hip_runtime.h>

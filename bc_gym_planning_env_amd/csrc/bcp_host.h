@@ -1,0 +1,184 @@
+// bcp_host.h -- what every host-side piece of libbcplan shares: the error record, the handle, and the few helpers that
+// launch kernels.  Included by bcplan.hip after the device headers and before the subsystems (bcp_field.h,
+// bcp_step_host.h, bcp_ego_host.h, bcp_worlds_host.h).
+#pragma once
+
+// The library exports its C entry points and nothing else: the member functions of the host-side types stay inside.
+#pragma GCC visibility push(hidden)
+
+#include "bcp_devbuf.h"
+
+// ------------------------------------------------------------------------------------------------ errors
+static thread_local char g_err[512] = "";
+
+static int fail(int code, const char* fmt, ...)
+{
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof(g_err), fmt, ap);
+    va_end(ap);
+    return code;
+}
+
+#define HIP_TRY(expr)                                                                                \
+    do {                                                                                             \
+        hipError_t e_ = (expr);                                                                      \
+        if (e_ != hipSuccess) return fail(BCP_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
+    } while (0)
+
+// ... and the same for a call that has filed its own error
+#define BCP_TRY(expr)                      \
+    do {                                   \
+        const int rc_ = (expr);            \
+        if (rc_ != BCP_OK) return rc_;     \
+    } while (0)
+
+// ------------------------------------------------------------------------------------------------ handle
+// Every device buffer the library owns is a DevBuf: it grows when a re-bind needs more room, and the handle's destructor
+// gives it back.  What the caller owns is a plain pointer.
+struct bcp_handle {
+    bcp_params params = {};
+    DevParams dev = {};
+    int64_t n = 0;
+    int device = 0;
+    int64_t env_id_base = 0;
+    uint64_t seed = 0;
+    DevBuf<uint64_t> tick;    // step counter (two views), noise seed, ticket -- see StepArgs::tick; [4]: waits that gave up
+    bool have_map = false, have_path = false, have_state = false, have_init = false;
+    double resolution = 0;
+    DevBuf<uint32_t> bitmap;
+    DevBuf<uint32_t> near_coarse;   // CullDesc::step_near when it is not the tiles themselves
+    int32_t near_shift = -1;  // BCP_NEAR_SHIFT / BCP_TUNE_NEAR_SHIFT: resolution of step_near for private maps (-1: the library's rule)
+    DevBuf<uint32_t> map_tiles;     // the bitmap once more in tiles of 32 x 32 cells (MapDesc::tiles)
+    DevBuf<double> path5;
+    DevBuf<uint32_t> path_pre;      // [paths][max_len][2] {x, y as uint16 steps | cos, sin as int16}: the prefilter record of private paths
+    DevBuf<double> path_bbox;
+    DevBuf<int16_t> path_index;
+    DevBuf<uint8_t> edt;            // distance transform of the shared costmap (padded)
+    DevBuf<uint8_t> edt_col;        // scratch of the transform
+    DevBuf<uint32_t> near;          // the field as 1-bit tiles (CullDesc::near)
+    MapDesc map = {};
+    CullDesc cull = {};
+    PathDesc path = {};
+    DevState st = {}, init = {};
+    StepStatic host_static = {};    // host image of the device-resident step parameters
+    StepHot host_hot = {};          // ... and of the copy of them that travels with a step's arguments (upload_step_static)
+    DevBuf<StepStatic> dev_static;
+    bool static_dirty = true;       // host_static must be rebuilt and uploaded before the next step
+    DevBuf<Pending> pending;        // [kShards][pending_cap]
+    DevBuf<int32_t> pending_count;  // two alternating sets of kShards counters
+    int32_t pending_cap = 0;        // parking slots per shard
+    int32_t defer = 1;              // settle undecided envs in a second kernel (shared map with distance field)
+    int32_t exact_mode = 0;         // 0 auto, 1 cooperative only, 2 per-thread only, 3 cooperative cell by cell
+    int32_t dense_threshold = 6;    // auto: more ambiguous lanes than this in a wave -> per-thread rasteriser
+    int32_t adaptive = 1;           // the threshold above is only the fallback: kernel 2 re-decides every step
+    DevBuf<int32_t> adapt;          // [2] thresholds + [2] in-place counters, alternating by step parity
+    int32_t cull_enabled = 1;
+    int32_t wide = 0;               // kernel image may exceed 96 px: 8-word row masks in the cooperative path
+    DevBuf<int32_t> ego_bins;       // [2][capacity / 2] image counts / first slots per map entry (egocentric views)
+    DevBuf<int32_t> ego_order;      // [2][capacity / 2] rank within the bin / images grouped by map entry
+    // sparse egocentric views (ego_sparse_kernel): per map entry the list of its non-zero cells
+    DevBuf<uint32_t> ego_cells;     // [entries][ego_cell_cap] (empty while the maps count as dense)
+    DevBuf<int32_t> ego_cell_counts;   // [entries] + [1] running maximum
+    int64_t ego_cells_entries = 0;
+    int32_t ego_cell_cap = 0;       // stride of a list, sized from the counting pass
+    bool ego_cells_built = false;   // counts (and lists, if any) describe the current maps (rebuilt entry by entry by a pool refresh)
+    bool ego_cells_refused = false; // allocation failed once: the sampling kernels serve this handle
+    int32_t ego_cells_max = -1;     // host copy of the maximum count, -1 = not fetched since the last (re)build
+    int32_t ego_sparse = 1;         // BCP_TUNE_EGO_SPARSE: 0 never, 1 cost model, >= 2 explicit limit of cells per map
+    int32_t ego_stride = 0;         // BCP_TUNE_EGO_LIST_STRIDE: 0 = lists sized from the counts, else this many cells per entry (tests)
+    int32_t ego_route[4] = {};      // what the last bcp_egocentric_costmaps call ran: kernel, largest count, list stride, limit
+    // watchdog of the step kernel's bounded waits: every kWatchdogSteps calls bcp_step copies tick[4] to pinned host memory
+    // behind the step (no synchronisation) and a later call looks at what arrived
+    uint64_t* waits_host = nullptr;       // owned, pinned
+    hipEvent_t waits_event = nullptr;     // owned
+    bool waits_in_flight = false;
+    uint64_t waits_seen = 0;
+    uint32_t steps_since_probe = 0;
+    hipEvent_t refresh_done = nullptr;    // owned: end of the last bcp_refresh_mini_worlds (whoever derives data from the maps on
+    bool refresh_recorded = false;        // another stream waits for it first)
+    hipStream_t side_stream = nullptr;    // owned: the CU-masked stream of bcp_side_stream (nullptr: not created)
+    int32_t side_share = 0;               // ... and the share of the CUs it was created with
+    const uint8_t* map_data = nullptr;    // caller-owned raw costmap(s) as given to bcp_set_costmaps (egocentric views read them)
+    const int32_t* map_valid_rows = nullptr;
+    const int32_t* map_valid_cols = nullptr;
+    int32_t n_geoms = 0;                  // > 0: geometry pool of that many entries
+    int32_t* geom_of_env = nullptr;       // caller-owned device int32 [n]
+    const int32_t* next_geom = nullptr;   // caller-owned device int32 [n_geoms] or nullptr
+    const double* path_src = nullptr;     // caller-owned way points [.,max_len,3] as given to bcp_set_paths
+    DevBuf<unsigned char> ring;           // scratch of bcp_refresh_mini_worlds (bytes: one int64 and three int32 arrays)
+    int32_t ring_episodes = 0;            // of the last bcp_plan_mini_worlds
+    bool ring_planned = false, ring_refreshed = false;   // plan -> refresh -> release, in that order
+    int32_t edt_in_lds = 1;         // distance transform of maps that fit: the LDS-resident kernel (BCP_TUNE_EDT_LDS)
+    int32_t last_step_form = -1;    // step_form() of the last step launched, -1: none yet
+    int32_t fused = 1;              // settle parked poses inside the step launch (step_local_kernel) instead of a second launch
+    DevBuf<uint64_t> parked_slots;  // a word per workgroup of step_local_kernel, its parked poses so far (bcp_parked_poses)
+    int32_t local_pairs = 0;        // BCP_TUNE_LOCAL_PAIRS: workgroup size of step_local_kernel (0 = default, 1, 2, 4 x 64 envs)
+    // near_dilate_kernel: 1-bit tiles without the uint8 field (pool refresh under the single-launch step)
+    int32_t near_dilate = 1;        // BCP_TUNE_NEAR_DILATE: 0 never, 1 pool refreshes (default), 2 every build (after the field: tests)
+    // The pair is used together or not at all; edt_stale's capacity is the number of entries of both.
+    DevBuf<uint8_t> edt_stale;      // [entries] 1 = the entry's uint8 field does not describe its map (tiles do)
+    DevBuf<int32_t> edt_stale_list; // [entries] + [1] count, scratch of ensure_fields
+    bool edt_lazy = false;          // a refresh has left stale fields behind since the last full build
+    // episode record (bcp_bind_episode_record): the caller's arrays, and the library's two words of the step's count
+    bool have_rec = false;
+    EpisodeRec rec = {};
+    DevBuf<RecPark> rec_park;       // [kShards][pending_cap] (two-launch form with a record)
+    DevBuf<uint32_t> rec_work;      // [3] slots taken in the running step, ticket of the parties that publish the count,
+                                    // steps that overflowed the capacity since bcp_episode_record_overflows last looked
+};
+
+// number of entries of a non-shared map / path / initial-state array
+static int64_t n_slots(const bcp_handle* h) { return h->n_geoms > 0 ? h->n_geoms : h->n; }
+
+// grid of a grid-stride kernel; a selection's size is only known on the device, so those launches get a chip-filling
+// grid that does not grow with the upper bound
+constexpr size_t kMaxDynamicLds = 150 * 1024;   // of the 160 KB a gfx950 workgroup can have
+
+static unsigned stride_grid(int64_t work_items, int threads, bool selection = false)
+{
+    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((work_items + threads - 1) / threads, selection ? 4096 : 65536));
+}
+
+// Lets `fn` be launched with `bytes` of dynamic LDS on `device`.  The attribute belongs to the FUNCTION on a device, not to
+// a handle, so it is only ever raised: the largest size any handle of this process has asked for stays set (two live handles
+// with different staging sizes would otherwise lower it under each other).
+static int raise_dynamic_lds(const void* fn, int device, size_t bytes)
+{
+    static std::mutex mutex;
+    static std::map<std::pair<const void*, int>, size_t> raised;   // (function, device) -> the attribute as it stands
+    std::lock_guard<std::mutex> lock(mutex);
+    size_t& cur = raised[std::make_pair(fn, device)];
+    if (bytes > cur) {
+        HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+        cur = bytes;
+    }
+    return BCP_OK;
+}
+
+// The one way to launch a kernel that exists in several variants: the caller picks the variant's function once, as a
+// pointer, and everything that follows -- the LDS attribute, an occupancy query, the launch -- goes through that pointer.
+// A workgroup gets 64 KiB of dynamic LDS without asking; more needs the function's attribute raised first.
+static int variant_lds(const bcp_handle* h, const void* fn, size_t lds)
+{
+    return lds > 64 * 1024 ? raise_dynamic_lds(fn, h->device, lds) : BCP_OK;
+}
+
+// `args` are the kernel's arguments, each of exactly the parameter's type.  The caller has seen to variant_lds.
+template <typename... Args>
+static int launch_fn(const void* fn, dim3 grid, dim3 block, size_t lds, hipStream_t s, const Args&... args)
+{
+    void* kargs[] = {(void*)&args...};
+    HIP_TRY(hipLaunchKernel(fn, grid, block, kargs, lds, s));
+    return BCP_OK;
+}
+
+template <typename... Args>
+static int launch_variant(const bcp_handle* h, const void* fn, dim3 grid, dim3 block, size_t lds, hipStream_t s,
+                          const Args&... args)
+{
+    const int rc = variant_lds(h, fn, lds);
+    return rc != BCP_OK ? rc : launch_fn(fn, grid, block, lds, s, args...);
+}
+
+#pragma GCC visibility pop

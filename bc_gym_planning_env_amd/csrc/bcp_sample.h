@@ -6,7 +6,7 @@
 //     same draw order as the reference) and the scalar geometry,
 //   * all 64 lanes clear the candidate's lethal bitmap in LDS, test both path ends against it with the cooperative
 //     rasteriser of the step kernels, and expand an accepted world's bitmap into its uint8 costmap.
-// Included by bcplan.hip (entry points bcp_mini_world_seed, bcp_sample_mini_worlds).
+// Included by bcplan.hip (entry points bcp_mini_world_seed, bcp_sample_mini_worlds: bcp_worlds_host.h).
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -1,6 +1,6 @@
 // bcp_step.h -- device code of the batched PlanEnv.step(): the parameter blocks shared with the host, the one-time
 // path kernels, the reward providers, the delay queues, and the step kernels (general / fast / pending).  Included by
-// bcplan.hip, which holds the handle and the C entry points.
+// bcplan.hip; the handle is in bcp_host.h, the step's launcher and C entry points in bcp_step_host.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -1681,7 +1681,7 @@ __global__ void __launch_bounds__(kBlock * kPendingWaves) step_pending_kernel(co
 // so one workgroup more than the chip holds, a sampler or an RCCL kernel resident on some CUs, costs a whole further round
 // (profiles/r03_n_sweep.txt: 65 536 envs 11.8 us, 65 792 envs 17.8 us); an 8-wave one can start beside a leaving neighbour.
 constexpr int kLocalPairsMax = 4;
-constexpr int kLocalPairsDefault = 4;   // (bcplan.hip: local_pairs)
+constexpr int kLocalPairsDefault = 4;   // (bcp_step_host.h: local_pairs)
 
 typedef const __attribute__((address_space(4))) StepArgs& KernArgs;   // the launch arguments where they lie: scalar loads on
                                                                       // demand instead of ~500 bytes pinned in SGPRs

@@ -1,0 +1,554 @@
+// bcp_step_host.h -- the host side of the step: which form a step takes, the device-resident parameter block, the launcher,
+// and the entry points built on it (bcp_step, bcp_rollout, bcp_lookahead, bcp_mppi, the watchdog and the timing calls).
+// The kernels are in bcp_step.h, bcp_lookahead.h and bcp_mppi.h.  Included by bcplan.hip after bcp_field.h.
+#pragma once
+
+// no delay queues and the continuous reward provider: the step kernels compile both out (their PLAIN variants)
+static bool step_is_plain(const bcp_handle* h)
+{
+    const bcp_params& p = h->params;
+    return p.control_delay == 0 && p.pose_delay == 0 && p.state_delay == 0 && p.reward_provider == BCP_REWARD_CONTINUOUS;
+}
+
+static bool step_uses_deferral(const bcp_handle* h)
+{
+    return h->defer && h->cull.on && h->exact_mode == 0 && h->pending.get() != nullptr;
+}
+
+// Which kernels a step of this handle launches as it is configured now -- the numbers bcp_step_form documents: 0 step_kernel,
+// 1 step_fast_pair_kernel alone, 2 that + step_pending_kernel, 3 step_local_kernel (the single-launch form).  Once
+// upload_step_static has run, S.pending != nullptr says the same as step_uses_deferral.
+// (an explicit BCP_TUNE_DENSE_THRESHOLD asks for poses to be settled inside the stepping wave: the two-launch form has that
+// path, and bcp_set_tuning clears `adaptive` with it -- form 3 never meets a negative threshold)
+static int step_form(const bcp_handle* h)
+{
+    if (!step_uses_deferral(h)) return 0;
+    if (h->dense_threshold < 0) return 1;
+    return (h->fused && h->adaptive) ? 3 : 2;
+}
+
+// (re)builds the device-resident StepStatic block and, from it, the StepHot image that every launch copies
+static int upload_step_static(bcp_handle* h, hipStream_t s)
+{
+    StepStatic& S = h->host_static;
+    S.P = h->dev;
+    S.map = h->map;
+    S.cull = h->cull;
+    S.path = h->path;
+    S.st = h->st;
+    S.init = h->init;
+    S.n = h->n;
+    S.env_id_base = h->env_id_base;
+    S.exact_mode = h->exact_mode;
+    S.dense_threshold = h->dense_threshold;   // (a negative value settles every undecided pose inside kernel 1)
+    S.wide = h->wide;
+    S.pending_cap = h->pending_cap;
+    const bool defer = step_uses_deferral(h);
+    S.pending = defer ? h->pending.get() : nullptr;
+    S.geom_of_env = h->n_geoms > 0 ? h->geom_of_env : nullptr;
+    S.next_geom = h->n_geoms > 0 ? h->next_geom : nullptr;
+    S.lds_path_doubles =
+        (defer && h->path.shared && h->path.max_len * 5 * sizeof(double) <= 24 * 1024) ? h->path.max_len * 5 : 0;
+    if (h->have_rec) {
+        if (defer) HIP_TRY(h->rec_park.reserve((size_t)kShards * h->pending_cap));   // (pending_cap never changes)
+        h->rec.park = defer ? h->rec_park.get() : nullptr;
+        S.rec = h->rec;
+    } else {
+        memset(&S.rec, 0, sizeof(S.rec));
+    }
+    HIP_TRY(h->dev_static.reserve(1));
+    // pageable source: the copy is staged before the call returns, so host_static may change afterwards
+    HIP_TRY(hipMemcpyAsync(h->dev_static.get(), &S, sizeof(StepStatic), hipMemcpyHostToDevice, s));
+    StepHot& hot = h->host_hot;   // (io_flags, io_actions, io_noise_z and io_tick belong to a launch: launch_step)
+    hot.st = S.st;
+    hot.n = S.n;
+    hot.geom_of_env = S.geom_of_env;
+    hot.path_pts = S.path.pts;
+    hot.path_pre = S.path.pre;
+    hot.path_bbox = S.path.bbox;
+    hot.path_index = S.path.index;
+    hot.pending = S.pending;
+    hot.map_bits = S.map.bits;
+    hot.map_env_stride = S.map.env_stride;
+    hot.model = S.P.model;
+    hot.lds_path_doubles = S.lds_path_doubles;
+    hot.path_shared = S.path.shared;
+    hot.pending_cap = S.pending_cap;
+    hot.map_rows = S.map.rows;
+    hot.map_cols = S.map.cols;
+    hot.map_wpr = S.map.wpr;
+    hot.map_shared = S.map.shared;
+    hot.path_max_len = S.path.max_len;
+    hot.near = S.cull.on ? S.cull.step_near : nullptr;
+    hot.noise_on = S.P.noise_on;
+    hot.n_verts = S.P.n_verts;
+    hot.control_delay = S.P.control_delay;
+    hot.pose_delay = S.P.pose_delay;
+    hot.state_delay = S.P.state_delay;
+    hot.dynamic_model = S.P.dynamic_model;
+    hot.noise_slot0 = (S.P.alpha[0] > 0.0 || S.P.alpha[1] > 0.0) ? 1 : 0;
+    hot.model_front_column_pid = S.P.model_front_column_pid;
+    hot.env_id_base = S.env_id_base;
+    hot.qverts = &h->dev_static.get()->P.qverts[0][0];
+    hot.map_origins = S.map.origins;
+    h->static_dirty = false;
+    return BCP_OK;
+}
+
+// The parity-keyed parking / adaptation counters are only maintained by the two-kernel step (kernel 1 zeroes the NEXT
+// step's set).  Whenever the step form changes (bcp_set_tuning between steps, a costmap without distance field, ...)
+// both sets are re-armed on the stream of the steps, so the two-kernel step never resumes on stale counts.
+static int rearm_parking(bcp_handle* h, hipStream_t s)
+{
+    if (h->pending_count.get()) HIP_TRY(hipMemsetAsync(h->pending_count.get(), 0, 2 * kShards * sizeof(int32_t), s));
+    if (h->adapt.get()) {
+        HIP_TRY(hipMemsetAsync(h->adapt.get() + 2, 0, 2 * kShards * sizeof(int32_t), s));
+        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)h->adapt.get(), h->dense_threshold, 2, s));
+    }
+    return BCP_OK;
+}
+
+// The two launches of step form 2, <WIDE, PLAIN>, indexed by variant = WIDE << 1 | PLAIN like local_step_fn below
+static const void* const kFastPairFn[4] = {(const void*)step_fast_pair_kernel<false, false>, (const void*)step_fast_pair_kernel<false, true>,
+                                           (const void*)step_fast_pair_kernel<true, false>, (const void*)step_fast_pair_kernel<true, true>};
+static const void* const kPendingFn[4] = {(const void*)step_pending_kernel<false, false>, (const void*)step_pending_kernel<false, true>,
+                                          (const void*)step_pending_kernel<true, false>, (const void*)step_pending_kernel<true, true>};
+
+// step_local_kernel<WIDE, PLAIN, PAIRS, ROLL>: variant = WIDE << 1 | PLAIN; the rollout form exists for the 16-wave workgroup
+static const void* local_step_fn(int variant, int pairs, bool roll = false)
+{
+    if (roll) {
+        switch (variant) {
+            case 3: return (const void*)step_local_kernel<true, true, 4, true>;
+            case 2: return (const void*)step_local_kernel<true, false, 4, true>;
+            case 1: return (const void*)step_local_kernel<false, true, 4, true>;
+            default: return (const void*)step_local_kernel<false, false, 4, true>;
+        }
+    }
+#define BCP_LOCAL_FN(W, P) (pairs == 4 ? (const void*)step_local_kernel<W, P, 4> : pairs == 2 ? (const void*)step_local_kernel<W, P, 2> \
+                                                                                              : (const void*)step_local_kernel<W, P, 1>)
+    switch (variant) {
+        case 3: return BCP_LOCAL_FN(true, true);
+        case 2: return BCP_LOCAL_FN(true, false);
+        case 1: return BCP_LOCAL_FN(false, true);
+        default: return BCP_LOCAL_FN(false, false);
+    }
+#undef BCP_LOCAL_FN
+}
+
+// Size of step_local_kernel's workgroups for this handle: BCP_TUNE_LOCAL_PAIRS, or (0) the default of the configuration.
+static int local_pairs(const bcp_handle* h)
+{
+    if (h->local_pairs == 1 || h->local_pairs == 2 || h->local_pairs == 4) return h->local_pairs;
+    return kLocalPairsDefault;
+}
+
+// rollout_steps > 1: only the single-launch form (step_local_kernel<.., ROLL = true>) takes several steps per launch; the
+// caller (bcp_rollout) steps the other forms one launch at a time.
+static int launch_step(bcp_handle* h, const bcp_step_io* io, uint32_t flags, hipStream_t s, bool first_only = false,
+                       int32_t rollout_steps = 1)
+{
+    if (h->static_dirty) BCP_TRY(upload_step_static(h, s));
+    const StepStatic& S = h->host_static;
+    const int form = step_form(h);
+    const bool fused = form == 3;
+    if (!fused && h->edt_lazy) BCP_TRY(ensure_fields(h, s));   // these forms read the uint8 field
+    if ((form == 1 || form == 2) && (h->last_step_form == 0 || h->last_step_form == 3)) BCP_TRY(rearm_parking(h, s));   // parking resumes after another form
+    h->last_step_form = form;
+    StepArgs a;
+    a.S = h->dev_static.get();
+    a.hot = h->host_hot;
+    a.actions = io->actions;
+    a.noise_z = io->noise_z;
+    a.noise_z_out = io->noise_z_out;
+    a.reward = io->reward;
+    a.done = io->done;
+    a.collided_now = io->collided_now;
+    a.err = io->err;
+    a.flags = flags;
+    if (h->have_rec) a.flags |= kStepRecord;   // (the kernels look at the record only with this flag)
+    // the step counter and the noise seed are read on the device (StepArgs::tick); the kernels resolve these themselves
+    a.seed = a.step_counter = 0;
+    a.pending_count = a.pending_next = nullptr;
+    a.threshold_now = nullptr;
+    a.threshold_next = a.inplace_count = a.inplace_next = nullptr;
+    const bool adapt = h->adaptive && h->adapt.get() && S.pending && S.dense_threshold >= 0;
+    a.tick = h->tick.get();
+    a.parked_slots = nullptr;
+    a.map_tiles = S.map.tiles;
+    a.rollout_steps = 1;
+    a.pending_base = h->pending_count.get();
+    a.adapt_base = adapt ? h->adapt.get() : nullptr;
+    const int blocks = (int)((h->n + kBlock - 1) / kBlock);
+    const int variant = (S.wide ? 2 : 0) | (step_is_plain(h) ? 1 : 0);
+    if (fused) {
+        // the whole step as one launch: 256 envs per workgroup of 16 waves; undecided poses are handed over in LDS and
+        // settled by all the workgroup's waves (step_local_kernel)
+        const bool roll = rollout_steps > 1;
+        const int pairs = roll ? 4 : local_pairs(h);
+        a.rollout_steps = rollout_steps;
+        const int64_t bitmap_words = (int64_t)S.map.rows * S.map.wpr;
+        const size_t lds = local_step_lds_bytes(h->params.n_verts, S.lds_path_doubles,
+                                                (S.map.shared && bitmap_words <= kLocalMapWords) ? (int)bitmap_words : 0,
+                                                step_is_plain(h), pairs);
+        a.flags |= kStepAdvances;
+        a.hot.io_flags = a.flags;   // (the prologue's copies, next to the rest of what it fetches)
+        a.hot.io_actions = a.actions;
+        a.hot.io_noise_z = a.noise_z;
+        a.hot.io_tick = a.tick;
+        const int envs_per_group = pairs * kBlock;
+        const dim3 grid((unsigned)((h->n + envs_per_group - 1) / envs_per_group)), block(4 * pairs * kBlock);
+        if (!h->parked_slots.get()) {   // (sized for the smallest workgroup: the size may change between steps)
+            HIP_TRY(h->parked_slots.reserve((size_t)((h->n + kBlock - 1) / kBlock)));
+            HIP_TRY(hipMemsetAsync(h->parked_slots.get(), 0, h->parked_slots.capacity() * sizeof(uint64_t), s));
+        }
+        a.parked_slots = h->parked_slots.get();
+        return launch_variant(h, local_step_fn(variant, pairs, roll), grid, block, lds, s, a);
+    }
+    if (rollout_steps > 1) return fail(BCP_E_STATE, "launch_step: only the single-launch step form takes several steps per launch");
+    if (form == 0) {
+        const size_t lds = collision_lds_bytes(h->params.n_verts, h->map.in_lds, h->map.rows, h->map.wpr);
+        a.flags |= kStepAdvances;
+        hipLaunchKernelGGL(step_kernel, dim3(blocks), dim3(kBlock), lds, s, a);
+        return BCP_OK;
+    }
+    // kernel 1 settles every env the distance field decides; kernel 2 rasterises the parked rest
+    const size_t lds1 = ((size_t)h->params.n_verts * 2 + S.lds_path_doubles) * sizeof(double);
+    const size_t lds2 = (size_t)2 * 4 * (S.wide ? 8 : 3) * 64 * sizeof(uint32_t);
+    const int waves = 2048;  // a multiple of kShards: 32 teams per shard, so that a shard rarely needs a second round
+    const bool second = !first_only && S.dense_threshold >= 0;  // (threshold < 0: everything settled in place)
+    if (!second) a.flags |= kStepAdvances;   // kernel 1 is the whole step
+    // kernel 1 runs with two wavefronts per 64 envs (mover + scorer, step_fast_pair_kernel)
+    const size_t lds1p = lds1 + ((size_t)6 * kBlock + 8) * sizeof(double) + 2 * kBlock * sizeof(uint32_t);
+    const int rc = launch_variant(h, kFastPairFn[variant], dim3(blocks), dim3(2 * kBlock), lds1p, s, a);
+    if (rc != BCP_OK || !second) return rc;
+    return launch_variant(h, kPendingFn[variant], dim3(waves), dim3(kBlock * kPendingWaves), lds2, s, a);
+}
+
+// Flags a caller may pass.  The ablation switches of bcp_step.h (timing experiments, results wrong by construction)
+// exist only in a -DBCP_DIAG build (tools/); kStepAdvances is internal and never accepted.
+#ifdef BCP_DIAG
+constexpr uint32_t kCallerFlags = BCP_STEP_AUTO_RESET | BCP_STEP_ACTIONS_F32 | kAblateNoCollision | kAblateNoReward |
+                                  kAblateNoCoop | kAblateNoPark | kAblateNoClassify | kDiagWithholdVerdicts;
+#else
+constexpr uint32_t kCallerFlags = BCP_STEP_AUTO_RESET | BCP_STEP_ACTIONS_F32;
+#endif
+
+static int check_step(bcp_handle* h, const bcp_step_io* io, uint32_t flags, const char* who)
+{
+    if (!h || !io) return fail(BCP_E_INVALID, "%s: null argument", who);
+    if (flags & ~kCallerFlags) return fail(BCP_E_INVALID, "%s: undefined flag bits 0x%x", who, flags & ~kCallerFlags);
+    if (!h->have_map || !h->have_path || !h->have_state)
+        return fail(BCP_E_STATE, "%s: costmaps, paths and state must be set first", who);
+    if ((flags & BCP_STEP_AUTO_RESET) && !h->have_init)
+        return fail(BCP_E_STATE, "%s: BCP_STEP_AUTO_RESET needs bcp_bind_initial_state", who);
+    if (!io->actions || !io->reward || !io->done) return fail(BCP_E_INVALID, "%s: actions/reward/done are required", who);
+    return BCP_OK;
+}
+
+// A wait of step_local_kernel that gives up lets its envs finish as free (bcp_step.h: BCP_ERR_INTERNAL): a training loop
+// that never calls bcp_expired_waits would not notice.  So bcp_step itself looks, without ever waiting for the GPU: every
+// kWatchdogSteps calls the counter is copied to pinned host memory behind the step just launched, and a later call, once
+// that copy has landed, compares it with what was seen before.
+constexpr uint32_t kWatchdogSteps = 256;
+
+static int step_watchdog(bcp_handle* h, hipStream_t s)
+{
+    if (step_form(h) != 3) return BCP_OK;   // (only step_local_kernel has such waits)
+    if (h->waits_in_flight) {
+        const hipError_t q = hipEventQuery(h->waits_event);
+        if (q == hipSuccess) {
+            h->waits_in_flight = false;
+            const uint64_t now = *h->waits_host;
+            if (now > h->waits_seen) {
+                const uint64_t fresh = now - h->waits_seen;
+                h->waits_seen = now;
+                return fail(BCP_E_INTERNAL, "bcp_step: %llu bounded wait(s) of the step kernel gave up during earlier steps "
+                                            "(BCP_ERR_INTERNAL in err[] marks the envs; their verdicts are unreliable)",
+                            (unsigned long long)fresh);
+            }
+        } else {
+            (void)hipGetLastError();   // hipErrorNotReady is not an error here
+        }
+        return BCP_OK;
+    }
+    if (++h->steps_since_probe < kWatchdogSteps) return BCP_OK;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) {
+        (void)hipGetLastError();
+        return BCP_OK;   // (a captured step is replayed without this function: the caller asks bcp_expired_waits)
+    }
+    if (!h->waits_host) {
+        HIP_TRY(hipHostMalloc((void**)&h->waits_host, sizeof(uint64_t), hipHostMallocDefault));
+        *h->waits_host = 0;
+        HIP_TRY(hipEventCreateWithFlags(&h->waits_event, hipEventDisableTiming));
+    }
+    HIP_TRY(hipMemcpyAsync(h->waits_host, h->tick.get() + 4, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipEventRecord(h->waits_event, s));
+    h->waits_in_flight = true;
+    h->steps_since_probe = 0;
+    return BCP_OK;
+}
+
+extern "C" int bcp_step(bcp_handle* h, const bcp_step_io* io, uint32_t flags, void* stream)
+{
+    BCP_TRY(check_step(h, io, flags, "bcp_step"));
+    HIP_TRY(hipSetDevice(h->device));
+    BCP_TRY(launch_step(h, io, flags, (hipStream_t)stream));
+    HIP_TRY(hipGetLastError());
+    return step_watchdog(h, (hipStream_t)stream);
+}
+
+// K steps per call for callers that hold the actions of a whole rollout (Monte-Carlo rollouts from one state, the use the
+// reference documents: /root/reference/README.md "many rollouts from one state"; StepEnvRoller's 128-step rollouts once the
+// policy is open-loop).  With the single-launch step form the K steps are ONE launch of step_local_kernel<.., ROLL = true>;
+// otherwise K launches.  Either way: the states and outputs of K calls of bcp_step with row k of the arrays, bit for bit.
+extern "C" int bcp_rollout(bcp_handle* h, const bcp_step_io* io, int32_t n_steps, uint32_t flags, void* stream)
+{
+    BCP_TRY(check_step(h, io, flags, "bcp_rollout"));
+    if (n_steps <= 0) return fail(BCP_E_INVALID, "bcp_rollout: n_steps must be positive");
+    if (h->have_rec) return fail(BCP_E_STATE, "bcp_rollout: an episode record is bound (rows over K steps are not kept)");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (step_form(h) == 3 && n_steps > 1) {
+        BCP_TRY(launch_step(h, io, flags, s, false, n_steps));
+        HIP_TRY(hipGetLastError());
+        return BCP_OK;
+    }
+    const int64_t n = h->n;
+    const size_t act = (flags & BCP_STEP_ACTIONS_F32) ? 8 : 16;
+    for (int32_t k = 0; k < n_steps; ++k) {
+        bcp_step_io row = *io;
+        row.actions = (const char*)io->actions + (size_t)k * n * act;
+        if (io->noise_z) row.noise_z = io->noise_z + (size_t)k * n * 3;
+        if (io->noise_z_out) row.noise_z_out = io->noise_z_out + (size_t)k * n * 3;
+        row.reward = io->reward + (size_t)k * n;
+        row.done = io->done + (size_t)k * n;
+        if (io->collided_now) row.collided_now = io->collided_now + (size_t)k * n;
+        if (io->err) row.err = io->err + (size_t)k * n;
+        BCP_TRY(launch_step(h, &row, flags, s));
+    }
+    HIP_TRY(hipGetLastError());
+    return BCP_OK;
+}
+
+// What bcp_lookahead and bcp_mppi (`who`) need of the handle before their kernels read it: complete, without delay queues,
+// its parameter block on the device and no stale uint8 field (collides_wave classifies with it).
+static int plan_ready(bcp_handle* h, const char* who, hipStream_t s)
+{
+    if (!h->have_map || !h->have_path || !h->have_state)
+        return fail(BCP_E_STATE, "%s: costmaps, paths and state must be set first", who);
+    const bcp_params& p = h->params;
+    if (p.control_delay > 0 || p.pose_delay > 0 || p.state_delay > 0)
+        return fail(BCP_E_INVALID, "%s: control_delay / pose_delay / state_delay > 0 are not supported (every "
+                                   "candidate would need delay queues of its own)", who);
+    HIP_TRY(hipSetDevice(h->device));
+    if (h->static_dirty) BCP_TRY(upload_step_static(h, s));
+    return h->edt_lazy ? ensure_fields(h, s) : BCP_OK;
+}
+
+// K candidate plans per env, scored on private copies of the env's state (bcp_lookahead.h).  Reads the handle, writes only
+// the caller's outputs: no step counter, ticket, parking counter, record or watchdog word is touched, so the steps before
+// and after the call are the steps of a handle that never looked ahead.
+extern "C" int bcp_lookahead(bcp_handle* h, const bcp_lookahead_io* io, uint32_t flags, void* stream)
+{
+    if (!h || !io) return fail(BCP_E_INVALID, "bcp_lookahead: null argument");
+    constexpr uint32_t allowed = BCP_STEP_ACTIONS_F32 | BCP_LOOKAHEAD_PER_ENV;
+    if (flags & ~allowed) return fail(BCP_E_INVALID, "bcp_lookahead: undefined flag bits 0x%x", flags & ~allowed);
+    hipStream_t s = (hipStream_t)stream;
+    BCP_TRY(plan_ready(h, "bcp_lookahead", s));
+    const bcp_params& p = h->params;
+    if (io->horizon < 1 || io->n_candidates < 1)
+        return fail(BCP_E_INVALID, "bcp_lookahead: horizon and n_candidates must be at least 1");
+    if (!io->actions || !io->ret || !io->steps || !io->reason)
+        return fail(BCP_E_INVALID, "bcp_lookahead: actions / ret / steps / reason are required");
+    if (io->noise_z && !p.noise_on)
+        return fail(BCP_E_INVALID, "bcp_lookahead: noise_z given, but the handle was created without noise (noise_on = 0)");
+    if (io->best_action && !io->best) return fail(BCP_E_INVALID, "bcp_lookahead: best_action needs best");
+    // element offsets are int64: the largest is 3 * H * N * K (noise_z); the grid has N * K / 64 workgroups
+    const int64_t limit = (int64_t)1 << 62;
+    const int64_t nk_max = limit / 3 / io->horizon;
+    if (h->n > nk_max / io->n_candidates)
+        return fail(BCP_E_INVALID, "bcp_lookahead: n_envs * n_candidates * horizon is too large for 64-bit element offsets");
+    const int64_t total = h->n * io->n_candidates;
+    const int64_t blocks = (total + kBlock - 1) / kBlock;
+    if (blocks > 0x7FFFFFFF) return fail(BCP_E_INVALID, "bcp_lookahead: n_envs * n_candidates exceeds the largest grid (2^37 lanes)");
+    LookaheadArgs a;
+    a.S = h->dev_static.get();
+    a.actions = io->actions;
+    a.noise_z = io->noise_z;
+    a.mask = io->mask;
+    a.ret = io->ret;
+    a.steps = io->steps;
+    a.reason = io->reason;
+    a.final_pose = io->final_pose;
+    a.final_target = io->final_target_idx;
+    a.err = io->err;
+    a.best = io->best;
+    a.best_action = io->best_action;
+    a.n = h->n;
+    a.total = total;
+    a.horizon = io->horizon;
+    a.k = io->n_candidates;
+    a.flags = flags;
+    const size_t lds = collision_lds_bytes(p.n_verts, h->map.in_lds, h->map.rows, h->map.wpr);
+    const bool plain = p.reward_provider == BCP_REWARD_CONTINUOUS && !io->noise_z;
+    const void* fn = plain ? (const void*)lookahead_kernel<true> : (const void*)lookahead_kernel<false>;
+    BCP_TRY(launch_variant(h, fn, dim3((unsigned)blocks), dim3(kBlock), lds, s, a));
+    if (io->best) {
+        int group = 1;
+        while (group < 64 && group < io->n_candidates) group <<= 1;
+        const int64_t lanes = h->n * group;
+        hipLaunchKernelGGL(lookahead_best_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, s, a, group);
+    }
+    HIP_TRY(hipGetLastError());
+    return BCP_OK;
+}
+
+// Sampling-based refinement of one plan per env (bcp_mppi.h): I iterations of sample, roll out, weight and update in one
+// launch.  Like bcp_lookahead it reads the handle and writes only the caller's arrays.
+extern "C" int bcp_mppi(bcp_handle* h, const bcp_mppi_params* p, const bcp_mppi_io* io, uint32_t flags, void* stream)
+{
+    if (!h || !p || !io) return fail(BCP_E_INVALID, "bcp_mppi: null argument");
+    if (flags & ~(uint32_t)BCP_STEP_ACTIONS_F32) return fail(BCP_E_INVALID, "bcp_mppi: undefined flag bits 0x%x", flags & ~(uint32_t)BCP_STEP_ACTIONS_F32);
+    hipStream_t s = (hipStream_t)stream;
+    BCP_TRY(plan_ready(h, "bcp_mppi", s));
+    const bcp_params& hp = h->params;
+    if (p->horizon < 1 || p->iterations < 1) return fail(BCP_E_INVALID, "bcp_mppi: horizon and iterations must be at least 1");
+    const int32_t K = p->n_candidates;
+    if (K < 8 || K > 1024 || (K & (K - 1)) != 0)
+        return fail(BCP_E_INVALID, "bcp_mppi: n_candidates must be a power of two in [8, 1024], got %d", K);
+    if (!(p->lambda_ > 0.0) || !std::isfinite(p->lambda_)) return fail(BCP_E_INVALID, "bcp_mppi: lambda_ must be positive and finite");
+    if (!std::isfinite(p->collision_penalty)) return fail(BCP_E_INVALID, "bcp_mppi: collision_penalty must be finite");
+    for (int d = 0; d < 2; ++d) {
+        if (!(p->sigma[d] >= 0.0) || !std::isfinite(p->sigma[d]))
+            return fail(BCP_E_INVALID, "bcp_mppi: sigma[%d] must be finite and not negative", d);
+        if (!std::isfinite(p->low[d]) || !std::isfinite(p->high[d])) return fail(BCP_E_INVALID, "bcp_mppi: the action box must be finite");
+        if (p->low[d] > p->high[d]) return fail(BCP_E_INVALID, "bcp_mppi: low[%d] > high[%d]", d, d);
+    }
+    if (!io->mean || !io->action) return fail(BCP_E_INVALID, "bcp_mppi: mean and action are required");
+    // element offsets are int64: the largest is 2 * I * N * K * H (eps); the bound leaves the room the header promises
+    const int64_t limit = (int64_t)1 << 62;
+    if (h->n > limit / 5 / p->iterations / K / p->horizon)
+        return fail(BCP_E_INVALID, "bcp_mppi: iterations * n_envs * n_candidates * horizon is too large for 64-bit element offsets");
+    const int group = K < kBlock ? K : kBlock;
+    const int64_t blocks = (h->n * group + kBlock - 1) / kBlock;
+    if (blocks > 0x7FFFFFFF) return fail(BCP_E_INVALID, "bcp_mppi: n_envs exceeds the largest grid");
+    MppiArgs a;
+    a.S = h->dev_static.get();
+    a.p = *p;
+    a.mean = io->mean;
+    a.action = io->action;
+    a.mask = io->mask;
+    a.eps_in = io->eps_in;
+    a.eps_out = io->eps_out;
+    a.draw_index = io->draw_index;
+    a.iter_mean = io->iter_mean;
+    a.iter_ret = io->iter_ret;
+    a.iter_reason = io->iter_reason;
+    a.err = io->err;
+    a.n = h->n;
+    a.flags = flags;
+    // the scores of a lane's chunks of candidates sit behind the collision area: 8 bytes per (lane, chunk)
+    const size_t collision = (collision_lds_bytes(hp.n_verts, h->map.in_lds, h->map.rows, h->map.wpr) + 7) & ~(size_t)7;
+    a.score_word = (int32_t)(collision / sizeof(uint32_t));
+    const size_t lds = collision + (size_t)(K / group) * kBlock * sizeof(double);
+    const bool plain = hp.reward_provider == BCP_REWARD_CONTINUOUS;
+    const void* fn = plain ? (const void*)mppi_kernel<true> : (const void*)mppi_kernel<false>;
+    // (the LDS can pass 64 KiB: a staged map of nearly that plus the scores)
+    return launch_variant(h, fn, dim3((unsigned)blocks), dim3(kBlock), lds, s, a);
+}
+
+extern "C" int bcp_expired_waits(bcp_handle* h, int64_t* count, void* stream)
+{
+    if (!h || !count) return fail(BCP_E_INVALID, "bcp_expired_waits: null argument");
+    HIP_TRY(hipSetDevice(h->device));
+    uint64_t v = 0;
+    HIP_TRY(hipMemcpyAsync(&v, h->tick.get() + 4, sizeof(v), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    *count = (int64_t)v;
+    return BCP_OK;
+}
+
+extern "C" int bcp_parked_poses(bcp_handle* h, int64_t* count, void* stream)
+{
+    if (!h || !count) return fail(BCP_E_INVALID, "bcp_parked_poses: null argument");
+    HIP_TRY(hipSetDevice(h->device));
+    *count = 0;
+    if (!h->parked_slots.get()) return BCP_OK;
+    std::vector<uint64_t> slots(h->parked_slots.capacity());
+    HIP_TRY(hipMemcpyAsync(slots.data(), h->parked_slots.get(), slots.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    uint64_t sum = 0;
+    for (uint64_t v : slots) sum += v;
+    *count = (int64_t)sum;
+    return BCP_OK;
+}
+
+extern "C" int bcp_step_form(bcp_handle* h)
+{
+    if (!h) return fail(BCP_E_INVALID, "bcp_step_form: null handle");
+    if (!h->have_map || !h->have_path || !h->have_state) return fail(BCP_E_STATE, "bcp_step_form: costmaps, paths and state must be set first");
+    return step_form(h);
+}
+
+// an event that is destroyed on every way out of its scope
+namespace {
+struct ScopedEvent {
+    hipEvent_t e = nullptr;
+    ~ScopedEvent() { if (e) (void)hipEventDestroy(e); }
+};
+}   // namespace
+
+// average device time of `steps` back-to-back step launches on `s` (first_only: of kernel 1 of the two-launch form alone)
+static int time_loop(bcp_handle* h, const bcp_step_io* io, uint32_t flags, int steps, hipStream_t s, bool first_only,
+                     float* avg_ms)
+{
+    ScopedEvent e0, e1;
+    HIP_TRY(hipEventCreate(&e0.e));
+    HIP_TRY(hipEventCreate(&e1.e));
+    HIP_TRY(hipEventRecord(e0.e, s));
+    int rc = BCP_OK;
+    for (int k = 0; k < steps && rc == BCP_OK; ++k) rc = launch_step(h, io, flags, s, first_only);
+    HIP_TRY(hipEventRecord(e1.e, s));
+    HIP_TRY(hipEventSynchronize(e1.e));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, e0.e, e1.e));
+    HIP_TRY(hipGetLastError());
+    if (rc != BCP_OK) return rc;
+    *avg_ms = ms / (float)steps;
+    return BCP_OK;
+}
+
+extern "C" int bcp_time_steps(bcp_handle* h, const bcp_step_io* io, uint32_t flags, int32_t steps, void* stream,
+                              float* avg_ms)
+{
+    BCP_TRY(check_step(h, io, flags, "bcp_time_steps"));
+    if (steps <= 0 || !avg_ms) return fail(BCP_E_INVALID, "bcp_time_steps: steps must be positive");
+    HIP_TRY(hipSetDevice(h->device));
+    return time_loop(h, io, flags, steps, (hipStream_t)stream, false, avg_ms);
+}
+
+extern "C" int bcp_time_step_kernels(bcp_handle* h, const bcp_step_io* io, uint32_t flags, int32_t steps, void* stream,
+                                     float* kernel_ms)
+{
+    BCP_TRY(check_step(h, io, flags, "bcp_time_step_kernels"));
+    if (steps <= 0 || !kernel_ms) return fail(BCP_E_INVALID, "bcp_time_step_kernels: bad steps / output");
+    if (h->have_rec)   // (its kernel-1-only loop would take record slots that no launch publishes)
+        return fail(BCP_E_STATE, "bcp_time_step_kernels: an episode record is bound");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    // full steps first (the state advances), then the same number of kernel-1-only launches on the reached state:
+    // envs parked by a lone step_kernel are never finished, so every launch of that loop sees the same batch.
+    float full = 0, first = 0;
+    BCP_TRY(time_loop(h, io, flags, steps, s, false, &full));
+    if (bcp_step_form(h) != 2) {   // the step is ONE launch (step_local_kernel, step_kernel): nothing to split, and no second loop
+        kernel_ms[0] = full;
+        kernel_ms[1] = 0.0f;
+        return BCP_OK;
+    }
+    BCP_TRY(time_loop(h, io, flags, steps, s, true, &first));
+    kernel_ms[0] = first;
+    kernel_ms[1] = full > first ? full - first : 0.0f;
+    return BCP_OK;
+}

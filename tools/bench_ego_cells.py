@@ -1,4 +1,4 @@
-"""Calibration of the sparse / sampling routing of bcp_egocentric_costmaps (csrc/bcplan.hip: ego_sparse_limit): time per call of
+"""Calibration of the sparse / sampling routing of bcp_egocentric_costmaps (csrc/bcp_ego_host.h: ego_sparse_limit): time per call of
 the fill-and-patch kernel against the number of non-zero cells of the map, beside the sampling kernel the same call would fall
 to, for a map that fits LDS (183 x 183) and one that does not (350 x 512).  65 536 images of 133 x 117 px, random poses
 inside the map (every window is full of map: the worst case for the patches)."""
