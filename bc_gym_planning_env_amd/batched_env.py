@@ -918,9 +918,11 @@ class BatchedPlanEnv(object):
         anything torch can put there).  Returns (reward float64 [K, N], done uint8 [K, N]) device tensors, no sync; the
         state ends where K calls of step() with actions[k] would leave it, bit for bit (auto-reset and the on-device
         noise stream included).  noise_z / noise_z_out: optional [K, N, 3]; collided_out uint8 / err_out int32: optional
-        [K, N] (without them only the last step's collided_now / err are kept).  With the single-launch step form the K
-        steps are ONE kernel launch -- open-loop Monte-Carlo rollouts from one state (the reference's README) pay launch,
-        argument fetch and staging once, and no workgroup waits for the chip's slowest one between steps."""
+        [K, N] (without them the rows go to cached internal buffers).  Afterwards the per-step views show the last row --
+        reward, done, collided_now -- except err, which is the OR over all K rows: check_errors() after a rollout raises
+        for an env that any of the K steps flagged.  With the single-launch step form the K steps are ONE kernel launch --
+        open-loop Monte-Carlo rollouts from one state (the reference's README) pay launch, argument fetch and staging once,
+        and no workgroup waits for the chip's slowest one between steps."""
         actions = self._device_tensor(actions)
         k, n = int(actions.shape[0]), self.n_envs
         assert tuple(actions.shape) == (k, n, 2) and k >= 1
@@ -940,18 +942,21 @@ class BatchedPlanEnv(object):
         io.reward, io.done = reward.data_ptr(), done.data_ptr()
         if collided_out is not None:
             assert collided_out.dtype == torch.uint8 and tuple(collided_out.shape) == (k, n) and collided_out.is_contiguous()
-            io.collided_now = collided_out.data_ptr()
         if err_out is not None:
             assert err_out.dtype == torch.int32 and tuple(err_out.shape) == (k, n) and err_out.is_contiguous()
-            io.err = err_out.data_ptr()
+        rows = self._cached_outputs("_rollout_buffers", k, {"collided": ((k, n), torch.uint8), "err": ((k, n), torch.int32)},
+                                    [name for name, given in (("collided", collided_out), ("err", err_out)) if given is None])
+        collided_out = rows["collided"] if collided_out is None else collided_out
+        err_out = rows["err"] if err_out is None else err_out
+        io.collided_now, io.err = collided_out.data_ptr(), err_out.data_ptr()
         _lib.check(self._lib.bcp_rollout(self._h, C.byref(io), k, flags, self._stream()))
-        # the per-step views of step() show the last row
+        # the per-step views of step() show the last row; err holds every bit that any of the K rows holds
         self.reward.copy_(reward[-1])
         self.done.copy_(done[-1])
-        if collided_out is not None:
-            self.collided_now.copy_(collided_out[-1])
-        if err_out is not None:
-            self.err.copy_(err_out[-1])
+        self.collided_now.copy_(collided_out[-1])
+        self.err.zero_()
+        for bit in (_lib.ERR_ANGLE_JUMP, _lib.ERR_TIME_ORDER, _lib.ERR_INTERNAL):
+            self.err |= (err_out & bit).amax(dim=0)
         self._last_inputs = tuple(keep)
         return reward, done
 

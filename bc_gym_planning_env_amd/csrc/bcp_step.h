@@ -649,6 +649,14 @@ __device__ __forceinline__ int coop_last_reached(const DevParams& P, LdsF64 path
 // one -- its limit, DevParams::ap_cos_min, carries -1e-4.  (Without it a pose that is near a way point but turned away from it
 // went through the exact test of every such way point, one memory round trip each: the waves that scan the part of the window
 // next to the target took 9 k cycles longer than the others on C4.)
+// The pose's heading is rounded to float32 before its cos / sin are taken.  For |th| < 32 rad that is half an ulp = 1e-6 and the
+// 2.5e-5 above stands (2.16e-5 from the record's cos / sin, the rest float32 rounding).  A heading is only normalised by a
+// step that moves the robot: one written into the state (set_state, state.robot[2], path[0] after a reset) arrives here as it is
+// when that step collides and rolls the pose back.  Up to |th| < 2048 rad half an ulp is 6.1e-5, the cosine is within 8.3e-5
+// and the -1e-4 of ap_cos_min still covers it; from 2048 rad on it does not.  No such heading gets here unflagged: a step from th
+// is free of BCP_ERR_ANGLE_JUMP only if |w| dt >= |th| - 3 pi (path_velocity corrects the difference to the normalised new
+// heading by one turn), i.e. for a robot that turns by more than 2000 rad in one step; every other one carries the error word,
+// which says that the reference raised there.  tests/headings.py keeps robot headings within 51 turns (320 rad).
 // So whatever the prefilter rejects fails the float64 test too: the result is the exact scan's, bit for bit.
 #ifndef BCP_PREFILTER_TRIP
 #define BCP_PREFILTER_TRIP 8

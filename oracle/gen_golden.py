@@ -18,6 +18,9 @@ Fixture list:
                             other tricycle dimensions, other alphas, other reward parameters, a short time-out
   g15_footprint_zoo.npz     the footprint zoo of tests/footprints.py: pre-fill polygons, scaled stock footprints and
                             pose_collides verdicts on the g6 maps   (python oracle/gen_golden.py footprint_zoo)
+  g17_headings.npz          robot steps from headings up to 50 turns outside [-pi, pi) -- with a `raised` flag where path_velocity
+                            raised -- and two PlanEnv trajectories on paths whose angles are shifted by whole turns
+                            (python oracle/gen_golden.py headings; written with fixed time stamps: a re-run is byte-identical)
 """
 import os
 import sys
@@ -854,6 +857,120 @@ def gen_offstock():
     assert n_collide >= 2, n_collide
 
 
+# ---- G17: headings outside [-pi, pi) ----------------------------------------------------------------------------
+def save_reproducible(name, **arrays):
+    """np.savez_compressed stamps every member with the time of day; this writes the same container with a fixed stamp, so
+    that making the fixture again gives the same bytes"""
+    import zipfile
+    path = os.path.join(OUT, name)
+    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_DEFLATED) as zf:
+        for key in sorted(arrays):
+            info = zipfile.ZipInfo(key + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            with zf.open(info, "w") as f:
+                np.lib.format.write_array(f, np.asanyarray(arrays[key]), allow_pickle=False)
+    print("wrote %-32s %7.1f KiB" % (name, os.path.getsize(path) / 1024.))
+
+
+def heading_cases(rng):
+    """Start states [n, 7] and commands [n, 2] (float32 values held in float64, from PlanEnv's action box) whose headings cover
+    [-pi, pi) and +-1, +-2, +-3, +-50 turns away from it; exactly +-pi and +-3 pi with their neighbouring doubles; and
+    +-(3 pi - eps), eps in {0, 1e-4, 1e-3, 5e-3, 2e-2}, each with commands of both turning signs (four per sign) from rest."""
+    box_low = np.array([60. * np.pi / 180. / 10, -np.pi / 2])
+    box_high = np.array([60. * np.pi / 180. / 2, np.pi / 2])
+    heads, turning, rest = [], [], []
+    for th in rng.uniform(-np.pi, np.pi, 24):
+        for turns in (0, 1, -1, 2, -2, 3, -3, 50, -50):
+            heads.append(th + turns * 2 * np.pi)
+            turning.append(0)
+            rest.append(False)
+    for base in (np.pi, -np.pi, 3 * np.pi, -3 * np.pi):
+        for th in (np.nextafter(base, -100.0), base, np.nextafter(base, 100.0)):
+            for sign in (1, -1):
+                heads.append(th)
+                turning.append(sign)
+                rest.append(True)
+    for eps in (0.0, 1e-4, 1e-3, 5e-3, 2e-2):
+        for side in (1.0, -1.0):
+            for sign in (1, -1):
+                for _ in range(4):
+                    heads.append(side * (3 * np.pi - eps))
+                    turning.append(sign)
+                    rest.append(True)
+    n = len(heads)
+    turning, rest = np.array(turning), np.array(rest)
+    st = np.zeros((n, 7))
+    st[:, 0:2] = rng.uniform(-3, 3, (n, 2))
+    st[:, 2] = heads
+    st[:, 3] = np.where(rest, 0.0, rng.uniform(0.0, 0.5, n))
+    st[:, 4] = np.where(rest, 0.0, rng.uniform(-0.5, 0.5, n))
+    st[:, 6] = np.where(rest, 0.0, rng.uniform(-0.6, 0.6, n))
+    cmd = rng.uniform(box_low, box_high, (n, 2))
+    cmd[:, 1] = np.where(turning != 0, turning * np.abs(cmd[:, 1]), cmd[:, 1])
+    return st, cmd.astype(np.float32).astype(np.float64), turning
+
+
+def gen_headings():
+    """G17: TricycleRobot.step (dynamic model + PID, and kinematic without PID) and DiffDriveRobot.step from the headings of
+    heading_cases -- the output state, or raised = 1 where the step raised "Path has missing/corrupted angle data" (the
+    state is not recorded there) -- and two PlanEnv trajectories (refine_path = False) on the g8 mini map and on one aisle
+    template with the path angles of way points j >= 1 shifted by whole turns (tests/headings.shift_path; path[0], the
+    start heading, stays)."""
+    from bc_gym_planning_env.robot_models.tricycle_model import TricycleRobot, TricycleRobotState
+    from bc_gym_planning_env.robot_models.differential_drive import DiffDriveRobot, DiffdriveRobotState
+    from bc_gym_planning_env.robot_models.robot_dimensions_examples import get_dimensions_example
+    from bc_gym_planning_env.envs.base.action import Action
+    from bc_gym_planning_env.envs.base.env import PlanEnv
+    from bc_gym_planning_env.envs.base.params import EnvParams
+    from bc_gym_planning_env.utilities.costmap_2d import CostMap2D
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import headings as HD
+    dt = 0.05
+    st, cmd, turning = heading_cases(np.random.RandomState(171))
+    n = len(st)
+    tri_dims = get_dimensions_example('industrial_tricycle_v1')
+    models = [("tri_dyn_pid", lambda: TricycleRobot(dimensions=tri_dims, noise_parameters=None)),
+              ("tri_kin_nopid", lambda: TricycleRobot(dimensions=tri_dims, noise_parameters=None, dynamic_model=False,
+                                                      model_front_column_pid=False)),
+              ("dd", lambda: DiffDriveRobot(dimensions=get_dimensions_example('industrial_diffdrive_v1'), noise_parameters=None))]
+    out = dict(state=st, cmd=cmd, turning=turning.astype(np.int32), dt=np.float64(dt), models=np.array([m for m, _ in models]))
+    for name, make in models:
+        robot = make()
+        res, raised = np.full((n, 7), np.nan), np.zeros(n, dtype=np.uint8)
+        for i in range(n):
+            if name == "dd":   # (the diff-drive command is (v, w): the steering column of cmd serves as w)
+                robot.set_state(DiffdriveRobotState(x=st[i, 0], y=st[i, 1], angle=st[i, 2], v=st[i, 3], w=st[i, 4]))
+            else:
+                robot.set_state(TricycleRobotState(x=st[i, 0], y=st[i, 1], angle=st[i, 2], v=st[i, 3], w=st[i, 4],
+                                                   steering_motor_command=st[i, 5], wheel_angle=st[i, 6]))
+            try:
+                robot.step(dt, Action(command=cmd[i]))
+            except Exception as e:
+                assert "missing/corrupted angle data" in str(e), e
+                raised[i] = 1
+                continue
+            res[i] = dd_state_vec(robot.get_state()) if name == "dd" else tri_state_vec(robot.get_state())
+        print("   %-14s raised %d of %d" % (name, raised.sum(), n))
+        out[name + "_out"], out[name + "_raised"] = res, raised
+    # (sp, ap) as the g8 trajectories of these worlds were recorded with; the short time-outs end the episodes
+    for tag, src, kw, steps, seeds in (("mini", "g8_traj_mini_00.npz", dict(goal_spat_dist=0.2, goal_ang_dist=np.pi / 8, iteration_timeout=60), 100, (1700, 2700)),
+                                       ("aisle", "g8_traj_aisle_c4_00.npz", dict(iteration_timeout=120), 150, (1701, 2701))):
+        g = np.load(os.path.join(OUT, src))
+        path = HD.shift_path(g["path"])
+        ep = EnvParams(resolution=float(g["resolution"]), refine_path=False, **kw)
+        env = PlanEnv(CostMap2D(g["costmap"].copy(), float(g["resolution"]), g["origin"].copy()), path, ep)
+        rec = record_trajectory(env, env, steps, action_seed=seeds[0], noise_seed=seeds[1])
+        assert rec["done"].any() and (rec["path"] == path).all() and rec["init_state"][2] == g["path"][0, 2], tag
+        rec.pop("costmap"), rec.pop("origin"), rec.pop("resolution")     # (those of `world`)
+        rec.update(world=np.array(src), dt=np.float64(ep.dt), iteration_timeout=np.int32(ep.iteration_timeout),
+                   spatial_precision=np.float64(ep.goal_spat_dist), angular_precision=np.float64(ep.goal_ang_dist),
+                   spatial_progress_multiplier=np.float64(0.0))
+        print("   traj %-6s done at %s, collided %d, final target %d of %d" % (
+            tag, np.nonzero(rec["done"])[0][:1], rec["collided"].any(), rec["target_idx"][-1], len(path)))
+        out.update(("traj_%s_%s" % (tag, k), v) for k, v in rec.items())
+    save_reproducible("g17_headings.npz", **out)
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     O.build()
@@ -863,6 +980,9 @@ def main():
         return
     if sys.argv[1:] == ["offstock"]:
         gen_offstock()
+        return
+    if sys.argv[1:] == ["headings"]:
+        gen_headings()
         return
     gen_robot_steps()
     gen_scalar_utils()
@@ -879,6 +999,7 @@ def main():
     gen_trajectories()
     gen_footprint_zoo()
     gen_offstock()
+    gen_headings()
 
 
 if __name__ == "__main__":

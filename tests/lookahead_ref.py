@@ -43,7 +43,8 @@ class StartState(object):
 def oracle_lookahead(oracle, params, world, start, actions, z=None, threads=8):
     """world: dict(costmaps, origins, resolution, paths[, lens, rows, cols]) as OracleBatch takes them (private entries
     are indexed by env, or by start.geom); actions [H, K, 2] or [H, N, K, 2]; z None or [H, N, K, 3] (poisoned where
-    the reference drew nothing).  Returns dict(ret, steps, reason, final_pose, final_target_idx) over [N, K]."""
+    the reference drew nothing).  Returns dict(ret, steps, reason, final_pose, final_target_idx, err) over [N, K]; err is the OR
+    of the oracle's error word over the steps a candidate ran."""
     actions = np.asarray(actions, dtype=np.float64)
     n = start.n
     if actions.ndim == 3:
@@ -73,7 +74,7 @@ def oracle_lookahead(oracle, params, world, start, actions, z=None, threads=8):
         last = paths[geom, m - 1, :2]
     pure_pursuit = params.reward_provider == oracle.REWARD_PURE_PURSUIT
     ret, steps, reason = np.zeros(nk), np.zeros(nk, np.int32), np.zeros(nk, np.uint8)
-    final_pose, final_target = np.zeros((nk, 3)), np.zeros(nk, np.int32)
+    final_pose, final_target, errs = np.zeros((nk, 3)), np.zeros(nk, np.int32), np.zeros(nk, np.int32)
     running = np.ones(nk, bool)
     for t in range(h):
         if not running.any():
@@ -82,6 +83,7 @@ def oracle_lookahead(oracle, params, world, start, actions, z=None, threads=8):
                 auto_reset=False, threads=threads)
         ret[running] += ob.reward[running]          # (one addition per step, in step order)
         steps[running] = t + 1
+        errs[running] |= ob.err[running]
         pose = np.stack(ob.st[:3], axis=1)
         final_pose[running] = pose[running]
         final_target[running] = ob.target_idx[running]
@@ -96,7 +98,7 @@ def oracle_lookahead(oracle, params, world, start, actions, z=None, threads=8):
         reason[ends] = why[ends]
         running &= ~ends
     out = dict(ret=ret.reshape(n, k), steps=steps.reshape(n, k), reason=reason.reshape(n, k),
-               final_pose=final_pose.reshape(n, k, 3), final_target_idx=final_target.reshape(n, k))
+               final_pose=final_pose.reshape(n, k, 3), final_target_idx=final_target.reshape(n, k), err=errs.reshape(n, k))
     out["best"] = select_best(out["ret"], out["reason"])
     return out
 

@@ -57,19 +57,22 @@ def host_eps(seed, iterations, n, k, horizon):
 
 def mppi_ref(oracle, params, world, start, mean, sigma, low, high, lam, collision_penalty, eps, threads=8):
     """I iterations on the oracle.  Returns dict(mean, action, iter_mean [I, N, H, 2], iter_ret, iter_reason [I, N, K],
-    iter_w [I, N, K])"""
+    iter_w [I, N, K], iter_err [I, N, K], err [N] = the OR of the oracle's error word over iterations and candidates)"""
     mean = np.array(mean, np.float64)
-    out = dict(iter_mean=[], iter_ret=[], iter_reason=[], iter_w=[])
+    out = dict(iter_mean=[], iter_ret=[], iter_reason=[], iter_w=[], iter_err=[])
+    err = np.zeros(start.n, np.int32)
     for j in range(eps.shape[0]):
         u = candidates(mean, sigma, eps[j], low, high)
         la = LR.oracle_lookahead(oracle, params, world, start, as_lookahead_actions(u), threads=threads)
+        err |= np.bitwise_or.reduce(la["err"], axis=1)
+        out["iter_err"].append(la["err"])
         out["iter_mean"].append(mean)
         out["iter_ret"].append(la["ret"])
         out["iter_reason"].append(la["reason"])
         mean, w = update(u, la["ret"], la["reason"], lam, collision_penalty)
         out["iter_w"].append(w)
     out = {k: np.stack(v) for k, v in out.items()}
-    out["mean"], out["action"] = mean, mean[:, 0].copy()
+    out["mean"], out["action"], out["err"] = mean, mean[:, 0].copy(), err
     return out
 
 

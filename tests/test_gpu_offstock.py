@@ -67,9 +67,13 @@ def test_recorded_trajectories_at_other_parameters(torch_cuda, path, form):
     """PlanEnv.step at another dt / reward parameters / time-out, replayed on three replicas with the recorded actions and
     normals: the assertions of test_full_step_trajectories_vs_reference, `time` (dt accumulated step by step) exact, and the
     replicas bit-identical to each other"""
-    torch = torch_cuda
+    replay_recorded(torch_cuda, dict(np.load(path)), form)
+
+
+def replay_recorded(torch, g, form):
+    """g: a recorded PlanEnv trajectory with its world and parameters (a g16_traj file, or one of g17_headings put together with
+    the world it names)"""
     from bc_gym_planning_env_amd import BatchedPlanEnv, CostMap2D, EnvParams, RewardParams
-    g = dict(np.load(path))
     res, dt = float(g["resolution"]), float(g["dt"])
     sp, ap, mult = float(g["spatial_precision"]), float(g["angular_precision"]), float(g["spatial_progress_multiplier"])
     params = EnvParams(dt=dt, goal_spat_dist=sp, goal_ang_dist=ap, iteration_timeout=int(g["iteration_timeout"]), resolution=res,

@@ -324,3 +324,91 @@ def test_g16_covers_the_parameter_points():
     assert any(float(g["angular_precision"]) >= np.pi for g in gs) and any(int(g["iteration_timeout"]) == 7 for g in gs)
     g = [g for g in gs if float(g["dt"]) == 0.1][0]     # time is dt accumulated, which is not iter * dt
     assert not np.array_equal(g["time"], (np.arange(len(g["time"])) + 1) * 0.1)
+
+
+# ---- G17: headings outside [-pi, pi) ----------------------------------------------------------------------------------
+G17_MODELS = {"tri_dyn_pid": ("tricycle", 1, 1), "tri_kin_nopid": ("tricycle", 0, 0), "dd": ("diffdrive", 1, 1)}
+
+
+@pytest.mark.parametrize("name", sorted(G17_MODELS))
+def test_g17_robot_steps_from_unnormalised_headings(oracle, golden_dir, name):
+    """the oracle's error word is set exactly where the reference raised, and elsewhere the state is the recorded one"""
+    g = load(golden_dir, "g17_headings.npz")
+    model, dyn, pid = G17_MODELS[name]
+    p = oracle.make_params(model, dt=float(g["dt"]), dynamic_model=dyn, model_front_column_pid=pid)
+    want, raised = g[name + "_out"], g[name + "_raised"]
+    assert name in [str(m) for m in g["models"]] and np.isnan(want[raised != 0]).all() and not np.isnan(want[raised == 0]).any()
+    for i, (st, cmd) in enumerate(zip(g["state"], g["cmd"])):
+        if name == "dd":     # (the diff-drive state has no wheel: the fixture's rows hold zeros there)
+            st = np.concatenate([st[:5], [0.0, 0.0]])
+        out, err, _ = oracle.robot_step(p, st, cmd)
+        assert (err != 0) == bool(raised[i]) and err in (0, oracle.ERR_ANGLE_JUMP), (name, i, st[2], err)
+        if not raised[i]:
+            np.testing.assert_array_equal(out, want[i], err_msg="%s row %d" % (name, i))
+            assert -np.pi <= out[2] < np.pi
+
+
+def test_g17_covers_the_headings():
+    """what the fixture claims to hold: every whole-turn shift, the exact multiples of pi with their neighbours, the knife edge
+    with both turning signs -- and what the reference did there"""
+    g = np.load(os.path.join(os.path.dirname(__file__), "golden", "g17_headings.npz"))
+    th, turning, n = g["state"][:, 2], g["turning"], len(g["state"])
+    assert 300 <= n <= 400
+    base = th[:24 * 9].reshape(24, 9)
+    np.testing.assert_allclose((base - base[:, :1]) / (2 * np.pi), np.broadcast_to([0, 1, -1, 2, -2, 3, -3, 50, -50], (24, 9)), atol=1e-9)
+    assert (np.abs(base[:, 0]) < np.pi).all()
+    for name in G17_MODELS:
+        raised = g[name + "_raised"]
+        # +-1 turn steps normally, +-2 turns or more raise
+        assert (raised[:24 * 9].reshape(24, 9) == np.array([0, 0, 0, 1, 1, 1, 1, 1, 1], dtype=np.uint8)).all(), name
+        for side in (1.0, -1.0):
+            for v in (np.nextafter(side * np.pi, -100.0), side * np.pi, np.nextafter(side * np.pi, 100.0)):
+                assert ((th == v) & (turning == 1)).sum() == 1 and ((th == v) & (turning == -1)).sum() == 1
+                assert not raised[th == v].any(), (name, v)
+            # at +3 pi exactly: raises when turning left (w > 0) and not when turning right; at -3 pi the mirror image
+            at = th == side * 3 * np.pi
+            assert at.sum() >= 2 + 8
+            assert raised[at & (turning == side)].all() and not raised[at & (turning == -side)].any(), (name, side)
+            for eps in (1e-4, 1e-3, 5e-3, 2e-2):
+                assert ((th == side * (3 * np.pi - eps)) & (turning == 1)).sum() == 4
+                assert ((th == side * (3 * np.pi - eps)) & (turning == -1)).sum() == 4
+                assert not raised[(th == side * (3 * np.pi - eps)) & (turning == -side)].any()
+        knife = (np.abs(th) > 3 * np.pi - 6e-3) & (np.abs(th) < 3 * np.pi) & (turning == np.sign(th))
+        print(name, "on the knife edge, turning towards it: %d of %d raised" % (raised[knife].sum(), knife.sum()))
+    # the command decides on the knife edge: the dynamic model from rest raises for some of the commands and not for others
+    assert 0 < g["tri_dyn_pid_raised"][knife].sum() < knife.sum()
+    for tag in ("mini", "aisle"):
+        path = g["traj_%s_path" % tag]
+        plain = np.load(os.path.join(os.path.dirname(__file__), "golden", str(g["traj_%s_world" % tag])))["path"]
+        turns = (path[:, 2] - plain[:, 2]) / (2 * np.pi)
+        np.testing.assert_allclose(turns[1:], np.array([0, 1, -1, 2, -2, 3, 50, -1000])[np.arange(1, len(path)) % 8], atol=1e-9)
+        assert turns[0] == 0 and g["traj_%s_done" % tag].any() and int(g["traj_%s_target_idx" % tag].max()) >= 8
+
+
+@pytest.mark.parametrize("tag", ["mini", "aisle"])
+def test_g17_trajectories(oracle, golden_dir, tag):
+    """as test_g16_trajectories: PlanEnv.step on a path whose angles are whole turns away from [-pi, pi), bit for bit"""
+    g17 = load(golden_dir, "g17_headings.npz")
+    g = dict((k[len("traj_%s_" % tag):], g17[k]) for k in g17.files if k.startswith("traj_%s_" % tag))
+    w = load(golden_dir, str(g["world"]))
+    p = oracle.make_params("tricycle", dt=float(g["dt"]), noise=oracle.PLANENV_NOISE,
+                           iteration_timeout=int(g["iteration_timeout"]), spatial_precision=float(g["spatial_precision"]),
+                           angular_precision=float(g["angular_precision"]),
+                           spatial_progress_multiplier=float(g["spatial_progress_multiplier"]))
+    env = oracle.OracleBatch(p, 1, w["costmap"], w["origin"], float(w["resolution"]), g["path"])
+    env.reset_from_paths()
+    assert env.target_idx[0] == int(g["init_target_idx"]) and env.min_dist[0] == float(g["init_min_dist"])
+    np.testing.assert_array_equal([env.st[f][0] for f in range(7)], g["init_state"])
+    assert g["done"].any()
+    for t in range(len(g["actions"])):
+        z = np.where(np.isnan(g["z"][t]), 1e300, g["z"][t])[None]
+        env.step(g["actions"][t][None], z)
+        np.testing.assert_array_equal([env.st[f][0] for f in range(7)], g["states"][t], err_msg="step %d" % t)
+        assert env.reward[0] == g["reward"][t], t
+        assert env.done[0] == g["done"][t], t
+        assert env.collided[0] == g["collided"][t], t
+        assert env.target_idx[0] == g["target_idx"][t], t
+        assert env.min_dist[0] == g["min_dist"][t], t
+        assert env.cur_time[0] == g["time"][t], t
+        assert len(g["path"]) - env.target_idx[0] == g["obs_path_len"][t] or env.target_idx[0] >= len(g["path"])
+        assert env.err[0] == 0, t
