@@ -19,7 +19,8 @@ TUNE_LOCAL_PAIRS, TUNE_EGO_LIST_STRIDE, TUNE_NEAR_SHIFT = 8, 9, 10
 E_NO_DEVICE = -2
 OPT_DIFFDRIVE_NOISE = 1
 EGO_KERNELS = {0: "none", 1: "ego_sparse_kernel", 2: "ego_costmap_kernel<staged>", 3: "ego_costmap_binned_kernel",
-               4: "ego_costmap_window_kernel", 5: "ego_costmap_kernel<global>"}
+               4: "ego_costmap_window_kernel", 5: "ego_costmap_kernel<global>", 6: "ego_pooled_sparse_kernel",
+               7: "ego_pooled_sampled_kernel"}
 
 _f64p = C.POINTER(C.c_double)
 _i32p = C.POINTER(C.c_int32)
@@ -147,6 +148,9 @@ SYMBOLS = {
     "bcp_egocentric_costmaps": (C.c_int, [_H, C.c_void_p, C.c_int64, _f64p, _f64p, C.c_uint8, C.c_void_p,
                                           C.c_void_p]),
     "bcp_egocentric_route": (C.c_int, [_H, _i32p]),
+    "bcp_egocentric_pooled_shape": (C.c_int, [_H, _f64p, C.c_int32, _i32p]),
+    "bcp_egocentric_costmaps_pooled": (C.c_int, [_H, C.c_void_p, C.c_int64, _f64p, _f64p, C.c_uint8, C.c_int32, C.c_void_p,
+                                                 C.c_void_p]),
     "bcp_goal_n_state": (C.c_int, [_H, _f64p, C.c_void_p, C.c_void_p]),
     "bcp_goal_direction_state": (C.c_int, [_H, _f64p, C.c_void_p, C.c_void_p]),
     "bcp_mini_world_seed": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
@@ -174,6 +178,7 @@ SYMBOLS = {
     "bcp_bind_episode_record": (C.c_int, [_H, C.POINTER(BcpEpisodeRecord)]),
     "bcp_episode_record_overflows": (C.c_int, [_H, C.POINTER(C.c_int64), C.c_void_p]),
     "bcp_final_egocentric_costmaps": (C.c_int, [_H, _f64p, _f64p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "bcp_final_egocentric_costmaps_pooled": (C.c_int, [_H, _f64p, _f64p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "bcp_final_goal_n_state": (C.c_int, [_H, _f64p, C.c_void_p, C.c_void_p]),
     "bcp_final_goal_direction_state": (C.c_int, [_H, _f64p, C.c_void_p, C.c_void_p]),
 }

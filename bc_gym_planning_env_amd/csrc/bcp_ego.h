@@ -837,12 +837,15 @@ static size_t ego_sparse_lds_bytes(int drows, int dcols, int waves)
 typedef int EgoI32x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) EgoI32x2* LdsI32x2;
 
-// the 3 x 3 candidates of one source cell: warpAffine's expression, from the tables, decides which of them copy the cell.
+// the 3 x 3 candidates of one source cell: warpAffine's expression, from the tables, decides which of them copy the cell;
+// sink(x, y, value) is called for each one that does (ego_sparse_kernel: a byte of the image, ego_pooled_sparse_kernel: a
+// maximum in LDS).
 // The forward position only has to put the candidates inside the block: float32 is within 2e-3 px of the float64 value
 // (every term is below 6 000 px when the sum is anywhere near the window), and a pixel that samples the cell lies within
 // 0.71 + 2^-9 px of the true position, so within 1.22 < 1.5 px of its rounding.
-__device__ __forceinline__ void ego_patch_cell(const EgoArgs& a, LdsI32x2 col_tab, LdsI32x2 row_tab, uint8_t* __restrict__ image,
-                                               uint32_t cell, float f0, float f1, float f2, float f3, float f4, float f5)
+template <class Sink>
+__device__ __forceinline__ void ego_cell_pixels(const EgoArgs& a, LdsI32x2 col_tab, LdsI32x2 row_tab, uint32_t cell, float f0,
+                                                float f1, float f2, float f3, float f4, float f5, const Sink& sink)
 {
     const int sx = (int)(cell & 0xFFFu), sy = (int)((cell >> 12) & 0xFFFu);
     const uint8_t v = (uint8_t)(cell >> 24);
@@ -863,9 +866,15 @@ __device__ __forceinline__ void ego_patch_cell(const EgoArgs& a, LdsI32x2 col_ta
         const EgoI32x2 rt = row_tab[y];
 #pragma unroll
         for (int j = 0; j < 3; ++j)
-            if (xin[j] && ((rt.x + ct[j].x) >> 10) == sx && ((rt.y + ct[j].y) >> 10) == sy)
-                image[(int64_t)y * a.dcols + (xc - 1 + j)] = v;
+            if (xin[j] && ((rt.x + ct[j].x) >> 10) == sx && ((rt.y + ct[j].y) >> 10) == sy) sink(xc - 1 + j, y, v);
     }
+}
+
+__device__ __forceinline__ void ego_patch_cell(const EgoArgs& a, LdsI32x2 col_tab, LdsI32x2 row_tab, uint8_t* __restrict__ image,
+                                               uint32_t cell, float f0, float f1, float f2, float f3, float f4, float f5)
+{
+    ego_cell_pixels(a, col_tab, row_tab, cell, f0, f1, f2, f3, f4, f5,
+                    [image, dcols = a.dcols](int x, int y, uint8_t v) { image[(int64_t)y * dcols + x] = v; });
 }
 
 // One wavefront per image (border value 0, cell lists built).  Order of a wave's work, chosen for what it waits on:
@@ -992,6 +1001,194 @@ __global__ void __launch_bounds__(64 * kEgoWaves) ego_sparse_kernel(const EgoArg
                     if (c0 + lane < held) ego_patch_cell(a, col_tab, row_tab, image, mine_cells[c0 + lane], f0, f1, f2, f3, f4, f5);
                 __builtin_amdgcn_wave_barrier();
             } while (next < n_cells);
+        }
+    }
+}
+
+// ---- pooled images: the block maximum of the egocentric image, made directly ----------------------------------------------
+// out[i][R][C] = max of full[i][y][x] over the p x p block R p <= y < min((R + 1) p, drows), C p <= x < min((C + 1) p, dcols)
+// of the image the kernels above would have written (edge blocks are partial).  The full image never exists: a policy that
+// looks at 17 x 15 cells instead of 133 x 117 pixels costs 255 bytes of HBM per env instead of 15 561.
+struct EgoPool {
+    int32_t pool;           // p: 2 .. 64
+    int32_t prows, pcols;   // ceil(drows / p), ceil(dcols / p)
+    uint32_t magic;         // floor(2^32 / p) + 1: v / p == umulhi(v, magic) for v p < 2^32 (v < 8192)
+};
+
+typedef __attribute__((address_space(3))) uint32_t* LdsU32;
+
+// LDS of ego_pooled_sparse_kernel, per wave: the tables and the held list of ego_sparse_kernel, then one 32-bit word per
+// pooled cell (the LDS maximum works on words), an even number of them so that the next wave's tables stay 8-byte aligned
+static size_t ego_pooled_lds_bytes(int drows, int dcols, int prows, int pcols, int waves)
+{
+    return (size_t)waves * ((size_t)(drows + dcols) * 8 + (size_t)kEgoHeld * 4 + (((size_t)prows * pcols + 1) & ~(size_t)1) * 4);
+}
+
+// one pooled image from global memory: lanes stride over pooled cells, a cell evaluates its <= p x p destination pixels with
+// ego_image_slow's expression and keeps the running maximum in a register.  Any map, any border value.
+__device__ __forceinline__ void ego_pooled_image_sampled(const EgoArgs& a, const EgoPool& Q, const EgoImage& I,
+                                                         const uint8_t* __restrict__ src, uint8_t* __restrict__ image, int lane)
+{
+    const int cells = Q.prows * Q.pcols;
+    for (int c = lane; c < cells; c += 64) {
+        const int R = c / Q.pcols, C = c - R * Q.pcols;
+        const int y1 = min((R + 1) * Q.pool, a.drows), x0 = C * Q.pool, x1 = min((C + 1) * Q.pool, a.dcols);
+        uint32_t best = 0;
+        for (int y = R * Q.pool; y < y1; ++y) {
+            const int rx = sat_int((I.m1 * y + I.m2) * 1024) + 512, ry = sat_int((I.m4 * y + I.m5) * 1024) + 512;
+            for (int x = x0; x < x1; ++x) {
+                const int X = (rx + sat_int(I.m0 * x * 1024)) >> 10;
+                const int Y = (ry + sat_int(I.m3 * x * 1024)) >> 10;
+                uint32_t v = (uint32_t)a.border;
+                if ((unsigned)X < (unsigned)I.vc && (unsigned)Y < (unsigned)I.vr) v = src[(int64_t)Y * a.cols + X];
+                best = max(best, v);
+            }
+        }
+        image[c] = (uint8_t)best;
+    }
+}
+
+// One wavefront per image, any map and any border value (dense maps, lists absent or over the limit): no LDS.
+__global__ void __launch_bounds__(64 * kEgoWaves) ego_pooled_sampled_kernel(const EgoArgs a, const EgoPool Q)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = blockDim.x >> 6;
+    const int64_t PP = (int64_t)Q.prows * Q.pcols;
+    const int64_t first = (int64_t)blockIdx.x * waves + wave, stride = (int64_t)gridDim.x * waves;
+    const int64_t n_img = ego_images(a);   // (a.live: an episode record's count)
+    for (int64_t base = first; base < n_img; base += 64 * stride) {
+        EgoXform T;
+        memset(&T, 0, sizeof(T));
+        const int64_t mine = base + lane * stride;   // lane l: transform of the wave's l-th image of this batch
+        if (mine < n_img) T = ego_transform(a, mine);
+        const int64_t left = (n_img - base + stride - 1) / stride;
+        const int count = (int)(left < 64 ? left : 64);
+        for (int k = 0; k < count; ++k) {
+            const int64_t img = base + k * stride;
+            const EgoImage I = ego_broadcast(T, k);
+            ego_pooled_image_sampled(a, Q, I, a.data + I.g * a.map_stride, a.out + img * PP, lane);
+        }
+    }
+}
+
+// One wavefront per image (border value 0, cell lists built), organised like ego_sparse_kernel: the cell list is culled into
+// the wave's LDS list (A), warpAffine's terms of the image go into the wave's tables, the 3 x 3 exact test runs per held cell
+// (C) -- but a pixel that samples a cell lands as a maximum on the word of pooled cell (y / p, x / p) in LDS (two cells with
+// different values can meet in one block: a plain store would keep whichever came last).  There is no zero fill of HBM and
+// nothing to wait for: the pooled image is zeroed in LDS, accumulates over all passes of a crowded window, and leaves once,
+// packed to bytes.  An entry whose list overflowed `cap` is drawn by ego_pooled_image_sampled.
+// All LDS traffic is the wave's own area; LDS operations of one wave complete in order, wave_lds_sync() keeps the compiler
+// from reordering across the phases (zeros -> maxima -> packing).
+__global__ void __launch_bounds__(64 * kEgoWaves) ego_pooled_sparse_kernel(const EgoArgs a, const EgoPool Q,
+                                                                            const uint32_t* __restrict__ cells,
+                                                                            const int32_t* __restrict__ counts, int cap)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = blockDim.x >> 6;
+    const int pcells = Q.prows * Q.pcols;
+    const int64_t first = (int64_t)blockIdx.x * waves + wave, stride = (int64_t)gridDim.x * waves;
+    const int per_wave_words = (a.drows + a.dcols) * 2 + kEgoHeld + ((pcells + 1) & ~1);
+    const LdsI32x2 col_tab = (LdsI32x2)((LdsU32)ego_lds + wave * per_wave_words);
+    const LdsI32x2 row_tab = col_tab + a.dcols;
+    const LdsU32 mine_cells = (LdsU32)(row_tab + a.drows);
+    const LdsU32 pooled = mine_cells + kEgoHeld;
+    const int64_t n_img = ego_images(a);   // (a.live: an episode record's count)
+    for (int64_t base = first; base < n_img; base += 64 * stride) {
+        EgoXform T;
+        memset(&T, 0, sizeof(T));
+        const int64_t mine = base + lane * stride;   // lane l: transform of the wave's l-th image of this batch
+        if (mine < n_img) T = ego_transform(a, mine);
+        const int64_t left = (n_img - base + stride - 1) / stride;
+        const int count = (int)(left < 64 ? left : 64);
+        for (int k = 0; k < count; ++k) {            // the wave's images, one at a time
+            const int64_t img = base + k * stride;
+            const EgoImage I = ego_broadcast(T, k);
+            uint8_t* const image = a.out + img * pcells;
+            const int n_cells = counts[I.g];
+            if (n_cells > cap) {
+                ego_pooled_image_sampled(a, Q, I, a.data + I.g * a.map_stride, image, lane);
+                continue;
+            }
+            for (int c = lane; c < pcells; c += 64) pooled[c] = 0u;
+            // forward map of a source cell: the inverse of the dst -> src matrix
+            float f0, f1, f2, f3, f4, f5;
+            {
+                const double det = I.m0 * I.m4 - I.m1 * I.m3;
+                const double id = det != 0.0 ? 1.0 / det : 0.0;
+                const double d0 = I.m4 * id, d1 = -I.m1 * id, d3 = -I.m3 * id, d4 = I.m0 * id;
+                f0 = (float)d0;
+                f1 = (float)d1;
+                f2 = (float)(-(d0 * I.m2 + d1 * I.m5));
+                f3 = (float)d3;
+                f4 = (float)d4;
+                f5 = (float)(-(d3 * I.m2 + d4 * I.m5));
+            }
+            const float x_hi = (float)a.dcols + 1.0f, y_hi = (float)a.drows + 1.0f;
+            const uint32_t* const list = cells + I.g * (int64_t)cap;
+            auto meets_window = [&](uint32_t cell) -> bool {
+                const float sx = (float)(cell & 0xFFFu), sy = (float)((cell >> 12) & 0xFFFu);
+                const float fx = f0 * sx + f1 * sy + f2, fy = f3 * sx + f4 * sy + f5;
+                return cell != 0u && fx > -2.0f && fx < x_hi && fy > -2.0f && fy < y_hi;   // (a listed cell has a non-zero value byte)
+            };
+            // passes of A and C: one unless the window holds more than kEgoHeld cells
+            int next = 0;            // first list cell not culled yet (uniform)
+            bool tabled = false;
+            do {
+                int held = 0;        // cells in the wave's LDS list (uniform)
+                bool full = false;
+                for (int c0 = next; c0 < n_cells && !full; c0 += 256) {
+                    uint32_t cell[4];
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) cell[u] = c0 + 64 * u + lane < n_cells ? list[c0 + 64 * u + lane] : 0u;
+                    next = c0 + 256;
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        const bool in = meets_window(cell[u]);
+                        const uint64_t hits = __ballot(in);
+                        const int more = __builtin_popcountll(hits);
+                        if (held + more > kEgoHeld) {   // (this chunk of 64 starts the next pass)
+                            full = true;
+                            next = c0 + 64 * u;
+                            break;
+                        }
+                        if (in) mine_cells[held + __builtin_amdgcn_mbcnt_hi((uint32_t)(hits >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hits, 0u))] = cell[u];
+                        held += more;
+                    }
+                }
+                if (held == 0) break;   // (the whole list was read and nothing of it is in the window; a full list holds something)
+                if (!tabled) {          // warpAffine's terms of this image
+                    for (int t = lane; t < a.dcols + a.drows; t += 64) {
+                        EgoI32x2 e;
+                        if (t < a.dcols) {
+                            e.x = sat_int(I.m0 * t * 1024);
+                            e.y = sat_int(I.m3 * t * 1024);
+                        } else {
+                            const int y = t - a.dcols;
+                            e.x = sat_int((I.m1 * y + I.m2) * 1024) + 512;
+                            e.y = sat_int((I.m4 * y + I.m5) * 1024) + 512;
+                        }
+                        col_tab[t] = e;   // (row_tab follows col_tab)
+                    }
+                    tabled = true;
+                }
+                wave_lds_sync();   // zeros, tables and the held list are written
+                for (int c0 = 0; c0 < held; c0 += 64)
+                    if (c0 + lane < held)
+                        ego_cell_pixels(a, col_tab, row_tab, mine_cells[c0 + lane], f0, f1, f2, f3, f4, f5,
+                                        [&](int x, int y, uint8_t v) {
+                                            const uint32_t at = __umulhi((uint32_t)y, Q.magic) * (uint32_t)Q.pcols + __umulhi((uint32_t)x, Q.magic);
+                                            (void)__hip_atomic_fetch_max(pooled + at, (uint32_t)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                                        });
+                wave_lds_sync();   // the held list is rewritten by the next pass
+            } while (next < n_cells);
+            wave_lds_sync();       // the accumulation is finished before the packing pass reads it
+            // packed to bytes and stored once (images are prows x pcols bytes apart: the 32-bit stores are generally unaligned)
+            for (int q = 4 * lane; q < pcells; q += 256) {
+                if (q + 4 <= pcells) {
+                    *reinterpret_cast<u32_unaligned*>(image + q) = pooled[q] | (pooled[q + 1] << 8) | (pooled[q + 2] << 16) | (pooled[q + 3] << 24);
+                } else {
+                    for (int j = q; j < pcells; ++j) image[j] = (uint8_t)pooled[j];
+                }
+            }
+            wave_lds_sync();       // the words are zeroed for the next image
         }
     }
 }

@@ -120,22 +120,32 @@ extern "C" int bcp_egocentric_route(bcp_handle* h, int32_t* info4)
     return BCP_OK;
 }
 
+// waves per workgroup of ego_pooled_sparse_kernel: as many of kEgoWaves as fit the 64 KB the sparse route budgets (a small
+// `pool` on a large window leaves many words per image); 0 = not even one, the sampled route takes the call
+static int ego_pooled_sparse_waves(int drows, int dcols, const EgoPool& Q)
+{
+    const size_t one = ego_pooled_lds_bytes(drows, dcols, Q.prows, Q.pcols, 1);
+    return (int)std::min<size_t>(kEgoWaves, 64 * 1024 / one);
+}
+
 // rec != nullptr: the final observations of an episode record (bcp_final_egocentric_costmaps) -- image j from final state j
 // on entry rec->geom[j] (private maps without a pool: env rec->env_id[j]), n = capacity, only the first *count drawn
+// pool > 1: the block maxima of those images (bcp_egocentric_costmaps_pooled), same arguments, same cell lists
 static int egocentric_costmaps(bcp_handle* h, const double* poses, int64_t n, const double* window_origin,
                                const double* window_size, uint8_t border_value, uint8_t* out, void* stream,
-                               const EpisodeRec* rec)
+                               const EpisodeRec* rec, int32_t pool = 1,
+                               const char* who = "bcp_egocentric_costmaps")
 {
-    if (!h || !out) return fail(BCP_E_INVALID, "bcp_egocentric_costmaps: null argument");
-    if (!h->have_map) return fail(BCP_E_STATE, "bcp_egocentric_costmaps: costmaps not set");
-    if (!poses && !h->have_state) return fail(BCP_E_STATE, "bcp_egocentric_costmaps: no poses given and no state bound");
-    if (n <= 0 || (!poses && !rec && n != h->n)) return fail(BCP_E_INVALID, "bcp_egocentric_costmaps: n must be n_envs without poses");
+    if (!h || !out) return fail(BCP_E_INVALID, "%s: null argument", who);
+    if (!h->have_map) return fail(BCP_E_STATE, "%s: costmaps not set", who);
+    if (!poses && !h->have_state) return fail(BCP_E_STATE, "%s: no poses given and no state bound", who);
+    if (n <= 0 || (!poses && !rec && n != h->n)) return fail(BCP_E_INVALID, "%s: n must be n_envs without poses", who);
     if ((window_origin == nullptr) != (window_size == nullptr))
-        return fail(BCP_E_INVALID, "bcp_egocentric_costmaps: window origin and size go together");
+        return fail(BCP_E_INVALID, "%s: window origin and size go together", who);
     EgoArgs a;
     memset(&a, 0, sizeof(a));
     if (!ego_shape(h, window_size, &a.drows, &a.dcols))
-        return fail(BCP_E_INVALID, "bcp_egocentric_costmaps: unsupported window size");
+        return fail(BCP_E_INVALID, "%s: unsupported window size", who);
     HIP_TRY(hipSetDevice(h->device));
     a.data = h->map_data;
     a.shared = h->map.shared;
@@ -185,7 +195,7 @@ static int egocentric_costmaps(bcp_handle* h, const double* poses, int64_t n, co
     a.out = out;
     a.n_images = n;
     a.cols_magic = (uint32_t)(((uint64_t)1 << 32) / (uint64_t)a.cols) + 1;   // (staged maps are < 64 KB: exact)
-    if (a.dcols < 4) return fail(BCP_E_INVALID, "bcp_egocentric_costmaps: windows narrower than 4 px are not supported");
+    if (a.dcols < 4) return fail(BCP_E_INVALID, "%s: windows narrower than 4 px are not supported", who);
     const bool px8 = a.dcols >= 8;   // 8 pixels (one 64-bit store) per lane; narrow windows fall back to 4
     hipStream_t st = (hipStream_t)stream;
     int cus = 0;
@@ -199,8 +209,11 @@ static int egocentric_costmaps(bcp_handle* h, const double* poses, int64_t n, co
     // non-zero border) keep the sampling kernels below.
     const bool fits_lds = map_bytes + 4 * row_bytes <= 150 * 1024;
     h->ego_route[0] = h->ego_route[1] = h->ego_route[2] = h->ego_route[3] = 0;
-    if (border_value == 0 && a.rows <= 4095 && a.cols <= 4095 && !h->ego_cells_refused && h->ego_sparse &&
-        ego_sparse_lds_bytes(a.drows, a.dcols, kEgoWaves) <= 64 * 1024) {
+    EgoPool Q = {pool, (a.drows + pool - 1) / pool, (a.dcols + pool - 1) / pool, (uint32_t)(((uint64_t)1 << 32) / (uint64_t)pool) + 1};
+    // (pooled: fewer waves per workgroup where the pooled words of eight images do not fit; none -> the sampled route)
+    const int sparse_waves = pool > 1 ? ego_pooled_sparse_waves(a.drows, a.dcols, Q)
+                                      : (ego_sparse_lds_bytes(a.drows, a.dcols, kEgoWaves) <= 64 * 1024 ? kEgoWaves : 0);
+    if (border_value == 0 && a.rows <= 4095 && a.cols <= 4095 && !h->ego_cells_refused && h->ego_sparse && sparse_waves > 0) {
         const int64_t entries = a.shared ? 1 : n_slots(h);
         const int32_t limit = ego_sparse_limit(h->ego_sparse, (int64_t)a.drows * a.dcols, fits_lds);
         if (h->refresh_recorded && (!h->ego_cells_built || h->ego_cells_max < 0))
@@ -252,7 +265,17 @@ static int egocentric_costmaps(bcp_handle* h, const double* poses, int64_t n, co
         h->ego_route[1] = h->ego_cells_max;
         h->ego_route[2] = h->ego_cell_cap;
         h->ego_route[3] = limit;
-        if (h->ego_cells.get() && h->ego_cells_built && h->ego_cells_max >= 0 && h->ego_cells_max <= limit) {
+        if (pool > 1 && h->ego_cells.get() && h->ego_cells_built && h->ego_cells_max >= 0 && h->ego_cells_max <= limit) {
+            // one image per wave as below; nothing but the pooled bytes goes to HBM
+            const dim3 grid((unsigned)((n + sparse_waves - 1) / sparse_waves));
+            const size_t lds = ego_pooled_lds_bytes(a.drows, a.dcols, Q.prows, Q.pcols, sparse_waves);   // (<= 64 KB)
+            hipLaunchKernelGGL(ego_pooled_sparse_kernel, grid, dim3(64 * sparse_waves), lds, st, a, Q, h->ego_cells.get(),
+                               h->ego_cell_counts.get(), h->ego_cell_cap);
+            HIP_TRY(hipGetLastError());
+            h->ego_route[0] = BCP_EGO_POOLED_SPARSE;
+            return BCP_OK;
+        }
+        if (pool == 1 && h->ego_cells.get() && h->ego_cells_built && h->ego_cells_max >= 0 && h->ego_cells_max <= limit) {
             // One image per wave, eight per workgroup: 8 192 short workgroups for 65 536 images.  (Round 3 first ran this kernel
             // persistently -- as many workgroups as the chip holds, 64 images per wave, the lanes sharing the transforms' float64
             // arithmetic: 11 % slower on the same box, 0.249 against 0.222 ms.  Stores from many short workgroups drain faster than
@@ -267,6 +290,14 @@ static int egocentric_costmaps(bcp_handle* h, const double* poses, int64_t n, co
             h->ego_route[0] = BCP_EGO_SPARSE;
             return BCP_OK;
         }
+    }
+    if (pool > 1) {
+        // any map, any border value: every pooled cell samples its block from global memory
+        const dim3 grid((unsigned)((n + kEgoWaves - 1) / kEgoWaves));
+        hipLaunchKernelGGL(ego_pooled_sampled_kernel, grid, dim3(64 * kEgoWaves), 0, st, a, Q);
+        HIP_TRY(hipGetLastError());
+        h->ego_route[0] = BCP_EGO_POOLED_SAMPLED;
+        return BCP_OK;
     }
     if (!a.shared && fits_lds && n < ((int64_t)1 << 31)) {
         h->ego_route[0] = BCP_EGO_BINNED;
@@ -381,6 +412,25 @@ extern "C" int bcp_egocentric_costmaps(bcp_handle* h, const double* poses, int64
     return egocentric_costmaps(h, poses, n, window_origin, window_size, border_value, out, stream, nullptr);
 }
 
+extern "C" int bcp_egocentric_pooled_shape(bcp_handle* h, const double* window_size, int32_t pool, int32_t* shape_hw)
+{
+    if (pool < 1 || pool > 64) return fail(BCP_E_INVALID, "bcp_egocentric_pooled_shape: pool must be in [1, 64]");
+    const int rc = bcp_egocentric_shape(h, window_size, shape_hw);
+    if (rc != BCP_OK) return rc;
+    shape_hw[0] = (shape_hw[0] + pool - 1) / pool;
+    shape_hw[1] = (shape_hw[1] + pool - 1) / pool;
+    return BCP_OK;
+}
+
+extern "C" int bcp_egocentric_costmaps_pooled(bcp_handle* h, const double* poses, int64_t n, const double* window_origin,
+                                              const double* window_size, uint8_t border_value, int32_t pool, uint8_t* out,
+                                              void* stream)
+{
+    if (pool < 1 || pool > 64) return fail(BCP_E_INVALID, "bcp_egocentric_costmaps_pooled: pool must be in [1, 64]");
+    return egocentric_costmaps(h, poses, n, window_origin, window_size, border_value, out, stream, nullptr, pool,
+                               "bcp_egocentric_costmaps_pooled");
+}
+
 extern "C" int bcp_goal_n_state(bcp_handle* h, const double* world_size, float* out, void* stream)
 {
     return goal_n_state(h, world_size, out, stream, nullptr, "bcp_goal_n_state");
@@ -457,7 +507,18 @@ extern "C" int bcp_final_egocentric_costmaps(bcp_handle* h, const double* window
     if (!h->have_rec) return fail(BCP_E_STATE, "bcp_final_egocentric_costmaps: no episode record bound");
     if (border_value < 0 || border_value > 255) return fail(BCP_E_INVALID, "bcp_final_egocentric_costmaps: border value");
     return egocentric_costmaps(h, nullptr, h->rec.capacity, window_origin, window_size, (uint8_t)border_value, out, stream,
-                               &h->rec);
+                               &h->rec, 1, "bcp_final_egocentric_costmaps");
+}
+
+extern "C" int bcp_final_egocentric_costmaps_pooled(bcp_handle* h, const double* window_origin, const double* window_size,
+                                                    int32_t border_value, int32_t pool, uint8_t* out, void* stream)
+{
+    if (!h) return fail(BCP_E_INVALID, "bcp_final_egocentric_costmaps_pooled: null handle");
+    if (!h->have_rec) return fail(BCP_E_STATE, "bcp_final_egocentric_costmaps_pooled: no episode record bound");
+    if (border_value < 0 || border_value > 255) return fail(BCP_E_INVALID, "bcp_final_egocentric_costmaps_pooled: border value");
+    if (pool < 1 || pool > 64) return fail(BCP_E_INVALID, "bcp_final_egocentric_costmaps_pooled: pool must be in [1, 64]");
+    return egocentric_costmaps(h, nullptr, h->rec.capacity, window_origin, window_size, (uint8_t)border_value, out, stream,
+                               &h->rec, pool, "bcp_final_egocentric_costmaps_pooled");
 }
 
 extern "C" int bcp_final_goal_n_state(bcp_handle* h, const double* world_size, float* out, void* stream)

@@ -24,10 +24,14 @@ class BatchedEgocentricCostmap(object):
     final_observation=True: the env's episode record is enabled (env.enable_episode_record) and step() adds
     info["final_observation"], the observation of every episode that ended in the step, drawn from its final state
     before the auto-reset (SB3's terminal_observation, gymnasium's final_obs): the same keys with leading dimension
-    `capacity`, row j belongs to env info["episode_ends"].env_ids[j] for j < count."""
+    `capacity`, row j belongs to env info["episode_ends"].env_ids[j] for j < count.
+    pool=p > 1: the images are the maxima of the p x p blocks of the full image (bcp_egocentric_costmaps_pooled), made
+    without the full image reaching memory: image_shape is the pooled shape, full_image_shape the window's (H, W); the
+    goal vectors stay those of the full window."""
 
-    def __init__(self, env, x_bounds=(-0.5, 3.), y_bounds=(-2., 2.), border_value=0, final_observation=False):
+    def __init__(self, env, x_bounds=(-0.5, 3.), y_bounds=(-2., 2.), border_value=0, final_observation=False, pool=1):
         self.env = env
+        self.pool = int(pool)
         self.action_space = env.action_space
         self._origin = _f64x2([x_bounds[0], y_bounds[0]])
         self._size = _f64x2([x_bounds[1] - x_bounds[0], y_bounds[1] - y_bounds[0]])
@@ -35,7 +39,12 @@ class BatchedEgocentricCostmap(object):
         self._lib = env._lib
         shape = (C.c_int32 * 2)()
         _lib.check(self._lib.bcp_egocentric_shape(env._h, self._size.ctypes.data_as(_lib._f64p), shape))
-        self.image_shape = (int(shape[0]), int(shape[1]))
+        self.full_image_shape = (int(shape[0]), int(shape[1]))
+        self.image_shape = self.full_image_shape
+        if self.pool != 1:
+            pooled = (C.c_int32 * 2)()
+            _lib.check(self._lib.bcp_egocentric_pooled_shape(env._h, self._size.ctypes.data_as(_lib._f64p), self.pool, pooled))
+            self.image_shape = (int(pooled[0]), int(pooled[1]))
         res = env.resolution
         # CostMap2D.world_size() of the extracted map (utilities/costmap_2d.py:107-121)
         self._world = _f64x2([(self._origin[0] + res * shape[1]) - self._origin[0],
@@ -56,10 +65,7 @@ class BatchedEgocentricCostmap(object):
     def observation(self, _observation=None):
         """Refresh and return the observation of the envs' current state (device tensors, no sync)."""
         e = self.env
-        stream = C.c_void_p(torch.cuda.current_stream(e.device).cuda_stream)
-        _lib.check(self._lib.bcp_egocentric_costmaps(
-            e._h, None, e.n_envs, self._origin.ctypes.data_as(_lib._f64p), self._size.ctypes.data_as(_lib._f64p),
-            self._border, self.images.data_ptr(), stream))
+        stream = self._refresh_images()
         _lib.check(self._lib.bcp_goal_n_state(e._h, self._world.ctypes.data_as(_lib._f64p),
                                               self.goal_n_state.data_ptr(), stream))
         return self._obs
@@ -67,9 +73,14 @@ class BatchedEgocentricCostmap(object):
     def _refresh_images(self):
         e = self.env
         stream = C.c_void_p(torch.cuda.current_stream(e.device).cuda_stream)
-        _lib.check(self._lib.bcp_egocentric_costmaps(
-            e._h, None, e.n_envs, self._origin.ctypes.data_as(_lib._f64p), self._size.ctypes.data_as(_lib._f64p),
-            self._border, self.images.data_ptr(), stream))
+        if self.pool == 1:
+            _lib.check(self._lib.bcp_egocentric_costmaps(
+                e._h, None, e.n_envs, self._origin.ctypes.data_as(_lib._f64p), self._size.ctypes.data_as(_lib._f64p),
+                self._border, self.images.data_ptr(), stream))
+        else:
+            _lib.check(self._lib.bcp_egocentric_costmaps_pooled(
+                e._h, None, e.n_envs, self._origin.ctypes.data_as(_lib._f64p), self._size.ctypes.data_as(_lib._f64p),
+                self._border, self.pool, self.images.data_ptr(), stream))
         return stream
 
     def route(self):
@@ -100,12 +111,21 @@ class BatchedEgocentricCostmap(object):
             self._alloc_final(ends.capacity)
         return self._final
 
+    def _final_images(self, stream):
+        e = self.env
+        if self.pool == 1:
+            _lib.check(self._lib.bcp_final_egocentric_costmaps(
+                e._h, self._origin.ctypes.data_as(_lib._f64p), self._size.ctypes.data_as(_lib._f64p), self._border,
+                self.final_images.data_ptr(), stream))
+        else:
+            _lib.check(self._lib.bcp_final_egocentric_costmaps_pooled(
+                e._h, self._origin.ctypes.data_as(_lib._f64p), self._size.ctypes.data_as(_lib._f64p), self._border,
+                self.pool, self.final_images.data_ptr(), stream))
+
     def _final_observation(self, stream):
         """The final observations of the record's slots (bcp_final_egocentric_costmaps / bcp_final_goal_n_state)."""
         e = self.env
-        _lib.check(self._lib.bcp_final_egocentric_costmaps(
-            e._h, self._origin.ctypes.data_as(_lib._f64p), self._size.ctypes.data_as(_lib._f64p), self._border,
-            self.final_images.data_ptr(), stream))
+        self._final_images(stream)
         _lib.check(self._lib.bcp_final_goal_n_state(e._h, self._world.ctypes.data_as(_lib._f64p),
                                                     self.final_vector.data_ptr(), stream))
 
@@ -149,8 +169,8 @@ class BatchedColoredEgoCostmap(BatchedEgocentricCostmap):
     OrderedDict(environment=uint8 [N, 133, 133, 1], goal=float64 [N, 5, 1]) -- the egocentric costmap 0.5 m behind to
     3.5 m ahead of the robot, and (unit direction to the final way point, v, w, wheel_angle)."""
 
-    def __init__(self, env, x_bounds=(-0.5, 3.5), y_bounds=(-2., 2.), border_value=0, final_observation=False):
-        super(BatchedColoredEgoCostmap, self).__init__(env, x_bounds, y_bounds, border_value, final_observation)
+    def __init__(self, env, x_bounds=(-0.5, 3.5), y_bounds=(-2., 2.), border_value=0, final_observation=False, pool=1):
+        super(BatchedColoredEgoCostmap, self).__init__(env, x_bounds, y_bounds, border_value, final_observation, pool)
         self.goal = torch.zeros((env.n_envs, 5, 1), dtype=torch.float64, device=env.device)
         self._obs = OrderedDict((('environment', self.images), ('goal', self.goal)))
 
@@ -161,9 +181,7 @@ class BatchedColoredEgoCostmap(BatchedEgocentricCostmap):
 
     def _final_observation(self, stream):
         e = self.env
-        _lib.check(self._lib.bcp_final_egocentric_costmaps(
-            e._h, self._origin.ctypes.data_as(_lib._f64p), self._size.ctypes.data_as(_lib._f64p), self._border,
-            self.final_images.data_ptr(), stream))
+        self._final_images(stream)
         _lib.check(self._lib.bcp_final_goal_direction_state(e._h, self._world.ctypes.data_as(_lib._f64p),
                                                             self.final_vector.data_ptr(), stream))
 

@@ -170,21 +170,31 @@ class NativeOps(object):
     def seed(self, seed):
         _lib.check(self._lib.bcp_seed(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF))
 
-    def extract_egocentric_costmap(self, poses, resulting_origin=None, resulting_size=None, border_value=0):
+    def extract_egocentric_costmap(self, poses, resulting_origin=None, resulting_size=None, border_value=0, pool=1):
         """The costmap given to set_costmap seen from each of poses [n,3] -> uint8 [n, rows, cols] (robot at (0, 0)
-        heading +x; resulting_origin / resulting_size in metres, both or neither)."""
+        heading +x; resulting_origin / resulting_size in metres, both or neither).  pool > 1: the maximum of every
+        pool x pool block of that image instead, [n, ceil(rows / pool), ceil(cols / pool)]
+        (bcp_egocentric_costmaps_pooled)."""
         p = self._dev(np.atleast_2d(poses) if not isinstance(poses, torch.Tensor) else poses, torch.float64)
         f64p = C.POINTER(C.c_double)
         org = sz = None
         if resulting_origin is not None:
             org = np.ascontiguousarray(resulting_origin, dtype=np.float64)
             sz = np.ascontiguousarray(resulting_size, dtype=np.float64)
+        org_p = org.ctypes.data_as(f64p) if org is not None else None
+        sz_p = sz.ctypes.data_as(f64p) if sz is not None else None
         shape = (C.c_int32 * 2)()
-        _lib.check(self._lib.bcp_egocentric_shape(self._h, sz.ctypes.data_as(f64p) if sz is not None else None, shape))
+        if pool == 1:
+            _lib.check(self._lib.bcp_egocentric_shape(self._h, sz_p, shape))
+        else:
+            _lib.check(self._lib.bcp_egocentric_pooled_shape(self._h, sz_p, int(pool), shape))
         out = torch.empty((p.shape[0], shape[0], shape[1]), dtype=torch.uint8, device=self.device)
-        _lib.check(self._lib.bcp_egocentric_costmaps(
-            self._h, p.data_ptr(), p.shape[0], org.ctypes.data_as(f64p) if org is not None else None,
-            sz.ctypes.data_as(f64p) if sz is not None else None, int(border_value), out.data_ptr(), self._stream()))
+        if pool == 1:
+            _lib.check(self._lib.bcp_egocentric_costmaps(self._h, p.data_ptr(), p.shape[0], org_p, sz_p, int(border_value),
+                                                         out.data_ptr(), self._stream()))
+        else:
+            _lib.check(self._lib.bcp_egocentric_costmaps_pooled(self._h, p.data_ptr(), p.shape[0], org_p, sz_p,
+                                                                int(border_value), int(pool), out.data_ptr(), self._stream()))
         return out
 
     def robot_step(self, state7, actions, noise_z=None):

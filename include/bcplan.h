@@ -332,8 +332,28 @@ int bcp_egocentric_costmaps(bcp_handle *h, const double *poses, int64_t n, const
  * any map entry (-1: not counted), stride of the cell lists, the limit of cells the route decision compared it with. */
 enum { BCP_EGO_NONE = 0, BCP_EGO_SPARSE = 1 /* ego_sparse_kernel */, BCP_EGO_STAGED = 2 /* ego_costmap_kernel, shared map in LDS */,
        BCP_EGO_BINNED = 3 /* ego_costmap_binned_kernel */, BCP_EGO_WINDOW = 4 /* ego_costmap_window_kernel */,
-       BCP_EGO_GLOBAL = 5 /* ego_costmap_kernel sampling global memory */ };
+       BCP_EGO_GLOBAL = 5 /* ego_costmap_kernel sampling global memory */,
+       BCP_EGO_POOLED_SPARSE = 6 /* ego_pooled_sparse_kernel */, BCP_EGO_POOLED_SAMPLED = 7 /* ego_pooled_sampled_kernel */ };
 int bcp_egocentric_route(bcp_handle *h, int32_t *info4 /*host*/);
+/* The pooled egocentric observation (no reference counterpart; what a resize wrapper around the env would compute, made
+ * without the full image ever reaching memory).  Let full[i] be the image bcp_egocentric_costmaps writes for the same
+ * arguments, H x W = bcp_egocentric_shape.  Then
+ *   out[i][R][C] = max{ full[i][y][x] : R pool <= y < min((R + 1) pool, H),  C pool <= x < min((C + 1) pool, W) },
+ * out: uint8 [n, ceil(H / pool), ceil(W / pool)] = bcp_egocentric_pooled_shape.  Edge blocks are partial: nothing outside the
+ * image takes part.  Everything else is as for the full-resolution call: poses == NULL means the bound state's poses (the
+ * delayed ones under pose_delay), window origin and size go together, a NULL window means the costmap's shape, windows
+ * narrower than 4 px are refused; bcp_final_egocentric_costmaps_pooled draws the record's slots j < min(*count, capacity)
+ * and leaves the rest untouched.  The call is asynchronous and allocates nothing after first use; the first sparse call
+ * after a (re)bind does the counting pass and its read-back.  Cell lists and counts belong to the handle and are shared
+ * with bcp_egocentric_costmaps: whichever call runs first builds them, and a pool refresh keeps them valid for both.
+ * pool must be in [1, 64] (BCP_E_INVALID otherwise); pool == 1 forwards to the full-resolution routine, identical bytes.
+ * Under a maximum 255 (NO_INFORMATION) outranks 254 (LETHAL): a block that holds both reads 255.  (The env families of this
+ * library hold only 0 and 254.)  bcp_egocentric_route reports BCP_EGO_POOLED_SPARSE / BCP_EGO_POOLED_SAMPLED for pool > 1. */
+int bcp_egocentric_pooled_shape(bcp_handle *h, const double *window_size /*host, or NULL*/, int32_t pool,
+                                int32_t *shape_hw /*host [2]*/);
+int bcp_egocentric_costmaps_pooled(bcp_handle *h, const double *poses, int64_t n, const double *window_origin /*host*/,
+                                   const double *window_size /*host*/, uint8_t border_value, int32_t pool,
+                                   uint8_t *out /*[n][ceil(H/pool)][ceil(W/pool)]*/, void *stream);
 /* EgocentricCostmap.observation's `goal_n_state` (envs/egocentric.py:140-160) for all envs: the next way point in
  * the robot frame (from_global_to_egocentric, coordinate_transformations.py:341-362) with its position divided by
  * world_size (host double[2] = CostMap2D.world_size() of the egocentric map) and clipped to [-1, 1], followed by
@@ -531,6 +551,9 @@ int bcp_episode_record_overflows(bcp_handle *h, int64_t *steps /*host*/, void *s
  * bcp_egocentric_costmaps / bcp_goal_n_state / bcp_goal_direction_state with [capacity] rows. */
 int bcp_final_egocentric_costmaps(bcp_handle *h, const double *window_origin /*host*/, const double *window_size /*host*/,
                                   int32_t border_value, uint8_t *out /*[capacity][H][W]*/, void *stream);
+/* the pooled images of those slots (bcp_egocentric_costmaps_pooled) */
+int bcp_final_egocentric_costmaps_pooled(bcp_handle *h, const double *window_origin /*host*/, const double *window_size /*host*/,
+                                         int32_t border_value, int32_t pool, uint8_t *out /*[capacity][..][..]*/, void *stream);
 int bcp_final_goal_n_state(bcp_handle *h, const double *world_size /*host*/, float *out, void *stream);
 int bcp_final_goal_direction_state(bcp_handle *h, const double *world_size /*host*/, double *out, void *stream);
 
