@@ -36,6 +36,7 @@ class Serializable(object):
         return state
 
 
+INSCRIBED_INFLATED_OBSTACLE = 253  # utilities/costmap_inflation.py:15
 CONTINUOUS_REWARD = 'continuous_reward'
 CONTINUOUS_REWARD_STATE = 'continuous_reward_state'
 CONTINUOUS_REWARD_PURE_PURSUIT_STATE = 'continuous_reward_pure_pursuit_state'

@@ -652,6 +652,66 @@ class BatchedPlanEnv(object):
             valid_cols.data_ptr() if valid_cols is not None else None, origins.data_ptr(), 1, float(resolution),
             self._stream()))
 
+    @property
+    def costmap_tensor(self):
+        """The device costmap(s) the library reads: uint8 [rows, cols] (shared) or [entries, rows, cols] (private maps,
+        pool entries), padded to one shape where the entries differ."""
+        return self._keep["map"]
+
+    def footprint(self):
+        """The footprint [n_verts, 2] in metres the handle was created with (footprint_scale applied)."""
+        p = self._bcp_params
+        return np.array([[p.verts[k][0], p.verts[k][1]] for k in range(p.n_verts)], dtype=np.float64)
+
+    def _inflate(self, maps, vr, vc, radius, cost_scaling_factor, out):
+        _lib.check(self._lib.bcp_inflate_costmaps(
+            self._h, maps.data_ptr(), maps.shape[0], maps.shape[1], maps.shape[2],
+            vr.data_ptr() if vr is not None else None, vc.data_ptr() if vc is not None else None, float(self.resolution),
+            float(radius), float(cost_scaling_factor), out.data_ptr(), None, self._stream()))
+
+    def inflate_costmaps(self, cost_scaling_factor, footprint=None):
+        """inflate_costmap (utilities/costmap_inflation.py:73-92) applied, in place and on the device, to every costmap
+        this env has bound -- the shared map, the private maps, or the entries of a geometry pool within their valid
+        shapes -- followed by a re-bind with the arguments of the original one, so that everything derived from the maps
+        (the egocentric cell lists among it) is rebuilt.  Exactly the lethal cells stay 254, so the env steps bit for bit
+        as before; the egocentric observations and every per-env Observation.costmap show the inflated costs.
+        `footprint` [k, 2] gives the inscribed radius (robots.inscribed_radius); None = the env's own footprint.
+        A pool that lives on the device (sampler="device_resident") is inflated where it is: whoever else holds that pool
+        sees the inflated entries.  Refused on endless=True pools (refresh() would write raw worlds into the inflated
+        pool; inflating re-sampled worlds is not implemented), and when called a second time."""
+        if getattr(self, "endless", False):
+            raise RuntimeError("inflate_costmaps: not supported on endless=True pools -- refresh() re-samples raw worlds "
+                               "into the pool, and inflating re-sampled worlds is out of scope")
+        if getattr(self, "_inflated", False):
+            raise RuntimeError("inflate_costmaps: the costmaps of this env are inflated already")
+        radius = robots.inscribed_radius(self.footprint() if footprint is None else footprint)
+        data = self._keep["map"]
+        maps = data[None] if data.dim() == 2 else data
+        vr, vc = (None, None) if self._shared_map else (self._keep.get("vr"), self._keep.get("vc"))
+        self._inflate(maps, vr, vc, radius, cost_scaling_factor, maps)
+        if self._shared_map:
+            _lib.check(self._lib.bcp_set_costmaps(self._h, data.data_ptr(), data.shape[0], data.shape[1], 1, None, None,
+                                                  self._origin_host.ctypes.data, 0, float(self.resolution), self._stream()))
+        else:
+            self.set_costmap_tensors(data, self._keep["origins"], self.resolution, vr, vc)
+        # the host copies behind envs[i].get_state().costmap (a device pool hands out copies of its tensors on demand)
+        if getattr(self, "_device_pool", None) is None:
+            host = list(self._costmaps)
+            rows, cols = max(c.get_data().shape[0] for c in host), max(c.get_data().shape[1] for c in host)
+            stack = np.zeros((len(host), rows, cols), dtype=np.uint8)
+            for k, c in enumerate(host):
+                d = c.get_data()
+                stack[k, :d.shape[0], :d.shape[1]] = d
+            shapes = np.array([c.get_data().shape for c in host], dtype=np.int32)
+            dev_stack = torch.from_numpy(stack).to(self.device)
+            self._inflate(dev_stack, torch.from_numpy(shapes[:, 0].copy()).to(self.device),
+                          torch.from_numpy(shapes[:, 1].copy()).to(self.device), radius, cost_scaling_factor, dev_stack)
+            inflated = dev_stack.cpu().numpy()
+            self._costmaps = [CostMap2D(inflated[k, :s[0], :s[1]].copy(), c.get_resolution(), c.get_origin())
+                              for k, (c, s) in enumerate(zip(host, shapes))]
+        torch.cuda.current_stream(self.device).synchronize()
+        self._inflated = True
+
     def _set_paths(self, path):
         refine = (lambda p: host_init.refine_path(p, self.params.path_delta)) if self.params.refine_path else (lambda p: p)
         if isinstance(path, np.ndarray) and path.ndim == 2:

@@ -120,6 +120,9 @@ struct bcp_handle {
     DevBuf<uint8_t> edt_stale;      // [entries] 1 = the entry's uint8 field does not describe its map (tiles do)
     DevBuf<int32_t> edt_stale_list; // [entries] + [1] count, scratch of ensure_fields
     bool edt_lazy = false;          // a refresh has left stale fields behind since the last full build
+    // bcp_inflate_costmaps: the 16-bit plane of maps beyond LDS, a slice per workgroup; grown on demand, never shrunk
+    DevBuf<uint16_t> inflate_scratch;
+    int32_t inflate_route = 0;      // BCP_TUNE_INFLATE_ROUTE: 0 by size, 2 always the global plane
     // episode record (bcp_bind_episode_record): the caller's arrays, and the library's two words of the step's count
     bool have_rec = false;
     EpisodeRec rec = {};

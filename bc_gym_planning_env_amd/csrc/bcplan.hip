@@ -3,12 +3,13 @@
 // One translation unit.  The device code is in bcp_device.h, bcp_raster.h, bcp_coop.h and bcp_step.h (the step: robot model
 // -> collision classification / exact rasteriser -> rollback -> reward provider -> done -> optional reset -> state
 // write-back), bcp_lookahead.h and bcp_mppi.h (the planners), bcp_ego.h (egocentric views), bcp_sample.h and bcp_aisle.h
-// (world samplers).  The host side is split by subsystem:
+// (world samplers), bcp_inflate.h (costmap inflation).  The host side is split by subsystem:
 //   bcp_host.h         errors, the handle (its device buffers are DevBuf, bcp_devbuf.h), the launch helpers
 //   bcp_field.h        distance field and tiles: kernels, and the launchers of everything derived from maps and paths
 //   bcp_step_host.h    step forms, the step's parameter block and launcher, bcp_step / bcp_rollout / bcp_lookahead / bcp_mppi
 //   bcp_ego_host.h     egocentric costmaps, goal-state vectors, the episode record and its final observations
 //   bcp_worlds_host.h  mini-world and aisle-world entry points
+//   bcp_inflate_host.h bcp_inflate_costmaps (kernel: bcp_inflate.h)
 // This file holds the footprint geometry, create / destroy / seed / pool / tuning, bcp_set_costmaps, bcp_set_paths, bind /
 // reset / broadcast, and the operator seams with their small kernels.
 // Compiled with -ffp-contract=off (numpy rounds every product and sum separately).  No CPU path exists here.
@@ -35,6 +36,7 @@
 #include "bcp_ego.h"
 #include "bcp_sample.h"
 #include "bcp_aisle.h"
+#include "bcp_inflate.h"
 
 using namespace bcp;
 
@@ -228,6 +230,7 @@ static int check_kernel_size(const bcp_params& p, double res)
 #include "bcp_step_host.h"
 #include "bcp_ego_host.h"
 #include "bcp_worlds_host.h"
+#include "bcp_inflate_host.h"
 
 // ------------------------------------------------------------------------------------------------ kernels (one-time, operator seams)
 __global__ void reset_kernel(DevState st, DevState init, const uint8_t* __restrict__ mask, int64_t n, int tri,
@@ -722,6 +725,10 @@ extern "C" int bcp_set_tuning(bcp_handle* h, int32_t key, int32_t value)
             if (value != 0 && value != 1 && value != 2 && value != 4)
                 return fail(BCP_E_INVALID, "bcp_set_tuning: BCP_TUNE_LOCAL_PAIRS takes 0 (default), 1, 2 or 4");
             h->local_pairs = value;
+            return BCP_OK;
+        case BCP_TUNE_INFLATE_ROUTE:
+            if (value != 0 && value != 2) return fail(BCP_E_INVALID, "bcp_set_tuning: BCP_TUNE_INFLATE_ROUTE takes 0 or 2");
+            h->inflate_route = value;
             return BCP_OK;
         case BCP_TUNE_CULL:
             h->cull_enabled = value ? 1 : 0;

@@ -9,6 +9,7 @@ try/except ImportError), batched over many inputs.
   robot_step            IRobot.step: tricycle_model.py:478-538 / differential_drive.py:236-265
   is_robot_colliding    utilities/costmap_utils.py:106-164; is_footprint_colliding (is_footprint_colliding_impl, :106-136)
   reward / find_last_reached / path_velocity   envs/base/reward.py:184-259, utilities/path_tools.py:432-448, :298-323
+  inflate_costmap       utilities/costmap_inflation.py:73-92 (cv2.distanceTransform + _pixel_distance_to_cost)
 """
 import ctypes as C
 
@@ -196,6 +197,37 @@ class NativeOps(object):
             _lib.check(self._lib.bcp_egocentric_costmaps_pooled(self._h, p.data_ptr(), p.shape[0], org_p, sz_p,
                                                                 int(border_value), int(pool), out.data_ptr(), self._stream()))
         return out
+
+    def footprint(self):
+        """The handle's own footprint [n_verts, 2] in metres."""
+        return np.array([[self._p.verts[k][0], self._p.verts[k][1]] for k in range(self._p.n_verts)], dtype=np.float64)
+
+    def inflate_costmap(self, data, resolution, cost_scaling_factor, footprint=None, inscribed_radius=None,
+                        valid_rows=None, valid_cols=None, return_distance=False):
+        """inflate_costmap(costmap, cost_scaling_factor, footprint).get_data() (costmap_inflation.py:73-92) for one map
+        [rows, cols] or a batch [n, rows, cols], numpy or torch -> uint8 device tensor of the same shape
+        (bcp_inflate_costmaps).  The robot enters through `inscribed_radius`, or through `footprint` [k, 2]
+        (robots.inscribed_radius of it); neither = the handle's own footprint.  valid_rows / valid_cols int32 [n]: the
+        true shape of every entry of a padded batch; the padding is ignored and comes out 0.  return_distance: also the
+        float32 distance in cells to the nearest lethal cell (+inf on a map without one)."""
+        d = self._dev(data, torch.uint8)
+        maps = d[None] if d.dim() == 2 else d
+        assert maps.dim() == 3
+        if inscribed_radius is None:
+            inscribed_radius = robots.inscribed_radius(self.footprint() if footprint is None else footprint)
+        assert (valid_rows is None) == (valid_cols is None)
+        vr = self._dev(valid_rows, torch.int32) if valid_rows is not None else None
+        vc = self._dev(valid_cols, torch.int32) if valid_cols is not None else None
+        assert vr is None or (vr.shape == (maps.shape[0],) and vc.shape == (maps.shape[0],))
+        out = torch.empty_like(maps)
+        dist = torch.empty(maps.shape, dtype=torch.float32, device=self.device) if return_distance else None
+        _lib.check(self._lib.bcp_inflate_costmaps(
+            self._h, maps.data_ptr(), maps.shape[0], maps.shape[1], maps.shape[2],
+            vr.data_ptr() if vr is not None else None, vc.data_ptr() if vc is not None else None, float(resolution),
+            float(inscribed_radius), float(cost_scaling_factor), out.data_ptr(),
+            dist.data_ptr() if dist is not None else None, self._stream()))
+        out = out.reshape(d.shape)
+        return (out, dist.reshape(d.shape)) if return_distance else out
 
     def robot_step(self, state7, actions, noise_z=None):
         """state7 [n,7] rows {x,y,angle,v,w,steering_motor_command,wheel_angle}, actions [n,2] -> (new [n,7], err)."""

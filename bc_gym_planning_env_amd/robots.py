@@ -42,6 +42,16 @@ def get_footprint(robot_name, footprint_scale=1.0):
     return FOOTPRINTS[robot_name] * footprint_scale
 
 
+def inscribed_radius(footprint):
+    """inscribed_radius (utilities/path_tools.py:519-528 with distance_to_segments, :451-470): the smallest distance from
+    the origin to any side of the footprint [n, 2] (consecutive vertices, closed), as a float64."""
+    origins = np.asarray(footprint, dtype=np.float64)
+    v = np.roll(origins, -1, axis=0) - origins
+    mu = np.sum((0. - origins) * v, axis=1) / (np.sum(v * v, axis=1) + 1e-12)
+    closest = origins + np.clip(mu, 0., 1.)[:, None] * v
+    return float(np.min(np.hypot(0. - closest[:, 0], 0. - closest[:, 1])))
+
+
 ROBOT_CONSTANTS = dict(front_wheel_from_axis=FRONT_WHEEL_FROM_AXIS, max_front_wheel_angle=MAX_FRONT_WHEEL_ANGLE,
                        max_front_wheel_speed=MAX_FRONT_WHEEL_SPEED, max_linear_acceleration=MAX_LINEAR_ACCELERATION,
                        max_angular_acceleration=MAX_ANGULAR_ACCELERATION, front_column_p_gain=FRONT_COLUMN_P_GAIN)

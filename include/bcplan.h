@@ -196,10 +196,13 @@ int bcp_seed(bcp_handle *h, uint64_t seed);
  *                             bit is the OR of the 2 x 2 / 4 x 4 / 8 x 8 cells it stands for: fewer lines of memory per pose, a few more
  *                             poses left to the exact test); -1 (default) = the library's choice.  In force from the next
  *                             bcp_set_costmaps on; results are the same bit for bit.  (Environment variable BCP_NEAR_SHIFT,
- *                             read by bcp_create: the knob's initial value.) */
+ *                             read by bcp_create: the knob's initial value.)
+ *   BCP_TUNE_INFLATE_ROUTE    where bcp_inflate_costmaps keeps its 16-bit intermediate plane: 0 (default) = in LDS when the
+ *                             map fits, else in the handle's global scratch; 2 = always in global scratch (lets tests
+ *                             compare the two routes on one map; the bytes are the same) */
 enum { BCP_TUNE_EXACT_MODE = 0, BCP_TUNE_DENSE_THRESHOLD = 1, BCP_TUNE_CULL = 2, BCP_TUNE_DEFER = 3, BCP_TUNE_EDT_LDS = 4,
        BCP_TUNE_FUSED = 5, BCP_TUNE_EGO_SPARSE = 6, BCP_TUNE_NEAR_DILATE = 7, BCP_TUNE_LOCAL_PAIRS = 8,
-       BCP_TUNE_EGO_LIST_STRIDE = 9, BCP_TUNE_NEAR_SHIFT = 10 };
+       BCP_TUNE_EGO_LIST_STRIDE = 9, BCP_TUNE_NEAR_SHIFT = 10, BCP_TUNE_INFLATE_ROUTE = 11 };
 int bcp_set_tuning(bcp_handle *h, int32_t key, int32_t value);
 
 /* ---- static per-episode inputs ------------------------------------------------------------------------ */
@@ -658,6 +661,35 @@ typedef struct bcp_mppi_io {
  *   - 5 * I * N * K * H >= 2^62 (the element offsets are 64-bit);
  *   - flag bits other than BCP_STEP_ACTIONS_F32; mean or action NULL. */
 int bcp_mppi(bcp_handle *h, const bcp_mppi_params *p, const bcp_mppi_io *io, uint32_t flags, void *stream);
+
+/* ---- costmap inflation ------------------------------------------------------------------------------------ */
+/* inflate_costmap (utilities/costmap_inflation.py:73-92) for n_maps maps in one call: the ROS inflation layer.  Per map
+ * `data` [rows][cols] with valid shape (vr, vc) = (valid_rows[m], valid_cols[m]) clamped to [0, rows] x [0, cols], or the
+ * full shape when both pointers are NULL:
+ *   - a cell is an obstacle exactly where data == 254 inside the valid shape (:83: 254 - data wraps, and the distance is
+ *     to the nearest zero pixel; 255, 253 and every other value are free space);
+ *   - d = (float32) sqrt(d2), correctly rounded, d2 the exact squared Euclidean distance in cells to the nearest obstacle
+ *     cell, never clamped (:84, cv2.distanceTransform(DIST_L2, DIST_MASK_PRECISE));
+ *   - _pixel_distance_to_cost (:47-70) in float64 on that d, every product and sum rounded on its own:
+ *     pir = inscribed_radius / resolution, psf = cost_scaling_factor * resolution;
+ *     d < pir / 1000.0 -> 254; otherwise d <= pir -> 253; otherwise (uint8) trunc(252.0 * exp(-psf * ((double)d - pir)));
+ *   - a map without an obstacle cell has every d = +inf and every cost 0;
+ *   - cells outside the valid shape are not read; cost 0 (and d 0) is written there.
+ * inscribed_radius is path_tools.py:519-528 of the footprint (the caller computes it).  Exactly the lethal cells come out
+ * as 254, so a handle bound to the inflated maps steps bit for bit like one bound to the raw maps (env.py:464-489).
+ * Independent of what the handle has bound: the handle names the device and owns the scratch (allocated on first use, grown
+ * only when a later call needs more, freed by bcp_destroy).  Asynchronous on `stream`, no host synchronisation.  `out`
+ * may be `data` itself: every read of a map is finished before any of its cells is written.
+ * Refused with BCP_E_INVALID: NULL h; n_maps < 0; NULL data or out with n_maps > 0; rows or cols outside [1, 2048] (which
+ * keeps d2 < 2^24: the float holds it exactly); resolution, inscribed_radius or cost_scaling_factor not finite or not > 0;
+ * only one of valid_rows / valid_cols; out overlapping data without being equal to it.  n_maps == 0 succeeds and does
+ * nothing. */
+int bcp_inflate_costmaps(bcp_handle *h, const uint8_t *data, int64_t n_maps, int32_t rows, int32_t cols,
+                         const int32_t *valid_rows, const int32_t *valid_cols,   /* device [n_maps], both or neither */
+                         double resolution, double inscribed_radius, double cost_scaling_factor,
+                         uint8_t *out,          /* [n_maps][rows][cols]; may be `data` itself (in place) */
+                         float *distance_out,   /* optional [n_maps][rows][cols]: d in cells, +inf / 0 as above */
+                         void *stream);
 
 /* ---- measurement -------------------------------------------------------------------------------------- */
 /* Which kernels a bcp_step() of this handle launches, as configured now: 0 = step_kernel alone (no distance field, or a
