@@ -10,6 +10,7 @@
 #include <cstring>
 
 #include "bcp_coop.h"   // bcast_i / bcast_d
+#include "bcp_ego_route.h"   // kEgoWaves, kEgoHeld, ...: the constants the host's LDS arithmetic shares with the kernels
 
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
 #error "bcp_ego.h is written for gfx950 (MI355X): lds_byte_shifted_16 relies on d16 loads writing the whole register (SRAM-ECC targets), and the sampling kernels on 160 KB of LDS per workgroup"
@@ -264,8 +265,6 @@ __device__ __forceinline__ EgoStage ego_stage_of(int lds_base, int c0, int r0, i
 // that put every pixel of it on the ring's left column (it is only sampled when it shares a bundle of rows with a live
 // one).  A row that is not off the map stays within (window width) cells of it, so the shifted terms fit as long as the
 // map is narrower than 2^15 - 2 dcols cells (LDS-resident maps are).
-constexpr int kEgoBoundInts = 16;   // behind the tables: {first live row, first inside row, inside end, live end} per wave
-
 // ints of one table: row terms, row bounds
 __device__ __forceinline__ int ego_table_ints(const EgoArgs& a) { return 2 * a.drows + kEgoBoundInts; }
 
@@ -516,8 +515,6 @@ __device__ __forceinline__ void ego_pixels(const EgoArgs& a, const EgoImage& I, 
 }
 
 
-constexpr int kEgoWaves = 8;   // wavefronts (= images in flight) per workgroup of ego_costmap_kernel
-
 // One WAVEFRONT per image, persistent workgroups of kEgoWaves waves that stage a shared costmap in LDS once and then
 // walk over images.
 //   * transforms: lane l of a wave prepares the (inverted) warp matrix of the wave's l-th image, so the float64
@@ -762,8 +759,6 @@ __global__ void __launch_bounds__(256) ego_costmap_window_kernel(const EgoArgs a
 // Lists of the non-zero cells are built per map entry (ego_cells_kernel: a counting pass sizes them, round 4); an entry with
 // more than `cap` of them (a pool entry re-sampled after the lists were sized) is drawn pixel by pixel (ego_image_slow), and
 // the host routes whole calls whose maps are dense -- or whose border value is not 0 -- to the sampling kernels above.
-constexpr int kEgoCellCapMin = 512;   // least stride of a list (a RandomMiniEnv world: <= 2 x 183 cells; pool entries change)
-
 // list[entry][k] = value << 24 | row << 12 | column of the k-th non-zero cell inside the entry's valid region (any order);
 // counts[entry] = how many there are (may exceed `cap`: the list then holds the first `cap` found); *max_count = running
 // maximum over the entries built so far.  One workgroup per entry.  cells == nullptr: the counting pass only.
@@ -823,16 +818,6 @@ __device__ __forceinline__ void ego_image_slow(const EgoArgs& a, const EgoImage&
 }
 
 typedef uint32_t EgoU32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kEgoHeld = 768;   // cells a wave can hold back in LDS between the culling pass and the patches
-
-// LDS of ego_sparse_kernel, per wave: cv::hal::warpAffine's column terms {adelta, bdelta}(x) = {sat(M0 x 1024), sat(M3 x 1024)}
-// for every column of the window, its row terms {sat((M1 y + M2) 1024) + 512, sat((M4 y + M5) 1024) + 512} for every row,
-// and the list of cells held back.
-static size_t ego_sparse_lds_bytes(int drows, int dcols, int waves)
-{
-    return (size_t)waves * ((size_t)(drows + dcols) * 8 + (size_t)kEgoHeld * 4);
-}
 
 typedef int EgoI32x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) EgoI32x2* LdsI32x2;
@@ -1016,13 +1001,6 @@ struct EgoPool {
 };
 
 typedef __attribute__((address_space(3))) uint32_t* LdsU32;
-
-// LDS of ego_pooled_sparse_kernel, per wave: the tables and the held list of ego_sparse_kernel, then one 32-bit word per
-// pooled cell (the LDS maximum works on words), an even number of them so that the next wave's tables stay 8-byte aligned
-static size_t ego_pooled_lds_bytes(int drows, int dcols, int prows, int pcols, int waves)
-{
-    return (size_t)waves * ((size_t)(drows + dcols) * 8 + (size_t)kEgoHeld * 4 + (((size_t)prows * pcols + 1) & ~(size_t)1) * 4);
-}
 
 // one pooled image from global memory: lanes stride over pooled cells, a cell evaluates its <= p x p destination pixels with
 // ego_image_slow's expression and keeps the running maximum in a register.  Any map, any border value.

@@ -305,15 +305,6 @@ __global__ void stale_fields_list_kernel(uint8_t* __restrict__ stale, int64_t n,
 
 // Derived map data (1-bit lethal mask, distance field) and path data (cos/sin columns, bounding boxes, bucket index)
 // of the selected entries; `max_entries` bounds sel.size() and only sizes the grids.
-static void launch_ego_cells(bcp_handle* h, EntrySelect sel, int64_t max_entries, hipStream_t s)
-{
-    const MapDesc& m = h->map;
-    hipLaunchKernelGGL(ego_cells_kernel, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(max_entries, 8192))), dim3(256), 0, s,
-                       h->map_data, sel, m.rows, m.cols, h->map_valid_rows, h->map_valid_cols, h->ego_cell_cap, h->ego_cells.get(),
-                       h->ego_cell_counts.get(), h->ego_cell_counts.get() + h->ego_cells_entries);
-    h->ego_cells_max = -1;
-}
-
 static void launch_pack_bitmap(bcp_handle* h, EntrySelect sel, int64_t max_entries, hipStream_t s)
 {
     const MapDesc& m = h->map;
@@ -321,10 +312,8 @@ static void launch_pack_bitmap(bcp_handle* h, EntrySelect sel, int64_t max_entri
                        h->bitmap.get(), h->map_tiles.get(), sel, m.rows, m.cols, m.wpr, h->map_valid_rows, h->map_valid_cols);
     // the cell lists of the sparse egocentric views follow the maps: all of them are rebuilt lazily after a re-bind
     // (sel.list == nullptr), the re-sampled entries of a pool refresh right here, in stream order
-    if (h->ego_cells_built) {
-        if (sel.list && h->ego_cell_counts.get()) launch_ego_cells(h, sel, max_entries, s);
-        else h->ego_cells_built = false;
-    }
+    if (sel.list) h->ego_cells.recount(h, sel, max_entries, s);
+    else h->ego_cells.invalidate();
 }
 
 static void launch_near_tiles(bcp_handle* h, EntrySelect sel, int64_t max_entries, hipStream_t s)

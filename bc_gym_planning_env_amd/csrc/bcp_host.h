@@ -33,6 +33,41 @@ static int fail(int code, const char* fmt, ...)
         if (rc_ != BCP_OK) return rc_;     \
     } while (0)
 
+// ------------------------------------------------------------------------------------------------ cell lists
+struct bcp_handle;
+
+// Sparse egocentric views (ego_sparse_kernel, ego_pooled_sparse_kernel): per map entry the list of its non-zero cells, and
+// the counts a call's route is decided from -- a counting pass over the maps on the first candidate call after the maps were
+// (re)bound, one read-back of the largest count, lists sized from it; a pool refresh keeps counts and lists of the entries it
+// re-samples up to date.  The state is written by the methods alone (defined below the handle).
+class EgoCells {
+    DevBuf<uint32_t> cells;    // [entries][cap] (empty while the maps count as dense)
+    DevBuf<int32_t> counts;    // [entries] + [1] running maximum
+    int64_t entries = 0;
+    int32_t cap = 0;           // stride of a list, sized from the counting pass
+    bool built = false;        // counts (and lists, if any) describe the current maps (rebuilt entry by entry by a pool refresh)
+    bool refusal = false;      // allocation failed once: the sampling kernels serve this handle
+    int32_t max = -1;          // host copy of the maximum count, -1 = not fetched since the last (re)build
+    void launch(bcp_handle* h, EntrySelect sel, int64_t max_entries, hipStream_t s);
+    int fetch_max(hipStream_t s);
+
+public:
+    // the maps were re-bound, or the tuning the lists were sized for changed: the next candidate call counts again
+    void invalidate() { built = false; }
+    // a pool refresh re-sampled the entries of `sel`: their counts and lists again, in stream order
+    void recount(bcp_handle* h, EntrySelect sel, int64_t max_entries, hipStream_t s);
+    // counts and (if the largest is within `limit`) lists of `n_entries` map entries, whatever state they were in
+    int ensure(bcp_handle* h, int64_t n_entries, int32_t limit, hipStream_t s);
+    // lists exist, describe the maps, and no entry has more cells than `limit`
+    bool usable(int32_t limit) const { return cells.get() && built && max >= 0 && max <= limit; }
+    // what a launch and bcp_egocentric_route read
+    const uint32_t* lists() const { return cells.get(); }
+    const int32_t* list_counts() const { return counts.get(); }
+    int32_t stride() const { return cap; }
+    int32_t largest() const { return max; }
+    bool refused() const { return refusal; }
+};
+
 // ------------------------------------------------------------------------------------------------ handle
 // Every device buffer the library owns is a DevBuf: it grows when a re-bind needs more room, and the handle's destructor
 // gives it back.  What the caller owns is a plain pointer.
@@ -77,14 +112,7 @@ struct bcp_handle {
     int32_t wide = 0;               // kernel image may exceed 96 px: 8-word row masks in the cooperative path
     DevBuf<int32_t> ego_bins;       // [2][capacity / 2] image counts / first slots per map entry (egocentric views)
     DevBuf<int32_t> ego_order;      // [2][capacity / 2] rank within the bin / images grouped by map entry
-    // sparse egocentric views (ego_sparse_kernel): per map entry the list of its non-zero cells
-    DevBuf<uint32_t> ego_cells;     // [entries][ego_cell_cap] (empty while the maps count as dense)
-    DevBuf<int32_t> ego_cell_counts;   // [entries] + [1] running maximum
-    int64_t ego_cells_entries = 0;
-    int32_t ego_cell_cap = 0;       // stride of a list, sized from the counting pass
-    bool ego_cells_built = false;   // counts (and lists, if any) describe the current maps (rebuilt entry by entry by a pool refresh)
-    bool ego_cells_refused = false; // allocation failed once: the sampling kernels serve this handle
-    int32_t ego_cells_max = -1;     // host copy of the maximum count, -1 = not fetched since the last (re)build
+    EgoCells ego_cells;             // sparse egocentric views: the lists of non-zero cells
     int32_t ego_sparse = 1;         // BCP_TUNE_EGO_SPARSE: 0 never, 1 cost model, >= 2 explicit limit of cells per map
     int32_t ego_stride = 0;         // BCP_TUNE_EGO_LIST_STRIDE: 0 = lists sized from the counts, else this many cells per entry (tests)
     int32_t ego_route[4] = {};      // what the last bcp_egocentric_costmaps call ran: kernel, largest count, list stride, limit
@@ -133,6 +161,76 @@ struct bcp_handle {
 
 // number of entries of a non-shared map / path / initial-state array
 static int64_t n_slots(const bcp_handle* h) { return h->n_geoms > 0 ? h->n_geoms : h->n; }
+
+// ------------------------------------------------------------------------------------------------ cell lists, continued
+inline void EgoCells::launch(bcp_handle* h, EntrySelect sel, int64_t max_entries, hipStream_t s)
+{
+    const MapDesc& m = h->map;
+    hipLaunchKernelGGL(ego_cells_kernel, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(max_entries, 8192))), dim3(256), 0, s,
+                       h->map_data, sel, m.rows, m.cols, h->map_valid_rows, h->map_valid_cols, cap, cells.get(), counts.get(),
+                       counts.get() + entries);
+    max = -1;
+}
+
+inline int EgoCells::fetch_max(hipStream_t s)
+{
+    HIP_TRY(hipMemcpyAsync(&max, counts.get() + entries, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return BCP_OK;
+}
+
+inline void EgoCells::recount(bcp_handle* h, EntrySelect sel, int64_t max_entries, hipStream_t s)
+{
+    if (!built) return;   // (nothing to keep up to date: the next candidate call counts everything)
+    if (counts.get()) launch(h, sel, max_entries, s);
+    else invalidate();
+}
+
+inline int EgoCells::ensure(bcp_handle* h, int64_t n_entries, int32_t limit, hipStream_t s)
+{
+    if (h->refresh_recorded && (!built || max < 0))
+        HIP_TRY(hipStreamWaitEvent(s, h->refresh_done, 0));   // (a refresh on another stream may still be writing the maps / counts)
+    if (entries != n_entries || !counts.get()) {
+        (void)cells.reset();
+        entries = 0;
+        cap = 0;
+        built = false;
+        if (counts.reserve((size_t)n_entries + 1) != hipSuccess) {
+            (void)hipGetLastError();
+            refusal = true;   // (no room: not an error, the sampling kernels take over)
+        } else {
+            entries = n_entries;
+        }
+    }
+    if (counts.get() && !built) {
+        // counting pass -> largest count -> stride of the lists -> lists
+        const EntrySelect all = {nullptr, nullptr, entries};
+        (void)cells.reset();   // (the counting pass is the one without lists; they are sized from its result)
+        cap = 0;
+        HIP_TRY(hipMemsetAsync(counts.get() + entries, 0, sizeof(int32_t), s));
+        launch(h, all, entries, s);
+        BCP_TRY(fetch_max(s));
+        built = true;
+        if (max <= limit) {
+            // pool entries change under a refresh: leave room for a world with more cells than today's largest
+            int64_t stride = std::max<int64_t>(kEgoCellCapMin, ((int64_t)max + 63) & ~(int64_t)63);
+            const int64_t budget = (int64_t)1 << 30;   // bytes of lists per handle
+            if (entries * stride * 4 > budget) stride = ((int64_t)max + 63) & ~(int64_t)63;
+            if (h->ego_stride > 0) stride = h->ego_stride;   // (tests: entries with more cells than this are drawn pixel by pixel)
+            if (stride > 0 && entries * stride * 4 <= budget && cells.reserve((size_t)entries * stride) == hipSuccess) {
+                cap = (int32_t)stride;
+                const int32_t counted = max;
+                launch(h, all, entries, s);   // (the same counts again, and the lists)
+                max = counted;
+            } else {
+                (void)hipGetLastError();
+                if (stride > 0) refusal = true;
+            }
+        }
+    }
+    if (counts.get() && built && max < 0) BCP_TRY(fetch_max(s));   // (a refresh re-counted some entries)
+    return BCP_OK;
+}
 
 // grid of a grid-stride kernel; a selection's size is only known on the device, so those launches get a chip-filling
 // grid that does not grow with the upper bound

@@ -4,10 +4,11 @@
 // -> collision classification / exact rasteriser -> rollback -> reward provider -> done -> optional reset -> state
 // write-back), bcp_lookahead.h and bcp_mppi.h (the planners), bcp_ego.h (egocentric views), bcp_sample.h and bcp_aisle.h
 // (world samplers), bcp_inflate.h (costmap inflation).  The host side is split by subsystem:
-//   bcp_host.h         errors, the handle (its device buffers are DevBuf, bcp_devbuf.h), the launch helpers
+//   bcp_host.h         errors, the handle (its device buffers are DevBuf, bcp_devbuf.h), EgoCells, the launch helpers
 //   bcp_field.h        distance field and tiles: kernels, and the launchers of everything derived from maps and paths
 //   bcp_step_host.h    step forms, the step's parameter block and launcher, bcp_step / bcp_rollout / bcp_lookahead / bcp_mppi
-//   bcp_ego_host.h     egocentric costmaps, goal-state vectors, the episode record and its final observations
+//   bcp_ego_host.h     egocentric costmaps (routed by bcp_ego_route.h, which has no HIP in it), goal-state vectors, the
+//                      episode record and its final observations
 //   bcp_worlds_host.h  mini-world and aisle-world entry points
 //   bcp_inflate_host.h bcp_inflate_costmaps (kernel: bcp_inflate.h)
 // This file holds the footprint geometry, create / destroy / seed / pool / tuning, bcp_set_costmaps, bcp_set_paths, bind /
@@ -706,12 +707,12 @@ extern "C" int bcp_set_tuning(bcp_handle* h, int32_t key, int32_t value)
             return BCP_OK;
         case BCP_TUNE_EGO_SPARSE:
             if (value < 0) return fail(BCP_E_INVALID, "bcp_set_tuning: BCP_TUNE_EGO_SPARSE takes 0, 1 or a limit of cells per map");
-            if (value != h->ego_sparse) h->ego_cells_built = false;   // (the lists are sized for the limit in force)
+            if (value != h->ego_sparse) h->ego_cells.invalidate();   // (the lists are sized for the limit in force)
             h->ego_sparse = value;
             return BCP_OK;
         case BCP_TUNE_EGO_LIST_STRIDE:
             if (value < 0 || (value & 63)) return fail(BCP_E_INVALID, "bcp_set_tuning: BCP_TUNE_EGO_LIST_STRIDE takes 0 or a multiple of 64");
-            if (value != h->ego_stride) h->ego_cells_built = false;
+            if (value != h->ego_stride) h->ego_cells.invalidate();
             h->ego_stride = value;
             return BCP_OK;
         case BCP_TUNE_FUSED:

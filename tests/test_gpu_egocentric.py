@@ -79,7 +79,8 @@ def test_g10_observation_from_reference_states(torch_cuda, name):
                          ids=["shared-map", "private-maps", "large-shared-map", "medium-shared-map"])
 def test_random_poses_vs_oracle(torch_cuda, oracle, shared):
     """random poses (inside and far outside the map), several windows and border values, a costmap with arbitrary
-    byte values; private maps of different shapes go through the global-memory gather"""
+    byte values; private maps of different shapes go through the global-memory gather.  Every call also names the kernel the
+    router must have chosen for its map and window (bcp_egocentric_route)."""
     torch = torch_cuda
     from bc_gym_planning_env_amd import BatchedPlanEnv, CostMap2D, EnvParams
     rng = np.random.RandomState(8)
@@ -107,15 +108,22 @@ def test_random_poses_vs_oracle(torch_cuda, oracle, shared):
     import ctypes as C
     from bc_gym_planning_env_amd import _lib
     f64p = C.POINTER(C.c_double)
-    for org, size, border in (((-0.5, -2.0), (3.5, 4.0), 0), ((-1.0, -1.0), (2.0, 2.0), 255), (None, None, 7),
-                              ((-3.0, -0.7), (6.05, 1.45), 100),
-                              ((-0.1, -0.15), (0.3, 0.25), 9)):   # (6 x 5 px: the 4-pixels-per-lane kernels)
+    windows = [((-0.5, -2.0), (3.5, 4.0), 0), ((-1.0, -1.0), (2.0, 2.0), 255), (None, None, 7),
+               ((-3.0, -0.7), (6.05, 1.45), 100),
+               ((-0.1, -0.15), (0.3, 0.25), 9)]   # (6 x 5 px: the 4-pixels-per-lane kernels)
+    if large and not medium:
+        # 250 rows x 6 columns: the part of the map the window sees (a square of 256 cells) is beyond the window kernel's LDS,
+        # so the global-memory kernel draws it, four pixels per lane
+        windows.append(((-0.15, -6.0), (0.3, 12.5), 31))
+    for org, size, border in windows:
         o = None if org is None else np.array(org, dtype=np.float64)
         s = None if size is None else np.array(size, dtype=np.float64)
         shape = (C.c_int32 * 2)()
         _lib.check(env._lib.bcp_egocentric_shape(env._h, s.ctypes.data_as(f64p) if s is not None else None, shape))
         if size is None and not shared:
             assert tuple(shape) == (300, 260)        # allocation shape of the padded private maps
+        if size == (0.3, 12.5):
+            assert tuple(shape) == (250, 6)
         out = torch.full((n, shape[0], shape[1]), 99, dtype=torch.uint8, device="cuda")
         guard = torch.full((16,), 123, dtype=torch.uint8, device="cuda")  # (allocated right after `out`, not adjacent)
         _lib.check(env._lib.bcp_egocentric_costmaps(env._h, pt.data_ptr(), n, o.ctypes.data_as(f64p) if o is not None else None,
@@ -123,6 +131,11 @@ def test_random_poses_vs_oracle(torch_cuda, oracle, shared):
                                                     out.data_ptr(), None))
         got = out.cpu().numpy()
         assert (guard.cpu().numpy() == 123).all()
+        # the maps are dense (random bytes): the zero-border call counts their cells and finds them over the sparse limit
+        want_kernel = ("ego_costmap_binned_kernel" if not shared else
+                       "ego_costmap_kernel<staged>" if medium or not large else
+                       "ego_costmap_kernel<global>" if size is None or size == (0.3, 12.5) else "ego_costmap_window_kernel")
+        assert _route(env)[0] == want_kernel, (org, size, _route(env))
         for i in range(n):
             k = 0 if shared else i % 3
             if size is None and not shared:
