@@ -9,7 +9,7 @@ from .api import (Action, Box, ContinuousRewardProviderState, CostMap2D, Diffdri
 __all__ = ["Action", "Box", "ContinuousRewardProviderState", "CostMap2D", "DiffdriveRobotState", "EnvParams",
            "INDUSTRIAL_DIFFDRIVE_V1", "INDUSTRIAL_TRICYCLE_V1", "Observation", "RewardParams", "State",
            "TricycleRobotState", "BatchedPlanEnv", "BatchedRandomAisleTurnEnv", "NativeOps", "Lookahead", "ShootingPlanner",
-           "constant_command_library", "Mppi", "MPPIPlanner"]
+           "constant_command_library", "Mppi", "MPPIPlanner", "BatchedRangeScan"]
 
 
 def __getattr__(name):
@@ -23,6 +23,9 @@ def __getattr__(name):
     if name in ("ShootingPlanner", "constant_command_library", "MPPIPlanner"):
         from . import planning
         return getattr(planning, name)
+    if name == "BatchedRangeScan":
+        from .range_scan import BatchedRangeScan
+        return BatchedRangeScan
     if name == "NativeOps":
         from .ops import NativeOps
         return NativeOps

@@ -183,6 +183,10 @@ SYMBOLS = {
     "bcp_final_goal_direction_state": (C.c_int, [_H, _f64p, C.c_void_p, C.c_void_p]),
     "bcp_inflate_costmaps": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_double,
                                        C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bcp_range_scan": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p]),
+    "bcp_final_range_scan": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]),
 }
 
 _lib = None

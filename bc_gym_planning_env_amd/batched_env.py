@@ -6,6 +6,7 @@ Observation / State objects for one env.  Device tensors are torch tensors only 
 raw pointers (tensor.data_ptr()); all arithmetic happens in libbcplan.so.
 """
 import ctypes as C
+from collections import OrderedDict
 
 import attr
 
@@ -413,6 +414,24 @@ class Mppi(object):
         self.mean, self.action = mean, action
         for name in self.FIELDS:
             setattr(self, name, tensors.get(name))
+
+
+SCAN_CACHE_ENTRIES = 8   # beam tables / output buffer sets of range_scan kept per env (least recently used go first)
+
+
+def beam_table_cached(tables, beam_angles, device):
+    """The device table [B, 2] of (cos, sin) of beam_angles for bcp_range_scan, from `tables` (an OrderedDict keyed by the
+    angles' bytes, least recently used first) or uploaded and added to it; at most SCAN_CACHE_ENTRIES tables are kept."""
+    angles = np.ascontiguousarray(beam_angles.detach().cpu().numpy() if isinstance(beam_angles, torch.Tensor) else beam_angles,
+                                  dtype=np.float64).reshape(-1)
+    key = angles.tobytes()
+    if key in tables:
+        tables.move_to_end(key)
+    else:
+        tables[key] = torch.from_numpy(np.stack([np.cos(angles), np.sin(angles)], axis=1)).to(device).contiguous()
+        while len(tables) > SCAN_CACHE_ENTRIES:
+            tables.popitem(last=False)
+    return tables[key]
 
 
 class BatchedPlanEnv(object):
@@ -1131,6 +1150,45 @@ class BatchedPlanEnv(object):
         _lib.check(self._lib.bcp_mppi(self._h, C.byref(p), C.byref(io), flags, self._stream()))
         self._last_mppi_inputs = tuple(keep)   # alive until the stream has consumed them
         return Mppi(h, k, it, mean, **out)
+
+    def _beam_table(self, beam_angles):
+        """The device table [B, 2] of (cos, sin) of the beam angles (beam_table_cached)."""
+        return beam_table_cached(self.__dict__.setdefault("_beam_tables", OrderedDict()), beam_angles, self.device)
+
+    def range_scan(self, beam_angles, max_range, poses=None, want=()):
+        """A planar range scan per env (bcp_range_scan, one kernel launch, nothing of the env changes): the distance in
+        metres from the robot to the nearest lethal cell along each beam, beam_angles [B] being the beams' angles from the
+        robot's heading, counter-clockwise; max_range where nothing lethal lies within max_range.  Only cells that are 254
+        inside a map's valid shape stop a ray -- the set pose_collides tests -- so inflated maps scan like raw ones.
+        poses: None = every env's current pose (the delayed one under pose_delay), or [n, 3] (row i on the map of env
+        i % n_envs).  want: optional outputs from "hit" (int32 [n, B]: row * cols + col of the cell that stopped the ray,
+        -1 for none) and "heading_cs" (float64 [n, 2]: the cos / sin of the heading the walk used).  Returns ranges float32
+        [n, B], or (ranges, *wanted in the order given), device tensors, no sync.  The (cos, sin) table of an angle set is
+        uploaded once; the outputs are cached per (n, B), so a caller that scans every tick allocates nothing (both caches keep
+        the SCAN_CACHE_ENTRIES most recently used entries)."""
+        table = self._beam_table(beam_angles)
+        b = int(table.shape[0])
+        unknown = set(want) - {"hit", "heading_cs"}
+        if unknown:
+            raise ValueError("range_scan: unknown outputs %s" % sorted(unknown))
+        keep = [table]
+        if poses is not None:
+            poses = self._device_tensor(poses, torch.float64)
+            assert poses.dim() == 2 and poses.shape[1] == 3
+            keep.append(poses)
+        n = self.n_envs if poses is None else int(poses.shape[0])
+        shapes = {"ranges": ((n, b), torch.float32), "hit": ((n, b), torch.int32), "heading_cs": ((n, 2), torch.float64)}
+        buffers = self.__dict__.setdefault("_range_scan_buffers", OrderedDict())
+        out = self._cached_outputs("_range_scan_buffers", (n, b), shapes, ["ranges"] + [w for w in want])
+        buffers.move_to_end((n, b))
+        while len(buffers) > SCAN_CACHE_ENTRIES:   # (a caller that sweeps shapes does not pile up device memory)
+            buffers.popitem(last=False)
+        _lib.check(self._lib.bcp_range_scan(
+            self._h, poses.data_ptr() if poses is not None else None, n, table.data_ptr(), b, float(max_range),
+            out["ranges"].data_ptr(), out["hit"].data_ptr() if "hit" in out else None,
+            out["heading_cs"].data_ptr() if "heading_cs" in out else None, self._stream()))
+        self._last_scan_inputs = tuple(keep)   # alive until the stream has consumed them
+        return out["ranges"] if not want else (out["ranges"],) + tuple(out[w] for w in want)
 
     def enable_episode_record(self, capacity=None):
         """Keep what every episode end leaves behind (bcp_bind_episode_record): from now on step() returns

@@ -1,9 +1,10 @@
 // bcplan.hip -- libbcplan.so: batched PlanEnv.step() for MI355X (gfx950).  C ABI in include/bcplan.h.
 //
-// One translation unit.  The device code is in bcp_device.h, bcp_raster.h, bcp_coop.h and bcp_step.h (the step: robot model
-// -> collision classification / exact rasteriser -> rollback -> reward provider -> done -> optional reset -> state
-// write-back), bcp_lookahead.h and bcp_mppi.h (the planners), bcp_ego.h (egocentric views), bcp_sample.h and bcp_aisle.h
-// (world samplers), bcp_inflate.h (costmap inflation).  The host side is split by subsystem:
+// One translation unit.  The device code is in bcp_device.h, bcp_raster.h, bcp_coop.h and bcp_step.h (the step: robot model ->
+// collision classification / exact rasteriser -> rollback -> reward provider -> done -> optional reset -> state write-back),
+// bcp_lookahead.h and bcp_mppi.h (the planners), bcp_ego.h (egocentric views), bcp_sample.h and bcp_aisle.h (world samplers),
+// bcp_inflate.h (costmap inflation), bcp_scan.h (range scans; the walk: bcp_scan_march.h, no HIP in it).  The host side is
+// split by subsystem:
 //   bcp_host.h         errors, the handle (its device buffers are DevBuf, bcp_devbuf.h), EgoCells, the launch helpers
 //   bcp_field.h        distance field and tiles: kernels, and the launchers of everything derived from maps and paths
 //   bcp_step_host.h    step forms, the step's parameter block and launcher, bcp_step / bcp_rollout / bcp_lookahead / bcp_mppi
@@ -11,6 +12,7 @@
 //                      episode record and its final observations
 //   bcp_worlds_host.h  mini-world and aisle-world entry points
 //   bcp_inflate_host.h bcp_inflate_costmaps (kernel: bcp_inflate.h)
+//   bcp_scan_host.h    bcp_range_scan / bcp_final_range_scan (kernel: bcp_scan.h)
 // This file holds the footprint geometry, create / destroy / seed / pool / tuning, bcp_set_costmaps, bcp_set_paths, bind /
 // reset / broadcast, and the operator seams with their small kernels.
 // Compiled with -ffp-contract=off (numpy rounds every product and sum separately).  No CPU path exists here.
@@ -38,6 +40,7 @@
 #include "bcp_sample.h"
 #include "bcp_aisle.h"
 #include "bcp_inflate.h"
+#include "bcp_scan.h"
 
 using namespace bcp;
 
@@ -232,6 +235,7 @@ static int check_kernel_size(const bcp_params& p, double res)
 #include "bcp_ego_host.h"
 #include "bcp_worlds_host.h"
 #include "bcp_inflate_host.h"
+#include "bcp_scan_host.h"
 
 // ------------------------------------------------------------------------------------------------ kernels (one-time, operator seams)
 __global__ void reset_kernel(DevState st, DevState init, const uint8_t* __restrict__ mask, int64_t n, int tri,

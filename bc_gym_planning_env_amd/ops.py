@@ -10,14 +10,17 @@ try/except ImportError), batched over many inputs.
   is_robot_colliding    utilities/costmap_utils.py:106-164; is_footprint_colliding (is_footprint_colliding_impl, :106-136)
   reward / find_last_reached / path_velocity   envs/base/reward.py:184-259, utilities/path_tools.py:432-448, :298-323
   inflate_costmap       utilities/costmap_inflation.py:73-92 (cv2.distanceTransform + _pixel_distance_to_cost)
+  range_scan            no counterpart: distances to the nearest lethal cell along beams (bcp_range_scan)
 """
 import ctypes as C
+from collections import OrderedDict
 
 import numpy as np
 import torch
 
 from . import _lib, robots
 from .api import EnvParams, INDUSTRIAL_TRICYCLE_V1
+from .batched_env import beam_table_cached
 
 
 class NativeOps(object):
@@ -197,6 +200,28 @@ class NativeOps(object):
             _lib.check(self._lib.bcp_egocentric_costmaps_pooled(self._h, p.data_ptr(), p.shape[0], org_p, sz_p,
                                                                 int(border_value), int(pool), out.data_ptr(), self._stream()))
         return out
+
+    def range_scan(self, poses, beam_angles, max_range, want=()):
+        """Range scans of the costmap given to set_costmap from each of poses [n,3] (bcp_range_scan): the distance in
+        metres to the nearest lethal (254) cell along each of beam_angles [B], angles from the pose's heading,
+        counter-clockwise; max_range where there is none within max_range -> float32 [n, B], or (ranges, *wanted) with
+        want from "hit" (int32 [n, B], row * cols + col of the cell, -1 for none) and "heading_cs" (float64 [n, 2]).
+        The (cos, sin) table of an angle set is uploaded once."""
+        p = self._dev(np.atleast_2d(poses) if not isinstance(poses, torch.Tensor) else poses, torch.float64)
+        table = beam_table_cached(self._keep.setdefault("beam_tables", OrderedDict()), beam_angles, self.device)
+        unknown = set(want) - {"hit", "heading_cs"}
+        if unknown:
+            raise ValueError("range_scan: unknown outputs %s" % sorted(unknown))
+        n, b = p.shape[0], table.shape[0]
+        out = {"ranges": torch.empty((n, b), dtype=torch.float32, device=self.device)}
+        if "hit" in want:
+            out["hit"] = torch.empty((n, b), dtype=torch.int32, device=self.device)
+        if "heading_cs" in want:
+            out["heading_cs"] = torch.empty((n, 2), dtype=torch.float64, device=self.device)
+        _lib.check(self._lib.bcp_range_scan(self._h, p.data_ptr(), n, table.data_ptr(), b, float(max_range),
+                                            out["ranges"].data_ptr(), out["hit"].data_ptr() if "hit" in out else None,
+                                            out["heading_cs"].data_ptr() if "heading_cs" in out else None, self._stream()))
+        return out["ranges"] if not want else (out["ranges"],) + tuple(out[w] for w in want)
 
     def footprint(self):
         """The handle's own footprint [n_verts, 2] in metres."""

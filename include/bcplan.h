@@ -560,6 +560,56 @@ int bcp_final_egocentric_costmaps_pooled(bcp_handle *h, const double *window_ori
 int bcp_final_goal_n_state(bcp_handle *h, const double *world_size /*host*/, float *out, void *stream);
 int bcp_final_goal_direction_state(bcp_handle *h, const double *world_size /*host*/, double *out, void *stream);
 
+/* ---- range observation: distances to the nearest obstacle along beams fixed to the robot ------------------ */
+/* A planar range scan per row, by an exact walk over the grid (no reference counterpart: the reference's observations are
+ * images; this is what a navigation learner is usually fed instead).  One launch, asynchronous on `stream`, no allocation,
+ * no host synchronisation; the launch arguments depend only on the pointers and numbers given, so a call can be captured
+ * into a HIP graph -- after one ordinary call with the same maps bound: with a shared map staged in LDS the first call on a
+ * device may have to raise the kernel's dynamic-LDS limit, which is not a stream operation.
+ * Rows: exactly those of bcp_egocentric_costmaps.  poses is [n,3] device doubles, row i is seen on the map entry of env
+ * i % n_envs (geom_of_env under a pool); poses == NULL requires n == n_envs and means the bound state's pose (pose_seen when
+ * pose_delay > 0).  bcp_final_range_scan draws slots j < min(*count, capacity) of the bound episode record on entry geom[j]
+ * (private maps without a pool: env_id[j]) and leaves the other rows untouched, in every output.
+ * Beams: beam_cs[b] = (cos phi_b, sin phi_b), phi_b the beam's angle from the robot's heading, counter-clockwise: a device
+ * table [n_beams][2] the caller makes and owns.  The library computes no transcendental per beam.
+ * Obstacles: a cell is an obstacle exactly where the lethal mask is set, data == 254 inside the entry's valid shape -- the
+ * set bcp_pose_collides tests.  255, 253 and inflated costs are free space, and so is everything outside the valid shape,
+ * padding included: inflating the maps changes no range.
+ * Arithmetic: float64 throughout, every product, quotient and sum rounded on its own.  For a row with pose (x, y, theta)
+ * on an entry with origin (ox, oy):
+ *   (c, s) = (cos theta, sin theta)                  the device's; written to heading_cs_out[row] when given
+ *   u = (x - ox) * inv_res + 0.5                     inv_res = 1 / resolution as bcp_set_costmaps rounds it
+ *   v = (y - oy) * inv_res + 0.5                     cell (row, col) covers [col, col + 1) x [row, row + 1)
+ *   R = max_range * inv_res
+ *   for each beam b with (cb, sb):
+ *     dx = c*cb - s*sb ;  dy = s*cb + c*sb
+ *     col = floor(u), row = floor(v)
+ *     sx = dx > 0 ? 1 : -1,  sy likewise
+ *     tdx = dx != 0 ? |1.0 / dx| : +inf,  tdy likewise
+ *     tmx = dx > 0 ? (col + 1 - u) / dx : dx < 0 ? (col - u) / dx : +inf        tmy likewise with row, v, dy
+ *     t = 0.0
+ *     while t < R:
+ *         if 0 <= row < valid_rows and 0 <= col < valid_cols and lethal(row, col):
+ *             -> ranges = (float)(t * resolution), hit = row * cols + col ; done
+ *         if tmx < tmy: t = tmx; tmx += tdx; col += sx
+ *         else:         t = tmy; tmy += tdy; row += sy          (a tie steps in y)
+ *     -> ranges = (float)max_range, hit = -1
+ * A start cell that is lethal gives range 0; a pose outside the map walks free space until it enters the map or reaches R.
+ * The loop crosses one grid line per trip and is cut after 2 * ceil(R) + 4 trips (a miss), which no ray of unit direction
+ * reaches.  Rows whose pose has a non-finite component, or with |u| or |v| >= 2^30, get max_range / -1 in every beam, and
+ * their heading_cs_out is unspecified.  A ray that passes exactly through the shared corner of two diagonally adjacent wall
+ * cells may slip through an 8-connected wall (a cv2.line wall); every other ray cannot: the walk visits every cell the ray
+ * touches.
+ * ranges: float32 [n][n_beams] in metres; hit: optional int32 [n][n_beams]; heading_cs_out: optional float64 [n][2].
+ * BCP_E_INVALID: NULL h, beam_cs or ranges; n_beams outside [1, 1024]; n <= 0, or n != n_envs without poses; max_range not
+ * finite, not > 0, or max_range * inv_res > 4096.  BCP_E_STATE: no costmaps bound; no state bound with poses == NULL; no
+ * record bound (bcp_final_range_scan). */
+int bcp_range_scan(bcp_handle *h, const double *poses, int64_t n, const double *beam_cs /*device [n_beams][2]*/,
+                   int32_t n_beams, double max_range, float *ranges /*[n][n_beams]*/, int32_t *hit /*optional [n][n_beams]*/,
+                   double *heading_cs_out /*optional [n][2]*/, void *stream);
+int bcp_final_range_scan(bcp_handle *h, const double *beam_cs, int32_t n_beams, double max_range,
+                         float *ranges /*[capacity][n_beams]*/, int32_t *hit, double *heading_cs_out, void *stream);
+
 /* ---- look-ahead: score K candidate plans per env without stepping it ------------------------------------- */
 /* bcp_lookahead flags (it also takes BCP_STEP_ACTIONS_F32) */
 enum {

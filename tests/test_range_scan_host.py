@@ -1,0 +1,264 @@
+"""The range scan's arithmetic (csrc/bcp_scan_march.h: the walk of one ray, the test of a row's pose, the argument checks)
+as a stand-alone host program under AddressSanitizer and UBSan, bit for bit against the contract restated in numpy
+(tests/range_scan_ref.py).  tests/c_abi/range_scan_main.cpp includes that header alone -- it has no HIP in it -- and calls
+the very functions range_scan_kernel calls; the program reads the mask through a bounds-checked accessor, so a walk that
+left the map fails here, without a GPU.  Known answers are checked against both sides."""
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import range_scan_ref as RR
+from util import GOLDEN
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW_SYMBOLS = ["bcp_range_scan", "bcp_final_range_scan"]
+
+
+def _compiler():
+    for cand in ("g++", "/opt/rocm/llvm/bin/clang++", "clang++"):
+        path = shutil.which(cand)
+        if path:
+            return path
+    raise AssertionError("no host C++ compiler found (g++ or ROCm's clang++)")
+
+
+@pytest.fixture(scope="module")
+def program(tmp_path_factory):
+    exe = str(tmp_path_factory.mktemp("range_scan") / "range_scan_main")
+    cxx = _compiler()
+    static_runtime = ["-static-libasan", "-static-libubsan"] if cxx.endswith("g++") else []   # (clang's is static already)
+    cmd = [cxx] + static_runtime + ["-std=c++17", "-Wall", "-Werror", "-g", "-O1", "-ffp-contract=off",
+                                    "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                                    "-I" + os.path.join(ROOT, "bc_gym_planning_env_amd", "csrc"),
+                                    os.path.join(ROOT, "tests", "c_abi", "range_scan_main.cpp"), "-o", exe]
+    built = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=300)
+    assert built.returncode == 0, built.stdout
+    return exe
+
+
+def _run(exe, mode, path):
+    ran = subprocess.run([exe, mode, path], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=120)
+    assert ran.returncode == 0, ran.stdout[-4000:]
+    assert "range scan ok" in ran.stdout
+    for word in ("Sanitizer", "runtime error"):
+        assert word not in ran.stdout, ran.stdout[-4000:]
+    return ran.stdout.split("\n")
+
+
+def _both(exe, tmp_path, data, valid, origin, resolution, poses, heading_cs, beam_cs, max_range):
+    """One case through the program and through the reference; asserts bit-for-bit equality and that the trip bound is
+    never reached.  -> ranges float32 [n, B], hit int32 [n, B]"""
+    rows, cols = data.shape
+    bits = RR.pack_bits(data == RR.LETHAL)   # (NOT cut to the valid shape: the walk's own test of it is under test)
+    poses = np.ascontiguousarray(poses, dtype=np.float64)
+    heading_cs = np.ascontiguousarray(heading_cs, dtype=np.float64)
+    beam_cs = np.ascontiguousarray(beam_cs, dtype=np.float64)
+    n, n_beams = len(poses), len(beam_cs)
+    path = str(tmp_path / "case.bin")
+    with open(path, "wb") as f:
+        f.write(np.array([rows, cols, bits.shape[1], valid[0], valid[1], n, n_beams, 0], dtype=np.int32).tobytes())
+        f.write(np.array([origin[0], origin[1], resolution, max_range], dtype=np.float64).tobytes())
+        f.write(bits.tobytes())
+        f.write(np.concatenate([poses, heading_cs], axis=1).tobytes())
+        f.write(beam_cs.tobytes())
+    lines = _run(exe, "scan", path)
+    want_r, want_h, want_t, bound = RR.range_scan(data[None], [valid[0]], [valid[1]], np.array([origin], dtype=np.float64),
+                                                  resolution, np.zeros(n, dtype=np.int64), poses, heading_cs, beam_cs, max_range)
+    assert lines[0] == "bound %d" % bound
+    rays = [ln.split() for ln in lines[1:1 + n * n_beams]]
+    got_r = np.array([int(r[0], 16) for r in rays], dtype=np.uint32).view(np.float32).reshape(n, n_beams)
+    got_h = np.array([int(r[1]) for r in rays], dtype=np.int32).reshape(n, n_beams)
+    got_t = np.array([int(r[2]) for r in rays], dtype=np.int64).reshape(n, n_beams)
+    np.testing.assert_array_equal(got_h, want_h)
+    np.testing.assert_array_equal(got_r.view(np.uint32), want_r.view(np.uint32))
+    np.testing.assert_array_equal(got_t, want_t)
+    assert got_t.max() < bound, "the trip bound was reached"
+    # what every result satisfies, whatever the map
+    miss = got_h < 0
+    assert (got_r[miss] == np.float32(max_range)).all()
+    assert (got_r[~miss] <= np.float32(max_range)).all() and (got_r[~miss] >= 0).all()
+    hr, hc = got_h[~miss] // cols, got_h[~miss] % cols
+    assert (data[hr, hc] == RR.LETHAL).all() and (hr < valid[0]).all() and (hc < valid[1]).all()
+    return got_r, got_h
+
+
+def _mini_map(k):
+    g = np.load(os.path.join(GOLDEN, "g9_mini_geometry.npz"))
+    cols = int(g["map_shape"][1])
+    lethal = np.unpackbits(g["maps"][k], axis=1)[:, :cols].astype(bool)
+    return (lethal * np.uint8(254)).astype(np.uint8), g["origin"].astype(np.float64), float(g["resolution"])
+
+
+def _numpy_cs(poses):
+    with np.errstate(all="ignore"):
+        return np.stack([np.cos(poses[:, 2]), np.sin(poses[:, 2])], axis=1)
+
+
+AXES = np.array([[1.0, 0.0], [0.0, 1.0], [-1.0, 0.0], [0.0, -1.0]])
+
+
+@pytest.mark.parametrize("which", ["mini64", "mini183"])
+def test_mini_maps_bit_for_bit(program, tmp_path, which):
+    data, origin, res = _mini_map(5)
+    if which == "mini64":
+        r0, c0 = 60, 60   # a cut through the middle of the world, where its obstacles are
+        data = np.ascontiguousarray(data[r0:r0 + 64, c0:c0 + 64])
+        origin = origin + np.array([c0, r0]) * res
+        assert (data == 254).sum() > 50
+    rng = np.random.RandomState(3)
+    poses = RR.edge_rows(rng, data, data.shape, origin, res)
+    beams = RR.beam_table(RR.wrapper_angles(33, 2 * np.pi))
+    # 3 m = 100 cells of 3 cm; 1.24 m ends inside a cell (41.33 cells)
+    for max_range in (3.0, 1.24):
+        assert max_range == 3.0 or 0.1 < (max_range / res) % 1 < 0.9
+        ranges, hit = _both(program, tmp_path, data, data.shape, origin, res, poses, _numpy_cs(poses), beams, max_range)
+        assert (hit[:4] >= 0).all() and (ranges[:4] == 0).all()        # a start cell that is lethal: range 0 in every beam
+        assert (hit[10:16] == -1).all()                                 # non-finite, or beyond 2^30 cells: all misses
+        assert (hit[4:9] >= 0).any() or max_range < 2                   # from outside, some ray enters the map and hits
+        assert (hit[9] == -1).all()                                     # 50 m away: nothing within reach
+    # theta = 0 exactly with the four axis beams: dx or dy is exactly 0
+    axis_poses = poses[16:].copy()
+    axis_poses[:, 2] = 0.0
+    cs = np.tile([1.0, 0.0], (len(axis_poses), 1))
+    _both(program, tmp_path, data, data.shape, origin, res, axis_poses, cs, AXES, 3.0)
+
+
+def test_start_on_a_grid_line(program, tmp_path):
+    """u (or v, or both) exactly an integer: at a resolution that is a power of two the contract's u is exact"""
+    res, origin = 0.25, np.array([-2.0, 1.5])
+    rng = np.random.RandomState(9)
+    data = np.where(rng.uniform(size=(40, 45)) < 0.08, 254, 0).astype(np.uint8)
+    data[rng.uniform(size=data.shape) < 0.05] = 253   # (free space, like 255 and every other cost)
+    data[rng.uniform(size=data.shape) < 0.05] = 255
+    ks = rng.randint(1, 39, size=(30, 2)).astype(np.float64)
+    poses = np.stack([origin[0] + (ks[:, 0] - 0.5) * res, origin[1] + (ks[:, 1] - 0.5) * res, rng.uniform(-np.pi, np.pi, 30)], axis=1)
+    poses[10:20, 1] += 0.1        # only u on a line
+    poses[20:, 2] = 0.0           # on a corner, and along the axes
+    u = (poses[:, 0] - origin[0]) * (1.0 / res) + 0.5
+    v = (poses[:, 1] - origin[1]) * (1.0 / res) + 0.5
+    assert (u == np.floor(u)).all() and (v[:10] == np.floor(v[:10])).all() and (v[10:20] != np.floor(v[10:20])).all()
+    cs = _numpy_cs(poses)
+    assert (cs[20:] == [1.0, 0.0]).all()
+    beams = np.concatenate([AXES, RR.beam_table(RR.wrapper_angles(16, 2 * np.pi)), RR.beam_table([np.pi / 4, -3 * np.pi / 4])])
+    _both(program, tmp_path, data, data.shape, origin, res, poses, cs, beams, 6.1)
+
+
+def test_padding_is_free_space(program, tmp_path):
+    """valid < allocated with 254s in the padding: no ray ends there"""
+    res, origin = 0.05, np.array([0.3, -0.7])
+    rng = np.random.RandomState(21)
+    data = np.zeros((48, 70), dtype=np.uint8)
+    valid = (30, 37)
+    data[:valid[0], :valid[1]] = np.where(rng.uniform(size=valid) < 0.03, 254, 0)
+    data[valid[0]:, :] = 254
+    data[:, valid[1]:] = 254
+    poses = RR.edge_rows(rng, data, valid, origin, res)
+    ranges, hit = _both(program, tmp_path, data, valid, origin, res, poses, _numpy_cs(poses), RR.beam_table(RR.wrapper_angles(40, 2 * np.pi)), 2.5)
+    assert (hit == -1).any() and (hit >= 0).any()
+    # the same map without the padding's 254s gives the same bytes
+    clean = data.copy()
+    clean[valid[0]:, :] = 0
+    clean[:, valid[1]:] = 0
+    ranges2, hit2 = _both(program, tmp_path, clean, valid, origin, res, poses, _numpy_cs(poses), RR.beam_table(RR.wrapper_angles(40, 2 * np.pi)), 2.5)
+    assert (ranges.view(np.uint32) == ranges2.view(np.uint32)).all() and (hit == hit2).all()
+
+
+def test_known_range_to_a_wall(program, tmp_path):
+    """from the centre of cell (10, 10) along +x to a wall in column 40 at 5 cm: (40 - 10 - 0.5) cells"""
+    res, origin = 0.05, np.array([0.0, 0.0])
+    data = np.zeros((64, 64), dtype=np.uint8)
+    data[:, 40] = 254
+    poses = np.array([[10 * res, 10 * res, 0.0]])
+    ranges, hit = _both(program, tmp_path, data, data.shape, origin, res, poses, [[1.0, 0.0]], AXES, 3.0)
+    assert ranges[0, 0] == np.float32((40 - 10 - 0.5) * 0.05) and hit[0, 0] == 10 * 64 + 40
+    assert (hit[0, 1:] == -1).all() and (ranges[0, 1:] == np.float32(3.0)).all()
+    # backwards from beyond the wall, and a range that stops half a cell short of it
+    poses = np.array([[50 * res, 10 * res, 0.0]])
+    ranges, hit = _both(program, tmp_path, data, data.shape, origin, res, poses, [[1.0, 0.0]], AXES, 3.0)
+    assert ranges[0, 2] == np.float32((50.5 - 41) * 0.05) and hit[0, 2] == 10 * 64 + 40
+    poses = np.array([[10 * res, 10 * res, 0.0]])
+    ranges, hit = _both(program, tmp_path, data, data.shape, origin, res, poses, [[1.0, 0.0]], AXES, 29.0 * 0.05)
+    assert hit[0, 0] == -1
+
+
+def test_no_ray_crosses_a_diagonal_wall(program, tmp_path):
+    """An 8-connected diagonal wall, cells touching at corners only: of 2 000 seeded rays aimed across it none misses (only
+    a ray through a shared corner EXACTLY could, and none of these is)"""
+    res, origin, side = 0.05, np.array([-1.0, 2.0]), 96
+    data = np.zeros((side, side), dtype=np.uint8)
+    data[np.arange(side), np.arange(side)] = 254
+    rng = np.random.RandomState(77)
+    n = 2000
+    # from below the diagonal (col > row) to above it, both ends well inside the map
+    a = rng.uniform(4, side - 4, size=(3 * n, 2))
+    a = a[a[:, 0] > a[:, 1] + 1.5][:n]          # (u, v) with u > v
+    b = rng.uniform(4, side - 4, size=(3 * n, 2))
+    b = b[b[:, 1] > b[:, 0] + 1.5][:n]
+    assert len(a) == n and len(b) == n
+    th = np.arctan2(b[:, 1] - a[:, 1], b[:, 0] - a[:, 0])
+    poses = np.stack([origin[0] + (a[:, 0] - 0.5) * res, origin[1] + (a[:, 1] - 0.5) * res, th], axis=1)
+    ranges, hit = _both(program, tmp_path, data, data.shape, origin, res, poses, _numpy_cs(poses), [[1.0, 0.0]], 8.0)
+    assert (hit >= 0).all()
+    assert (hit // side == hit % side).all()
+    # the ray stops where it enters a wall cell: no later than where it meets the line u = v, and no farther from that line
+    # than half a cell's diagonal
+    d = (a[:, 0] - a[:, 1]) / (np.sin(th) - np.cos(th)) * res
+    assert (ranges[:, 0] <= d + 1e-5).all()
+    end = a + (ranges[:, 0:1].astype(np.float64) / res) * np.stack([np.cos(th), np.sin(th)], axis=1)
+    assert (np.abs(end[:, 0] - end[:, 1]) / np.sqrt(2) <= np.sqrt(0.5) + 1e-4).all()
+
+
+def test_argument_checks(program, tmp_path):
+    inf, nan = float("inf"), float("nan")
+    table = [
+        # have_h, beams, ranges, n_beams, n, n_envs, have_poses, final, max_range, inv_res -> refusal
+        ((1, 1, 1, 64, 8, 8, 0, 0, 3.0, 20.0), 0),
+        ((1, 1, 1, 1, 5, 8, 1, 0, 3.0, 20.0), 0),
+        ((1, 1, 1, 1024, 8, 8, 0, 0, 204.8, 20.0), 0),
+        ((1, 1, 1, 64, 0, 8, 0, 1, 3.0, 20.0), 0),          # the final form: n is the record's
+        ((1, 1, 1, 64, 8, 8, 0, 0, 1e300, 0.0), 0),         # no costmaps bound yet: that refusal is the caller's
+        ((0, 1, 1, 64, 8, 8, 0, 0, 3.0, 20.0), 1),
+        ((1, 0, 1, 64, 8, 8, 0, 0, 3.0, 20.0), 1),
+        ((1, 1, 0, 64, 8, 8, 0, 0, 3.0, 20.0), 1),
+        ((1, 1, 1, 0, 8, 8, 0, 0, 3.0, 20.0), 2),
+        ((1, 1, 1, -3, 8, 8, 0, 0, 3.0, 20.0), 2),
+        ((1, 1, 1, 1025, 8, 8, 0, 0, 3.0, 20.0), 2),
+        ((1, 1, 1, 64, 0, 8, 1, 0, 3.0, 20.0), 3),
+        ((1, 1, 1, 64, -1, 8, 1, 0, 3.0, 20.0), 3),
+        ((1, 1, 1, 64, 7, 8, 0, 0, 3.0, 20.0), 3),
+        ((1, 1, 1, 64, 9, 8, 0, 0, 3.0, 20.0), 3),
+        ((1, 1, 1, 64, 8, 8, 0, 0, 0.0, 20.0), 4),
+        ((1, 1, 1, 64, 8, 8, 0, 0, -1.0, 20.0), 4),
+        ((1, 1, 1, 64, 8, 8, 0, 0, inf, 20.0), 4),
+        ((1, 1, 1, 64, 8, 8, 0, 0, nan, 20.0), 4),
+        ((1, 1, 1, 64, 8, 8, 0, 0, 204.81, 20.0), 4),
+        ((1, 1, 1, 64, 8, 8, 0, 0, inf, 0.0), 4),
+        ((0, 0, 0, 0, 0, 8, 0, 0, nan, 20.0), 1),           # the order: null arguments first, then beams, rows, range
+        ((1, 1, 1, 0, 0, 8, 0, 0, nan, 20.0), 2),
+        ((1, 1, 1, 64, 0, 8, 0, 0, nan, 20.0), 3),
+    ]
+    path = str(tmp_path / "args.txt")
+    with open(path, "w") as f:
+        for args, _want in table:
+            f.write(" ".join([str(a) for a in args[:8]] + [float(a).hex() if np.isfinite(a) else str(a) for a in args[8:]]) + "\n")
+    got = [int(ln) for ln in _run(program, "args", path)[:len(table)]]
+    assert got == [want for _args, want in table]
+    assert [RR.check_args(*args) for args, _want in table] == got
+
+
+def test_library_exports_the_scan_symbols_and_lib_binds_them():
+    import ctypes as C
+    from bc_gym_planning_env_amd import _lib, build
+    build.build()
+    raw = C.CDLL(_lib.LIB_PATH)
+    for name in NEW_SYMBOLS:
+        assert hasattr(raw, name), name
+        assert name in _lib.SYMBOLS, name
+    lib = _lib.load()
+    assert lib.bcp_range_scan.argtypes[2] is C.c_int64 and lib.bcp_range_scan.argtypes[4:6] == [C.c_int32, C.c_double]
+    assert len(lib.bcp_range_scan.argtypes) == 10 and len(lib.bcp_final_range_scan.argtypes) == 8
+    assert lib.bcp_final_range_scan.argtypes[2:4] == [C.c_int32, C.c_double]
+    assert _lib.ABI_VERSION == 2
