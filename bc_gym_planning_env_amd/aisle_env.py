@@ -22,7 +22,8 @@ import torch
 
 from . import _lib, robots
 from .api import CostMap2D, EnvParams
-from .batched_env import BatchedPlanEnv, DeviceGeometryPool
+from .batched_env import BatchedPlanEnv
+from .geometry import DeviceGeometryPool, pool_or_sample
 from .mini_env import add_wall, map_shape
 
 # one world record of the device sampler (bcp_sample_aisle_worlds, include/bcplan.h)
@@ -317,22 +318,8 @@ class BatchedRandomAisleTurnEnv(BatchedPlanEnv):
     def __init__(self, n_envs, params=None, pool=None, seeds=None, n_chains=None, episodes=4, device=0,
                  draw_new_turn_on_reset=True, sampler="device", ranges=None, **kw):
         params = EnvParams() if params is None else params
-        if pool is None:
-            if seeds is None:
-                seeds = range(int(n_chains) if n_chains else min(int(n_envs), 1024))
-            if sampler == "device_resident":
-                pool = sample_aisle_pool_device(params, list(seeds), episodes, device, keep_on_device=True, ranges=ranges)
-            elif sampler == "device":
-                pool = sample_aisle_pool_device(params, list(seeds), episodes, device, ranges=ranges)
-            elif sampler == "host":
-                pool = sample_aisle_pool(params, list(seeds), episodes, ranges)
-            else:
-                raise ValueError("sampler must be 'device', 'device_resident' or 'host', not %r" % (sampler,))
-        chains, per = len(pool.seeds), pool.episodes
-        i = np.arange(int(n_envs))
-        geom = (i % chains) * per + (i // chains) % per
-        self.pool = pool
-        on_device = isinstance(pool, DeviceGeometryPool)
-        super(BatchedRandomAisleTurnEnv, self).__init__(
-            pool if on_device else pool.costmaps, None if on_device else pool.paths, params, n_envs=n_envs,
-            device=device, geom_of_env=geom, next_geom=pool.next_geom if draw_new_turn_on_reset else None, **kw)
+        pool = pool_or_sample(pool, {
+            "device": lambda s: sample_aisle_pool_device(params, s, episodes, device, ranges=ranges),
+            "device_resident": lambda s: sample_aisle_pool_device(params, s, episodes, device, keep_on_device=True, ranges=ranges),
+            "host": lambda s: sample_aisle_pool(params, s, episodes, ranges)}, sampler, seeds, n_chains, n_envs)
+        self._init_from_pool(pool, params, n_envs, pool.next_geom if draw_new_turn_on_reset else None, device=device, **kw)

@@ -6,6 +6,7 @@ Observation / State objects for one env.  Device tensors are torch tensors only 
 raw pointers (tensor.data_ptr()); all arithmetic happens in libbcplan.so.
 """
 import ctypes as C
+import functools
 from collections import OrderedDict
 
 import attr
@@ -14,11 +15,16 @@ import numpy as np
 import torch
 
 from . import _lib, host_init, robots
-from .api import (Action, Box, CONTINUOUS_REWARD_PURE_PURSUIT, ContinuousRewardProviderState,
-                  ContinuousRewardPurePursuitProviderState, CostMap2D, DiffdriveRobotState, EnvParams,
-                  INDUSTRIAL_TRICYCLE_V1, Observation, State, TricycleRobotState)
+from .api import Action, Box, CONTINUOUS_REWARD_PURE_PURSUIT, CostMap2D, EnvParams, INDUSTRIAL_TRICYCLE_V1, State
+from .episode_record import EpisodeEnds
+from .geometry import DeviceGeometryPool, chain_layout, stack_costmaps, stack_paths
+from .handle import Handle, SCAN_CACHE_ENTRIES, beam_table_cached, cached
+from .planning import Lookahead, Mppi
+from .state import BatchedObservation, BatchedState, EnvView, _EnvViews
 
-_STATE_FIELDS = ("x", "y", "angle", "v", "w", "steering_motor_command", "wheel_angle")
+# (everything that was ever importable from here still is)
+__all__ = ["BatchedPlanEnv", "DeviceGeometryPool", "BatchedState", "BatchedObservation", "EnvView", "EpisodeEnds",
+           "Lookahead", "Mppi", "beam_table_cached", "SCAN_CACHE_ENTRIES"]
 
 
 def _as_device_actions(actions, n, device):
@@ -39,402 +45,7 @@ def _as_device_actions(actions, n, device):
     return t
 
 
-class DeviceGeometryPool(object):
-    """G geometries that already live on the GPU (e.g. from mini_env.sample_device_pool): what BatchedPlanEnv's
-    geometry-pool mode needs, as device tensors.  `costmaps` / `paths` hand out host copies on demand, for the per-env
-    views (envs[i].get_state())."""
-
-    def __init__(self, maps, origin, resolution, paths, lens, init, origins=None, valid_rows=None, valid_cols=None):
-        self.maps = maps                  # uint8 [G, rows, cols]
-        self.origin = np.asarray(origin, dtype=np.float64) if origin is not None else None   # one origin for all entries
-        self.resolution = float(resolution)
-        self.path_points = paths          # float64 [G, max_len, 3], already refined
-        self.lens = lens                  # int32 [G]
-        self.init = init                  # float64 [G, 2] = (min_spat_dist_so_far, target_idx)
-        # optional, for entries of different sizes: float64 [G, 2] origin of every entry, int32 [G] true shape of every
-        # entry (the rest of its [rows, cols] is padding); None = one origin, every entry uses all of [rows, cols]
-        self.origins, self.valid_rows, self.valid_cols = origins, valid_rows, valid_cols
-
-    def __len__(self):
-        return int(self.maps.shape[0])
-
-    class _Lazy(object):
-        def __init__(self, n, fetch):
-            self._n, self._fetch = n, fetch
-
-        def __len__(self):
-            return self._n
-
-        def __getitem__(self, k):
-            if not -self._n <= k < self._n:
-                raise IndexError(k)
-            return self._fetch(int(k) % self._n)
-
-    @property
-    def costmaps(self):
-        if self.origins is None:
-            return self._Lazy(len(self), lambda k: CostMap2D(self.maps[k].cpu().numpy(), self.resolution, self.origin))
-
-        def fetch(k):   # the entry cropped to its true shape, with its own origin
-            vr = int(self.valid_rows[k]) if self.valid_rows is not None else self.maps.shape[1]
-            vc = int(self.valid_cols[k]) if self.valid_cols is not None else self.maps.shape[2]
-            return CostMap2D(self.maps[k, :vr, :vc].cpu().numpy(), self.resolution, self.origins[k].cpu().numpy())
-        return self._Lazy(len(self), fetch)
-
-    def entry_origins(self, device):
-        """float64 [G, 2] device tensor: the origin of every entry."""
-        if self.origins is not None:
-            return self.origins.to(device).contiguous()
-        return torch.from_numpy(np.tile(self.origin, (len(self), 1))).to(device)
-
-    @property
-    def paths(self):
-        return self._Lazy(len(self), lambda k: self.path_points[k, :int(self.lens[k])].cpu().numpy())
-
-
-class BatchedState(object):
-    """Snapshot of every env's mutable state (what PlanEnv.get_state() deep-copies, env.py:287-291)."""
-
-    # with delays > 0 (EnvParams.pose_delay / state_delay / control_delay, env.py:27-49, 363-398): what State exposes
-    # and the FIFO contents; `robot` is always the robot's TRUE state.  Element k pushed since the last reset lives
-    # in slot (k - 1) % delay.
-    DELAY_FIELDS = ("pose_seen", "robot_state_seen", "control_queue", "poses_queue", "robot_state_queue")
-
-    def __init__(self, robot, min_spat_dist_so_far, target_idx, current_iter, robot_collided, pose_seen=None,
-                 robot_state_seen=None, control_queue=None, poses_queue=None, robot_state_queue=None):
-        self.robot = robot                      # float64 [7, N]: x, y, angle, v, w, steering_motor_command, wheel_angle
-        self.min_spat_dist_so_far = min_spat_dist_so_far
-        self.target_idx = target_idx
-        self.current_iter = current_iter
-        self.robot_collided = robot_collided
-        self.pose_seen = pose_seen                      # [3, N] State.pose when pose_delay > 0
-        self.robot_state_seen = robot_state_seen        # [7, N] State.robot_state when state_delay > 0
-        self.control_queue = control_queue              # [control_delay, 2, N]
-        self.poses_queue = poses_queue                  # [pose_delay, 3, N]
-        self.robot_state_queue = robot_state_queue      # [state_delay, 7, N]
-
-    FIELDS = ("robot", "min_spat_dist_so_far", "target_idx", "current_iter", "robot_collided") + DELAY_FIELDS
-    VERSION = 1
-
-    def copy(self):
-        extra = {k: (getattr(self, k).clone() if getattr(self, k) is not None else None) for k in self.DELAY_FIELDS}
-        return BatchedState(self.robot.clone(), self.min_spat_dist_so_far.clone(), self.target_idx.clone(),
-                            self.current_iter.clone(), self.robot_collided.clone(), **extra)
-
-    def serialize(self):
-        """Basic python types only (dict of numpy arrays + version), as the reference's Serializable objects
-        (utilities/serialize.py): picklable, device independent."""
-        out = {k: (getattr(self, k).cpu().numpy() if getattr(self, k) is not None else None) for k in self.FIELDS}
-        out['version'] = self.VERSION
-        return out
-
-    @classmethod
-    def deserialize(cls, state, device="cpu"):
-        state = dict(state)
-        assert state.pop('version') == cls.VERSION
-        return cls(**{k: (torch.from_numpy(np.ascontiguousarray(v)).to(device) if v is not None else None)
-                      for k, v in state.items()})
-
-
-class BatchedObservation(object):
-    """Observation of all envs after a step: references to the live device tensors (as the reference's Observation
-    holds references, obs.py:14-23).  `obs[i]` builds the reference-shaped Observation of env i."""
-
-    def __init__(self, env):
-        self._env = env
-        st = env.state
-        # (with delays the observation shows the delayed pose / robot state, env.py:377-394)
-        self.pose = st.pose_seen if st.pose_seen is not None else st.robot[0:3]          # [3, N]
-        seen = st.robot_state_seen if st.robot_state_seen is not None else st.robot
-        self.robot_state = seen[3:7]              # [4, N] view: v, w, steering_motor_command, wheel_angle
-        self.target_idx = env.state.target_idx
-        self.current_iter = env.state.current_iter
-        self.dt = env.params.dt
-
-    @property
-    def time(self):
-        return self._env.time_of(self.current_iter)
-
-    def __len__(self):
-        return self._env.n_envs
-
-    def __getitem__(self, i):
-        return self._env.envs[i].observation()
-
-
-class EnvView(object):
-    """One env of the batch behind the reference's per-env API (copies a few scalars from the device on demand)."""
-
-    def __init__(self, env, i):
-        self._env, self._i = env, i
-
-    def _robot_state(self, col):
-        if self._env.is_tricycle:
-            return TricycleRobotState(*[float(v) for v in col])
-        return DiffdriveRobotState(*[float(v) for v in col[:5]])
-
-    def get_state(self):
-        e, i = self._env, self._i
-        s = e.state
-        col = s.robot[:, i].cpu().numpy()
-        path = e.path_of(i)
-        tidx = int(s.target_idx[i])
-        it = int(s.current_iter[i])
-        cls = (ContinuousRewardPurePursuitProviderState if e.params.reward_provider_name == CONTINUOUS_REWARD_PURE_PURSUIT
-               else ContinuousRewardProviderState)
-        rps = cls(min_spat_dist_so_far=float(s.min_spat_dist_so_far[i]), path=path, target_idx=tidx)
-        pose = s.pose_seen[:, i].cpu().numpy() if s.pose_seen is not None else col[:3].copy()
-        seen = s.robot_state_seen[:, i].cpu().numpy() if s.robot_state_seen is not None else col
-
-        def fifo(q):   # the queue as the reference's list: oldest element first
-            if q is None:
-                return []
-            d = q.shape[0]
-            rows = q[:, :, i].cpu().numpy()
-            return [rows[(k - 1) % d].copy() for k in range(max(1, it - d + 1), it + 1)]
-
-        return State(reward_provider_state=rps, path=rps.current_path(), original_path=np.copy(path),
-                     costmap=e.costmap_of(i), iter_timeout=e.params.iteration_timeout,
-                     current_time=float(e.time_of(s.current_iter[i:i + 1])[0]), current_iter=it,
-                     robot_collided=bool(s.robot_collided[i]), poses_queue=fifo(s.poses_queue),
-                     robot_state_queue=[self._robot_state(v) for v in fifo(s.robot_state_queue)],
-                     control_queue=[Action(command=v) for v in fifo(s.control_queue)], pose=pose,
-                     robot_state=self._robot_state(seen))
-
-    VERSION = 1
-
-    def serialize(self):
-        """PlanEnv.serialize (env.py:251-261): this env, its parametrisation included, as basic python types;
-        BatchedPlanEnv.deserialize builds a batch from such records."""
-        st = self.get_state()
-        return {'version': self.VERSION, 'state': st.serialize(), 'params': self._env.params.serialize(),
-                'path': st.original_path, 'costmap': st.costmap.get_state()}
-
-    def set_state(self, state):
-        """PlanEnv.set_state (env.py:278-285) for this env: like the reference, the robot takes over
-        `state.robot_state` (with a state delay that is the delayed state -- the reference does the same)."""
-        e, i = self._env, self._i
-        s = e.state
-
-        def vec(rs):
-            return [rs.x, rs.y, rs.angle, rs.v, rs.w, getattr(rs, "steering_motor_command", 0.0),
-                    getattr(rs, "wheel_angle", 0.0)]
-
-        s.robot[:, i] = torch.tensor(vec(state.robot_state), dtype=torch.float64)
-        s.min_spat_dist_so_far[i] = state.reward_provider_state.min_spat_dist_so_far
-        s.target_idx[i] = state.reward_provider_state.target_idx
-        s.current_iter[i] = state.current_iter
-        s.robot_collided[i] = int(state.robot_collided)
-        if s.pose_seen is not None:
-            s.pose_seen[:, i] = torch.tensor(np.asarray(state.pose, dtype=np.float64))
-        if s.robot_state_seen is not None:
-            s.robot_state_seen[:, i] = torch.tensor(vec(state.robot_state), dtype=torch.float64)
-        it = int(state.current_iter)
-        for q, items in ((s.poses_queue, [np.asarray(p, dtype=np.float64) for p in state.poses_queue]),
-                         (s.robot_state_queue, [np.array(vec(r)) for r in state.robot_state_queue]),
-                         (s.control_queue, [np.asarray(a.command, dtype=np.float64) for a in state.control_queue])):
-            if q is None:
-                continue
-            d = q.shape[0]
-            # the list holds pushes it - len + 1 .. it (oldest first); push k lives in slot (k - 1) % d
-            for k, item in zip(range(it - len(items) + 1, it + 1), items):
-                q[(k - 1) % d, :, i] = torch.tensor(item)
-
-    def observation(self):
-        s = self.get_state()
-        return Observation(pose=s.pose, path=s.path, costmap=s.costmap, robot_state=s.robot_state,
-                           time=s.current_time, dt=self._env.params.dt)
-
-
-class _EnvViews(object):
-    def __init__(self, env):
-        self._env = env
-
-    def __len__(self):
-        return self._env.n_envs
-
-    def __getitem__(self, i):
-        if not -self._env.n_envs <= i < self._env.n_envs:
-            raise IndexError(i)
-        return EnvView(self._env, i % self._env.n_envs)
-
-
-class EpisodeEnds(object):
-    """The episodes that ended in the last step (libbcplan's episode record, bcp_bind_episode_record): what a caller of the
-    reference's PlanEnv sees from step() before it calls reset() (envs/base/env.py:334-361, 293-303), kept although the
-    step has already auto-reset the env.  Device tensors, filled by the step kernel itself (no sync, no extra launch):
-
-      reason        uint8 [N]          BCP_DONE_* bits of every env (GOAL | TIMEOUT | COLLIDED, env.py:400-419), 0 = not done
-      count         int32 [1]          envs that ended in the last step (may exceed `capacity`: overflow)
-      env_ids       int32 [capacity]   slot j < count: which env ended (order unspecified)
-      geom          int32 [capacity]   the geometry-pool entry the episode ran on (-1 without a pool)
-      final_state   BatchedState over the slots: the state the env held after its last step, before the reset
-                    (robot, reward-provider state, current_iter = episode length, robot_collided; the seen pose / robot
-                    state with delays; no queues)
-      final_return  float64 [capacity] the episode's return, the float64 sum of its rewards in step order
-      ret           float64 [N]        every env's running return (zeroed by every reset; set_state / fan_out leave it)
-
-    The running returns start at 0 when the record is bound: bound in the middle of episodes, each env's first
-    final_return covers only the steps since then (bind right after a reset() for whole-episode returns).
-    """
-
-    GOAL, TIMEOUT, COLLIDED = _lib.DONE_GOAL, _lib.DONE_TIMEOUT, _lib.DONE_COLLIDED
-
-    def __init__(self, env, capacity):
-        n, dev, cap = env.n_envs, env.device, int(capacity)
-        if cap < 1:
-            raise ValueError("capacity must be positive")
-        self._env, self.capacity = env, cap
-
-        def zeros(*shape, dtype=torch.float64):
-            return torch.zeros(*shape, dtype=dtype, device=dev)
-
-        self.reason = zeros(n, dtype=torch.uint8)
-        self.ret = zeros(n)
-        self.count = zeros(1, dtype=torch.int32)
-        self.env_ids = zeros(cap, dtype=torch.int32)
-        self.geom = torch.full((cap,), -1, dtype=torch.int32, device=dev)
-        self.final_return = zeros(cap)
-        pd, sd = int(env.params.pose_delay), int(env.params.state_delay)
-        self.final_state = BatchedState(zeros(7, cap), zeros(cap), zeros(cap, dtype=torch.int32),
-                                        zeros(cap, dtype=torch.int32), zeros(cap, dtype=torch.uint8),
-                                        pose_seen=zeros(3, cap) if pd else None,
-                                        robot_state_seen=zeros(7, cap) if sd else None)
-
-    def _c_struct(self):
-        rec = _lib.BcpEpisodeRecord()
-        rec.capacity = self.capacity
-        rec.reason, rec.ret, rec.count = self.reason.data_ptr(), self.ret.data_ptr(), self.count.data_ptr()
-        rec.env_id, rec.geom, rec.final_ret = self.env_ids.data_ptr(), self.geom.data_ptr(), self.final_return.data_ptr()
-        f = self.final_state
-        for k, name in enumerate(_STATE_FIELDS):
-            setattr(rec.final, name, f.robot[k].data_ptr())
-        rec.final.min_spat_dist_so_far = f.min_spat_dist_so_far.data_ptr()
-        rec.final.target_idx = f.target_idx.data_ptr()
-        rec.final.current_iter = f.current_iter.data_ptr()
-        rec.final.robot_collided = f.robot_collided.data_ptr()
-        rec.final.pose_seen = f.pose_seen.data_ptr() if f.pose_seen is not None else None
-        rec.final.robot_state_seen = f.robot_state_seen.data_ptr() if f.robot_state_seen is not None else None
-        return rec
-
-    @property
-    def length(self):
-        """int32 [capacity]: the episodes' lengths in steps (final_state.current_iter)."""
-        return self.final_state.current_iter
-
-    def terminated(self):
-        """bool [N]: the episode ended in a terminal state -- goal reached or collided (a time-out together with one
-        of them counts as terminal)."""
-        return (self.reason & (self.GOAL | self.COLLIDED)) != 0
-
-    def truncated(self):
-        """bool [N]: the episode was cut by the time limit alone (gymnasium's `truncated`, SB3's TimeLimit.truncated):
-        bootstrap V(final observation) there."""
-        return self.reason == self.TIMEOUT
-
-    def overflowed(self):
-        """True if more envs ended in the last step than there are slots (synchronises)."""
-        return int(self.count[0]) > self.capacity
-
-    def slots(self):
-        """Number of filled slots of the last step, min(count, capacity) (synchronises)."""
-        return min(int(self.count[0]), self.capacity)
-
-    def to_host(self):
-        """The last step's episode ends as a list of (env id, reference State, reason bits, return, length); the States
-        hold no delay queues.  Synchronises -- for debugging and tests."""
-        e = self._env
-        m = self.slots()
-        ids = self.env_ids[:m].cpu().numpy()
-        geom = self.geom[:m].cpu().numpy()
-        reason = self.reason.cpu().numpy()
-        ret = self.final_return[:m].cpu().numpy()
-        f = self.final_state
-        robot = f.robot[:, :m].cpu().numpy()
-        md = f.min_spat_dist_so_far[:m].cpu().numpy()
-        ti = f.target_idx[:m].cpu().numpy()
-        it = f.current_iter[:m].cpu().numpy()
-        col = f.robot_collided[:m].cpu().numpy()
-        ps = f.pose_seen[:, :m].cpu().numpy() if f.pose_seen is not None else None
-        rs = f.robot_state_seen[:, :m].cpu().numpy() if f.robot_state_seen is not None else None
-        view = EnvView(e, 0)
-        cls = (ContinuousRewardPurePursuitProviderState if e.params.reward_provider_name == CONTINUOUS_REWARD_PURE_PURSUIT
-               else ContinuousRewardProviderState)
-        out = []
-        for j in range(m):
-            i, g = int(ids[j]), int(geom[j])
-            path = e._paths[g] if g >= 0 else e.path_of(i)
-            costmap = e._costmaps[g] if g >= 0 else e.costmap_of(i)
-            rps = cls(min_spat_dist_so_far=float(md[j]), path=path, target_idx=int(ti[j]))
-            n_it = int(it[j])
-            st = State(reward_provider_state=rps, path=rps.current_path(), original_path=np.copy(path), costmap=costmap,
-                       iter_timeout=e.params.iteration_timeout,
-                       current_time=float(e.time_of(f.current_iter[j:j + 1])[0]), current_iter=n_it,
-                       robot_collided=bool(col[j]), poses_queue=[], robot_state_queue=[], control_queue=[],
-                       pose=ps[:, j].copy() if ps is not None else robot[:3, j].copy(),
-                       robot_state=view._robot_state(rs[:, j] if rs is not None else robot[:, j]))
-            out.append((i, st, int(reason[i]), float(ret[j]), n_it))
-        return out
-
-
-class Lookahead(object):
-    """What BatchedPlanEnv.lookahead() returns: device tensors over [N, K] candidates (no sync).  `ret` float64 return of
-    the steps taken, `steps` int32, `reason` uint8 DONE_* bits (0: not done within the horizon); optional, None unless
-    asked for: `final_pose` [N, K, 3], `final_target_idx`, `err`, `best` int32 [N], `best_action` [N, 2].  The tensors
-    are the env's cached buffers for this (H, K): the next lookahead() with the same shape overwrites them."""
-
-    FIELDS = ("ret", "steps", "reason", "final_pose", "final_target_idx", "err", "best", "best_action")
-
-    def __init__(self, horizon, n_candidates, **tensors):
-        self.horizon, self.n_candidates = horizon, n_candidates
-        for name in self.FIELDS:
-            setattr(self, name, tensors.get(name))
-
-    def collided(self):
-        """bool [N, K]: the candidate ends in a collision"""
-        return (self.reason & _lib.DONE_COLLIDED) != 0
-
-    def timed_out(self):
-        return (self.reason & _lib.DONE_TIMEOUT) != 0
-
-    def reached_goal(self):
-        return (self.reason & _lib.DONE_GOAL) != 0
-
-
-class Mppi(object):
-    """What BatchedPlanEnv.mppi() returns (device tensors, no sync): `mean` [N, H, 2] float64, the refined plan; `action`
-    [N, 2] = mean[:, 0], ready for step(); optional, None unless asked for: `eps` [I, N, K, H, 2] float32 (the
-    perturbations used), `iter_mean` [I, N, H, 2] (the mean going into each iteration), `iter_ret` / `iter_reason`
-    [I, N, K], `err` int32 [N].  Everything but `mean` is a cached buffer of the env for this (H, K, I)."""
-
-    FIELDS = ("eps", "iter_mean", "iter_ret", "iter_reason", "err")
-
-    def __init__(self, horizon, n_candidates, iterations, mean, action, **tensors):
-        self.horizon, self.n_candidates, self.iterations = horizon, n_candidates, iterations
-        self.mean, self.action = mean, action
-        for name in self.FIELDS:
-            setattr(self, name, tensors.get(name))
-
-
-SCAN_CACHE_ENTRIES = 8   # beam tables / output buffer sets of range_scan kept per env (least recently used go first)
-
-
-def beam_table_cached(tables, beam_angles, device):
-    """The device table [B, 2] of (cos, sin) of beam_angles for bcp_range_scan, from `tables` (an OrderedDict keyed by the
-    angles' bytes, least recently used first) or uploaded and added to it; at most SCAN_CACHE_ENTRIES tables are kept."""
-    angles = np.ascontiguousarray(beam_angles.detach().cpu().numpy() if isinstance(beam_angles, torch.Tensor) else beam_angles,
-                                  dtype=np.float64).reshape(-1)
-    key = angles.tobytes()
-    if key in tables:
-        tables.move_to_end(key)
-    else:
-        tables[key] = torch.from_numpy(np.stack([np.cos(angles), np.sin(angles)], axis=1)).to(device).contiguous()
-        while len(tables) > SCAN_CACHE_ENTRIES:
-            tables.popitem(last=False)
-    return tables[key]
-
-
-class BatchedPlanEnv(object):
+class BatchedPlanEnv(Handle):
     """N planning envs on one MI355X.
 
     :param costmap: CostMap2D shared by all envs, or a list of N CostMap2D of equal resolution (private maps)
@@ -470,23 +81,16 @@ class BatchedPlanEnv(object):
         self.params = params
         self._pure_pursuit = params.reward_provider_name == CONTINUOUS_REWARD_PURE_PURSUIT
         self.n_envs = int(n_envs)
-        self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
         self.robot_name = params.robot_name if robot_name is None else robot_name
         self.is_tricycle = self.robot_name == INDUSTRIAL_TRICYCLE_V1
         if noise_parameters == 'planenv':
             noise_parameters = dict(robots.PLANENV_NOISE) if self.is_tricycle else None
         self.noise_parameters = noise_parameters
         self.auto_reset = bool(auto_reset)
-        self._lib = _lib.load()  # raises when libbcplan.so is missing: no fallback
-        if not torch.cuda.is_available():
-            raise RuntimeError("BatchedPlanEnv needs a GPU (libbcplan has no CPU path)")
-        self._bcp_params = robots.make_bcp_params(params, self.robot_name, noise_parameters, footprint_scale,
-                                                  dynamic_model, model_front_column_pid, unpinned_diffdrive_noise,
-                                                  robot_constants)
-        self._h = C.c_void_p()
-        dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        _lib.check(self._lib.bcp_create(C.byref(self._bcp_params), self.n_envs, dev_index, int(env_id_base),
-                                        C.byref(self._h)))
+        super(BatchedPlanEnv, self).__init__(
+            robots.make_bcp_params(params, self.robot_name, noise_parameters, footprint_scale, dynamic_model,
+                                   model_front_column_pid, unpinned_diffdrive_noise, robot_constants),
+            self.n_envs, device, env_id_base, needs_gpu="BatchedPlanEnv")
         self.action_space = Box(low=np.array([robots.MAX_FRONT_WHEEL_SPEED / 10, -np.pi / 2]),
                                 high=np.array([robots.MAX_FRONT_WHEEL_SPEED / 2, np.pi / 2]), dtype=np.float32)
         self.reward_range = (0.0, 1.0)
@@ -509,33 +113,31 @@ class BatchedPlanEnv(object):
         self.collided_now = torch.zeros(n, dtype=torch.uint8, device=dev)
         self.err = torch.zeros(n, dtype=torch.int32, device=dev)
         self.envs = _EnvViews(self)
-        self._keep = {}  # device buffers the library holds pointers to
+        # what only some modes or subclasses change, at its neutral value
+        self.endless = False       # BatchedRandomMiniEnv(endless=True)
+        self._inflated = False     # inflate_costmaps()
+        self._rollout_buffers, self._lookahead_buffers, self._mppi_buffers = OrderedDict(), OrderedDict(), OrderedDict()
+        self._range_scan_buffers = OrderedDict()
 
+        # the geometry, in one of five modes (a shared costmap may go with private paths and the other way round)
         self._map_storage = (0, 0) if map_storage is None else (int(map_storage[0]), int(map_storage[1]))
         self._template_of_env = None if template_of_env is None else np.asarray(template_of_env, dtype=np.int64)
+        self._device_pool = None
         self.geom_of_env = None
         if geom_of_env is not None:
             assert template_of_env is None
-            self._device_pool = costmap if isinstance(costmap, DeviceGeometryPool) else None
-            if self._device_pool is not None:
-                costmap, path = self._device_pool.costmaps, self._device_pool.paths
-            else:
+            if isinstance(costmap, DeviceGeometryPool):   # DEVICE POOL: everything is on the device already
+                self._device_pool = costmap
+                self._set_geometry_pool(len(costmap), geom_of_env, next_geom)
+                self._set_from_device_pool(costmap)
+            else:                                         # HOST POOL: the library indexes the entries itself
                 costmap, path = list(costmap), list(path)
-            g0 = np.asarray(geom_of_env, dtype=np.int32)
-            assert g0.shape == (n,) and len(costmap) == len(path) and 0 <= g0.min() and g0.max() < len(costmap)
-            self.geom_of_env = torch.from_numpy(g0.copy()).to(dev)
-            nxt = None
-            if next_geom is not None:
-                nx = np.asarray(next_geom, dtype=np.int32)
-                assert nx.shape == (len(costmap),) and 0 <= nx.min() and nx.max() < len(costmap)
-                nxt = torch.from_numpy(nx.copy()).to(dev)
-            self._keep.update(next_geom=nxt)
-            _lib.check(self._lib.bcp_set_geometry_pool(self._h, len(costmap), self.geom_of_env.data_ptr(),
-                                                       nxt.data_ptr() if nxt is not None else None))
-            self._set_from_templates(costmap, path)
-        elif self._template_of_env is not None:
-            self._set_from_templates(list(costmap), list(path))
-        else:
+                assert len(costmap) == len(path)
+                self._set_geometry_pool(len(costmap), geom_of_env, next_geom)
+                self._set_from_templates(costmap, path, None)
+        elif self._template_of_env is not None:           # TEMPLATES: expanded to private copies on the device
+            self._set_from_templates(list(costmap), list(path), self._template_of_env)
+        else:                                             # SHARED (one object) or ONE PER ENV (a list), each of the two
             self._set_costmaps(costmap)
             self._set_paths(path)
         self._bind(self.state, self._lib.bcp_bind_state)
@@ -557,104 +159,92 @@ class BatchedPlanEnv(object):
         self.seed(seed)
         self.reset()
 
-    # ------------------------------------------------------------------ construction helpers
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+    def _init_from_pool(self, pool, params, n_envs, next_geom, **kw):
+        """The constructor of the pool envs (BatchedRandomMiniEnv, BatchedRandomAisleTurnEnv): geometry-pool mode with env i
+        on chain i % chains of `pool` (geometry.chain_layout); a pool on the device is bound as it is, a host pool through
+        its costmaps and paths."""
+        self.pool = pool
+        on_device = isinstance(pool, DeviceGeometryPool)
+        BatchedPlanEnv.__init__(self, pool if on_device else pool.costmaps, None if on_device else pool.paths, params,
+                                n_envs=n_envs, geom_of_env=chain_layout(n_envs, len(pool.seeds), pool.episodes),
+                                next_geom=next_geom, **kw)
 
+    # ------------------------------------------------------------------ construction helpers
     def _bind(self, s, fn):
-        st = _lib.BcpState()
-        for k, name in enumerate(_STATE_FIELDS):
-            setattr(st, name, s.robot[k].data_ptr())
-        st.min_spat_dist_so_far = s.min_spat_dist_so_far.data_ptr()
-        st.target_idx = s.target_idx.data_ptr()
-        st.current_iter = s.current_iter.data_ptr()
-        st.robot_collided = s.robot_collided.data_ptr()
-        for name in BatchedState.DELAY_FIELDS:
-            t = getattr(s, name)
-            setattr(st, name, t.data_ptr() if t is not None else None)
-        _lib.check(fn(self._h, C.byref(st)))
+        _lib.check(fn(self._h, C.byref(s.fill_pointers(_lib.BcpState()))))
+
+    def _refine(self):
+        """What every path given to the constructor goes through: refine_path at params.path_delta, or nothing."""
+        if self.params.refine_path:
+            return functools.partial(host_init.refine_path, delta=self.params.path_delta)
+        return lambda p: p
+
+    def _set_geometry_pool(self, n_entries, geom_of_env, next_geom):
+        g0 = np.asarray(geom_of_env, dtype=np.int32)
+        assert g0.shape == (self.n_envs,) and 0 <= g0.min() and g0.max() < n_entries
+        self.geom_of_env = torch.from_numpy(g0.copy()).to(self.device)
+        nxt = None
+        if next_geom is not None:
+            nx = np.asarray(next_geom, dtype=np.int32)
+            assert nx.shape == (n_entries,) and 0 <= nx.min() and nx.max() < n_entries
+            nxt = torch.from_numpy(nx.copy()).to(self.device)
+        self._keep.update(next_geom=nxt)
+        _lib.check(self._lib.bcp_set_geometry_pool(self._h, n_entries, self.geom_of_env.data_ptr(),
+                                                   nxt.data_ptr() if nxt is not None else None))
 
     def _set_costmaps(self, costmap):
-        n = self.n_envs
         if isinstance(costmap, CostMap2D) or hasattr(costmap, "get_data") and not isinstance(costmap, (list, tuple)):
             self._costmaps, self._shared_map = [costmap], True
             data = np.ascontiguousarray(costmap.get_data(), dtype=np.uint8)
             rows, cols = data.shape
             origins = np.ascontiguousarray(costmap.get_origin(), dtype=np.float64)
-            res = float(costmap.get_resolution())
+            self.resolution = float(costmap.get_resolution())
             data_dev = torch.from_numpy(data).to(self.device)
             self._keep["map"] = data_dev
             self._origin_host = origins
             _lib.check(self._lib.bcp_set_costmaps(self._h, data_dev.data_ptr(), rows, cols, 1, None, None,
-                                                  origins.ctypes.data, 0, res, self._stream()))
+                                                  origins.ctypes.data, 0, self.resolution, self._stream()))
         else:
             costmaps = list(costmap)
-            if len(costmaps) != n:
-                raise ValueError("need one costmap per env (%d), got %d" % (n, len(costmaps)))
-            res = float(costmaps[0].get_resolution())
-            if any(float(c.get_resolution()) != res for c in costmaps):
-                raise ValueError("all costmaps must share one resolution")
-            self._costmaps, self._shared_map = costmaps, False
-            rows = max(self._map_storage[0], max(c.get_data().shape[0] for c in costmaps))
-            cols = max(self._map_storage[1], max(c.get_data().shape[1] for c in costmaps))
-            data = np.zeros((n, rows, cols), dtype=np.uint8)
-            vr = np.zeros(n, dtype=np.int32)
-            vc = np.zeros(n, dtype=np.int32)
-            origins = np.zeros((n, 2), dtype=np.float64)
-            for i, c in enumerate(costmaps):
-                d = c.get_data()
-                data[i, :d.shape[0], :d.shape[1]] = d
-                vr[i], vc[i] = d.shape
-                origins[i] = c.get_origin()
-            self.set_costmap_tensors(torch.from_numpy(data).to(self.device), torch.from_numpy(origins).to(self.device),
-                                     res, torch.from_numpy(vr).to(self.device), torch.from_numpy(vc).to(self.device))
-        self.resolution = res
+            if len(costmaps) != self.n_envs:
+                raise ValueError("need one costmap per env (%d), got %d" % (self.n_envs, len(costmaps)))
+            data, shapes, origins, res = stack_costmaps(costmaps, self._map_storage)
+            self._costmaps = costmaps
+            self.set_costmap_tensors(self._device_tensor(data, torch.uint8), self._device_tensor(origins), res,
+                                     self._device_tensor(shapes[:, 0], torch.int32),
+                                     self._device_tensor(shapes[:, 1], torch.int32))
 
-    def _set_from_templates(self, costmaps, paths):
-        """Private per-env costmaps / paths expanded on the device from a few templates."""
-        n, dev = self.n_envs, self.device
-        dp = getattr(self, "_device_pool", None)
-        if dp is not None:   # everything is on the device already (refined paths included)
-            self._costmaps, self._paths, self._shared_path = costmaps, paths, False
-            self.set_costmap_tensors(dp.maps, dp.entry_origins(dev), dp.resolution, dp.valid_rows, dp.valid_cols)
-            self._keep.update(path=dp.path_points, lens=dp.lens)
-            _lib.check(self._lib.bcp_set_paths(self._h, dp.path_points.data_ptr(), dp.lens.data_ptr(),
-                                               int(dp.path_points.shape[1]), 0, self._stream()))
-            torch.cuda.current_stream(dev).synchronize()
-            return
-        if self.geom_of_env is not None:   # geometry pool: the library indexes the entries itself
-            idx = torch.arange(len(costmaps), device=dev)
-        else:
-            idx = torch.from_numpy(self._template_of_env).to(dev)
-            assert idx.numel() == n and int(idx.max()) < len(costmaps) == len(paths)
-        res = float(costmaps[0].get_resolution())
-        rows = max(self._map_storage[0], max(c.get_data().shape[0] for c in costmaps))
-        cols = max(self._map_storage[1], max(c.get_data().shape[1] for c in costmaps))
-        t_data = np.zeros((len(costmaps), rows, cols), dtype=np.uint8)
-        t_shape = np.zeros((len(costmaps), 2), dtype=np.int32)
-        t_org = np.zeros((len(costmaps), 2), dtype=np.float64)
-        for t, c in enumerate(costmaps):
-            d = c.get_data()
-            t_data[t, :d.shape[0], :d.shape[1]] = d
-            t_shape[t] = d.shape
-            t_org[t] = c.get_origin()
-        data = torch.from_numpy(t_data).to(dev)[idx].contiguous()
-        shape = torch.from_numpy(t_shape).to(dev)[idx]
-        self._costmaps, self._shared_map = costmaps, False
-        self.set_costmap_tensors(data, torch.from_numpy(t_org).to(dev)[idx].contiguous(), res,
+    def _set_from_device_pool(self, dp):
+        """A pool whose maps, refined paths and initial states are on the device already: bound where they are."""
+        self._costmaps, self._paths, self._shared_path = dp.costmaps, dp.paths, False
+        self.set_costmap_tensors(dp.maps, dp.entry_origins(self.device), dp.resolution, dp.valid_rows, dp.valid_cols)
+        self._bind_paths(dp.path_points, dp.lens)
+
+    def _set_from_templates(self, costmaps, paths, template_of_env):
+        """Private costmaps / paths from a few templates: one copy per env, expanded on the device, or -- template_of_env
+        None -- the templates themselves, as the entries of a geometry pool."""
+        dev = self.device
+        pick = lambda t: t   # noqa: E731
+        if template_of_env is not None:
+            idx = torch.from_numpy(template_of_env).to(dev)
+            assert idx.numel() == self.n_envs and int(idx.max()) < len(costmaps) == len(paths)
+            pick = lambda t: t[idx]   # noqa: E731
+        data, shapes, origins, res = stack_costmaps(costmaps, self._map_storage)
+        shape = pick(torch.from_numpy(shapes).to(dev))
+        self._costmaps = costmaps
+        self.set_costmap_tensors(pick(torch.from_numpy(data).to(dev)).contiguous(),
+                                 pick(torch.from_numpy(origins).to(dev)).contiguous(), res,
                                  shape[:, 0].contiguous(), shape[:, 1].contiguous())
-        refine = (lambda p: host_init.refine_path(p, self.params.path_delta)) if self.params.refine_path else (lambda p: p)
-        tp = [np.ascontiguousarray(refine(np.asarray(p)), dtype=np.float64) for p in paths]
-        max_len = max(len(p) for p in tp)
-        buf = np.zeros((len(tp), max_len, 3), dtype=np.float64)
-        for t, p in enumerate(tp):
-            buf[t, :len(p)] = p
-        self._paths, self._shared_path = tp, False
-        pdev = torch.from_numpy(buf).to(dev)[idx].contiguous()
-        lens = torch.from_numpy(np.array([len(p) for p in tp], dtype=np.int32)).to(dev)[idx].contiguous()
-        self._keep.update(path=pdev, lens=lens)
-        _lib.check(self._lib.bcp_set_paths(self._h, pdev.data_ptr(), lens.data_ptr(), max_len, 0, self._stream()))
-        torch.cuda.current_stream(dev).synchronize()
+        points, lens, self._paths = stack_paths(paths, self._refine())
+        self._shared_path = False
+        self._bind_paths(pick(torch.from_numpy(points).to(dev)).contiguous(), pick(torch.from_numpy(lens).to(dev)).contiguous())
+
+    def _bind_paths(self, points, lens):
+        """Device paths [., max_len, 3] of lens [.] points each; lens None: ONE path [len, 3] shared by all envs."""
+        self._keep.update(path=points, lens=lens)
+        _lib.check(self._lib.bcp_set_paths(self._h, points.data_ptr(), lens.data_ptr() if lens is not None else None,
+                                           int(points.shape[-2]), int(lens is None), self._stream()))
+        torch.cuda.current_stream(self.device).synchronize()  # a staging tensor may now be released
 
     def set_costmap_tensors(self, data, origins, resolution, valid_rows=None, valid_cols=None):
         """Private costmaps straight from device tensors: data uint8 [N, rows, cols], origins float64 [N, 2]
@@ -677,11 +267,6 @@ class BatchedPlanEnv(object):
         pool entries), padded to one shape where the entries differ."""
         return self._keep["map"]
 
-    def footprint(self):
-        """The footprint [n_verts, 2] in metres the handle was created with (footprint_scale applied)."""
-        p = self._bcp_params
-        return np.array([[p.verts[k][0], p.verts[k][1]] for k in range(p.n_verts)], dtype=np.float64)
-
     def _inflate(self, maps, vr, vc, radius, cost_scaling_factor, out):
         _lib.check(self._lib.bcp_inflate_costmaps(
             self._h, maps.data_ptr(), maps.shape[0], maps.shape[1], maps.shape[2],
@@ -698,10 +283,10 @@ class BatchedPlanEnv(object):
         A pool that lives on the device (sampler="device_resident") is inflated where it is: whoever else holds that pool
         sees the inflated entries.  Refused on endless=True pools (refresh() would write raw worlds into the inflated
         pool; inflating re-sampled worlds is not implemented), and when called a second time."""
-        if getattr(self, "endless", False):
+        if self.endless:
             raise RuntimeError("inflate_costmaps: not supported on endless=True pools -- refresh() re-samples raw worlds "
                                "into the pool, and inflating re-sampled worlds is out of scope")
-        if getattr(self, "_inflated", False):
+        if self._inflated:
             raise RuntimeError("inflate_costmaps: the costmaps of this env are inflated already")
         radius = robots.inscribed_radius(self.footprint() if footprint is None else footprint)
         data = self._keep["map"]
@@ -714,17 +299,12 @@ class BatchedPlanEnv(object):
         else:
             self.set_costmap_tensors(data, self._keep["origins"], self.resolution, vr, vc)
         # the host copies behind envs[i].get_state().costmap (a device pool hands out copies of its tensors on demand)
-        if getattr(self, "_device_pool", None) is None:
+        if self._device_pool is None:
             host = list(self._costmaps)
-            rows, cols = max(c.get_data().shape[0] for c in host), max(c.get_data().shape[1] for c in host)
-            stack = np.zeros((len(host), rows, cols), dtype=np.uint8)
-            for k, c in enumerate(host):
-                d = c.get_data()
-                stack[k, :d.shape[0], :d.shape[1]] = d
-            shapes = np.array([c.get_data().shape for c in host], dtype=np.int32)
+            stack, shapes, _, _ = stack_costmaps(host)
             dev_stack = torch.from_numpy(stack).to(self.device)
-            self._inflate(dev_stack, torch.from_numpy(shapes[:, 0].copy()).to(self.device),
-                          torch.from_numpy(shapes[:, 1].copy()).to(self.device), radius, cost_scaling_factor, dev_stack)
+            self._inflate(dev_stack, self._device_tensor(shapes[:, 0], torch.int32),
+                          self._device_tensor(shapes[:, 1], torch.int32), radius, cost_scaling_factor, dev_stack)
             inflated = dev_stack.cpu().numpy()
             self._costmaps = [CostMap2D(inflated[k, :s[0], :s[1]].copy(), c.get_resolution(), c.get_origin())
                               for k, (c, s) in enumerate(zip(host, shapes))]
@@ -732,67 +312,38 @@ class BatchedPlanEnv(object):
         self._inflated = True
 
     def _set_paths(self, path):
-        refine = (lambda p: host_init.refine_path(p, self.params.path_delta)) if self.params.refine_path else (lambda p: p)
-        if isinstance(path, np.ndarray) and path.ndim == 2:
-            p = np.ascontiguousarray(refine(path), dtype=np.float64)
-            assert p.shape[1] == 3
-            self._paths, self._shared_path = [p], True
-            dev = torch.from_numpy(p).to(self.device)
-            self._keep["path"] = dev
-            _lib.check(self._lib.bcp_set_paths(self._h, dev.data_ptr(), None, p.shape[0], 1, self._stream()))
+        self._shared_path = isinstance(path, np.ndarray) and path.ndim == 2
+        points, lens, self._paths = stack_paths([path] if self._shared_path else path, self._refine())
+        if self._shared_path:
+            self._bind_paths(torch.from_numpy(points[0]).to(self.device), None)
         else:
-            paths = [np.ascontiguousarray(refine(np.asarray(p)), dtype=np.float64) for p in path]
-            if len(paths) != self.n_envs:
-                raise ValueError("need one path per env (%d), got %d" % (self.n_envs, len(paths)))
-            self._paths, self._shared_path = paths, False
-            max_len = max(len(p) for p in paths)
-            buf = np.zeros((self.n_envs, max_len, 3), dtype=np.float64)
-            lens = np.zeros(self.n_envs, dtype=np.int32)
-            for i, p in enumerate(paths):
-                buf[i, :len(p)] = p
-                lens[i] = len(p)
-            dev, lens_dev = torch.from_numpy(buf).to(self.device), torch.from_numpy(lens).to(self.device)
-            self._keep.update(path=dev, lens=lens_dev)
-            _lib.check(self._lib.bcp_set_paths(self._h, dev.data_ptr(), lens_dev.data_ptr(), max_len, 0,
-                                               self._stream()))
-        torch.cuda.current_stream(self.device).synchronize()  # the [.,3] staging tensor may now be released
+            if len(self._paths) != self.n_envs:
+                raise ValueError("need one path per env (%d), got %d" % (self.n_envs, len(self._paths)))
+            self._bind_paths(torch.from_numpy(points).to(self.device), torch.from_numpy(lens).to(self.device))
 
     def _make_initial_state(self):
         """make_initial_state (env.py:179-214): pose = path[0], v = w = 0, wheel at initial_wheel_angle... the
         reference's TricycleRobotState() default wheel angle is 0.0 and PlanEnv never applies
         params.initial_wheel_angle to it, so neither do we."""
+        dev, dp = self.device, self._device_pool
         n = self.n_envs if self.geom_of_env is None else len(self._paths)
-        dp = getattr(self, "_device_pool", None)
         if dp is not None:   # initial states computed on the device with the paths (bcp_mini_world_paths)
-            dev = self.device
             robot_t = torch.zeros(7, n, dtype=torch.float64, device=dev)
             robot_t[0:3] = dp.path_points[:, 0, :].t()
             return BatchedState(robot_t, dp.init[:, 0].contiguous(), dp.init[:, 1].to(torch.int32).contiguous(),
                                 torch.zeros(n, dtype=torch.int32, device=dev), torch.zeros(n, dtype=torch.uint8, device=dev))
-        robot = np.zeros((7, n), dtype=np.float64)
-        md = np.zeros(n, dtype=np.float64)
-        ti = np.zeros(n, dtype=np.int32)
-        rp = self.params.reward_provider_params
-        if self.geom_of_env is not None:   # one initial state per pool entry
-            for g, p in enumerate(self._paths):
-                md[g], ti[g] = self._first_reward_state(p, rp)
-                robot[0:3, g] = p[0]
-        elif self._shared_path:
-            p = self._paths[0]
-            m0, t0 = self._first_reward_state(p, rp)
-            robot[0:3, :] = p[0][:, None]
-            md[:], ti[:] = m0, t0
+        # one initial state per stored path, then per env (per entry with a geometry pool) the one of its path
+        per = [self._first_reward_state(p, self.params.reward_provider_params) for p in self._paths]
+        if self._shared_path:
+            of = np.zeros(n, dtype=np.int64)
         elif self._template_of_env is not None:
-            per = [self._first_reward_state(p, rp) for p in self._paths]
-            tix = self._template_of_env
-            md[:] = np.array([m for m, _ in per])[tix]
-            ti[:] = np.array([t for _, t in per])[tix]
-            robot[0:3, :] = np.stack([p[0] for p in self._paths])[tix].T
+            of = self._template_of_env
         else:
-            for i, p in enumerate(self._paths):
-                md[i], ti[i] = self._first_reward_state(p, rp)
-                robot[0:3, i] = p[0]
-        dev = self.device
+            of = np.arange(n)
+        robot = np.zeros((7, n), dtype=np.float64)
+        robot[0:3] = np.stack([p[0] for p in self._paths])[of].T
+        md = np.array([m for m, _ in per], dtype=np.float64)[of]
+        ti = np.array([t for _, t in per], dtype=np.int32)[of]
         return BatchedState(torch.from_numpy(robot).to(dev), torch.from_numpy(md).to(dev), torch.from_numpy(ti).to(dev),
                             torch.zeros(n, dtype=torch.int32, device=dev), torch.zeros(n, dtype=torch.uint8, device=dev))
 
@@ -822,17 +373,6 @@ class BatchedPlanEnv(object):
         for i, r in enumerate(records):
             env.envs[i].set_state(State.deserialize(r['state']))
         return env
-
-    def set_tuning(self, exact_mode=None, dense_threshold=None, cull=None, defer=None, edt_lds=None, fused=None,
-                   ego_sparse=None, near_dilate=None, local_pairs=None, ego_list_stride=None, near_shift=None):
-        """Execution knobs of libbcplan (bcp_set_tuning); results never depend on them.
-        (near_shift takes effect when the costmaps are bound the next time.)"""
-        for key, val in ((_lib.TUNE_EXACT_MODE, exact_mode), (_lib.TUNE_DENSE_THRESHOLD, dense_threshold),
-                         (_lib.TUNE_CULL, cull), (_lib.TUNE_DEFER, defer), (_lib.TUNE_EDT_LDS, edt_lds),
-                         (_lib.TUNE_FUSED, fused), (_lib.TUNE_EGO_SPARSE, ego_sparse), (_lib.TUNE_LOCAL_PAIRS, local_pairs), (_lib.TUNE_EGO_LIST_STRIDE, ego_list_stride),
-                         (_lib.TUNE_NEAR_DILATE, near_dilate), (_lib.TUNE_NEAR_SHIFT, near_shift)):
-            if val is not None:
-                _lib.check(self._lib.bcp_set_tuning(self._h, key, int(val)))
 
     def distance_field(self, first=0, count=1):
         """The distance fields libbcplan pre-classifies poses with (bcp_get_distance_field), for `count` map entries
@@ -887,11 +427,6 @@ class BatchedPlanEnv(object):
         return self._time_table_dev[idx]
 
     # ------------------------------------------------------------------ reference API
-    def seed(self, seed=None):
-        """Seeds the on-device odometry-noise stream (the reference draws from numpy's global RNG)."""
-        if seed is not None:
-            _lib.check(self._lib.bcp_seed(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF))
-
     def reset(self, mask=None):
         """PlanEnv.reset for all envs, or for those with mask[i] != 0 (uint8/bool device tensor)."""
         ptr = None
@@ -929,7 +464,7 @@ class BatchedPlanEnv(object):
             mask = mask.to(self.device).to(torch.uint8).contiguous()
             ptr = mask.data_ptr()
         _lib.check(self._lib.bcp_broadcast_state(self._h, int(src), ptr, self._stream()))
-        self._last_inputs = (mask,)   # keep the mask alive until the stream has consumed it
+        self._alive["fan_out"] = (mask,)   # keep the mask alive until the stream has consumed it
 
     def step(self, actions, noise_z=None, noise_z_out=None, done_out=None):
         """One tick for every env.  actions: [N,2] (float32 or float64) tensor / array, or a list of Action.
@@ -966,24 +501,13 @@ class BatchedPlanEnv(object):
         rc = self._bcp_step(self._h, self._io_ref, flags, torch.cuda.current_stream(self.device).cuda_stream)
         if rc:
             _lib.check(rc)
-        self._last_inputs = (actions, z, done)  # keep inputs alive until the stream has consumed them
+        self._alive["step"] = (actions, z, done)  # keep inputs alive until the stream has consumed them
         return self._obs, self.reward, done, self._info
 
-    def _device_tensor(self, x, dtype=None, shape=None):
-        """A tensor, or anything numpy can wrap, on the env's device and contiguous.  dtype None keeps float32 / float64
-        and widens everything else to float64; a shape, if given, is asserted."""
-        if not isinstance(x, torch.Tensor):
-            x = torch.from_numpy(np.ascontiguousarray(x))
-        if dtype is None:
-            dtype = x.dtype if x.dtype in (torch.float32, torch.float64) else torch.float64
-        x = x.to(self.device).to(dtype).contiguous()
-        assert shape is None or tuple(x.shape) == shape
-        return x
-
-    def _cached_outputs(self, cache_name, key, shapes, names):
-        """{name: zero-initialised device buffer of shapes[name] = (shape, dtype)}, made on first use and cached in
-        self.<cache_name>[key] -- a planner that calls every tick allocates nothing."""
-        buf = self.__dict__.setdefault(cache_name, {}).setdefault(key, {})
+    def _cached_outputs(self, cache, key, shapes, names, limit=None):
+        """{name: zero-initialised device buffer of shapes[name] = (shape, dtype)}, made on first use and kept in
+        cache[key] -- a planner that calls every tick allocates nothing."""
+        buf = cached(cache, key, dict, limit)
         out = {}
         for name in names:
             shape, dtype = shapes[name]
@@ -1023,7 +547,7 @@ class BatchedPlanEnv(object):
             assert collided_out.dtype == torch.uint8 and tuple(collided_out.shape) == (k, n) and collided_out.is_contiguous()
         if err_out is not None:
             assert err_out.dtype == torch.int32 and tuple(err_out.shape) == (k, n) and err_out.is_contiguous()
-        rows = self._cached_outputs("_rollout_buffers", k, {"collided": ((k, n), torch.uint8), "err": ((k, n), torch.int32)},
+        rows = self._cached_outputs(self._rollout_buffers, k, {"collided": ((k, n), torch.uint8), "err": ((k, n), torch.int32)},
                                     [name for name, given in (("collided", collided_out), ("err", err_out)) if given is None])
         collided_out = rows["collided"] if collided_out is None else collided_out
         err_out = rows["err"] if err_out is None else err_out
@@ -1036,7 +560,7 @@ class BatchedPlanEnv(object):
         self.err.zero_()
         for bit in (_lib.ERR_ANGLE_JUMP, _lib.ERR_TIME_ORDER, _lib.ERR_INTERNAL):
             self.err |= (err_out & bit).amax(dim=0)
-        self._last_inputs = tuple(keep)
+        self._alive["rollout"] = tuple(keep)
         return reward, done
 
     def lookahead(self, actions, noise_z=None, mask=None, want=("final_pose", "best")):
@@ -1079,12 +603,12 @@ class BatchedPlanEnv(object):
             mask = self._device_tensor(mask, torch.uint8, (n,))
             io.mask = mask.data_ptr()
             keep.append(mask)
-        out = self._cached_outputs("_lookahead_buffers", (h, k), shapes,
+        out = self._cached_outputs(self._lookahead_buffers, (h, k), shapes,
                                    [name for name in Lookahead.FIELDS if name in want or name in Lookahead.FIELDS[:3]])
         for name, t in out.items():
             setattr(io, name, t.data_ptr())
         _lib.check(self._lib.bcp_lookahead(self._h, C.byref(io), flags, self._stream()))
-        self._last_lookahead_inputs = tuple(keep)   # alive until the stream has consumed them
+        self._alive["lookahead"] = tuple(keep)   # alive until the stream has consumed them
         return Lookahead(h, k, **out)
 
     def mppi(self, mean, sigma, iterations, n_candidates, lam, collision_penalty, seed=0, draw_index=0, mask=None, eps=None,
@@ -1142,18 +666,18 @@ class BatchedPlanEnv(object):
         shapes = {"action": ((n, 2), action_dtype), "eps": ((it, n, k, h, 2), torch.float32),
                   "iter_mean": ((it, n, h, 2), torch.float64), "iter_ret": ((it, n, k), torch.float64),
                   "iter_reason": ((it, n, k), torch.uint8), "err": ((n,), torch.int32)}
-        out = self._cached_outputs("_mppi_buffers", (h, k, it), shapes,
+        out = self._cached_outputs(self._mppi_buffers, (h, k, it), shapes,
                                    ["action"] + [name for name in Mppi.FIELDS if name in want])
         for name, t in out.items():
             setattr(io, "eps_out" if name == "eps" else name, t.data_ptr())
         flags = _lib.STEP_ACTIONS_F32 if action_dtype == torch.float32 else 0
         _lib.check(self._lib.bcp_mppi(self._h, C.byref(p), C.byref(io), flags, self._stream()))
-        self._last_mppi_inputs = tuple(keep)   # alive until the stream has consumed them
+        self._alive["mppi"] = tuple(keep)   # alive until the stream has consumed them
         return Mppi(h, k, it, mean, **out)
 
     def _beam_table(self, beam_angles):
         """The device table [B, 2] of (cos, sin) of the beam angles (beam_table_cached)."""
-        return beam_table_cached(self.__dict__.setdefault("_beam_tables", OrderedDict()), beam_angles, self.device)
+        return beam_table_cached(self._beam_tables, beam_angles, self.device)
 
     def range_scan(self, beam_angles, max_range, poses=None, want=()):
         """A planar range scan per env (bcp_range_scan, one kernel launch, nothing of the env changes): the distance in
@@ -1166,29 +690,12 @@ class BatchedPlanEnv(object):
         [n, B], or (ranges, *wanted in the order given), device tensors, no sync.  The (cos, sin) table of an angle set is
         uploaded once; the outputs are cached per (n, B), so a caller that scans every tick allocates nothing (both caches keep
         the SCAN_CACHE_ENTRIES most recently used entries)."""
-        table = self._beam_table(beam_angles)
-        b = int(table.shape[0])
-        unknown = set(want) - {"hit", "heading_cs"}
-        if unknown:
-            raise ValueError("range_scan: unknown outputs %s" % sorted(unknown))
-        keep = [table]
         if poses is not None:
             poses = self._device_tensor(poses, torch.float64)
             assert poses.dim() == 2 and poses.shape[1] == 3
-            keep.append(poses)
-        n = self.n_envs if poses is None else int(poses.shape[0])
-        shapes = {"ranges": ((n, b), torch.float32), "hit": ((n, b), torch.int32), "heading_cs": ((n, 2), torch.float64)}
-        buffers = self.__dict__.setdefault("_range_scan_buffers", OrderedDict())
-        out = self._cached_outputs("_range_scan_buffers", (n, b), shapes, ["ranges"] + [w for w in want])
-        buffers.move_to_end((n, b))
-        while len(buffers) > SCAN_CACHE_ENTRIES:   # (a caller that sweeps shapes does not pile up device memory)
-            buffers.popitem(last=False)
-        _lib.check(self._lib.bcp_range_scan(
-            self._h, poses.data_ptr() if poses is not None else None, n, table.data_ptr(), b, float(max_range),
-            out["ranges"].data_ptr(), out["hit"].data_ptr() if "hit" in out else None,
-            out["heading_cs"].data_ptr() if "heading_cs" in out else None, self._stream()))
-        self._last_scan_inputs = tuple(keep)   # alive until the stream has consumed them
-        return out["ranges"] if not want else (out["ranges"],) + tuple(out[w] for w in want)
+        return self._range_scan(poses, self.n_envs if poses is None else int(poses.shape[0]), beam_angles, max_range, want,
+                                lambda n, b, shapes, names: self._cached_outputs(self._range_scan_buffers, (n, b), shapes,
+                                                                                 names, SCAN_CACHE_ENTRIES))
 
     def enable_episode_record(self, capacity=None):
         """Keep what every episode end leaves behind (bcp_bind_episode_record): from now on step() returns
@@ -1231,10 +738,9 @@ class BatchedPlanEnv(object):
     def geometry_digest(self):
         """Digest of the geometry this rank's envs share (distributed.geometry_digest): the costmap(s) and path(s) as they
         were given -- for distributed.check_same_geometry at set-up of a sharded job."""
-        import numpy as np
         from . import distributed
         parts = []
-        dp = getattr(self, "_device_pool", None)
+        dp = self._device_pool
         if dp is not None:   # a pool that lives on the GPU: its first entries stand for it
             return distributed.geometry_digest(dp.maps[:16].cpu().numpy(), dp.origin, np.float64(dp.resolution),
                                                dp.path_points[:16].cpu().numpy(), dp.lens[:16].cpu().numpy())
@@ -1289,14 +795,3 @@ class BatchedPlanEnv(object):
 
     def render(self, mode='human'):
         raise NotImplementedError("rendering is out of scope of the batched step path")
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            self._lib.bcp_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -179,6 +179,7 @@ class DoneGather(object):
         if self.packed and self.n_local % 8:
             raise ValueError("DoneGather(packed=True) needs a multiple of 8 envs per rank, got %d" % self.n_local)
         self.out = torch.zeros(self.world * (self.n_local // 8 if self.packed else self.n_local), dtype=torch.uint8, device=device)
+        self._work = [None, None]   # the pipelined form's gathers in flight
 
     def __call__(self, done_local, async_op=False):
         if self.packed:
@@ -204,7 +205,6 @@ class DoneGather(object):
             self._stage = [torch.empty(self.n_local // 8 if self.packed else self.n_local, dtype=torch.uint8, device=done_local.device)
                            for _ in range(2)]
             self._outs = [self.out, torch.empty_like(self.out)]
-            self._work = [None, None]
             self._k = 0
         k = self._k
         if self._work[k] is not None:  # buffer k was used two launches ago: its gather must have completed
@@ -237,6 +237,6 @@ class DoneGather(object):
 
     def flush(self):
         for k in range(2):
-            if getattr(self, "_work", [None, None])[k] is not None:
+            if self._work[k] is not None:
                 self._work[k].wait()
                 self._work[k] = None

@@ -9,6 +9,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .wrappers import BatchedObservationWrapper
 
 
 def _f64x2(v):
@@ -17,26 +18,21 @@ def _f64x2(v):
     return a
 
 
-class BatchedEgocentricCostmap(object):
+class BatchedEgocentricCostmap(BatchedObservationWrapper):
     """Observation wrapper around a BatchedPlanEnv (or BatchedRandomMiniEnv): step() / reset() return
     OrderedDict(env=uint8 [N, H, W, 1], goal_n_state=float32 [N, 9, 1]) device tensors (8 rows for a diff-drive robot).
     The window defaults are the reference's: 0.5 m behind to 3 m ahead of the robot, 2 m to each side.
-    final_observation=True: the env's episode record is enabled (env.enable_episode_record) and step() adds
-    info["final_observation"], the observation of every episode that ended in the step, drawn from its final state
-    before the auto-reset (SB3's terminal_observation, gymnasium's final_obs): the same keys with leading dimension
-    `capacity`, row j belongs to env info["episode_ends"].env_ids[j] for j < count.
+    final_observation=True: step() adds info["final_observation"] (BatchedObservationWrapper).
     pool=p > 1: the images are the maxima of the p x p blocks of the full image (bcp_egocentric_costmaps_pooled), made
     without the full image reaching memory: image_shape is the pooled shape, full_image_shape the window's (H, W); the
     goal vectors stay those of the full window."""
 
     def __init__(self, env, x_bounds=(-0.5, 3.), y_bounds=(-2., 2.), border_value=0, final_observation=False, pool=1):
-        self.env = env
+        super(BatchedEgocentricCostmap, self).__init__(env)
         self.pool = int(pool)
-        self.action_space = env.action_space
         self._origin = _f64x2([x_bounds[0], y_bounds[0]])
         self._size = _f64x2([x_bounds[1] - x_bounds[0], y_bounds[1] - y_bounds[0]])
         self._border = int(border_value)
-        self._lib = env._lib
         shape = (C.c_int32 * 2)()
         _lib.check(self._lib.bcp_egocentric_shape(env._h, self._size.ctypes.data_as(_lib._f64p), shape))
         self.full_image_shape = (int(shape[0]), int(shape[1]))
@@ -49,30 +45,20 @@ class BatchedEgocentricCostmap(object):
         # CostMap2D.world_size() of the extracted map (utilities/costmap_2d.py:107-121)
         self._world = _f64x2([(self._origin[0] + res * shape[1]) - self._origin[0],
                               (self._origin[1] + res * shape[0]) - self._origin[1]])
-        n, dev = env.n_envs, env.device
-        self.n_state = 6 if env.is_tricycle else 5
-        self.images = torch.zeros((n,) + self.image_shape + (1,), dtype=torch.uint8, device=dev)
-        self.goal_n_state = torch.zeros((n, 3 + self.n_state, 1), dtype=torch.float32, device=dev)
+        self.images = torch.zeros((env.n_envs,) + self.image_shape + (1,), dtype=torch.uint8, device=env.device)
+        self.goal_n_state = self._goal_vector(env.n_envs)
         self._obs = OrderedDict((('env', self.images), ('goal_n_state', self.goal_n_state)))
-        self._final = None
-        if final_observation:
-            ends = env.episode_ends if env.episode_ends is not None else env.enable_episode_record()
-            self._alloc_final(ends.capacity)
-
-    def unwrapped(self):
-        return self.env
+        self._init_final(final_observation)
 
     def observation(self, _observation=None):
         """Refresh and return the observation of the envs' current state (device tensors, no sync)."""
-        e = self.env
         stream = self._refresh_images()
-        _lib.check(self._lib.bcp_goal_n_state(e._h, self._world.ctypes.data_as(_lib._f64p),
+        _lib.check(self._lib.bcp_goal_n_state(self.env._h, self._world.ctypes.data_as(_lib._f64p),
                                               self.goal_n_state.data_ptr(), stream))
         return self._obs
 
     def _refresh_images(self):
-        e = self.env
-        stream = C.c_void_p(torch.cuda.current_stream(e.device).cuda_stream)
+        e, stream = self.env, self._stream()
         if self.pool == 1:
             _lib.check(self._lib.bcp_egocentric_costmaps(
                 e._h, None, e.n_envs, self._origin.ctypes.data_as(_lib._f64p), self._size.ctypes.data_as(_lib._f64p),
@@ -94,22 +80,12 @@ class BatchedEgocentricCostmap(object):
     _FINAL_KEYS = ('env', 'goal_n_state')
 
     def _final_vector(self, cap):
-        return torch.zeros((cap, 3 + self.n_state, 1), dtype=torch.float32, device=self.env.device)
+        return self._goal_vector(cap)
 
     def _alloc_final(self, cap):
         self.final_images = torch.zeros((cap,) + self.image_shape + (1,), dtype=torch.uint8, device=self.env.device)
         self.final_vector = self._final_vector(cap)
-        self._final = OrderedDict(zip(self._FINAL_KEYS, (self.final_images, self.final_vector)))
-
-    def _final_buffers(self):
-        """The buffers follow the env's record: a record bound again with another capacity gets buffers of that size."""
-        ends = self.env.episode_ends
-        if ends is None:
-            raise RuntimeError("final_observation=True needs the env's episode record (env.disable_episode_record() "
-                               "was called)")
-        if self.final_images.shape[0] != ends.capacity:
-            self._alloc_final(ends.capacity)
-        return self._final
+        return OrderedDict(zip(self._FINAL_KEYS, (self.final_images, self.final_vector)))
 
     def _final_images(self, stream):
         e = self.env
@@ -122,46 +98,11 @@ class BatchedEgocentricCostmap(object):
                 e._h, self._origin.ctypes.data_as(_lib._f64p), self._size.ctypes.data_as(_lib._f64p), self._border,
                 self.pool, self.final_images.data_ptr(), stream))
 
-    def _final_observation(self, stream):
+    def _draw_final(self, stream):
         """The final observations of the record's slots (bcp_final_egocentric_costmaps / bcp_final_goal_n_state)."""
-        e = self.env
         self._final_images(stream)
-        _lib.check(self._lib.bcp_final_goal_n_state(e._h, self._world.ctypes.data_as(_lib._f64p),
+        _lib.check(self._lib.bcp_final_goal_n_state(self.env._h, self._world.ctypes.data_as(_lib._f64p),
                                                     self.final_vector.data_ptr(), stream))
-
-    def step(self, actions, **kw):
-        _o, reward, done, info = self.env.step(actions, **kw)
-        if self._final is not None:
-            # drawn now, on the step's stream: a pool refresh after this step may release the worlds the envs just left
-            final = self._final_buffers()
-            self._final_observation(C.c_void_p(torch.cuda.current_stream(self.env.device).cuda_stream))
-            info = dict(info, final_observation=final)   # (a copy: the env's own info dict stays as the env keeps it)
-        return self.observation(), reward, done, info
-
-    def reset(self, mask=None):
-        self.env.reset(mask)
-        return self.observation()
-
-    def seed(self, seed=None):
-        self.env.seed(seed)
-
-    def lookahead(self, actions, **kw):
-        return self.env.lookahead(actions, **kw)
-
-    def mppi(self, mean, *args, **kw):
-        return self.env.mppi(mean, *args, **kw)
-
-    def get_state(self):
-        return self.env.get_state()
-
-    def set_state(self, state):
-        self.env.set_state(state)
-
-    def render(self, mode='human'):
-        return self.env.render(mode)
-
-    def close(self):
-        self.env.close()
 
 
 class BatchedColoredEgoCostmap(BatchedEgocentricCostmap):
@@ -179,10 +120,9 @@ class BatchedColoredEgoCostmap(BatchedEgocentricCostmap):
     def _final_vector(self, cap):
         return torch.zeros((cap, 5, 1), dtype=torch.float64, device=self.env.device)
 
-    def _final_observation(self, stream):
-        e = self.env
+    def _draw_final(self, stream):
         self._final_images(stream)
-        _lib.check(self._lib.bcp_final_goal_direction_state(e._h, self._world.ctypes.data_as(_lib._f64p),
+        _lib.check(self._lib.bcp_final_goal_direction_state(self.env._h, self._world.ctypes.data_as(_lib._f64p),
                                                             self.final_vector.data_ptr(), stream))
 
     def observation(self, _observation=None):

@@ -19,7 +19,9 @@ import torch
 
 from . import _lib, robots
 from .api import CostMap2D, EnvParams
-from .batched_env import BatchedPlanEnv, DeviceGeometryPool
+from .batched_env import BatchedPlanEnv
+from .geometry import DeviceGeometryPool, pool_or_sample
+from .handle import Handle
 
 _TWO_PI = 2 * np.pi
 _MAX_TRIES = 1000
@@ -252,20 +254,16 @@ def prepare_map_and_path(mp, out=None):
 
 
 # ---- batched acceptance test on the GPU -----------------------------------------------------------------------
-class PoseCollider(object):
+class PoseCollider(Handle):
     """pose_collides of the two path ends for up to `capacity` candidate worlds per call (one launch)."""
 
     def __init__(self, env_params, capacity, device=0):
-        self._lib = _lib.load()
-        if not torch.cuda.is_available():
-            raise RuntimeError("sampling mini-env geometries needs a GPU (libbcplan has no CPU path)")
-        self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
         self.capacity = int(capacity)
         # the reference tests with a TricycleRobot carrying the configured robot's footprint (mini_env.py:336-337)
-        self._p = robots.make_bcp_params(env_params, env_params.robot_name, None)
-        self._h = C.c_void_p()
-        _lib.check(self._lib.bcp_create(C.byref(self._p), self.capacity, self.device.index or 0, 0, C.byref(self._h)))
+        super(PoseCollider, self).__init__(robots.make_bcp_params(env_params, env_params.robot_name, None), self.capacity,
+                                           device, needs_gpu="sampling mini-env geometries")
         self.resolution = float(env_params.resolution)
+        self._maps = None
 
     def __call__(self, costmaps, paths, batch=None):
         """costmaps: list of K <= capacity CostMap2D of one shape; paths: list of K [2,3] -> bool [K, 2].
@@ -280,29 +278,18 @@ class PoseCollider(object):
             origins[j] = costmaps[j].get_origin()
             poses[:, j] = paths[j]
         dev = self.device
-        if getattr(self, "_maps", None) is None or tuple(self._maps.shape[1:]) != (rows, cols):
+        if self._maps is None or tuple(self._maps.shape[1:]) != (rows, cols):
             self._maps = torch.zeros((cap, rows, cols), dtype=torch.uint8, device=dev)   # rows >= k keep stale maps:
         d = self._maps                                                                   # their poses are ignored
         d[:k].copy_(torch.from_numpy(np.ascontiguousarray(batch)))
         o, p = torch.from_numpy(origins).to(dev), torch.from_numpy(poses).to(dev)
         out = torch.empty(2 * cap, dtype=torch.uint8, device=dev)
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = self._stream()
         _lib.check(self._lib.bcp_set_costmaps(self._h, d.data_ptr(), rows, cols, 0, None, None, o.data_ptr(), 1,
                                               self.resolution, stream))
         _lib.check(self._lib.bcp_pose_collides(self._h, p.data_ptr(), 2 * cap, out.data_ptr(), stream))
         hit = out.cpu().numpy().reshape(2, cap)[:, :k].T.astype(bool)   # (synchronises: d, o, p may go)
         return hit
-
-    def close(self):
-        if self._h:
-            self._lib.bcp_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class _Chain(object):
@@ -507,27 +494,19 @@ class BatchedRandomMiniEnv(BatchedPlanEnv):
             sampler, seeds = "device_resident", (range(base, base + int(n_envs)) if seeds is None else seeds)
             if len(list(seeds)) != int(n_envs):
                 raise ValueError("endless=True needs one seed per env")
-        if pool is None:
-            if seeds is None:
-                seeds = range(int(n_chains) if n_chains else min(int(n_envs), 1024))
-            if sampler == "device_resident":
-                pool = sample_pool_device(params, list(seeds), episodes, device, keep_on_device=True)
-            else:
-                pool = {"device": sample_pool_device, "host": sample_pool}[sampler](params, list(seeds), episodes, device)
+        pool = pool_or_sample(pool, {
+            "device": lambda s: sample_pool_device(params, s, episodes, device),
+            "device_resident": lambda s: sample_pool_device(params, s, episodes, device, keep_on_device=True),
+            "host": lambda s: sample_pool(params, s, episodes, device)}, sampler, seeds, n_chains, n_envs)
         chains, per = len(pool.seeds), pool.episodes
-        i = np.arange(int(n_envs))
-        geom = (i % chains) * per + (i // chains) % per
-        self.pool = pool
-        on_device = isinstance(pool, DeviceGeometryPool)
         next_geom = pool.next_geom if draw_new_turn_on_reset else None
-        self.endless = bool(endless)
         if endless:   # the newest world's entry is the ring's guard (bcp_refresh_mini_worlds)
             next_geom = next_geom.copy()
             newest = np.arange(chains) * per + per - 1
             next_geom[newest] = newest
-        super(BatchedRandomMiniEnv, self).__init__(
-            pool if on_device else pool.costmaps, None if on_device else pool.paths, params.env_params, n_envs=n_envs,
-            device=device, geom_of_env=geom, next_geom=next_geom, **kw)
+        self._init_from_pool(pool, params.env_params, n_envs, next_geom, device=device, **kw)
+        self.endless = bool(endless)
+        self.side_cu_percent = 100   # share of the compute units of the overlapped refresh's stream (_make_side_stream)
         if endless:
             dev = self.device
             self._generated = torch.full((chains,), per, dtype=torch.int64, device=dev)
@@ -584,7 +563,7 @@ class BatchedRandomMiniEnv(BatchedPlanEnv):
         entries, refresh every 128 steps): 0.064 ms/step on an ordinary side stream, 0.078 with 50 % or 25 % of the
         compute units -- a refresh is throughput-bound (distance fields of ~7000 re-sampled maps), so confining it only
         makes it last longer; the default stays 100."""
-        share = int(getattr(self, "side_cu_percent", 100))
+        share = int(self.side_cu_percent)
         if 0 < share < 100:
             ptr = C.c_void_p()
             if self._lib.bcp_side_stream(self._h, share, C.byref(ptr)) == 0 and ptr.value:

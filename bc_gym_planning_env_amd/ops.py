@@ -13,56 +13,33 @@ try/except ImportError), batched over many inputs.
   range_scan            no counterpart: distances to the nearest lethal cell along beams (bcp_range_scan)
 """
 import ctypes as C
-from collections import OrderedDict
 
 import numpy as np
 import torch
 
 from . import _lib, robots
 from .api import EnvParams, INDUSTRIAL_TRICYCLE_V1
-from .batched_env import beam_table_cached
+from .handle import Handle
 
 
-class NativeOps(object):
+class NativeOps(Handle):
     """A libbcplan handle used only for the stand-alone operators (no env state bound)."""
 
     def __init__(self, robot_name=INDUSTRIAL_TRICYCLE_V1, device=0, noise_parameters=None, params=None,
                  footprint_scale=1.0, dynamic_model=True, model_front_column_pid=True, robot_constants=None):
-        self._lib = _lib.load()
-        if not torch.cuda.is_available():
-            raise RuntimeError("NativeOps needs a GPU (libbcplan has no CPU path)")
-        self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
         self.params = EnvParams() if params is None else params
-        self._p = robots.make_bcp_params(self.params, robot_name, noise_parameters, footprint_scale, dynamic_model,
-                                         model_front_column_pid, robot_constants=robot_constants)
-        self._h = C.c_void_p()
-        self._n_maps = 1
-        _lib.check(self._lib.bcp_create(C.byref(self._p), 1, self.device.index or 0, 0, C.byref(self._h)))
-        self._keep = {}
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def set_tuning(self, exact_mode=None, dense_threshold=None, cull=None, defer=None):
-        """Execution knobs of libbcplan (bcp_set_tuning); results never depend on them.  `cull` must be chosen
-        before set_costmap()."""
-        for key, val in ((_lib.TUNE_EXACT_MODE, exact_mode), (_lib.TUNE_DENSE_THRESHOLD, dense_threshold),
-                         (_lib.TUNE_CULL, cull), (_lib.TUNE_DEFER, defer)):
-            if val is not None:
-                _lib.check(self._lib.bcp_set_tuning(self._h, key, int(val)))
-
-    def _dev(self, a, dtype):
-        t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
-        return t.to(self.device, dtype).contiguous()
+        super(NativeOps, self).__init__(
+            robots.make_bcp_params(self.params, robot_name, noise_parameters, footprint_scale, dynamic_model,
+                                   model_front_column_pid, robot_constants=robot_constants), 1, device)
 
     def normalize_angle(self, z):
-        zin = self._dev(np.atleast_1d(z) if not isinstance(z, torch.Tensor) else z, torch.float64)
+        zin = self._device_tensor(np.atleast_1d(z) if not isinstance(z, torch.Tensor) else z, torch.float64)
         out = torch.empty_like(zin)
         _lib.check(self._lib.bcp_normalize_angle(self._h, zin.data_ptr(), out.data_ptr(), zin.numel(), self._stream()))
         return out
 
     def world_to_pixel(self, world_coords, origin, resolution):
-        xy = self._dev(world_coords, torch.float64)
+        xy = self._device_tensor(world_coords, torch.float64)
         flat = xy.reshape(-1, 2)
         out = torch.empty(flat.shape, dtype=torch.int64, device=self.device)
         org = np.ascontiguousarray(origin, dtype=np.float64)
@@ -73,11 +50,10 @@ class NativeOps(object):
 
     def get_pixel_footprint(self, angles, map_resolution, side=None):
         """-> (masks uint8 [n, side, side], shape_hw int32 [n, 2]); image i is masks[i, :h, :w]."""
-        ang = self._dev(np.atleast_1d(angles) if not isinstance(angles, torch.Tensor) else angles, torch.float64)
+        ang = self._device_tensor(np.atleast_1d(angles) if not isinstance(angles, torch.Tensor) else angles, torch.float64)
         n = ang.numel()
         if side is None:
-            fp = np.array([[self._p.verts[k][0], self._p.verts[k][1]] for k in range(self._p.n_verts)])
-            side = 2 * int(np.ceil(np.linalg.norm(fp, axis=1).max() / map_resolution)) + 3
+            side = 2 * int(np.ceil(np.linalg.norm(self.footprint(), axis=1).max() / map_resolution)) + 3
         masks = torch.empty((n, side, side), dtype=torch.uint8, device=self.device)
         shape = torch.zeros((n, 2), dtype=torch.int32, device=self.device)
         _lib.check(self._lib.bcp_pixel_footprint(self._h, ang.data_ptr(), n, float(map_resolution), masks.data_ptr(),
@@ -85,7 +61,7 @@ class NativeOps(object):
         return masks, shape
 
     def set_costmap(self, data, origin, resolution):
-        d = self._dev(data, torch.uint8)
+        d = self._device_tensor(data, torch.uint8)
         org = np.ascontiguousarray(origin, dtype=np.float64)
         self._keep["map"] = d
         _lib.check(self._lib.bcp_set_costmaps(self._h, d.data_ptr(), d.shape[0], d.shape[1], 1, None, None,
@@ -93,7 +69,7 @@ class NativeOps(object):
 
     def pose_collides(self, poses):
         """poses [n,3] against the costmap given to set_costmap -> uint8 [n]."""
-        p = self._dev(poses, torch.float64)
+        p = self._device_tensor(poses, torch.float64)
         out = torch.empty(p.shape[0], dtype=torch.uint8, device=self.device)
         _lib.check(self._lib.bcp_pose_collides(self._h, p.data_ptr(), p.shape[0], out.data_ptr(), self._stream()))
         return out
@@ -101,15 +77,15 @@ class NativeOps(object):
     def is_robot_colliding(self, poses):
         """is_robot_colliding (costmap_utils.py:106-164) for poses [n,3]: pose_collides, but never when the robot's own
         pixel is off the map -> uint8 [n]."""
-        p = self._dev(poses, torch.float64)
+        p = self._device_tensor(poses, torch.float64)
         out = torch.empty(p.shape[0], dtype=torch.uint8, device=self.device)
         _lib.check(self._lib.bcp_is_robot_colliding(self._h, p.data_ptr(), p.shape[0], out.data_ptr(), self._stream()))
         return out
 
     def is_footprint_colliding(self, image_slices, blit_masks, lethal=254):
         """is_footprint_colliding_impl(image_slice, blit_mask, lethal) for n pairs [n, rows, cols] -> uint8 [n]."""
-        sl = self._dev(image_slices, torch.uint8)
-        mk = self._dev(blit_masks, torch.uint8)
+        sl = self._device_tensor(image_slices, torch.uint8)
+        mk = self._device_tensor(blit_masks, torch.uint8)
         if sl.dim() == 2:
             sl, mk = sl[None], mk[None]
         assert sl.shape == mk.shape and sl.dim() == 3
@@ -120,7 +96,7 @@ class NativeOps(object):
 
     def set_path(self, path):
         """The (already refined) path [m,3] the reward operators below score against."""
-        p = self._dev(path, torch.float64)
+        p = self._device_tensor(path, torch.float64)
         assert p.dim() == 2 and p.shape[1] == 3
         self._keep["path"] = p
         _lib.check(self._lib.bcp_set_paths(self._h, p.data_ptr(), None, p.shape[0], 1, self._stream()))
@@ -129,11 +105,11 @@ class NativeOps(object):
     def reward(self, poses, min_spat_dist_so_far, target_idx, robot_collided=None):
         """reward_provider.reward(state) / .done(state) (reward.py:184-259) for n (pose, provider state) pairs ->
         (reward float64 [n], new min_spat_dist_so_far [n], new target_idx int32 [n], goal_reached uint8 [n])."""
-        p = self._dev(poses, torch.float64)
+        p = self._device_tensor(poses, torch.float64)
         n = p.shape[0]
-        md = self._dev(min_spat_dist_so_far, torch.float64).clone()
-        ti = self._dev(target_idx, torch.int32).clone()
-        col = self._dev(robot_collided, torch.uint8) if robot_collided is not None else None
+        md = self._device_tensor(min_spat_dist_so_far, torch.float64).clone()
+        ti = self._device_tensor(target_idx, torch.int32).clone()
+        col = self._device_tensor(robot_collided, torch.uint8) if robot_collided is not None else None
         rew = torch.empty(n, dtype=torch.float64, device=self.device)
         goal = torch.empty(n, dtype=torch.uint8, device=self.device)
         _lib.check(self._lib.bcp_reward(self._h, p.data_ptr(), n, md.data_ptr(), ti.data_ptr(),
@@ -143,7 +119,7 @@ class NativeOps(object):
 
     def find_last_reached(self, poses):
         """find_last_reached (path_tools.py:432-448) for poses [n,3] against the path of set_path -> int32 [n], -1 = None."""
-        p = self._dev(poses, torch.float64)
+        p = self._device_tensor(poses, torch.float64)
         out = torch.empty(p.shape[0], dtype=torch.int32, device=self.device)
         _lib.check(self._lib.bcp_find_last_reached(self._h, p.data_ptr(), p.shape[0], out.data_ptr(), self._stream()))
         return out
@@ -151,7 +127,7 @@ class NativeOps(object):
     def path_velocity(self, path_txyth):
         """path_velocity (path_tools.py:298-323): rows of (t, x, y, angle) -> (v, w) of the n - 1 segments; raises like
         the reference on corrupted angle data / non-increasing time stamps."""
-        p = self._dev(path_txyth, torch.float64)
+        p = self._device_tensor(path_txyth, torch.float64)
         n = p.shape[0]
         v = torch.empty(n - 1, dtype=torch.float64, device=self.device)
         w = torch.empty(n - 1, dtype=torch.float64, device=self.device)
@@ -171,15 +147,12 @@ class NativeOps(object):
                                                 out.data_ptr(), self._stream()))
         return out
 
-    def seed(self, seed):
-        _lib.check(self._lib.bcp_seed(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF))
-
     def extract_egocentric_costmap(self, poses, resulting_origin=None, resulting_size=None, border_value=0, pool=1):
         """The costmap given to set_costmap seen from each of poses [n,3] -> uint8 [n, rows, cols] (robot at (0, 0)
         heading +x; resulting_origin / resulting_size in metres, both or neither).  pool > 1: the maximum of every
         pool x pool block of that image instead, [n, ceil(rows / pool), ceil(cols / pool)]
         (bcp_egocentric_costmaps_pooled)."""
-        p = self._dev(np.atleast_2d(poses) if not isinstance(poses, torch.Tensor) else poses, torch.float64)
+        p = self._device_tensor(np.atleast_2d(poses) if not isinstance(poses, torch.Tensor) else poses, torch.float64)
         f64p = C.POINTER(C.c_double)
         org = sz = None
         if resulting_origin is not None:
@@ -207,25 +180,9 @@ class NativeOps(object):
         counter-clockwise; max_range where there is none within max_range -> float32 [n, B], or (ranges, *wanted) with
         want from "hit" (int32 [n, B], row * cols + col of the cell, -1 for none) and "heading_cs" (float64 [n, 2]).
         The (cos, sin) table of an angle set is uploaded once."""
-        p = self._dev(np.atleast_2d(poses) if not isinstance(poses, torch.Tensor) else poses, torch.float64)
-        table = beam_table_cached(self._keep.setdefault("beam_tables", OrderedDict()), beam_angles, self.device)
-        unknown = set(want) - {"hit", "heading_cs"}
-        if unknown:
-            raise ValueError("range_scan: unknown outputs %s" % sorted(unknown))
-        n, b = p.shape[0], table.shape[0]
-        out = {"ranges": torch.empty((n, b), dtype=torch.float32, device=self.device)}
-        if "hit" in want:
-            out["hit"] = torch.empty((n, b), dtype=torch.int32, device=self.device)
-        if "heading_cs" in want:
-            out["heading_cs"] = torch.empty((n, 2), dtype=torch.float64, device=self.device)
-        _lib.check(self._lib.bcp_range_scan(self._h, p.data_ptr(), n, table.data_ptr(), b, float(max_range),
-                                            out["ranges"].data_ptr(), out["hit"].data_ptr() if "hit" in out else None,
-                                            out["heading_cs"].data_ptr() if "heading_cs" in out else None, self._stream()))
-        return out["ranges"] if not want else (out["ranges"],) + tuple(out[w] for w in want)
-
-    def footprint(self):
-        """The handle's own footprint [n_verts, 2] in metres."""
-        return np.array([[self._p.verts[k][0], self._p.verts[k][1]] for k in range(self._p.n_verts)], dtype=np.float64)
+        p = self._device_tensor(np.atleast_2d(poses) if not isinstance(poses, torch.Tensor) else poses, torch.float64)
+        return self._range_scan(p, p.shape[0], beam_angles, max_range, want, lambda n, b, shapes, names: {
+            name: torch.empty(shapes[name][0], dtype=shapes[name][1], device=self.device) for name in names})
 
     def inflate_costmap(self, data, resolution, cost_scaling_factor, footprint=None, inscribed_radius=None,
                         valid_rows=None, valid_cols=None, return_distance=False):
@@ -235,14 +192,14 @@ class NativeOps(object):
         (robots.inscribed_radius of it); neither = the handle's own footprint.  valid_rows / valid_cols int32 [n]: the
         true shape of every entry of a padded batch; the padding is ignored and comes out 0.  return_distance: also the
         float32 distance in cells to the nearest lethal cell (+inf on a map without one)."""
-        d = self._dev(data, torch.uint8)
+        d = self._device_tensor(data, torch.uint8)
         maps = d[None] if d.dim() == 2 else d
         assert maps.dim() == 3
         if inscribed_radius is None:
             inscribed_radius = robots.inscribed_radius(self.footprint() if footprint is None else footprint)
         assert (valid_rows is None) == (valid_cols is None)
-        vr = self._dev(valid_rows, torch.int32) if valid_rows is not None else None
-        vc = self._dev(valid_cols, torch.int32) if valid_cols is not None else None
+        vr = self._device_tensor(valid_rows, torch.int32) if valid_rows is not None else None
+        vc = self._device_tensor(valid_cols, torch.int32) if valid_cols is not None else None
         assert vr is None or (vr.shape == (maps.shape[0],) and vc.shape == (maps.shape[0],))
         out = torch.empty_like(maps)
         dist = torch.empty(maps.shape, dtype=torch.float32, device=self.device) if return_distance else None
@@ -256,22 +213,11 @@ class NativeOps(object):
 
     def robot_step(self, state7, actions, noise_z=None):
         """state7 [n,7] rows {x,y,angle,v,w,steering_motor_command,wheel_angle}, actions [n,2] -> (new [n,7], err)."""
-        st = self._dev(state7, torch.float64).t().contiguous()  # SoA [7, n]
-        a = self._dev(actions, torch.float64)
+        st = self._device_tensor(state7, torch.float64).t().contiguous()  # SoA [7, n]
+        a = self._device_tensor(actions, torch.float64)
         n = a.shape[0]
-        z = self._dev(noise_z, torch.float64) if noise_z is not None else None
+        z = self._device_tensor(noise_z, torch.float64) if noise_z is not None else None
         err = torch.zeros(n, dtype=torch.int32, device=self.device)
         _lib.check(self._lib.bcp_robot_step(self._h, st.data_ptr(), n, a.data_ptr(),
                                             z.data_ptr() if z is not None else None, err.data_ptr(), self._stream()))
         return st.t().contiguous(), err
-
-    def close(self):
-        if self._h:
-            self._lib.bcp_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

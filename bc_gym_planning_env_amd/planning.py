@@ -7,6 +7,47 @@ plan's first action; the rest of the plan is the next tick's warm start."""
 import numpy as np
 import torch
 
+from . import _lib
+
+
+class Lookahead(object):
+    """What BatchedPlanEnv.lookahead() returns: device tensors over [N, K] candidates (no sync).  `ret` float64 return of
+    the steps taken, `steps` int32, `reason` uint8 DONE_* bits (0: not done within the horizon); optional, None unless
+    asked for: `final_pose` [N, K, 3], `final_target_idx`, `err`, `best` int32 [N], `best_action` [N, 2].  The tensors
+    are the env's cached buffers for this (H, K): the next lookahead() with the same shape overwrites them."""
+
+    FIELDS = ("ret", "steps", "reason", "final_pose", "final_target_idx", "err", "best", "best_action")
+
+    def __init__(self, horizon, n_candidates, **tensors):
+        self.horizon, self.n_candidates = horizon, n_candidates
+        for name in self.FIELDS:
+            setattr(self, name, tensors.get(name))
+
+    def collided(self):
+        """bool [N, K]: the candidate ends in a collision"""
+        return (self.reason & _lib.DONE_COLLIDED) != 0
+
+    def timed_out(self):
+        return (self.reason & _lib.DONE_TIMEOUT) != 0
+
+    def reached_goal(self):
+        return (self.reason & _lib.DONE_GOAL) != 0
+
+
+class Mppi(object):
+    """What BatchedPlanEnv.mppi() returns (device tensors, no sync): `mean` [N, H, 2] float64, the refined plan; `action`
+    [N, 2] = mean[:, 0], ready for step(); optional, None unless asked for: `eps` [I, N, K, H, 2] float32 (the
+    perturbations used), `iter_mean` [I, N, H, 2] (the mean going into each iteration), `iter_ret` / `iter_reason`
+    [I, N, K], `err` int32 [N].  Everything but `mean` is a cached buffer of the env for this (H, K, I)."""
+
+    FIELDS = ("eps", "iter_mean", "iter_ret", "iter_reason", "err")
+
+    def __init__(self, horizon, n_candidates, iterations, mean, action, **tensors):
+        self.horizon, self.n_candidates, self.iterations = horizon, n_candidates, iterations
+        self.mean, self.action = mean, action
+        for name in self.FIELDS:
+            setattr(self, name, tensors.get(name))
+
 
 def constant_command_library(action_space, n_v, n_angle, horizon):
     """[horizon, n_v * n_angle, 2] float32: every candidate holds ONE command for the whole horizon; the commands form

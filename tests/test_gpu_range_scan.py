@@ -540,4 +540,4 @@ def test_native_ops_range_scan(torch_cuda):
     _same_bits((ranges.cpu().numpy(), hit.cpu().numpy()), (want_r, want_h), "NativeOps.range_scan")
     assert (want_h >= 0).any() and trips.max() < bound
     alone = ops.range_scan(poses, angles, 3.0)
-    assert torch.equal(alone, ranges) and len(ops._keep["beam_tables"]) == 1
+    assert torch.equal(alone, ranges) and len(ops._beam_tables) == 1

@@ -1,5 +1,5 @@
 """Step time of the C3 geometry at small batch sizes: launched step by step (libbcplan's own timing loop: no Python
-between the launches), from Python (env.step per step), and replayed from a captured HIP graph of 32 steps."""
+between the launches), from Python (env.step per step), and replayed from a captured HIP graph of 32 steps.  Usage: python tools/small_n.py [n_envs ...] (default: 256 .. 65 536)."""
 import os
 import sys
 import time
@@ -10,7 +10,7 @@ import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import bench  # noqa: E402
 
-for n in (256, 1024, 4096, 16384, 32768, 65536):
+for n in [int(a) for a in sys.argv[1:]] or (256, 1024, 4096, 16384, 32768, 65536):
     env, g = bench.make_env(n, 0, 0, 1)
     rng = np.random.RandomState(0)
     pool = torch.from_numpy(np.stack([env.action_space.sample_batch(n, rng) for _ in range(8)])).cuda()
