@@ -17,40 +17,12 @@
 //    i.e. XOR of suffix masks starting at floor(x_e) + 1 -- no sorting, any contour.
 #pragma once
 
+#include "bcp_desc.h"
 #include "bcp_raster.h"
 
 namespace bcp {
 
-constexpr int kMaxSamples = 8;
-
-// distance-field description (kernel argument)
-struct CullDesc {
-    const uint8_t* edt;   // [(rows + 2 pad) * (cols + 2 pad)] floor(min(clamp, distance to nearest lethal cell))
-    int64_t env_stride;   // bytes per env (0: one field shared by all envs)
-    int32_t on;           // 0: no distance field -> every in-map pose is AMBIGUOUS
-    int32_t pad, width, height;  // padding on each side, padded row width / row count
-    int32_t clamp;        // the field saturates at this distance
-    int32_t reach;        // any footprint pixel is within `reach` px of the robot pixel (off-map test)
-    int32_t n_out, n_in;
-    int32_t t_out;        // free  <=>  edt >= t_out at every outer sample
-    int32_t t_in[kMaxSamples];   // hit <=  edt <= t_in[j] at inner sample j
-    double out_x[kMaxSamples], in_x[kMaxSamples];  // sample abscissae on the robot axis, in pixels
-    double axis_y;        // ordinate of the sample axis in the robot frame, in pixels
-    // The outer test only asks "is a lethal cell closer than t_out": the field as ONE BIT per cell, in tiles of
-    // 32 x 32 cells (32 row words = one 128-byte line each; the samples of a pose lie on a line of <= 2 reach px, so
-    // they meet three to five lines instead of one each).  word = near[((y >> 5) * near_tx + (x >> 5)) * 32 + (y & 31)]
-    const uint32_t* near;
-    int64_t near_stride;  // words per env (0: shared)
-    int32_t near_tx, near_words;   // tiles per tile row; words of one entry
-    // What step_local_kernel's outer test reads: `near` itself (shift 0), or a copy at 1/2 or 1/4 of the resolution -- a bit
-    // of it is the OR of the 2 x 2 / 4 x 4 cells it stands for (near_coarsen_kernel), so "not near" still holds for every
-    // one of them.  A 128-byte line then covers 64 x 64 / 128 x 128 cells: the samples of a pose meet fewer lines (each a
-    // full line of memory traffic for maps that do not stay in cache), at the price of a few more undecided poses.
-    const uint32_t* step_near;
-    int64_t step_near_stride;
-    int32_t step_near_tx, step_near_shift;
-};
-
+// (CullDesc, the distance-field description, and kMaxSamples: bcp_desc.h)
 enum { kFree = 0, kHit = 1, kAmbiguous = 2 };
 
 // distance-field value at padded cell (x, y); `outside` when the cell is not stored (small padding of private maps)

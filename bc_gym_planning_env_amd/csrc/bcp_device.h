@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "../../include/bcplan.h"
+#include "bcp_desc.h"   // DevParams
 
 namespace bcp {
 
@@ -27,24 +28,6 @@ __device__ __forceinline__ GlobalPtr<T> as_global(T* p)
 
 constexpr double kPi = 3.14159265358979323846;
 constexpr double kTwoPi = 2.0 * kPi;
-
-// Device copy of the parameters (kernel argument, lives in SGPRs / scalar cache).
-struct DevParams {
-    int32_t model, n_verts, dynamic_model, model_front_column_pid, noise_on, iteration_timeout;
-    double dt, L, max_wheel_angle, max_wheel_speed, max_lin_acc, max_ang_acc, p_gain;
-    double inv_dt, inv_L;    // 1 / dt, 1 / L, correctly rounded (host): div_by_const; directly behind p_gain (step_local_kernel
-                             // fetches dt .. inv_L as nine adjacent values)
-    double alpha[6];
-    double sp, ap, progress_mult;
-    double par_thr;          // -sp / 9, utilities/path_tools.py:423
-    double sp2_lo, sp2_hi;   // sp^2 (1 -+ 1e-13): dx^2+dy^2 outside this band decides hypot(dx,dy) < sp on its own
-    double sp_prune;         // sp nudged up two ulps: |dx| > sp_prune  =>  hypot(dx,dy) >= sp for any faithful hypot
-    double qverts[BCP_MAX_VERTS][2];  // footprint / resolution (path_tools.py:145), divided on the host in fp64
-    float qbox[4];                    // bounding box of qverts in the robot frame: xmin, xmax, ymin, ymax (pixels)
-    int32_t reward_provider;          // BCP_REWARD_*
-    int32_t control_delay, pose_delay, state_delay;   // EnvParams delays (envs/base/params.py:28-30)
-    float ap_cos_min;                 // cos(ap) - 1e-4 (-2 when ap >= pi): the heading test of the quantised prefilter records
-};
 
 // numpy float `%`: the result takes the sign of the divisor (npy_divmod)
 __device__ __forceinline__ double py_mod(double a, double b)

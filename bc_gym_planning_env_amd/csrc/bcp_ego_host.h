@@ -290,8 +290,8 @@ static int egocentric_costmaps(bcp_handle* h, const double* poses, int64_t n, co
     h->ego_route[0] = h->ego_route[1] = h->ego_route[2] = h->ego_route[3] = 0;
     EgoCells& cells = h->ego_cells;
     int32_t limit = 0;
-    if (ego_sparse_candidate(call, h->ego_sparse, cells.refused())) {
-        limit = ego_sparse_limit(h->ego_sparse, (int64_t)drows * dcols, ego_fits_lds(a.rows, a.cols, drows));
+    if (ego_sparse_candidate(call, h->tune.ego_sparse, cells.refused())) {
+        limit = ego_sparse_limit(h->tune.ego_sparse, (int64_t)drows * dcols, ego_fits_lds(a.rows, a.cols, drows));
         BCP_TRY(cells.ensure(h, a.shared ? 1 : n_slots(h), limit, st));
         h->ego_route[1] = cells.largest();
         h->ego_route[2] = cells.stride();

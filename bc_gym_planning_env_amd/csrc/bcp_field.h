@@ -1,6 +1,7 @@
 // bcp_field.h -- what is derived from the caller's maps and paths when they are bound or refreshed: the distance field of
-// the lethal cells and its 1-bit tiles (the kernels are here), and the launchers of these and of the bitmap / path-table
-// kernels of bcp_raster.h and bcp_step.h for a selection of entries.  Included by bcplan.hip after bcp_host.h.
+// the lethal cells and its 1-bit tiles (the kernels are here, and the methods of their owner, DistanceField), and the
+// launchers of the bitmap / path-table kernels of bcp_raster.h and bcp_step.h for a selection of entries.  The shapes come
+// from bcp_field_plan.h.  Included by bcplan.hip after bcp_host.h.
 #pragma once
 
 // ---- Euclidean distance transform of the lethal cells over the padded map(s) (classify(), bcp_coop.h) ----------
@@ -316,87 +317,122 @@ static void launch_pack_bitmap(bcp_handle* h, EntrySelect sel, int64_t max_entri
     else h->ego_cells.invalidate();
 }
 
-static void launch_near_tiles(bcp_handle* h, EntrySelect sel, int64_t max_entries, hipStream_t s)
+// ---- DistanceField (declared in bcp_host.h) --------------------------------------------------------------------
+inline hipError_t DistanceField::reserve_marks(size_t entries)
 {
-    const CullDesc& C = h->cull;
-    if (!C.near) return;
-    const int tiles_y = C.near_words / (32 * C.near_tx);
+    hipError_t e = stale.reserve(entries);
+    if (e == hipSuccess) e = stale_list.reserve(entries + 1);
+    if (e != hipSuccess) {   // (without the list there are no marks)
+        (void)stale.reset();
+        (void)stale_list.reset();
+    }
+    return e;
+}
+
+inline int DistanceField::bind(bcp_handle* h, const FieldPlan& f, hipStream_t s)
+{
+    plan = f;
+    CullDesc& C = h->cull;
+    C = f.cull;
+    if (!f.field) return BCP_OK;   // (culling off: the geometry alone, every in-map pose is AMBIGUOUS)
+    C.on = 0;                      // (until everything below stands)
+    HIP_TRY(edt.reserve(f.n_edt));
+    HIP_TRY(edt_col.reserve(f.n_edt_col));
+    HIP_TRY(near.reserve(f.n_near));
+    HIP_TRY(near_coarse.reserve(f.n_near_coarse));
+    // the stale marks of tiles-only rebuilds: the caller rebuilds every field next, so none is stale
+    lazy = false;
+    if (f.n_stale) HIP_TRY(reserve_marks(f.n_stale));
+    if (stale.get()) HIP_TRY(hipMemsetAsync(stale.get(), 0, stale.capacity(), s));
+    C.edt = edt.get();
+    C.near = near.get();
+    C.step_near = f.cull.step_near_shift > 0 ? near_coarse.get() : near.get();
+    C.on = f.cull.on;
+    return BCP_OK;
+}
+
+inline bool DistanceField::bind_reads_tiles_only(const bcp_handle* h, const FieldPlan& f)
+{
+    const Tuning& t = h->tune;
+    return !h->map.shared && f.n_maps >= 32 && t.fused && t.adaptive && f.cull.on && t.near_dilate == 1;
+}
+
+inline bool DistanceField::refresh_reads_tiles_only(const bcp_handle* h)
+{
+    return h->parking.slots() && h->tune.fused && h->tune.adaptive && h->cull.on;
+}
+
+inline void DistanceField::launch_near_tiles(EntrySelect sel, int64_t max_entries, hipStream_t s)
+{
+    const CullDesc& C = plan.cull;
     hipLaunchKernelGGL(near_tiles_kernel, dim3(stride_grid(max_entries * C.near_words, 256, sel.list != nullptr)), dim3(256), 0, s,
-                       h->edt.get(), sel, C.width, C.height, C.near_tx, tiles_y, C.t_out, h->near.get());
+                       edt.get(), sel, C.width, C.height, C.near_tx, plan.tiles_y, C.t_out, near.get());
 }
 
 // near_dilate_kernel serves these maps: radius within a word, rows + margins in LDS
-static size_t near_dilate_lds(const bcp_handle* h)
+inline size_t DistanceField::near_dilate_lds() const
 {
-    const CullDesc& C = h->cull;
-    if (!C.near || C.t_out < 1 || C.t_out > 32 || C.pad < C.t_out - 1) return 0;
-    const int tiles_y = C.near_words / (32 * C.near_tx);
-    const size_t bytes = ((size_t)(tiles_y * 32 + 2 * (C.t_out - 1)) * (C.near_tx + 2) + C.t_out) * sizeof(uint32_t);
+    const CullDesc& C = plan.cull;
+    if (C.t_out < 1 || C.t_out > 32 || C.pad < C.t_out - 1) return 0;
+    const size_t bytes = ((size_t)(plan.tiles_y * 32 + 2 * (C.t_out - 1)) * (C.near_tx + 2) + C.t_out) * sizeof(uint32_t);
     return bytes <= 64 * 1024 ? bytes : 0;
 }
 
-static void launch_near_dilate(bcp_handle* h, EntrySelect sel, int64_t max_entries, uint8_t* stale, hipStream_t s)
+inline void DistanceField::launch_near_dilate(bcp_handle* h, EntrySelect sel, int64_t max_entries, uint8_t* marks, hipStream_t s)
 {
     const MapDesc& m = h->map;
-    const CullDesc& C = h->cull;
-    const size_t lds = near_dilate_lds(h);
+    const CullDesc& C = plan.cull;
     const int64_t blocks = std::min<int64_t>(max_entries, sel.list ? 4096 : 16384);
-    hipLaunchKernelGGL(near_dilate_kernel, dim3((unsigned)std::max<int64_t>(blocks, 1)), dim3(256), lds, s, h->bitmap.get(), sel, m.rows,
-                       m.cols, m.wpr, C.pad, C.t_out, C.width, C.height, C.near_tx, C.near_words / (32 * C.near_tx), h->near.get(), stale);
+    hipLaunchKernelGGL(near_dilate_kernel, dim3((unsigned)std::max<int64_t>(blocks, 1)), dim3(256), near_dilate_lds(), s, h->bitmap.get(), sel,
+                       m.rows, m.cols, m.wpr, C.pad, C.t_out, C.width, C.height, C.near_tx, plan.tiles_y, near.get(), marks);
 }
 
-static void launch_edt(bcp_handle* h, EntrySelect sel, int64_t max_entries, hipStream_t s)
+inline void DistanceField::launch_edt(bcp_handle* h, EntrySelect sel, int64_t max_entries, hipStream_t s)
 {
     const MapDesc& m = h->map;
-    const CullDesc& C = h->cull;
+    const CullDesc& C = plan.cull;
     const size_t lds = ((size_t)m.rows * m.wpr + (size_t)C.height * ((C.width + 3) / 4)) * sizeof(uint32_t) +
                        (((size_t)C.clamp * C.clamp + 1 + 3) & ~(size_t)3);
     // (one workgroup per map: worth it from a few dozen maps on; a lone shared map keeps the two wide kernels)
-    if (C.clamp <= 60 && lds <= kMaxDynamicLds && h->edt_in_lds && max_entries >= 32) {
+    if (C.clamp <= 60 && lds <= kMaxDynamicLds && h->tune.edt_in_lds && max_entries >= 32) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(edt_lds_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)lds);
         const int64_t blocks = std::min<int64_t>(max_entries, sel.list ? 2048 : 16384);
         hipLaunchKernelGGL(edt_lds_kernel, dim3((unsigned)std::max<int64_t>(blocks, 1)), dim3(256), lds, s, h->bitmap.get(), sel,
-                           m.rows, m.cols, m.wpr, C.pad, C.clamp, h->edt.get());
+                           m.rows, m.cols, m.wpr, C.pad, C.clamp, edt.get());
         return;
     }
     hipLaunchKernelGGL(edt_columns_kernel, dim3(stride_grid(max_entries * C.width, 64, sel.list != nullptr)), dim3(64), 0, s, h->bitmap.get(), sel, m.rows,
-                       m.cols, m.wpr, C.pad, C.clamp, h->edt_col.get());
-    hipLaunchKernelGGL(edt_rows_kernel, dim3(stride_grid(max_entries * C.width * C.height, 256, sel.list != nullptr)), dim3(256), 0, s, h->edt_col.get(),
-                       sel, C.width, C.height, C.clamp, h->edt.get());
+                       m.cols, m.wpr, C.pad, C.clamp, edt_col.get());
+    hipLaunchKernelGGL(edt_rows_kernel, dim3(stride_grid(max_entries * C.width * C.height, 256, sel.list != nullptr)), dim3(256), 0, s, edt_col.get(),
+                       sel, C.width, C.height, C.clamp, edt.get());
 }
 
-// CullDesc::step_near of private maps unless BCP_TUNE_NEAR_SHIFT says otherwise: a quarter of the resolution (measured on one
-// box, shift 0 / 1 / 2: one private 64 x 64 world per env 821 / 751 / 719 bytes of memory traffic per env-step and 21.1 / 20.6 /
-// 20.6 us per step; 65 536 private 256 x 141 aisle maps 2.58 / 2.53 / 2.60e9 env-steps/s -- profiles/r04_near_shift.txt;
-// shift 3, an eighth: 687 bytes, but 19.6 against 19.1 us and the aisle maps 2.24e9 -- more poses go to the exact test)
-constexpr int kNearShiftPrivate = 2;
-
-static void launch_near_coarse(bcp_handle* h, EntrySelect sel, int64_t max_entries, hipStream_t s)
+inline void DistanceField::launch_near_coarse(EntrySelect sel, int64_t max_entries, hipStream_t s)
 {
-    const CullDesc& C = h->cull;
-    if (!C.near || C.step_near_shift == 0) return;
-    const int tiles_y = C.near_words / (32 * C.near_tx);
-    const int cty = (int)(C.step_near_stride / (32 * C.step_near_tx));   // (private maps only: the stride is an entry's words)
-    hipLaunchKernelGGL(near_coarsen_kernel, dim3(stride_grid(max_entries * C.step_near_tx * cty * 32, 256, sel.list != nullptr)), dim3(256),
-                       0, s, h->near.get(), sel, C.near_tx, tiles_y, C.step_near_shift, C.step_near_tx, cty, h->near_coarse.get());
+    const CullDesc& C = plan.cull;
+    if (C.step_near_shift == 0) return;
+    hipLaunchKernelGGL(near_coarsen_kernel, dim3(stride_grid(max_entries * C.step_near_tx * plan.cty * 32, 256, sel.list != nullptr)), dim3(256),
+                       0, s, near.get(), sel, C.near_tx, plan.tiles_y, C.step_near_shift, C.step_near_tx, plan.cty, near_coarse.get());
 }
 
-// Distance field + tiles of the selected entries.  `tiles_only`: the caller's consumers read nothing but the tiles (a pool
-// refresh under the single-launch step) -- when near_dilate_kernel can serve the maps, the uint8 field is left stale and
-// marked so; ensure_fields() brings it up to date for whoever asks for it later.
-static int launch_distance_field(bcp_handle* h, EntrySelect sel, int64_t max_entries, hipStream_t s, bool tiles_only = false)
+// `tiles_only`: the caller's consumers read nothing but the tiles (the single-launch step) -- when near_dilate_kernel can
+// serve the maps, the uint8 field is left stale and marked so; ensure_fields() brings it up to date for whoever asks for it
+// later.
+inline int DistanceField::rebuild(bcp_handle* h, EntrySelect sel, int64_t max_entries, hipStream_t s, bool tiles_only)
 {
-    if (tiles_only && h->near_dilate >= 1 && near_dilate_lds(h) && (int64_t)h->edt_stale.capacity() >= n_slots(h)) {
-        launch_near_dilate(h, sel, max_entries, h->edt_stale.get(), s);
-        launch_near_coarse(h, sel, max_entries, s);
-        h->edt_lazy = true;
+    if (!h->cull.edt) return BCP_OK;   // (bound with culling off)
+    const int32_t dilate = h->tune.near_dilate;
+    if (tiles_only && dilate >= 1 && near_dilate_lds() && (int64_t)stale.capacity() >= n_slots(h)) {
+        launch_near_dilate(h, sel, max_entries, stale.get(), s);
+        launch_near_coarse(sel, max_entries, s);
+        lazy = true;
         return BCP_OK;
     }
     launch_edt(h, sel, max_entries, s);
-    launch_near_tiles(h, sel, max_entries, s);
-    if (h->near_dilate == 2 && near_dilate_lds(h)) launch_near_dilate(h, sel, max_entries, nullptr, s);
-    launch_near_coarse(h, sel, max_entries, s);
+    launch_near_tiles(sel, max_entries, s);
+    if (dilate == 2 && near_dilate_lds()) launch_near_dilate(h, sel, max_entries, nullptr, s);
+    launch_near_coarse(sel, max_entries, s);
     return BCP_OK;
 }
 
@@ -405,26 +441,41 @@ static int launch_distance_field(bcp_handle* h, EntrySelect sel, int64_t max_ent
 // Before anything reads the uint8 field (two-launch and single-kernel step forms, bcp_pose_collides,
 // bcp_get_distance_field): the transform of the entries a tiles-only refresh has left stale, on the reader's stream.  An
 // entry is marked at the end of its refresh, in the refresh's stream order, so a refresh still running on another stream
-// is simply picked up by the next call; the flag of the handle stays up for as long as such refreshes may be in flight.
-static int ensure_fields(bcp_handle* h, hipStream_t s)
+// is simply picked up by the next call; the flag stays up for as long as such refreshes may be in flight.
+inline int DistanceField::ensure_fields(bcp_handle* h, hipStream_t s)
 {
-    if (!h->edt_lazy || !h->cull.edt || !h->edt_stale.get()) return BCP_OK;
+    if (!lazy || !h->cull.edt || !stale.get()) return BCP_OK;
     // Has every tiles-only refresh issued so far finished?  Then this pass leaves no stale field behind and later calls can
     // skip their three launches until the next such refresh (which raises the flag again).
     bool settled = true;   // (no refresh ever issued: the stale marks come from bcp_set_costmaps, in stream order)
     if (h->refresh_recorded) {
-        settled = hipEventQuery(h->refresh_done) == hipSuccess;
+        settled = hipEventQuery(h->refresh_done.get()) == hipSuccess;
         if (!settled) (void)hipGetLastError();   // (hipErrorNotReady)
     }
-    const int64_t entries = (int64_t)h->edt_stale.capacity();
-    int32_t* count = h->edt_stale_list.get() + entries;
+    const int64_t entries = (int64_t)stale.capacity();
+    int32_t* count = stale_list.get() + entries;
     HIP_TRY(hipMemsetAsync(count, 0, sizeof(int32_t), s));
-    hipLaunchKernelGGL(stale_fields_list_kernel, dim3(stride_grid(entries, 256)), dim3(256), 0, s, h->edt_stale.get(), entries,
-                       h->edt_stale_list.get(), count);
-    const EntrySelect sel = {h->edt_stale_list.get(), count, entries};
+    hipLaunchKernelGGL(stale_fields_list_kernel, dim3(stride_grid(entries, 256)), dim3(256), 0, s, stale.get(), entries,
+                       stale_list.get(), count);
+    const EntrySelect sel = {stale_list.get(), count, entries};
     launch_edt(h, sel, entries, s);
     HIP_TRY(hipGetLastError());
-    if (settled) h->edt_lazy = false;
+    if (settled) lazy = false;
+    return BCP_OK;
+}
+
+inline int DistanceField::copy_field(bcp_handle* h, int64_t first_entry, int64_t n_entries, uint8_t* out, hipStream_t s)
+{
+    BCP_TRY(ensure_fields(h, s));
+    const size_t per = (size_t)plan.cull.width * plan.cull.height;
+    HIP_TRY(hipMemcpyAsync(out, edt.get() + first_entry * per, n_entries * per, hipMemcpyDeviceToDevice, s));
+    return BCP_OK;
+}
+
+inline int DistanceField::copy_near(int64_t first_entry, int64_t n_entries, uint32_t* out, hipStream_t s)
+{
+    const size_t per = (size_t)plan.cull.near_words;
+    HIP_TRY(hipMemcpyAsync(out, near.get() + first_entry * per, n_entries * per * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
     return BCP_OK;
 }
 

@@ -47,7 +47,7 @@ extern "C" int bcp_inflate_costmaps(bcp_handle* h, const uint8_t* data, int64_t 
     a.lethal_below = a.pir / 1000.;                // :59
     const size_t fixed = (size_t)inflate_fixed_words(rows, a.wpr) * sizeof(uint32_t);
     const size_t with_plane = fixed + (((size_t)cells * sizeof(uint16_t) + 3) & ~(size_t)3);
-    const bool in_lds = with_plane <= kMaxDynamicLds && h->inflate_route != 2;
+    const bool in_lds = with_plane <= kMaxDynamicLds && h->tune.inflate_route != 2;
     if (!in_lds && fixed > kMaxDynamicLds)   // (2048 x 2048: 64 KiB of mask + 8 KiB of lists -- cannot happen within the limits above)
         return fail(BCP_E_INVALID, "bcp_inflate_costmaps: the map's bit mask does not fit the LDS");
     // a workgroup's threads: enough cells each to be worth their barriers

@@ -1,5 +1,6 @@
 // bcp_step_host.h -- the host side of the step: which form a step takes, the device-resident parameter block, the launcher,
-// and the entry points built on it (bcp_step, bcp_rollout, bcp_lookahead, bcp_mppi, the watchdog and the timing calls).
+// the methods of Parking and WaitWatchdog, and the entry points built on them (bcp_step, bcp_rollout, bcp_lookahead, bcp_mppi,
+// the timing calls).
 // The kernels are in bcp_step.h, bcp_lookahead.h and bcp_mppi.h.  Included by bcplan.hip after bcp_field.h.
 #pragma once
 
@@ -12,7 +13,7 @@ static bool step_is_plain(const bcp_handle* h)
 
 static bool step_uses_deferral(const bcp_handle* h)
 {
-    return h->defer && h->cull.on && h->exact_mode == 0 && h->pending.get() != nullptr;
+    return h->tune.defer && h->cull.on && h->tune.exact_mode == 0 && h->parking.slots() != nullptr;
 }
 
 // Which kernels a step of this handle launches as it is configured now -- the numbers bcp_step_form documents: 0 step_kernel,
@@ -23,8 +24,8 @@ static bool step_uses_deferral(const bcp_handle* h)
 static int step_form(const bcp_handle* h)
 {
     if (!step_uses_deferral(h)) return 0;
-    if (h->dense_threshold < 0) return 1;
-    return (h->fused && h->adaptive) ? 3 : 2;
+    if (h->tune.dense_threshold < 0) return 1;
+    return (h->tune.fused && h->tune.adaptive) ? 3 : 2;
 }
 
 // (re)builds the device-resident StepStatic block and, from it, the StepHot image that every launch copies
@@ -39,19 +40,18 @@ static int upload_step_static(bcp_handle* h, hipStream_t s)
     S.init = h->init;
     S.n = h->n;
     S.env_id_base = h->env_id_base;
-    S.exact_mode = h->exact_mode;
-    S.dense_threshold = h->dense_threshold;   // (a negative value settles every undecided pose inside kernel 1)
+    S.exact_mode = h->tune.exact_mode;
+    S.dense_threshold = h->tune.dense_threshold;   // (a negative value settles every undecided pose inside kernel 1)
     S.wide = h->wide;
-    S.pending_cap = h->pending_cap;
+    S.pending_cap = h->parking.slots_per_shard();
     const bool defer = step_uses_deferral(h);
-    S.pending = defer ? h->pending.get() : nullptr;
+    S.pending = defer ? h->parking.slots() : nullptr;
     S.geom_of_env = h->n_geoms > 0 ? h->geom_of_env : nullptr;
     S.next_geom = h->n_geoms > 0 ? h->next_geom : nullptr;
     S.lds_path_doubles =
         (defer && h->path.shared && h->path.max_len * 5 * sizeof(double) <= 24 * 1024) ? h->path.max_len * 5 : 0;
     if (h->have_rec) {
-        if (defer) HIP_TRY(h->rec_park.reserve((size_t)kShards * h->pending_cap));   // (pending_cap never changes)
-        h->rec.park = defer ? h->rec_park.get() : nullptr;
+        BCP_TRY(h->parking.record_slots(defer, &h->rec.park));
         S.rec = h->rec;
     } else {
         memset(&S.rec, 0, sizeof(S.rec));
@@ -95,16 +95,46 @@ static int upload_step_static(bcp_handle* h, hipStream_t s)
     return BCP_OK;
 }
 
+// ---- Parking (declared in bcp_host.h) ---------------------------------------------------------------------------
 // The parity-keyed parking / adaptation counters are only maintained by the two-kernel step (kernel 1 zeroes the NEXT
-// step's set).  Whenever the step form changes (bcp_set_tuning between steps, a costmap without distance field, ...)
-// both sets are re-armed on the stream of the steps, so the two-kernel step never resumes on stale counts.
-static int rearm_parking(bcp_handle* h, hipStream_t s)
+// step's set), so whoever restarts the count of steps (bcp_seed) or resumes that form after another re-arms both sets.
+inline int Parking::arm(int32_t threshold, hipStream_t s)
 {
-    if (h->pending_count.get()) HIP_TRY(hipMemsetAsync(h->pending_count.get(), 0, 2 * kShards * sizeof(int32_t), s));
-    if (h->adapt.get()) {
-        HIP_TRY(hipMemsetAsync(h->adapt.get() + 2, 0, 2 * kShards * sizeof(int32_t), s));
-        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)h->adapt.get(), h->dense_threshold, 2, s));
+    if (pending_count.get()) HIP_TRY(hipMemsetAsync(pending_count.get(), 0, 2 * kShards * sizeof(int32_t), s));
+    if (adapt.get()) {
+        HIP_TRY(hipMemsetAsync(adapt.get() + 2, 0, 2 * kShards * sizeof(int32_t), s));
+        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)adapt.get(), threshold, 2, s));
     }
+    return BCP_OK;
+}
+
+inline int Parking::bind(int64_t n_envs, int32_t threshold, hipStream_t s)
+{
+    if (pending.get()) return BCP_OK;
+    const int64_t blocks = (n_envs + kBlock - 1) / kBlock;
+    cap = (int32_t)(((blocks + kShards - 1) / kShards) * kBlock);  // every env of a shard's blocks
+    HIP_TRY(pending_count.reserve(2 * kShards));
+    HIP_TRY(adapt.reserve(2 + 2 * kShards));
+    BCP_TRY(arm(threshold, s));
+    HIP_TRY(hipStreamSynchronize(s));   // (the first bind has always returned with the counters in place)
+    // (last: the slots mark this block as done, so a failure above is met again by the next call)
+    HIP_TRY(pending.reserve((size_t)kShards * cap));
+    return BCP_OK;
+}
+
+// Whenever the step form changes (bcp_set_tuning between steps, a costmap without distance field, ...) both sets are
+// re-armed on the stream of the steps, so the two-kernel step never resumes on stale counts.
+inline int Parking::step_takes_form(int form, int32_t threshold, hipStream_t s)
+{
+    if ((form == 1 || form == 2) && (last_form == 0 || last_form == 3)) BCP_TRY(arm(threshold, s));
+    last_form = form;
+    return BCP_OK;
+}
+
+inline int Parking::record_slots(bool defer, RecPark** out)
+{
+    if (defer) HIP_TRY(rec_park.reserve((size_t)kShards * cap));   // (cap never changes)
+    *out = defer ? rec_park.get() : nullptr;
     return BCP_OK;
 }
 
@@ -139,7 +169,8 @@ static const void* local_step_fn(int variant, int pairs, bool roll = false)
 // Size of step_local_kernel's workgroups for this handle: BCP_TUNE_LOCAL_PAIRS, or (0) the default of the configuration.
 static int local_pairs(const bcp_handle* h)
 {
-    if (h->local_pairs == 1 || h->local_pairs == 2 || h->local_pairs == 4) return h->local_pairs;
+    const int32_t pairs = h->tune.local_pairs;
+    if (pairs == 1 || pairs == 2 || pairs == 4) return pairs;
     return kLocalPairsDefault;
 }
 
@@ -152,9 +183,8 @@ static int launch_step(bcp_handle* h, const bcp_step_io* io, uint32_t flags, hip
     const StepStatic& S = h->host_static;
     const int form = step_form(h);
     const bool fused = form == 3;
-    if (!fused && h->edt_lazy) BCP_TRY(ensure_fields(h, s));   // these forms read the uint8 field
-    if ((form == 1 || form == 2) && (h->last_step_form == 0 || h->last_step_form == 3)) BCP_TRY(rearm_parking(h, s));   // parking resumes after another form
-    h->last_step_form = form;
+    if (!fused && h->field.has_stale_fields()) BCP_TRY(h->field.ensure_fields(h, s));   // these forms read the uint8 field
+    BCP_TRY(h->parking.step_takes_form(form, h->tune.dense_threshold, s));
     StepArgs a;
     a.S = h->dev_static.get();
     a.hot = h->host_hot;
@@ -172,13 +202,13 @@ static int launch_step(bcp_handle* h, const bcp_step_io* io, uint32_t flags, hip
     a.pending_count = a.pending_next = nullptr;
     a.threshold_now = nullptr;
     a.threshold_next = a.inplace_count = a.inplace_next = nullptr;
-    const bool adapt = h->adaptive && h->adapt.get() && S.pending && S.dense_threshold >= 0;
+    const bool adapt = h->tune.adaptive && h->parking.thresholds() && S.pending && S.dense_threshold >= 0;
     a.tick = h->tick.get();
     a.parked_slots = nullptr;
     a.map_tiles = S.map.tiles;
     a.rollout_steps = 1;
-    a.pending_base = h->pending_count.get();
-    a.adapt_base = adapt ? h->adapt.get() : nullptr;
+    a.pending_base = h->parking.counters();
+    a.adapt_base = adapt ? h->parking.thresholds() : nullptr;
     const int blocks = (int)((h->n + kBlock - 1) / kBlock);
     const int variant = (S.wide ? 2 : 0) | (step_is_plain(h) ? 1 : 0);
     if (fused) {
@@ -252,17 +282,17 @@ static int check_step(bcp_handle* h, const bcp_step_io* io, uint32_t flags, cons
 // that copy has landed, compares it with what was seen before.
 constexpr uint32_t kWatchdogSteps = 256;
 
-static int step_watchdog(bcp_handle* h, hipStream_t s)
+inline int WaitWatchdog::after_step(bcp_handle* h, hipStream_t s)
 {
     if (step_form(h) != 3) return BCP_OK;   // (only step_local_kernel has such waits)
-    if (h->waits_in_flight) {
-        const hipError_t q = hipEventQuery(h->waits_event);
+    if (in_flight) {
+        const hipError_t q = hipEventQuery(event.get());
         if (q == hipSuccess) {
-            h->waits_in_flight = false;
-            const uint64_t now = *h->waits_host;
-            if (now > h->waits_seen) {
-                const uint64_t fresh = now - h->waits_seen;
-                h->waits_seen = now;
+            in_flight = false;
+            const uint64_t now = *host.get();
+            if (now > seen) {
+                const uint64_t fresh = now - seen;
+                seen = now;
                 return fail(BCP_E_INTERNAL, "bcp_step: %llu bounded wait(s) of the step kernel gave up during earlier steps "
                                             "(BCP_ERR_INTERNAL in err[] marks the envs; their verdicts are unreliable)",
                             (unsigned long long)fresh);
@@ -272,21 +302,21 @@ static int step_watchdog(bcp_handle* h, hipStream_t s)
         }
         return BCP_OK;
     }
-    if (++h->steps_since_probe < kWatchdogSteps) return BCP_OK;
+    if (++steps_since_probe < kWatchdogSteps) return BCP_OK;
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) {
         (void)hipGetLastError();
         return BCP_OK;   // (a captured step is replayed without this function: the caller asks bcp_expired_waits)
     }
-    if (!h->waits_host) {
-        HIP_TRY(hipHostMalloc((void**)&h->waits_host, sizeof(uint64_t), hipHostMallocDefault));
-        *h->waits_host = 0;
-        HIP_TRY(hipEventCreateWithFlags(&h->waits_event, hipEventDisableTiming));
+    if (!host) {
+        HIP_TRY(hipHostMalloc((void**)host.put(), sizeof(uint64_t), hipHostMallocDefault));
+        *host.get() = 0;
+        HIP_TRY(hipEventCreateWithFlags(event.put(), hipEventDisableTiming));
     }
-    HIP_TRY(hipMemcpyAsync(h->waits_host, h->tick.get() + 4, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipEventRecord(h->waits_event, s));
-    h->waits_in_flight = true;
-    h->steps_since_probe = 0;
+    HIP_TRY(hipMemcpyAsync(host.get(), h->tick.get() + 4, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipEventRecord(event.get(), s));
+    in_flight = true;
+    steps_since_probe = 0;
     return BCP_OK;
 }
 
@@ -296,7 +326,7 @@ extern "C" int bcp_step(bcp_handle* h, const bcp_step_io* io, uint32_t flags, vo
     HIP_TRY(hipSetDevice(h->device));
     BCP_TRY(launch_step(h, io, flags, (hipStream_t)stream));
     HIP_TRY(hipGetLastError());
-    return step_watchdog(h, (hipStream_t)stream);
+    return h->watchdog.after_step(h, (hipStream_t)stream);
 }
 
 // K steps per call for callers that hold the actions of a whole rollout (Monte-Carlo rollouts from one state, the use the
@@ -344,7 +374,7 @@ static int plan_ready(bcp_handle* h, const char* who, hipStream_t s)
                                    "candidate would need delay queues of its own)", who);
     HIP_TRY(hipSetDevice(h->device));
     if (h->static_dirty) BCP_TRY(upload_step_static(h, s));
-    return h->edt_lazy ? ensure_fields(h, s) : BCP_OK;
+    return h->field.has_stale_fields() ? h->field.ensure_fields(h, s) : BCP_OK;
 }
 
 // K candidate plans per env, scored on private copies of the env's state (bcp_lookahead.h).  Reads the handle, writes only
@@ -492,28 +522,20 @@ extern "C" int bcp_step_form(bcp_handle* h)
     return step_form(h);
 }
 
-// an event that is destroyed on every way out of its scope
-namespace {
-struct ScopedEvent {
-    hipEvent_t e = nullptr;
-    ~ScopedEvent() { if (e) (void)hipEventDestroy(e); }
-};
-}   // namespace
-
 // average device time of `steps` back-to-back step launches on `s` (first_only: of kernel 1 of the two-launch form alone)
 static int time_loop(bcp_handle* h, const bcp_step_io* io, uint32_t flags, int steps, hipStream_t s, bool first_only,
                      float* avg_ms)
 {
-    ScopedEvent e0, e1;
-    HIP_TRY(hipEventCreate(&e0.e));
-    HIP_TRY(hipEventCreate(&e1.e));
-    HIP_TRY(hipEventRecord(e0.e, s));
+    OwnedEvent e0, e1;   // (destroyed on every way out)
+    HIP_TRY(hipEventCreate(e0.put()));
+    HIP_TRY(hipEventCreate(e1.put()));
+    HIP_TRY(hipEventRecord(e0.get(), s));
     int rc = BCP_OK;
     for (int k = 0; k < steps && rc == BCP_OK; ++k) rc = launch_step(h, io, flags, s, first_only);
-    HIP_TRY(hipEventRecord(e1.e, s));
-    HIP_TRY(hipEventSynchronize(e1.e));
+    HIP_TRY(hipEventRecord(e1.get(), s));
+    HIP_TRY(hipEventSynchronize(e1.get()));
     float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, e0.e, e1.e));
+    HIP_TRY(hipEventElapsedTime(&ms, e0.get(), e1.get()));
     HIP_TRY(hipGetLastError());
     if (rc != BCP_OK) return rc;
     *avg_ms = ms / (float)steps;

@@ -118,17 +118,14 @@ extern "C" int bcp_refresh_mini_worlds(bcp_handle* h, const bcp_mini_world_param
                        (int)(h->params.reward_provider == BCP_REWARD_PURE_PURSUIT), (int)h->path.max_len, paths, lens, init,
                        path_status);
     launch_pack_bitmap(h, sel, G, s);
-    if (h->cull.edt) {
-        // under the single-launch step nothing reads the uint8 fields: tiles only, the fields follow on demand
-        const bool tiles_only = h->pending.get() && h->fused && h->adaptive && h->cull.on;
-        BCP_TRY(launch_distance_field(h, sel, G, s, tiles_only));
-    }
+    // under the single-launch step nothing reads the uint8 fields: tiles only, the fields follow on demand
+    BCP_TRY(h->field.rebuild(h, sel, G, s, DistanceField::refresh_reads_tiles_only(h)));
     launch_path_data(h, sel, G, s);
     hipLaunchKernelGGL(pool_initial_state_kernel, dim3(stride_grid(G, 256, true)), dim3(256), 0, s, sel, paths,
                        (int)h->path.max_len, init, h->init);
     HIP_TRY(hipGetLastError());
-    if (!h->refresh_done) HIP_TRY(hipEventCreateWithFlags(&h->refresh_done, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(h->refresh_done, s));
+    if (!h->refresh_done) HIP_TRY(hipEventCreateWithFlags(h->refresh_done.put(), hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(h->refresh_done.get(), s));
     h->refresh_recorded = true;
     h->ring_planned = false;
     h->ring_refreshed = true;

@@ -9,7 +9,7 @@ import contextlib
 
 import numpy as np
 
-# ---- constants restated from the native headers (include/bcplan.h, csrc/bcp_coop.h, csrc/bcplan.hip) --------------
+# ---- constants restated from the native headers (include/bcplan.h, csrc/bcp_desc.h, csrc/bcp_field_plan.h) --------------
 MAX_VERTS = 32               # BCP_MAX_VERTS
 MAX_KERNEL_HALF = 127        # BCP_MAX_KERNEL_HALF
 MAX_SAMPLES = 8              # kMaxSamples
@@ -116,12 +116,12 @@ def diameter(verts):
 
 
 def footprint_is_wide(verts, res):
-    """footprint_is_wide (bcplan.hip): the cooperative rasteriser's row masks need more than three words"""
+    """footprint_is_wide (bcp_field_plan.h): the cooperative rasteriser's row masks need more than three words"""
     return diameter(verts) / res + 3.0 > NARROW_MASK_PX
 
 
 def check_kernel_size(verts, res):
-    """check_kernel_size (bcplan.hip): the rotated image stays within 255 x 255 px"""
+    """check_kernel_size (bcp_field_plan.h): the rotated image stays within 255 x 255 px"""
     return radius(verts) / res + 2.0 <= MAX_KERNEL_HALF
 
 
@@ -300,7 +300,7 @@ def oracle_masks(oracle, verts, res, angles):
     return np.array(ivs), shapes, masks
 
 
-# ---- host restatement of build_cull_geometry (bcplan.hip) ----------------------------------------------------------
+# ---- host restatement of build_cull_geometry (bcp_field_plan.h) ----------------------------------------------------------
 def _seg_dist(px, py, ax, ay, bx, by):
     vx, vy, wx, wy = bx - ax, by - ay, px - ax, py - ay
     vv = vx * vx + vy * vy
