@@ -9,7 +9,7 @@ from .api import (Action, Box, ContinuousRewardProviderState, CostMap2D, Diffdri
 __all__ = ["Action", "Box", "ContinuousRewardProviderState", "CostMap2D", "DiffdriveRobotState", "EnvParams",
            "INDUSTRIAL_DIFFDRIVE_V1", "INDUSTRIAL_TRICYCLE_V1", "Observation", "RewardParams", "State",
            "TricycleRobotState", "BatchedPlanEnv", "BatchedRandomAisleTurnEnv", "NativeOps", "Lookahead", "ShootingPlanner",
-           "constant_command_library", "Mppi", "MPPIPlanner", "BatchedRangeScan"]
+           "constant_command_library", "Mppi", "MPPIPlanner", "BatchedRangeScan", "BatchedGoalField", "GoalField"]
 
 
 def __getattr__(name):
@@ -26,6 +26,9 @@ def __getattr__(name):
     if name == "BatchedRangeScan":
         from .range_scan import BatchedRangeScan
         return BatchedRangeScan
+    if name in ("BatchedGoalField", "GoalField"):
+        from . import goal_field
+        return getattr(goal_field, name)
     if name == "NativeOps":
         from .ops import NativeOps
         return NativeOps

@@ -15,7 +15,8 @@ LOOKAHEAD_PER_ENV = 1 << 8
 ERR_ANGLE_JUMP, ERR_TIME_ORDER, ERR_INTERNAL = 1, 2, 4
 DONE_GOAL, DONE_TIMEOUT, DONE_COLLIDED = 1, 2, 4
 TUNE_EXACT_MODE, TUNE_DENSE_THRESHOLD, TUNE_CULL, TUNE_DEFER, TUNE_EDT_LDS, TUNE_FUSED, TUNE_EGO_SPARSE, TUNE_NEAR_DILATE = 0, 1, 2, 3, 4, 5, 6, 7
-TUNE_LOCAL_PAIRS, TUNE_EGO_LIST_STRIDE, TUNE_NEAR_SHIFT, TUNE_INFLATE_ROUTE = 8, 9, 10, 11
+TUNE_LOCAL_PAIRS, TUNE_EGO_LIST_STRIDE, TUNE_NEAR_SHIFT, TUNE_INFLATE_ROUTE, TUNE_GOAL_ROUTE = 8, 9, 10, 11, 12
+GOAL_ORTHO, GOAL_DIAG, GOAL_FAR, GOAL_NONE = 12, 17, 65534, 65535
 E_NO_DEVICE = -2
 OPT_DIFFDRIVE_NOISE = 1
 EGO_KERNELS = {0: "none", 1: "ego_sparse_kernel", 2: "ego_costmap_kernel<staged>", 3: "ego_costmap_binned_kernel",
@@ -187,6 +188,12 @@ SYMBOLS = {
                                  C.c_void_p, C.c_void_p]),
     "bcp_final_range_scan": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p]),
+    "bcp_goal_field": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bcp_goal_field_sample": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
+                                        C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bcp_final_goal_field_sample": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_double,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

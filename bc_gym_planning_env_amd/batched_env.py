@@ -697,6 +697,20 @@ class BatchedPlanEnv(Handle):
                                 lambda n, b, shapes, names: self._cached_outputs(self._range_scan_buffers, (n, b), shapes,
                                                                                  names, SCAN_CACHE_ENTRIES))
 
+    def goal_field(self, clearance=None, seeds="goal", max_passes=0):
+        """The geodesic cost-to-go of every bound map to its path's goal (bcp_goal_field, one launch): for each free cell
+        the length of the cheapest route through free space to the nearest seed, as a goal_field.GoalField whose sample()
+        gives distance to go and route direction at any pose.  clearance: how far in metres a route keeps from every
+        lethal cell; None = robots.inscribed_radius of the env's footprint (clearance_d2 = floor((clearance /
+        resolution)^2): 151 for the tricycle at 0.03).  seeds: "goal" = the last way point of each entry's path, "path" =
+        every way point (the field is then the distance to the path).  max_passes: 0 = as many as it takes.
+        Fields: one for a shared map with a shared path, one per pool entry, one per env for private maps -- and one per env
+        for a shared map with private paths, the one map read n_envs times: n_envs * rows * cols * 2 bytes of fields.
+        Only cells == 254 are obstacles, so inflated maps give the same fields.  Refused on endless=True pools: a
+        refresh() would leave stale fields."""
+        from . import goal_field
+        return goal_field.build(self, clearance, seeds, max_passes)
+
     def enable_episode_record(self, capacity=None):
         """Keep what every episode end leaves behind (bcp_bind_episode_record): from now on step() returns
         info = {"episode_ends": EpisodeEnds} -- why each env's episode ended, its final state before the auto-reset, its

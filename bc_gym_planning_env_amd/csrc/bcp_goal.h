@@ -1,0 +1,268 @@
+// bcp_goal.h -- goal_field_kernel and goal_sample_kernel: the geodesic cost-to-go of bcp_goal_field and its per-row reads
+// (include/bcplan.h).  The arithmetic of a cell -- the pull relaxation, the widening of a mask word, the carrot walk -- is
+// bcp_goal_cell.h, which has no HIP in it and which the host tests run as it stands; this file decides who works on which
+// cell and where the words live.
+//
+// goal_field_kernel: one workgroup per map (a grid stride over maps), phases with a barrier between them:
+//   0  clear the 1-bit lethal mask [rows][wpr], the pass flags and the counter
+//   1  read the map ONCE, four cells per aligned dword, as inflate_kernel does; a lethal byte inside the valid shape sets its bit
+//   2  `closed` [rows][wpr] = the lethal mask dilated by the clearance disc, OR everything outside the valid shape: per
+//      destination word the OR over the source rows |dr| <= reach of the words around it widened by that row's half-width
+//      (goal_widen_word: shifts on 64-bit words).  A thread per word.
+//   3  the uint16 plane = kGoalNone everywhere; then the seeds inside the valid shape: value 0, their closed bit cleared
+//   4  passes: a wave per row, a lane per column; a thread PULLS for its own cells (eight neighbour reads, goal_relax_cell)
+//      and writes only those, with ordinary stores.  A read may see a neighbour's value of this pass or of the last one:
+//      values only fall and every value is the length of an admissible route, so either is right.  A thread that lowered a
+//      cell raises the pass's flag; after the barrier a pass that raised none ends the loop -- everything it read was written
+//      before the barrier in front of it, so nothing can change any more.  The flags rotate over three words: the word of
+//      pass p + 1 is cleared during pass p, when its last readers (after pass p - 2) are two barriers behind.
+//   5  copy the plane to `out` and count the cells that hold a value; info = {count, gave_up}
+// The masks and the plane live in LDS when they fit (kLds); otherwise the masks are a slice of handle-owned scratch per
+// workgroup and the plane IS the map's slab of `out`.  A workgroup runs on one CU and its barriers order its own global
+// stores and loads (workgroup scope); no workgroup touches another's map.  The code is one template: the bytes are the same.
+#pragma once
+
+#include "bcp_device.h"
+#include "bcp_goal_cell.h"
+
+namespace bcp {
+
+typedef __attribute__((address_space(3))) uint16_t* GoalLdsU16;
+
+struct GoalArgs {
+    const uint8_t* data;         // [n_maps][rows][cols], or [rows][cols] when shared
+    const int32_t* valid_rows;   // optional [n_maps], with valid_cols
+    const int32_t* valid_cols;
+    const int32_t* seeds;        // [n_maps][n_seeds][2] (row, col)
+    uint16_t* out;               // [n_maps][rows][cols]
+    int32_t* info;               // optional [n_maps][2]
+    uint32_t* scratch;           // global route: [gridDim.x][2][rows][wpr]
+    int64_t n_maps;
+    int32_t rows, cols, wpr, shared;
+    int32_t n_seeds, clearance_d2, reach, max_passes;   // reach = floor(sqrt(clearance_d2)); max_passes >= 1
+};
+
+constexpr int kGoalFixedWords = 128 + 4;   // half-widths [128], pass flags [3], counter
+
+template <bool kLds> struct GoalMem;
+template <> struct GoalMem<true> {
+    typedef LdsU32 Words;
+    typedef GoalLdsU16 Plane;
+};
+template <> struct GoalMem<false> {
+    typedef uint32_t* Words;
+    typedef uint16_t* Plane;
+};
+
+template <typename Plane>
+struct GoalPlaneGet {
+    Plane p;
+    int32_t cols;
+    __device__ __forceinline__ uint16_t operator()(int32_t r, int32_t c) const { return p[r * cols + c]; }
+};
+
+// dynamic LDS of the kernel: the fixed words, and on the LDS route both masks and the plane
+__host__ __device__ inline size_t goal_lds_bytes(int rows, int cols, int wpr, bool in_lds)
+{
+    const size_t fixed = (size_t)kGoalFixedWords * 4;
+    return in_lds ? fixed + (size_t)2 * rows * wpr * 4 + (((size_t)rows * cols * 2 + 3) & ~(size_t)3) : fixed;
+}
+
+template <bool kLds>
+__global__ void __launch_bounds__(1024) goal_field_kernel(GoalArgs a)
+{
+    typedef typename GoalMem<kLds>::Words Words;
+    typedef typename GoalMem<kLds>::Plane Plane;
+    const int rows = a.rows, cols = a.cols, wpr = a.wpr, cells = rows * cols, n_words = rows * wpr;
+    const int tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63, wave = tid >> 6, n_waves = nthr >> 6;
+    const LdsU32 half_width = (LdsU32)lds_dyn;     // [reach + 1]
+    const LdsU32 flags = half_width + 128;         // [3]
+    const LdsU32 counter = flags + 3;
+    Words lethal, closed;
+    Plane plane;
+    if constexpr (kLds) {
+        lethal = counter + 1;
+        closed = lethal + n_words;
+        plane = (GoalLdsU16)(closed + n_words);
+    } else {
+        lethal = a.scratch + (int64_t)blockIdx.x * 2 * n_words;
+        closed = lethal + n_words;
+        plane = nullptr;
+    }
+    for (int dr = tid; dr <= a.reach; dr += nthr) half_width[dr] = (uint32_t)goal_half_width(a.clearance_d2, dr);
+
+    for (int64_t m = blockIdx.x; m < a.n_maps; m += gridDim.x) {
+        uint16_t* const dst = a.out + m * (int64_t)cells;
+        if constexpr (!kLds) plane = dst;
+        int vr = rows, vc = cols;
+        if (a.valid_rows) {
+            vr = min(max(a.valid_rows[m], 0), rows);
+            vc = min(max(a.valid_cols[m], 0), cols);
+        }
+        // ---- 0: clear (the previous map's phases 4 and 5 read neither the lethal mask nor, after thread 0 is done, the counter)
+        for (int i = tid; i < n_words; i += nthr) lethal[i] = 0u;
+        if (tid == 0) flags[0] = flags[1] = flags[2] = *counter = 0u;
+        __syncthreads();
+        // ---- 1: the map, once.  Dword j of the aligned run that covers the map holds cells 4 j - head .. 4 j - head + 3
+        {
+            const uint8_t* src = a.data + (a.shared ? 0 : m) * (int64_t)cells;
+            const int head = (int)((uintptr_t)src & 3u);
+            const uint32_t* words = reinterpret_cast<const uint32_t*>(src - head);
+            const int n_dwords = (cells + head + 3) >> 2;
+            for (int j = tid; j < n_dwords; j += nthr) {
+                const uint32_t y = words[j] ^ 0xFEFEFEFEu;   // a zero byte = a lethal cell
+                if (((y - 0x01010101u) & ~y & 0x80808080u) == 0u) continue;
+                for (int b = 0; b < 4; ++b) {
+                    const int p = 4 * j - head + b;          // (bytes before and after the map belong to others: skipped)
+                    if (((y >> (8 * b)) & 255u) != 0u || p < 0 || p >= cells) continue;
+                    const int r = p / cols, c = p - r * cols;
+                    if (r < vr && c < vc)
+                        __hip_atomic_fetch_or(lethal + r * wpr + (c >> 5), 1u << (c & 31), __ATOMIC_RELAXED,
+                                              __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
+            }
+        }
+        __syncthreads();
+        // ---- 2: closed = blocked, or outside the valid shape
+        for (int i = tid; i < n_words; i += nthr) {
+            const int r = i / wpr, w = i - r * wpr, first = 32 * w;
+            const uint32_t inside = r < vr && vc > first ? (vc - first >= 32 ? ~0u : (1u << (vc - first)) - 1u) : 0u;
+            uint32_t acc = 0u;
+            if (inside) {
+                const int lo = max(r - a.reach, 0), hi = min(r + a.reach, vr - 1);
+                for (int rr = lo; rr <= hi; ++rr) {
+                    const int hw = (int)half_width[rr > r ? rr - r : r - rr], kw = (hw + 31) >> 5;
+                    const int k0 = max(w - kw, 0), k1 = min(w + kw, wpr - 1);
+                    for (int k = k0; k <= k1; ++k) acc |= goal_widen_word(lethal[rr * wpr + k], 32 * (k - w), hw);
+                }
+            }
+            closed[i] = (acc & inside) | ~inside;
+        }
+        // ---- 3: the plane and the seeds
+        for (int i = tid; i < cells; i += nthr) plane[i] = (uint16_t)kGoalNone;
+        __syncthreads();
+        for (int s = tid; s < a.n_seeds; s += nthr) {
+            const int32_t* seed = a.seeds + (m * a.n_seeds + s) * 2;
+            const int sr = seed[0], sc = seed[1];
+            if ((uint32_t)sr < (uint32_t)vr && (uint32_t)sc < (uint32_t)vc) {
+                plane[sr * cols + sc] = (uint16_t)0;
+                __hip_atomic_fetch_and(closed + sr * wpr + (sc >> 5), ~(1u << (sc & 31)), __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
+        }
+        __syncthreads();
+        // ---- 4: passes
+        int gave_up = 0;
+        {
+            const GoalPlaneGet<Plane> get = {plane, cols};
+            int mine = 0, next = 1;   // flag words of this pass and of the one after it
+            for (int pass = 0;; ++pass) {
+                if (pass == a.max_passes) {   // (the pass before this one lowered a cell)
+                    gave_up = 1;
+                    break;
+                }
+                if (tid == 0) flags[next] = 0u;
+                bool lowered = false;
+                for (int r = wave; r < vr; r += n_waves) {
+                    for (int c = lane; c < vc; c += 64) {
+                        if ((closed[r * wpr + (c >> 5)] >> (c & 31)) & 1u) continue;
+                        const int32_t own = plane[r * cols + c];
+                        if (own == 0) continue;
+                        const int32_t now = goal_relax_cell(get, vr, vc, r, c, own);
+                        if (now != own) {
+                            plane[r * cols + c] = (uint16_t)now;
+                            lowered = true;
+                        }
+                    }
+                }
+                if (lowered) flags[mine] = 1u;
+                __syncthreads();
+                if (flags[mine] == 0u) break;
+                mine = next;
+                next = next == 2 ? 0 : next + 1;
+            }
+        }
+        // ---- 5: out and info
+        {
+            uint32_t n_set = 0u;
+            for (int i = tid; i < cells; i += nthr) {
+                const uint16_t v = plane[i];
+                if constexpr (kLds) dst[i] = v;
+                n_set += v != (uint16_t)kGoalNone ? 1u : 0u;
+            }
+            if (a.info) {
+                if (n_set) __hip_atomic_fetch_add(counter, n_set, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                __syncthreads();
+                if (tid == 0) {
+                    a.info[2 * m] = (int32_t)*counter;
+                    a.info[2 * m + 1] = gave_up;
+                }
+            }
+        }
+        // (no barrier here: phase 0 of the next map writes the lethal mask, the flags and -- thread 0 alone, after its read
+        //  above -- the counter; its barrier keeps closed and the plane intact until every thread has left phase 5)
+    }
+}
+
+// ---- per-row reads of finished fields ---------------------------------------------------------------------------
+struct GoalSampleArgs {
+    const uint16_t* field;       // [n_fields][rows][cols]
+    int64_t n_fields, n_entries;   // n_entries: pool entries, or n_envs without a pool
+    int32_t rows, cols, shared, carrot_cells;
+    const int32_t* valid_rows;   // per entry, or nullptr: the allocated shape
+    const int32_t* valid_cols;
+    const double* origins;       // per entry, or nullptr: (ox, oy)
+    double ox, oy, inv_res, resolution, max_dist;
+    const double* poses;         // [n][3] or nullptr: sx, sy, sth
+    const double *sx, *sy, *sth;
+    const int32_t* entry;        // entry of an env (pool entry, or env of a record's slot), or nullptr: the env index itself
+    const int32_t* live;         // rows beyond min(*live, n) are left alone, or nullptr
+    const int32_t* row_env;      // env of row i, or nullptr: i % n_envs
+    int64_t n_envs, n;
+    float* out3;
+    int32_t* cell_value;         // or nullptr
+    int32_t* carrot;             // or nullptr
+};
+
+struct GoalFieldGet {
+    const uint16_t* p;
+    int32_t cols;
+    __device__ __forceinline__ uint16_t operator()(int32_t r, int32_t c) const { return p[r * cols + c]; }
+};
+
+__global__ void __launch_bounds__(256) goal_sample_kernel(GoalSampleArgs a)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t n_rows = a.live ? min(a.n, (int64_t)max(*a.live, 0)) : a.n;
+    if (i >= n_rows) return;
+    GoalSample s = goal_no_sample(a.max_dist);
+    const int64_t me = a.row_env ? (int64_t)a.row_env[i] : i % a.n_envs;
+    if (me >= 0 && me < a.n_envs) {
+        // the env's entry among the non-shared arrays: it picks the field; the map it is read on is entry 0 when shared
+        const int64_t slot = a.entry ? (int64_t)a.entry[me] : me;
+        if (slot >= 0 && slot < a.n_entries) {
+            const int64_t g = a.shared ? 0 : slot;
+            const double ox = a.origins ? a.origins[2 * g] : a.ox, oy = a.origins ? a.origins[2 * g + 1] : a.oy;
+            const double x = a.poses ? a.poses[3 * i] : a.sx[i];
+            const double y = a.poses ? a.poses[3 * i + 1] : a.sy[i];
+            const double th = a.poses ? a.poses[3 * i + 2] : a.sth[i];
+            const double lim = 1.7976931348623157e308;
+            const bool finite = x >= -lim && x <= lim && y >= -lim && y <= lim && th >= -lim && th <= lim;
+            const double ct = finite ? cos(th) : 0.0, st = finite ? sin(th) : 0.0;
+            const int32_t vr = a.valid_rows ? max(0, min(a.valid_rows[g], a.rows)) : a.rows;
+            const int32_t vc = a.valid_cols ? max(0, min(a.valid_cols[g], a.cols)) : a.cols;
+            const GoalFieldGet get = {a.field + (a.n_fields == 1 ? 0 : slot) * ((int64_t)a.rows * a.cols), a.cols};
+            s = goal_sample_row(get, vr, vc, x, y, ct, st, finite, ox, oy, a.inv_res, a.resolution, a.carrot_cells, a.max_dist);
+        }
+    }
+    a.out3[3 * i] = s.out3[0];
+    a.out3[3 * i + 1] = s.out3[1];
+    a.out3[3 * i + 2] = s.out3[2];
+    if (a.cell_value) a.cell_value[i] = s.cell_value;
+    if (a.carrot) {
+        a.carrot[2 * i] = s.carrot_row;
+        a.carrot[2 * i + 1] = s.carrot_col;
+    }
+}
+
+}  // namespace bcp

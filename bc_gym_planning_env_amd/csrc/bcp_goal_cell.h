@@ -1,0 +1,211 @@
+// bcp_goal_cell.h -- the goal field's arithmetic (bcp_goal_field, bcp_goal_field_sample; include/bcplan.h): the argument
+// checks, the half-widths of the clearance disc and the widening of one mask word, the pull relaxation of one cell, and the
+// sampling of one row with its carrot walk.  Plain C++ with no HIP in it: goal_field_kernel and goal_sample_kernel
+// (bcp_goal.h) call these functions on the device, tests/c_abi/goal_field_main.cpp calls the same ones on the host, and there
+// is no other copy of them.  The float64 arithmetic rounds every product, quotient, root and sum on its own
+// (-ffp-contract=off).
+//
+// A field is a uint16 plane [rows][cols]: kGoalNone where no route exists (blocked, outside the valid shape, not connected
+// to a seed), else min(length of the cheapest admissible route to a seed, kGoalFar) with steps of kGoalOrtho to an edge
+// neighbour and kGoalDiag to a corner neighbour.  A corner step is admissible only if both edge neighbours it passes
+// between are free.  While the plane is being relaxed "free" is read off the plane itself: a cell counts as free once it
+// holds a value.  That only delays a corner step until both edge cells are reached -- and they are reached whenever the
+// corner's far end is, being edge neighbours of it -- so the fixed point is the same, and every intermediate value is
+// still the length of an admissible route.
+#pragma once
+
+#include <cstdint>
+
+#if defined(__HIPCC__)
+#define BCP_HD __host__ __device__
+#else
+#define BCP_HD
+#endif
+
+namespace bcp {
+
+constexpr int32_t kGoalOrtho = 12;
+constexpr int32_t kGoalDiag = 17;
+constexpr int32_t kGoalFar = 65534;
+constexpr int32_t kGoalNone = 65535;
+constexpr int32_t kGoalMaxSide = 2048;
+constexpr int32_t kGoalMaxSeeds = 4096;
+constexpr int32_t kGoalMaxClearance = 127 * 127;   // BCP_MAX_KERNEL_HALF squared
+constexpr int32_t kGoalMaxCarrot = 256;
+
+// neighbour k: E, NE, N, NW, W, SW, S, SE
+BCP_HD inline int32_t goal_dcol(int k) { return k == 0 || k == 1 || k == 7 ? 1 : (k == 2 || k == 6 ? 0 : -1); }
+BCP_HD inline int32_t goal_drow(int k) { return k >= 1 && k <= 3 ? 1 : (k == 0 || k == 4 ? 0 : -1); }
+
+// what bcp_goal_field refuses with BCP_E_INVALID, in the order it looks
+enum GoalRefusal {
+    kGoalOk = 0, kGoalHandle = 1, kGoalMaps = 2, kGoalShape = 3, kGoalSeeds = 4, kGoalClearance = 5, kGoalPasses = 6,
+    kGoalValidPair = 7, kGoalValidShared = 8, kGoalPointers = 9
+};
+
+BCP_HD inline int goal_field_check_args(bool have_handle, int64_t n_maps, bool have_data, bool have_seeds, bool have_out,
+                                        int32_t rows, int32_t cols, int32_t n_seeds, int32_t clearance_d2, int32_t max_passes,
+                                        bool have_valid_rows, bool have_valid_cols, bool shared)
+{
+    if (!have_handle) return kGoalHandle;
+    if (n_maps < 0) return kGoalMaps;
+    if (rows < 1 || rows > kGoalMaxSide || cols < 1 || cols > kGoalMaxSide) return kGoalShape;
+    if (n_seeds < 1 || n_seeds > kGoalMaxSeeds) return kGoalSeeds;
+    if (clearance_d2 < 0 || clearance_d2 > kGoalMaxClearance) return kGoalClearance;
+    if (max_passes < 0) return kGoalPasses;
+    if (have_valid_rows != have_valid_cols) return kGoalValidPair;
+    if (shared && have_valid_rows) return kGoalValidShared;
+    if (n_maps > 0 && (!have_data || !have_seeds || !have_out)) return kGoalPointers;
+    return kGoalOk;
+}
+
+// ... and bcp_goal_field_sample.  n_entries: fields the binding has (0 while no costmaps are bound: the comparisons with the
+// binding are then the caller's BCP_E_STATE); final_form: the rows are the record's, n is not the caller's to choose
+enum GoalSampleRefusal {
+    kGoalSampleOk = 0, kGoalSampleNull = 1, kGoalSampleCarrot = 2, kGoalSampleDist = 3, kGoalSampleRows = 4,
+    kGoalSampleRowEnv = 5, kGoalSampleShape = 6, kGoalSampleFields = 7
+};
+
+BCP_HD inline int goal_sample_check_args(bool have_handle, bool have_field, bool have_out3, int32_t carrot_cells, double max_dist,
+                                         int64_t n, int64_t n_envs, bool have_poses, bool have_row_env, bool final_form,
+                                         int32_t rows, int32_t cols, int32_t map_rows, int32_t map_cols, int64_t n_fields,
+                                         int64_t n_entries)
+{
+    if (!have_handle || !have_field || !have_out3) return kGoalSampleNull;
+    if (carrot_cells < 1 || carrot_cells > kGoalMaxCarrot) return kGoalSampleCarrot;
+    if (!(max_dist > 0.0)) return kGoalSampleDist;   // (a NaN fails the comparison; +inf passes)
+    if (!final_form && (n <= 0 || (!have_poses && n != n_envs))) return kGoalSampleRows;
+    if (!have_poses && have_row_env) return kGoalSampleRowEnv;
+    if (n_entries > 0 && (rows != map_rows || cols != map_cols)) return kGoalSampleShape;
+    if (n_entries > 0 && n_fields != 1 && n_fields != n_entries) return kGoalSampleFields;
+    return kGoalSampleOk;
+}
+
+BCP_HD inline int32_t goal_isqrt(int32_t n)   // floor(sqrt(n)), 0 <= n <= kGoalMaxClearance
+{
+    int32_t r = 0;
+    while ((r + 1) * (r + 1) <= n) ++r;
+    return r;
+}
+
+// half-width of the clearance disc `dr` rows from its centre, |dr| <= goal_isqrt(clearance_d2)
+BCP_HD inline int32_t goal_half_width(int32_t clearance_d2, int32_t dr) { return goal_isqrt(clearance_d2 - dr * dr); }
+
+// One word of a bit row widened by `hw` to either side, as seen in the word `d` columns to its left (d = 32 * (source word -
+// destination word)): bit j of the result is set iff the source has a bit b with |d + b - j| <= hw.
+BCP_HD inline uint32_t goal_widen_word(uint32_t x, int32_t d, int32_t hw)
+{
+    const int32_t a = d - hw > -31 ? d - hw : -31, b = d + hw < 31 ? d + hw : 31;   // the shifts that land in the word
+    if (x == 0u || a > b) return 0u;
+    uint64_t y = (uint64_t)x << 32;              // the destination word is the upper half: right shifts keep their bits
+    y = a >= 0 ? y << a : y >> -a;
+    for (int32_t cover = 0, n = b - a; cover < n;) {   // y covers the shifts a .. a + cover
+        const int32_t s = cover + 1 < n - cover ? cover + 1 : n - cover;
+        y |= y << s;
+        cover += s;
+    }
+    return (uint32_t)(y >> 32);
+}
+
+// The pull relaxation of cell (r, c) of a plane whose valid shape is (vr, vc): the smallest of its own value and, over its
+// admissible neighbours, the neighbour's value plus the step, saturating at kGoalFar.  get(row, col) reads the plane and is
+// only ever called inside the valid shape.  The caller sees to it that a blocked cell is never relaxed.
+template <typename Get>
+BCP_HD inline int32_t goal_relax_cell(const Get& get, int32_t vr, int32_t vc, int32_t r, int32_t c, int32_t own)
+{
+    int32_t v[8];
+    for (int k = 0; k < 8; ++k) {
+        const int32_t rr = r + goal_drow(k), cc = c + goal_dcol(k);
+        v[k] = (uint32_t)rr < (uint32_t)vr && (uint32_t)cc < (uint32_t)vc ? (int32_t)get(rr, cc) : kGoalNone;
+    }
+    const int32_t nothing = 0x7FFFFFFF;
+    int32_t best = own == kGoalNone ? nothing : own;
+    for (int k = 0; k < 8; k += 2)
+        if (v[k] != kGoalNone) best = v[k] + kGoalOrtho < best ? v[k] + kGoalOrtho : best;
+    for (int k = 1; k < 8; k += 2)   // a corner step passes between edge neighbours k - 1 and k + 1
+        if (v[k] != kGoalNone && v[k - 1] != kGoalNone && v[(k + 1) & 7] != kGoalNone)
+            best = v[k] + kGoalDiag < best ? v[k] + kGoalDiag : best;
+    if (best == nothing) return kGoalNone;
+    return best < kGoalFar ? best : kGoalFar;   // (the sums stop at kGoalFar: a longer route reads kGoalFar, never kGoalNone)
+}
+
+// One step of the carrot walk on a finished field from (r, c): the admissible neighbour k that minimises field + step, ties
+// to the lowest k; -1 if no neighbour is admissible.
+template <typename Get>
+BCP_HD inline int goal_walk_step(const Get& get, int32_t vr, int32_t vc, int32_t r, int32_t c)
+{
+    int32_t v[8];
+    for (int k = 0; k < 8; ++k) {
+        const int32_t rr = r + goal_drow(k), cc = c + goal_dcol(k);
+        v[k] = (uint32_t)rr < (uint32_t)vr && (uint32_t)cc < (uint32_t)vc ? (int32_t)get(rr, cc) : kGoalNone;
+    }
+    int best_k = -1;
+    int32_t best = 0;
+    for (int k = 0; k < 8; ++k) {
+        if (v[k] == kGoalNone) continue;
+        if ((k & 1) && (v[k - 1] == kGoalNone || v[(k + 1) & 7] == kGoalNone)) continue;
+        const int32_t cost = v[k] + ((k & 1) ? kGoalDiag : kGoalOrtho);
+        if (best_k < 0 || cost < best) {
+            best_k = k;
+            best = cost;
+        }
+    }
+    return best_k;
+}
+
+struct GoalSample {
+    float out3[3];         // min(distance, max_dist) in metres, direction to the carrot in the robot frame
+    int32_t cell_value;    // the field at the pose's cell, kGoalNone for a row without a result
+    int32_t carrot_row, carrot_col;   // (-1, -1) for a row without a result
+};
+
+BCP_HD inline GoalSample goal_no_sample(double max_dist)
+{
+    GoalSample s;
+    s.out3[0] = (float)max_dist;
+    s.out3[1] = s.out3[2] = 0.0f;
+    s.cell_value = kGoalNone;
+    s.carrot_row = s.carrot_col = -1;
+    return s;
+}
+
+// One row of bcp_goal_field_sample: pose (x, y) with heading (cos, sin) = (ct, st) on a field with origin (ox, oy) and valid
+// shape (vr, vc); `finite`: x, y and the heading are finite numbers.
+template <typename Get>
+BCP_HD inline GoalSample goal_sample_row(const Get& get, int32_t vr, int32_t vc, double x, double y, double ct, double st,
+                                         bool finite, double ox, double oy, double inv_res, double resolution,
+                                         int32_t carrot_cells, double max_dist)
+{
+    if (!finite) return goal_no_sample(max_dist);
+    const double fc = __builtin_rint((x - ox) * inv_res), fr = __builtin_rint((y - oy) * inv_res);   // half to even
+    if (!(fc >= 0.0 && fc < (double)vc && fr >= 0.0 && fr < (double)vr)) return goal_no_sample(max_dist);
+    int32_t r = (int32_t)fr, c = (int32_t)fc;
+    const int32_t r0 = r, c0 = c;
+    int32_t v = (int32_t)get(r, c);
+    if (v == kGoalNone) return goal_no_sample(max_dist);
+    GoalSample s;
+    const double dist = ((double)v * resolution) / 12.0;
+    s.out3[0] = (float)(dist < max_dist ? dist : max_dist);
+    s.cell_value = v;
+    for (int32_t step = 0; step < carrot_cells && v != 0; ++step) {
+        const int k = goal_walk_step(get, vr, vc, r, c);
+        if (k < 0) break;
+        r += goal_drow(k);
+        c += goal_dcol(k);
+        v = (int32_t)get(r, c);
+    }
+    s.carrot_row = r;
+    s.carrot_col = c;
+    if (r == r0 && c == c0) {
+        s.out3[1] = s.out3[2] = 0.0f;
+        return s;
+    }
+    const double dx = (ox + (double)c * resolution) - x, dy = (oy + (double)r * resolution) - y;
+    const double norm = __builtin_sqrt(dx * dx + dy * dy);
+    const double ux = dx / norm, uy = dy / norm;
+    s.out3[1] = (float)(ux * ct + uy * st);
+    s.out3[2] = (float)(uy * ct - ux * st);
+    return s;
+}
+
+}  // namespace bcp

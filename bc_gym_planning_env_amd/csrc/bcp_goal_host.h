@@ -1,0 +1,153 @@
+// bcp_goal_host.h -- the host side of the goal field: bcp_goal_field (checks, the choice of where masks and plane live, the
+// launch), bcp_goal_field_sample / bcp_final_goal_field_sample over the rows of obs_rows() (bcp_ego_host.h), and the value
+// check of BCP_TUNE_GOAL_ROUTE.  The refusals are the checks of bcp_goal_cell.h, which the host tests run too; the kernels are
+// in bcp_goal.h.  Included by bcplan.hip after bcp_ego_host.h.
+// Capture: the launch arguments depend only on what the caller passes and nothing is uploaded, but a field kernel whose
+// dynamic LDS passes 64 KB needs its limit raised on first use (raise_dynamic_lds: not a stream operation), and the global
+// route may grow the scratch: one ordinary call with the same shapes must precede a capture.  The sample call uses no LDS.
+#pragma once
+
+// Global route: two masks per workgroup in scratch, so the grid is what sizes it (as for bcp_inflate_costmaps).
+constexpr int64_t kGoalGlobalGrid = 512;
+constexpr int64_t kGoalScratchBytes = 256ll << 20;
+
+static int goal_set_route(bcp_handle* h, int32_t value)
+{
+    if (value != 0 && value != 2) return fail(BCP_E_INVALID, "bcp_set_tuning: BCP_TUNE_GOAL_ROUTE takes 0 or 2");
+    h->tune.goal_route = value;
+    return BCP_OK;
+}
+
+extern "C" int bcp_goal_field(bcp_handle* h, const uint8_t* data, int64_t n_maps, int32_t rows, int32_t cols, int32_t shared,
+                              const int32_t* valid_rows, const int32_t* valid_cols, const int32_t* seeds, int32_t n_seeds,
+                              int32_t clearance_d2, int32_t max_passes, uint16_t* out, int32_t* info, void* stream)
+{
+    switch (goal_field_check_args(h != nullptr, n_maps, data != nullptr, seeds != nullptr, out != nullptr, rows, cols, n_seeds,
+                                  clearance_d2, max_passes, valid_rows != nullptr, valid_cols != nullptr, shared != 0)) {
+    case kGoalOk: break;
+    case kGoalHandle: return fail(BCP_E_INVALID, "bcp_goal_field: null handle");
+    case kGoalMaps: return fail(BCP_E_INVALID, "bcp_goal_field: n_maps %lld is negative", (long long)n_maps);
+    case kGoalShape: return fail(BCP_E_INVALID, "bcp_goal_field: shape %d x %d outside [1, 2048] x [1, 2048]", rows, cols);
+    case kGoalSeeds: return fail(BCP_E_INVALID, "bcp_goal_field: n_seeds %d outside [1, %d]", n_seeds, kGoalMaxSeeds);
+    case kGoalClearance: return fail(BCP_E_INVALID, "bcp_goal_field: clearance_d2 %d outside [0, %d]", clearance_d2, kGoalMaxClearance);
+    case kGoalPasses: return fail(BCP_E_INVALID, "bcp_goal_field: max_passes %d is negative", max_passes);
+    case kGoalValidPair: return fail(BCP_E_INVALID, "bcp_goal_field: valid_rows and valid_cols go together, both or neither");
+    case kGoalValidShared: return fail(BCP_E_INVALID, "bcp_goal_field: a shared map takes no valid shapes");
+    default: return fail(BCP_E_INVALID, "bcp_goal_field: null data / seeds / out");
+    }
+    if (n_maps == 0) return BCP_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+
+    GoalArgs a = {};
+    a.data = data;
+    a.valid_rows = valid_rows;
+    a.valid_cols = valid_cols;
+    a.seeds = seeds;
+    a.out = out;
+    a.info = info;
+    a.n_maps = n_maps;
+    a.rows = rows;
+    a.cols = cols;
+    a.wpr = (cols + 31) / 32;
+    a.shared = shared ? 1 : 0;
+    a.n_seeds = n_seeds;
+    a.clearance_d2 = clearance_d2;
+    a.reach = goal_isqrt(clearance_d2);
+    a.max_passes = max_passes > 0 ? max_passes : rows * cols;
+    const int64_t cells = (int64_t)rows * cols;
+    const bool in_lds = goal_lds_bytes(rows, cols, a.wpr, true) <= kMaxDynamicLds && h->tune.goal_route != 2;
+    // a workgroup's threads: enough cells each to be worth their barriers
+    const unsigned threads = cells >= 128 * 128 ? 1024u : 256u;
+    if (in_lds) {
+        const unsigned grid = (unsigned)std::min<int64_t>(n_maps, 16384);
+        return launch_variant(h, reinterpret_cast<const void*>(goal_field_kernel<true>), dim3(grid), dim3(threads),
+                              goal_lds_bytes(rows, cols, a.wpr, true), s, a);
+    }
+    const int64_t mask_words = (int64_t)2 * rows * a.wpr;
+    const int64_t fit = std::max<int64_t>(1, kGoalScratchBytes / (mask_words * (int64_t)sizeof(uint32_t)));
+    const int64_t grid = std::min(std::min(n_maps, kGoalGlobalGrid), fit);
+    if (h->goal_scratch.reserve((size_t)(grid * mask_words)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(BCP_E_HIP, "bcp_goal_field: cannot allocate %lld bytes of scratch", (long long)(grid * mask_words * 4));
+    }
+    a.scratch = h->goal_scratch.get();
+    return launch_variant(h, reinterpret_cast<const void*>(goal_field_kernel<false>), dim3((unsigned)grid), dim3(threads),
+                          goal_lds_bytes(rows, cols, a.wpr, false), s, a);
+}
+
+// rec != nullptr: the final states of the episode record, n = capacity, rows j < min(*count, capacity)
+static int goal_field_sample(bcp_handle* h, const uint16_t* field, int64_t n_fields, int32_t rows, int32_t cols,
+                             const double* poses, int64_t n, const int32_t* row_env, int32_t carrot_cells, double max_dist,
+                             float* out3, int32_t* cell_value, int32_t* carrot, void* stream, const EpisodeRec* rec,
+                             const char* who)
+{
+    const bool bound = h && h->have_map;
+    const int64_t n_entries = bound ? n_slots(h) : 0;   // (a shared map may go with private paths: a field per env)
+    switch (goal_sample_check_args(h != nullptr, field != nullptr, out3 != nullptr, carrot_cells, max_dist, n, h ? h->n : 0,
+                                   poses != nullptr, row_env != nullptr, rec != nullptr, rows, cols, bound ? h->map.rows : 0,
+                                   bound ? h->map.cols : 0, n_fields, n_entries)) {
+    case kGoalSampleOk: break;
+    case kGoalSampleNull: return fail(BCP_E_INVALID, "%s: null argument", who);
+    case kGoalSampleCarrot: return fail(BCP_E_INVALID, "%s: carrot_cells %d outside [1, %d]", who, carrot_cells, kGoalMaxCarrot);
+    case kGoalSampleDist: return fail(BCP_E_INVALID, "%s: max_dist must be > 0 (+inf is allowed)", who);
+    case kGoalSampleRows: return fail(BCP_E_INVALID, "%s: n must be positive, and n_envs without poses", who);
+    case kGoalSampleRowEnv: return fail(BCP_E_INVALID, "%s: row_env needs poses", who);
+    case kGoalSampleShape: return fail(BCP_E_INVALID, "%s: the field's shape %d x %d is not the bound maps' %d x %d", who, rows, cols,
+                                       h->map.rows, h->map.cols);
+    default: return fail(BCP_E_INVALID, "%s: n_fields %lld is neither 1 nor the %lld entries bound", who, (long long)n_fields,
+                         (long long)n_entries);
+    }
+    if (!h->have_map) return fail(BCP_E_STATE, "%s: costmaps not set", who);
+    if (!poses && !rec && !h->have_state) return fail(BCP_E_STATE, "%s: no poses given and no state bound", who);
+    HIP_TRY(hipSetDevice(h->device));
+    const ObsRows R = obs_rows(h, rec);
+    GoalSampleArgs a;
+    memset(&a, 0, sizeof(a));
+    a.field = field;
+    a.n_fields = n_fields;
+    a.n_entries = n_entries;
+    a.rows = rows;
+    a.cols = cols;
+    a.shared = h->map.shared;
+    a.carrot_cells = carrot_cells;
+    a.valid_rows = h->map_valid_rows;
+    a.valid_cols = h->map_valid_cols;
+    a.origins = h->map.origins;
+    a.ox = h->map.ox;
+    a.oy = h->map.oy;
+    a.inv_res = h->map.inv_res;
+    a.resolution = h->resolution;
+    a.max_dist = max_dist;
+    a.poses = poses;
+    const bool delayed = h->params.pose_delay > 0 && R.st.pose_seen;   // the observation shows State.pose, i.e. the delayed pose
+    a.sx = delayed ? R.st.pose_seen : R.st.x;
+    a.sy = delayed ? R.st.pose_seen + R.n : R.st.y;
+    a.sth = delayed ? R.st.pose_seen + 2 * R.n : R.st.angle;
+    a.entry = h->n_geoms > 0 ? (R.entry ? R.entry : h->geom_of_env) : R.entry;
+    a.live = R.live;
+    a.row_env = row_env;
+    a.n_envs = R.n;
+    a.n = n;
+    a.out3 = out3;
+    a.cell_value = cell_value;
+    a.carrot = carrot;
+    return launch_fn((const void*)goal_sample_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+}
+
+extern "C" int bcp_goal_field_sample(bcp_handle* h, const uint16_t* field, int64_t n_fields, int32_t rows, int32_t cols,
+                                     const double* poses, int64_t n, const int32_t* row_env, int32_t carrot_cells,
+                                     double max_dist, float* out3, int32_t* cell_value, int32_t* carrot, void* stream)
+{
+    return goal_field_sample(h, field, n_fields, rows, cols, poses, n, row_env, carrot_cells, max_dist, out3, cell_value, carrot,
+                             stream, nullptr, "bcp_goal_field_sample");
+}
+
+extern "C" int bcp_final_goal_field_sample(bcp_handle* h, const uint16_t* field, int64_t n_fields, int32_t rows, int32_t cols,
+                                           int32_t carrot_cells, double max_dist, float* out3, int32_t* cell_value,
+                                           int32_t* carrot, void* stream)
+{
+    if (h && !h->have_rec) return fail(BCP_E_STATE, "bcp_final_goal_field_sample: no episode record bound");
+    return goal_field_sample(h, field, n_fields, rows, cols, nullptr, h ? h->rec.capacity : 0, nullptr, carrot_cells, max_dist,
+                             out3, cell_value, carrot, stream, h ? &h->rec : nullptr, "bcp_final_goal_field_sample");
+}

@@ -1,6 +1,7 @@
 // bcp_host.h -- what every host-side piece of libbcplan shares: the error record, the handle with the owners of its state,
 // and the few helpers that launch kernels.  Included by bcplan.hip after the device headers and before the subsystems (bcp_field.h,
-// bcp_step_host.h, bcp_seams.h + bcp_seams_host.h, bcp_ego_host.h, bcp_worlds_host.h, bcp_inflate_host.h, bcp_scan_host.h).
+// bcp_step_host.h, bcp_seams.h + bcp_seams_host.h, bcp_ego_host.h, bcp_worlds_host.h, bcp_inflate_host.h, bcp_scan_host.h,
+// bcp_goal_host.h).
 #pragma once
 
 // The library exports its C entry points and nothing else: the member functions of the host-side types stay inside.
@@ -89,6 +90,7 @@ struct Tuning {
     int32_t ego_sparse = 1;         // BCP_TUNE_EGO_SPARSE: 0 never, 1 cost model, >= 2 explicit limit of cells per map
     int32_t ego_stride = 0;         // BCP_TUNE_EGO_LIST_STRIDE: 0 = lists sized from the counts, else this many cells per entry (tests)
     int32_t inflate_route = 0;      // BCP_TUNE_INFLATE_ROUTE: 0 by size, 2 always the global plane
+    int32_t goal_route = 0;         // BCP_TUNE_GOAL_ROUTE: 0 by size, 2 masks and plane always in global memory
 
     // the defaults of a new handle: the initialisers above, and what the environment says for every handle of the process
     static Tuning from_environment()
@@ -245,6 +247,8 @@ struct bcp_handle {
     int32_t side_share = 0;         // ... and the share of the CUs it was created with
     // ---- bcp_inflate_costmaps: the 16-bit plane of maps beyond LDS, a slice per workgroup; grown on demand, never shrunk
     DevBuf<uint16_t> inflate_scratch;
+    // ---- bcp_goal_field: the two bit masks of maps beyond LDS, a slice per workgroup; grown on demand, never shrunk
+    DevBuf<uint32_t> goal_scratch;
 };
 
 // number of entries of a non-shared map / path / initial-state array

@@ -1,0 +1,172 @@
+"""Goal fields for the whole batch: the geodesic cost-to-go of every bound map to its path's goal (bcp_goal_field, one
+launch per build) and what it says at a pose -- distance to go and the direction of the route -- per env and step
+(bcp_goal_field_sample, one tiny launch).  The terminal cost of a sampling planner, the dense shaping term and the
+"direction to goal" feature of a navigation policy.  The reference has no counterpart; the shape of the wrapper follows
+BatchedRangeScan (range_scan.py)."""
+from collections import OrderedDict
+
+import numpy as np
+import torch
+
+from . import _lib, robots
+from .handle import SCAN_CACHE_ENTRIES, cached
+from .wrappers import BatchedObservationWrapper
+
+
+def clearance_cells_squared(clearance, resolution):
+    """clearance in metres -> clearance_d2 of bcp_goal_field: floor((clearance / resolution)^2) in float64 (151 for the
+    tricycle's inscribed radius at 0.03)."""
+    return int(np.floor((np.float64(clearance) / np.float64(resolution)) ** 2))
+
+
+class GoalField(object):
+    """The fields of one owner's map binding (a BatchedPlanEnv, or a NativeOps after set_costmap): `field` uint16
+    [entries, rows, cols] on the device (GOAL_NONE = no route; else route length in units of resolution / GOAL_ORTHO),
+    `clearance_d2`, and `info` int32 [entries, 2] = (cells with a value, gave_up).  entries is 1 (every row reads field 0)
+    or the owner's entry count (pool entries, else n_envs)."""
+
+    def __init__(self, owner, field, clearance_d2, info=None, keep=(), resolution=None):
+        assert field.dtype == torch.uint16 and field.dim() == 3 and field.is_contiguous()
+        self.owner, self.field, self.clearance_d2, self.info = owner, field, int(clearance_d2), info
+        self.resolution = float(owner.resolution if resolution is None else resolution)
+        self._keep = keep           # the inputs of the build, alive until the stream has consumed them
+        self._buffers = OrderedDict()
+
+    def _call(self, final, poses, n, row_env, carrot_cells, max_dist, out3, cell_value, carrot):
+        o, f = self.owner, self.field
+        opt = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+        if final:
+            _lib.check(o._lib.bcp_final_goal_field_sample(o._h, f.data_ptr(), f.shape[0], f.shape[1], f.shape[2], int(carrot_cells),
+                                                          float(max_dist), out3.data_ptr(), opt(cell_value), opt(carrot), o._stream()))
+        else:
+            _lib.check(o._lib.bcp_goal_field_sample(o._h, f.data_ptr(), f.shape[0], f.shape[1], f.shape[2], opt(poses), n,
+                                                    opt(row_env), int(carrot_cells), float(max_dist), out3.data_ptr(),
+                                                    opt(cell_value), opt(carrot), o._stream()))
+
+    def sample(self, poses=None, row_env=None, carrot_cells=8, max_dist=np.inf, want=()):
+        """bcp_goal_field_sample: poses None = every env's current pose (the delayed one under pose_delay), or [n, 3]; row i
+        belongs to env row_env[i] (int32 [n]), or i % n_envs.  -> out3 float32 [n, 3] = (min(distance to go in metres,
+        max_dist), direction to the carrot in the robot frame), or (out3, *wanted) with want from "cell_value" (int32 [n],
+        GOAL_NONE for a row without a result) and "carrot" (int32 [n, 2] = (row, col), (-1, -1) likewise).  The carrot is
+        the cell reached by at most carrot_cells steps down the field.  Device tensors, no sync; the outputs are cached per
+        n (the SCAN_CACHE_ENTRIES most recently used), so a caller that samples every tick allocates nothing."""
+        o = self.owner
+        unknown = set(want) - {"cell_value", "carrot"}
+        if unknown:
+            raise ValueError("sample: unknown outputs %s" % sorted(unknown))
+        if poses is not None:
+            poses = o._device_tensor(poses, torch.float64)
+            assert poses.dim() == 2 and poses.shape[1] == 3
+        if row_env is not None:
+            row_env = o._device_tensor(row_env, torch.int32, (int(poses.shape[0]),))
+        n = int(poses.shape[0]) if poses is not None else int(getattr(o, "n_envs", 1))
+        shapes = {"out3": ((n, 3), torch.float32), "cell_value": ((n,), torch.int32), "carrot": ((n, 2), torch.int32)}
+        buf = cached(self._buffers, n, dict, SCAN_CACHE_ENTRIES)
+        for name in ["out3"] + list(want):
+            if name not in buf:
+                buf[name] = torch.zeros(shapes[name][0], dtype=shapes[name][1], device=o.device)
+        self._call(False, poses, n, row_env, carrot_cells, max_dist, buf["out3"], buf.get("cell_value") if "cell_value" in want else None,
+                   buf.get("carrot") if "carrot" in want else None)
+        o._alive["goal_field_sample"] = (poses, row_env)
+        return buf["out3"] if not want else (buf["out3"],) + tuple(buf[w] for w in want)
+
+    def metres(self):
+        """float32 [entries, rows, cols]: the fields in metres, inf where there is no route."""
+        f = self.field.to(torch.int32)
+        scale = self.resolution / _lib.GOAL_ORTHO
+        return torch.where(f == _lib.GOAL_NONE, torch.full((), float("inf"), device=f.device), f.to(torch.float32) * scale)
+
+
+def path_seeds(env, which):
+    """int32 [fields, S, 2] (row, col) seeds from the paths the env has bound, by world_to_pixel on each entry's origin:
+    "goal" = the last way point of each entry's path, "path" = every way point, filled with (-1, -1) up to max_len."""
+    if which not in ("goal", "path"):
+        raise ValueError('seeds must be "goal" or "path", got %r' % (which,))
+    pts, lens = env._keep["path"], env._keep["lens"]
+    dev = env.device
+    if lens is None:
+        pts, lens = pts[None], torch.full((1,), int(pts.shape[0]), dtype=torch.int32, device=dev)
+    origins = (torch.tensor(np.array(env._origin_host, dtype=np.float64), device=dev)[None] if env._shared_map
+               else env._keep["origins"])
+    inv_res = 1.0 / float(env.resolution)
+    cells = torch.round((pts[..., :2] - origins[:, None, :]) * inv_res)       # [fields, L, 2] = (col, row), half to even
+    cells = torch.nan_to_num(cells, nan=-1.0).clamp(-1.0, 1e9).to(torch.int32)
+    n_fields, length = int(cells.shape[0]), int(cells.shape[1])
+    lens = lens.to(torch.int64).expand(n_fields)
+    rc = torch.stack([cells[..., 1], cells[..., 0]], dim=-1)
+    if which == "goal":
+        last = (lens - 1).clamp(min=0)
+        return rc[torch.arange(n_fields, device=dev), last][:, None, :].contiguous()
+    if length > 4096:
+        raise ValueError('seeds="path": paths of more than 4096 way points are not supported (max_len %d)' % length)
+    beyond = torch.arange(length, device=dev)[None, :] >= lens[:, None]
+    return torch.where(beyond[..., None], torch.full((), -1, dtype=torch.int32, device=dev), rc).contiguous()
+
+
+def build(env, clearance=None, seeds="goal", max_passes=0):
+    """BatchedPlanEnv.goal_field: see there."""
+    if env.endless:
+        raise RuntimeError("goal_field: not supported on endless=True pools -- refresh() re-samples worlds into the pool, "
+                           "which would leave stale fields")
+    if clearance is None:
+        clearance = robots.inscribed_radius(env.footprint())
+    d2 = clearance_cells_squared(clearance, env.resolution)
+    s = path_seeds(env, seeds)
+    data = env._keep["map"]
+    n = int(s.shape[0])
+    vr = vc = None
+    if env._shared_map:
+        rows, cols = int(data.shape[0]), int(data.shape[1])
+    else:
+        rows, cols = int(data.shape[1]), int(data.shape[2])
+        vr, vc = env._keep.get("vr"), env._keep.get("vc")
+        assert n == int(data.shape[0])   # (one path for private maps: its way points on every entry's origin)
+    field = torch.empty((n, rows, cols), dtype=torch.uint16, device=env.device)
+    info = torch.zeros((n, 2), dtype=torch.int32, device=env.device)
+    _lib.check(env._lib.bcp_goal_field(
+        env._h, data.data_ptr(), n, rows, cols, int(env._shared_map and n > 1), vr.data_ptr() if vr is not None else None,
+        vc.data_ptr() if vc is not None else None, s.data_ptr(), int(s.shape[1]), d2, int(max_passes), field.data_ptr(),
+        info.data_ptr(), env._stream()))
+    return GoalField(env, field, d2, info, keep=(s, data, vr, vc))
+
+
+class BatchedGoalField(BatchedObservationWrapper):
+    """Observation wrapper around a BatchedPlanEnv (or a pool env): step() / reset() return
+    OrderedDict(goal_field=float32 [N, 3, 1], goal_n_state=float32 [N, 9, 1]) device tensors (8 rows for a diff-drive
+    robot).  goal_field is (min(distance to go, max_dist) in metres, dir_x, dir_y) straight from bcp_goal_field_sample: the
+    unit vector, in the robot frame, towards the cell carrot_cells steps down the field.  The fields are built once, in the
+    constructor (env.goal_field(clearance)); an observation costs two launches.  goal_n_state is the egocentric wrapper's
+    vector with world size (max_dist, max_dist).
+    final_observation=True: step() adds info["final_observation"] (BatchedObservationWrapper), sampled at every ended
+    episode's final pose on the field of the map it ran on."""
+
+    def __init__(self, env, carrot_cells=8, clearance=None, max_dist=10.0, final_observation=False):
+        super(BatchedGoalField, self).__init__(env)
+        self.carrot_cells, self.max_dist = int(carrot_cells), float(max_dist)
+        self.fields = env.goal_field(clearance)
+        self._world = np.array([self.max_dist, self.max_dist], dtype=np.float64)
+        self.goal_field = self._vector(env.n_envs)
+        self.goal_n_state = self._goal_vector(env.n_envs)
+        self._obs = OrderedDict((('goal_field', self.goal_field), ('goal_n_state', self.goal_n_state)))
+        self._init_final(final_observation)
+
+    def _vector(self, rows):
+        return torch.zeros((rows, 3, 1), dtype=torch.float32, device=self.env.device)
+
+    def observation(self, _observation=None):
+        """Refresh and return the observation of the envs' current state (device tensors, no sync)."""
+        e = self.env
+        self.fields._call(False, None, e.n_envs, None, self.carrot_cells, self.max_dist, self.goal_field, None, None)
+        _lib.check(self._lib.bcp_goal_n_state(e._h, self._world.ctypes.data_as(_lib._f64p), self.goal_n_state.data_ptr(),
+                                              self._stream()))
+        return self._obs
+
+    def _alloc_final(self, cap):
+        self.final_goal_field, self.final_vector = self._vector(cap), self._goal_vector(cap)
+        return OrderedDict((('goal_field', self.final_goal_field), ('goal_n_state', self.final_vector)))
+
+    def _draw_final(self, stream):
+        e = self.env
+        self.fields._call(True, None, 0, None, self.carrot_cells, self.max_dist, self.final_goal_field, None, None)
+        _lib.check(self._lib.bcp_final_goal_n_state(e._h, self._world.ctypes.data_as(_lib._f64p),
+                                                    self.final_vector.data_ptr(), stream))

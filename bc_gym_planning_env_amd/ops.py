@@ -11,6 +11,7 @@ try/except ImportError), batched over many inputs.
   reward / find_last_reached / path_velocity   envs/base/reward.py:184-259, utilities/path_tools.py:432-448, :298-323
   inflate_costmap       utilities/costmap_inflation.py:73-92 (cv2.distanceTransform + _pixel_distance_to_cost)
   range_scan            no counterpart: distances to the nearest lethal cell along beams (bcp_range_scan)
+  goal_field            no counterpart: geodesic cost-to-go of a map to its seed cells (bcp_goal_field)
 """
 import ctypes as C
 
@@ -210,6 +211,35 @@ class NativeOps(Handle):
             dist.data_ptr() if dist is not None else None, self._stream()))
         out = out.reshape(d.shape)
         return (out, dist.reshape(d.shape)) if return_distance else out
+
+    def goal_field(self, data, seeds, clearance_d2, valid=None, max_passes=0, want_info=False):
+        """The geodesic cost-to-go of bcp_goal_field for one map [rows, cols] or a batch [n, rows, cols], numpy or torch ->
+        uint16 device tensor of the same shape: min(length of the cheapest route through free space to the nearest seed,
+        GOAL_FAR) in steps of GOAL_ORTHO / GOAL_DIAG, GOAL_NONE where there is none.  seeds: int32 (row, col) pairs, [S, 2]
+        for one map or [n, S, 2] for a batch; one map with seeds [n, S, 2] is shared by n seed sets and gives n fields.
+        clearance_d2: a cell is blocked iff an obstacle cell (== 254) lies within that squared distance in cells.
+        valid: optional (valid_rows, valid_cols) int32 [n] each, the true shapes of a padded batch.  max_passes: 0 = as
+        many as it takes.  want_info: also int32 [n, 2] = (cells with a value, gave_up)."""
+        d = self._device_tensor(data, torch.uint8)
+        s = self._device_tensor(seeds, torch.int32)
+        maps = d[None] if d.dim() == 2 else d
+        assert maps.dim() == 3
+        shared = d.dim() == 2 and s.dim() == 3
+        s3 = s[None] if s.dim() == 2 else s
+        n = s3.shape[0]
+        assert s3.dim() == 3 and s3.shape[2] == 2 and (shared or n == maps.shape[0])
+        vr = vc = None
+        if valid is not None:
+            vr, vc = (self._device_tensor(v, torch.int32, (n,)) for v in valid)
+        out = torch.empty((n,) + tuple(maps.shape[1:]), dtype=torch.uint16, device=self.device)
+        info = torch.zeros((n, 2), dtype=torch.int32, device=self.device) if want_info else None
+        _lib.check(self._lib.bcp_goal_field(
+            self._h, maps.data_ptr(), n, maps.shape[1], maps.shape[2], int(shared),
+            vr.data_ptr() if vr is not None else None, vc.data_ptr() if vc is not None else None, s3.data_ptr(), s3.shape[1],
+            int(clearance_d2), int(max_passes), out.data_ptr(), info.data_ptr() if info is not None else None, self._stream()))
+        self._alive["goal_field"] = (maps, s3, vr, vc)
+        out = out[0] if d.dim() == 2 and s.dim() == 2 else out
+        return (out, info) if want_info else out
 
     def robot_step(self, state7, actions, noise_z=None):
         """state7 [n,7] rows {x,y,angle,v,w,steering_motor_command,wheel_angle}, actions [n,2] -> (new [n,7], err)."""

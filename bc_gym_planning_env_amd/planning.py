@@ -72,23 +72,48 @@ class ShootingPlanner(object):
 
     :param env: a BatchedPlanEnv (or a wrapper that forwards lookahead); delays must be 0
     :param library: [H, K, 2] candidate plans shared by all envs, e.g. constant_command_library(env.action_space, 5, 9, 16)
+    :param goal_field: optional goal_field.GoalField of the env (env.goal_field()): the candidates' final poses are then
+        scored by their distance to go through free space -- what the H steps of the look-ahead cannot see
+    :param terminal_weight: reward per metre of that distance; the key of a candidate is
+        (not collided, ret - terminal_weight * distance to go), the largest wins, ties go to the lowest k.  A final pose
+        without a route counts as the longest distance a field can hold (GOAL_FAR cells)
     """
 
-    def __init__(self, env, library):
+    def __init__(self, env, library, goal_field=None, terminal_weight=0.0):
         self.env = env
         device = getattr(env, "device", None) or env.unwrapped.device
         lib = library if isinstance(library, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(library))
         if lib.dim() != 3 or lib.shape[2] != 2:
             raise ValueError("library must have shape (H, K, 2), got %s" % (tuple(lib.shape),))
         self.library = lib.to(device).contiguous()
-        self.last = None   # the Lookahead of the latest act()
+        self.goal_field, self.terminal_weight = goal_field, float(terminal_weight)
+        self._row_env = None
+        self.last = None        # the Lookahead of the latest act()
+        self.last_best = None   # with a goal field: int64 [N], the candidates chosen by the latest act()
 
     def act(self, observation=None):
         """actions [N, 2] (device tensor, dtype of the library) for env.step().  The observation is not needed: the
         look-ahead reads the env's own state, which is what the challenge allows ("explicit information about the
         forward model of the robot")."""
-        self.last = self.env.lookahead(self.library, want=("best", "best_action"))
-        return self.last.best_action
+        if self.goal_field is None:
+            self.last = self.env.lookahead(self.library, want=("best", "best_action"))
+            return self.last.best_action
+        la = self.last = self.env.lookahead(self.library, want=("final_pose",))
+        n, k = la.ret.shape
+        if self._row_env is None or self._row_env.numel() != n * k:
+            self._row_env = torch.arange(n, dtype=torch.int32, device=la.ret.device).repeat_interleave(k)
+        field = self.goal_field
+        farthest = _lib.GOAL_FAR * field.resolution / _lib.GOAL_ORTHO
+        out3 = field.sample(la.final_pose.reshape(n * k, 3), row_env=self._row_env, carrot_cells=1, max_dist=farthest)
+        score = la.ret - self.terminal_weight * out3[:, 0].to(torch.float64).reshape(n, k)
+        # the largest key (not collided, score), ties to the lowest k: the eligible candidates are the ones that do not
+        # collide, or all of them where every one collides; among those with the best score the lowest index wins
+        free = ~la.collided()
+        eligible = free | ~free.any(dim=1, keepdim=True)
+        top = torch.where(eligible, score, torch.full_like(score, -float("inf"))).amax(dim=1, keepdim=True)
+        index = torch.arange(k, device=score.device).expand(n, k)
+        self.last_best = torch.where(eligible & (score == top), index, torch.full_like(index, k)).amin(dim=1)
+        return self.library[0, self.last_best]
 
 
 class MPPIPlanner(object):

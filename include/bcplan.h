@@ -199,10 +199,14 @@ int bcp_seed(bcp_handle *h, uint64_t seed);
  *                             read by bcp_create: the knob's initial value.)
  *   BCP_TUNE_INFLATE_ROUTE    where bcp_inflate_costmaps keeps its 16-bit intermediate plane: 0 (default) = in LDS when the
  *                             map fits, else in the handle's global scratch; 2 = always in global scratch (lets tests
- *                             compare the two routes on one map; the bytes are the same) */
+ *                             compare the two routes on one map; the bytes are the same)
+ *   BCP_TUNE_GOAL_ROUTE       where bcp_goal_field keeps its bit masks and its 16-bit working plane: 0 (default) = in LDS
+ *                             when they fit, else the masks in the handle's global scratch and the plane in `out` itself;
+ *                             2 = always in global memory (the bytes are the same on both routes) */
 enum { BCP_TUNE_EXACT_MODE = 0, BCP_TUNE_DENSE_THRESHOLD = 1, BCP_TUNE_CULL = 2, BCP_TUNE_DEFER = 3, BCP_TUNE_EDT_LDS = 4,
        BCP_TUNE_FUSED = 5, BCP_TUNE_EGO_SPARSE = 6, BCP_TUNE_NEAR_DILATE = 7, BCP_TUNE_LOCAL_PAIRS = 8,
-       BCP_TUNE_EGO_LIST_STRIDE = 9, BCP_TUNE_NEAR_SHIFT = 10, BCP_TUNE_INFLATE_ROUTE = 11 };
+       BCP_TUNE_EGO_LIST_STRIDE = 9, BCP_TUNE_NEAR_SHIFT = 10, BCP_TUNE_INFLATE_ROUTE = 11,
+       BCP_TUNE_GOAL_ROUTE = 12 };
 int bcp_set_tuning(bcp_handle *h, int32_t key, int32_t value);
 
 /* ---- static per-episode inputs ------------------------------------------------------------------------ */
@@ -740,6 +744,91 @@ int bcp_inflate_costmaps(bcp_handle *h, const uint8_t *data, int64_t n_maps, int
                          uint8_t *out,          /* [n_maps][rows][cols]; may be `data` itself (in place) */
                          float *distance_out,   /* optional [n_maps][rows][cols]: d in cells, +inf / 0 as above */
                          void *stream);
+
+/* ---- goal field: geodesic cost-to-go per map, sampled per env ---------------------------------------------- */
+/* A navigation function (no reference counterpart; the other half of the ROS costmap stack that inflation starts): for
+ * every free cell of a map the length of the cheapest route through free space to the nearest seed cell, as an integer
+ * fixed point that does not depend on the order of evaluation. */
+#define BCP_GOAL_ORTHO 12          /* cost of a step to an edge neighbour */
+#define BCP_GOAL_DIAG  17          /* ... to a corner neighbour (17/12 = 1.4167) */
+#define BCP_GOAL_FAR   65534       /* min(true cost, 65534): the arithmetic saturates */
+#define BCP_GOAL_NONE  65535       /* blocked, outside the valid shape, or not connected to a seed */
+
+/* bcp_goal_field: fields of n_maps maps in one launch.  Independent of what the handle has bound: the handle names the
+ * device and owns the scratch of the global route (allocated on first use, grown only when a later call needs more, freed
+ * by bcp_destroy).  Asynchronous on `stream`, no host synchronisation.
+ * Maps: `data` is [n_maps][rows][cols]; with shared != 0 it is ONE map [rows][cols] used for all n_maps seed sets, and the
+ * valid pointers must be NULL.  The valid shape (valid_rows[m], valid_cols[m]) is clamped to [0, rows] x [0, cols] as
+ * bcp_inflate_costmaps clamps it; both pointers NULL = the full shape.  A cell is an obstacle exactly where data == 254
+ * inside the valid shape -- the set bcp_pose_collides tests -- so inflating a map changes no field.
+ * Blocked cells: a cell of the valid shape is blocked iff some obstacle cell lies at squared cell distance <= clearance_d2
+ * (clearance_d2 = 0 blocks the obstacle cells alone).  Cells outside the valid shape are never entered and come out
+ * BCP_GOAL_NONE.
+ * Seeds: `seeds` is device int32 [n_maps][n_seeds][2] = (row, col).  A seed inside the valid shape is a source of cost 0
+ * and counts as a free cell for every purpose, even where it was blocked; a seed outside the valid shape, (-1, -1)
+ * included, is ignored; a map with no usable seed comes out all BCP_GOAL_NONE.
+ * Graph: from a free cell to each of its eight neighbours that is free and inside the valid shape, at BCP_GOAL_ORTHO or
+ * BCP_GOAL_DIAG.  A diagonal move is admissible only if BOTH edge neighbours it passes between are free: nothing slips
+ * through an 8-connected wall (a cv2.line wall) at clearance 0.
+ * Result: out = min(length of the cheapest admissible route to any seed, BCP_GOAL_FAR), or BCP_GOAL_NONE where there is
+ * none.  Exact, and unique: the weights are positive integers and the saturating addition is monotone, so the Bellman
+ * equations have one solution, whatever order the cells are relaxed in.
+ * info (optional, device int32 [n_maps][2]): {cells with out != BCP_GOAL_NONE, gave_up}.
+ * max_passes: the field is found by passes of a pull relaxation over the map, separated by workgroup barriers, until a
+ * pass changes nothing.  Every pass finalises at least one more edge of every cheapest route, so rows * cols passes always
+ * suffice: that is what 0 means.  A positive value caps the passes; when the cap ends the work, gave_up = 1 and every
+ * value is BCP_GOAL_NONE or the length of SOME admissible route, i.e. an upper bound.  The loop is bounded in every case.
+ * Refused with BCP_E_INVALID: NULL h; n_maps < 0; rows or cols outside [1, 2048]; n_seeds outside [1, 4096]; clearance_d2
+ * outside [0, 16129] (BCP_MAX_KERNEL_HALF squared); max_passes < 0; only one of valid_rows / valid_cols; valid pointers
+ * together with shared; NULL data, seeds or out with n_maps > 0.  n_maps == 0 succeeds and does nothing. */
+int bcp_goal_field(bcp_handle *h, const uint8_t *data, int64_t n_maps, int32_t rows, int32_t cols, int32_t shared,
+                   const int32_t *valid_rows, const int32_t *valid_cols,      /* device [n_maps], both or neither */
+                   const int32_t *seeds, int32_t n_seeds,                     /* device [n_maps][n_seeds][2] = (row, col) */
+                   int32_t clearance_d2, int32_t max_passes,
+                   uint16_t *out,                                             /* [n_maps][rows][cols] */
+                   int32_t *info,                                             /* optional [n_maps][2] */
+                   void *stream);
+
+/* bcp_goal_field_sample: what the fields say at a pose, per row -- distance to go, and the direction of the route.
+ * One launch, asynchronous on `stream`, no allocation, no host synchronisation; the launch arguments depend only on the
+ * pointers and numbers given, so a call can be captured into a HIP graph after one ordinary call.
+ * Rows: exactly those of bcp_range_scan.  poses is [n,3] device doubles; poses == NULL requires n == n_envs and row_env ==
+ * NULL and means the bound state's pose (pose_seen when pose_delay > 0).  Row i belongs to env row_env[i] (device int32
+ * [n]), or i % n_envs when row_env is NULL, and reads the map entry of its env: geom_of_env under a pool, the env index
+ * for private maps, 0 for a shared map.  Origins, inv_res and valid shapes are the handle's map binding; rows / cols must
+ * equal that binding's.  n_fields is 1 (every row reads field 0) or the handle's entry count -- the pool's entries, or
+ * n_envs without a pool -- and a row then reads the field of its env's entry (with a shared map and private paths: a field
+ * per env, all read with the one map's origin).  bcp_final_goal_field_sample draws slots j < min(*count, capacity) of the bound episode record on entry geom[j]
+ * (private maps without a pool: env_id[j]) and leaves the other rows untouched, in every output.
+ * Per row with pose (x, y, theta) on an entry with origin (ox, oy):
+ *   (col, row) = half-to-even of ((x - ox) * inv_res, (y - oy) * inv_res)        the handle's world-to-pixel rule
+ *   v = field[row][col]
+ * A row has no result if its cell is outside the valid shape, its pose is not finite, its row_env is out of range, or v is
+ * BCP_GOAL_NONE: out3 = (max_dist, 0, 0), cell_value = 65535, carrot = (-1, -1).  Otherwise
+ *   out3[0] = (float) min(((double)v * resolution) / 12.0, max_dist)
+ *   cell_value = v
+ * and the carrot walk takes at most carrot_cells steps from (row, col): each step moves to the admissible neighbour k that
+ * minimises field[neighbour] + w_k, neighbours in the order E, NE, N, NW, W, SW, S, SE with (dcol, drow) = (1,0), (1,1),
+ * (0,1), (-1,1), (-1,0), (-1,-1), (0,-1), (1,-1), ties to the lowest k.  A neighbour is admissible if it is inside the valid
+ * shape, its value is not BCP_GOAL_NONE and, for a diagonal, both edge cells' values are not BCP_GOAL_NONE (on a finished
+ * field that is "free").  The walk stops on a cell of value 0, or where no neighbour is admissible.
+ *   carrot = (row, col) of the cell reached
+ *   (out3[1], out3[2]) = the unit vector from (x, y) to that cell's centre (ox + col * resolution, oy + row * resolution),
+ *   turned into the robot frame: (ux * c + uy * s, uy * c - ux * s) with the device's (c, s) = (cos theta, sin theta);
+ *   float64 with every product, quotient, root and sum rounded on its own, then (float).  (0, 0) when the walk did not
+ *   leave the pose's cell.
+ * out3: float32 [n][3]; cell_value: optional int32 [n]; carrot: optional int32 [n][2] = (row, col).
+ * BCP_E_INVALID: NULL h, field or out3; carrot_cells outside [1, 256]; max_dist NaN or not > 0 (+inf is allowed); n <= 0, or
+ * n != n_envs without poses; row_env without poses; rows / cols other than the binding's; n_fields neither 1 nor the
+ * handle's entry count.  BCP_E_STATE: no costmaps bound; no state bound with poses == NULL; no record bound (the final
+ * variant). */
+int bcp_goal_field_sample(bcp_handle *h, const uint16_t *field, int64_t n_fields, int32_t rows, int32_t cols,
+                          const double *poses, int64_t n, const int32_t *row_env, int32_t carrot_cells, double max_dist,
+                          float *out3 /*[n][3]*/, int32_t *cell_value /*optional [n]*/, int32_t *carrot /*optional [n][2]*/,
+                          void *stream);
+int bcp_final_goal_field_sample(bcp_handle *h, const uint16_t *field, int64_t n_fields, int32_t rows, int32_t cols,
+                                int32_t carrot_cells, double max_dist, float *out3, int32_t *cell_value, int32_t *carrot,
+                                void *stream);
 
 /* ---- measurement -------------------------------------------------------------------------------------- */
 /* Which kernels a bcp_step() of this handle launches, as configured now: 0 = step_kernel alone (no distance field, or a
