@@ -106,6 +106,13 @@ class BcpMppiIO(C.Structure):
     ]
 
 
+class BcpMppiTerminal(C.Structure):
+    _fields_ = [
+        ("field", C.c_void_p), ("n_fields", C.c_int64), ("rows", C.c_int32), ("cols", C.c_int32), ("weight", C.c_double),
+        ("iter_value", C.c_void_p), ("iter_score", C.c_void_p),
+    ]
+
+
 # every symbol include/bcplan.h declares: (restype, argtypes)
 _H = C.c_void_p
 SYMBOLS = {
@@ -127,6 +134,8 @@ SYMBOLS = {
     "bcp_rollout": (C.c_int, [_H, C.POINTER(BcpStepIO), C.c_int32, C.c_uint32, C.c_void_p]),
     "bcp_lookahead": (C.c_int, [_H, C.POINTER(BcpLookaheadIO), C.c_uint32, C.c_void_p]),
     "bcp_mppi": (C.c_int, [_H, C.POINTER(BcpMppiParams), C.POINTER(BcpMppiIO), C.c_uint32, C.c_void_p]),
+    "bcp_mppi_field": (C.c_int, [_H, C.POINTER(BcpMppiParams), C.POINTER(BcpMppiIO), C.POINTER(BcpMppiTerminal), C.c_uint32,
+                                 C.c_void_p]),
     "bcp_expired_waits": (C.c_int, [_H, C.POINTER(C.c_int64), C.c_void_p]),
     "bcp_parked_poses": (C.c_int, [_H, C.POINTER(C.c_int64), C.c_void_p]),
     "bcp_side_stream": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_void_p)]),

@@ -612,7 +612,7 @@ class BatchedPlanEnv(Handle):
         return Lookahead(h, k, **out)
 
     def mppi(self, mean, sigma, iterations, n_candidates, lam, collision_penalty, seed=0, draw_index=0, mask=None, eps=None,
-             want=(), action_dtype=None):
+             want=(), action_dtype=None, goal_field=None, terminal_weight=0.0):
         """Refine one plan per env by sampling around it (bcp_mppi, one kernel launch, nothing of the env changes): for each
         of `iterations` rounds, n_candidates plans u = clip(mean + sigma * eps, action box) -- candidate 0 is the mean itself
         -- are rolled out with the noise-free forward model as lookahead() rolls them out, scored ret - collision_penalty *
@@ -623,8 +623,13 @@ class BatchedPlanEnv(Handle):
         int64 / uint64 tensor on the device, read by the kernel -- a captured call then draws afresh on every replay once the
         word was changed.  eps: optional [I, N, K, H, 2] float32 perturbations to use instead (replay).  mask: optional [N];
         rows of envs with mask 0 are left untouched.  want: from "eps", "iter_mean", "iter_ret", "iter_reason", "err".
-        action_dtype: torch.float64 (default) or torch.float32.  Returns an Mppi; buffers are cached per (H, K, I).  Delays
-        > 0 are refused."""
+        action_dtype: torch.float64 (default) or torch.float32.  goal_field: a goal_field.GoalField of this env
+        (self.goal_field()): the score of a candidate then also loses terminal_weight (reward per metre, finite, >= 0) times
+        the distance to go from its final pose through free space, read from the field inside the same launch
+        (bcp_mppi_field); a pose without a route counts as GOAL_FAR cells.  want then also takes "iter_value" (int32
+        [I, N, K], the field value read, GOAL_NONE = none) and "iter_score" (float64 [I, N, K], the scores as weighted).
+        Without a field the call is bcp_mppi as ever.  Returns an Mppi; buffers are cached per (H, K, I).  Delays > 0 are
+        refused."""
         n = self.n_envs
         mean = self._device_tensor(mean, torch.float64)   # (a contiguous float64 tensor on the device: itself)
         if mean.dim() != 3 or mean.shape[0] != n or mean.shape[2] != 2:
@@ -634,6 +639,10 @@ class BatchedPlanEnv(Handle):
         unknown = want - set(Mppi.FIELDS)
         if unknown:
             raise ValueError("mppi: unknown outputs %s" % sorted(unknown))
+        if goal_field is None and (want & set(Mppi.TERMINAL_FIELDS) or terminal_weight != 0.0):
+            raise ValueError("mppi: iter_value / iter_score / terminal_weight need a goal_field")
+        if goal_field is not None and goal_field.owner is not self:
+            raise ValueError("mppi: goal_field belongs to another env")
         action_dtype = torch.float64 if action_dtype is None else action_dtype
         if action_dtype not in (torch.float32, torch.float64):
             raise ValueError("action_dtype must be torch.float32 or torch.float64")
@@ -665,13 +674,22 @@ class BatchedPlanEnv(Handle):
             keep.append(eps)
         shapes = {"action": ((n, 2), action_dtype), "eps": ((it, n, k, h, 2), torch.float32),
                   "iter_mean": ((it, n, h, 2), torch.float64), "iter_ret": ((it, n, k), torch.float64),
-                  "iter_reason": ((it, n, k), torch.uint8), "err": ((n,), torch.int32)}
+                  "iter_reason": ((it, n, k), torch.uint8), "err": ((n,), torch.int32),
+                  "iter_value": ((it, n, k), torch.int32), "iter_score": ((it, n, k), torch.float64)}
         out = self._cached_outputs(self._mppi_buffers, (h, k, it), shapes,
                                    ["action"] + [name for name in Mppi.FIELDS if name in want])
+        term = _lib.BcpMppiTerminal()
         for name, t in out.items():
-            setattr(io, "eps_out" if name == "eps" else name, t.data_ptr())
+            setattr(term if name in Mppi.TERMINAL_FIELDS else io, "eps_out" if name == "eps" else name, t.data_ptr())
         flags = _lib.STEP_ACTIONS_F32 if action_dtype == torch.float32 else 0
-        _lib.check(self._lib.bcp_mppi(self._h, C.byref(p), C.byref(io), flags, self._stream()))
+        if goal_field is None:
+            _lib.check(self._lib.bcp_mppi(self._h, C.byref(p), C.byref(io), flags, self._stream()))
+        else:
+            f = goal_field.field
+            term.field, term.n_fields, term.rows, term.cols = f.data_ptr(), int(f.shape[0]), int(f.shape[1]), int(f.shape[2])
+            term.weight = float(terminal_weight)
+            keep.append(f)
+            _lib.check(self._lib.bcp_mppi_field(self._h, C.byref(p), C.byref(io), C.byref(term), flags, self._stream()))
         self._alive["mppi"] = tuple(keep)   # alive until the stream has consumed them
         return Mppi(h, k, it, mean, **out)
 

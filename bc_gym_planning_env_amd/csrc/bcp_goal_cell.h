@@ -1,8 +1,9 @@
 // bcp_goal_cell.h -- the goal field's arithmetic (bcp_goal_field, bcp_goal_field_sample; include/bcplan.h): the argument
-// checks, the half-widths of the clearance disc and the widening of one mask word, the pull relaxation of one cell, and the
-// sampling of one row with its carrot walk.  Plain C++ with no HIP in it: goal_field_kernel and goal_sample_kernel
-// (bcp_goal.h) call these functions on the device, tests/c_abi/goal_field_main.cpp calls the same ones on the host, and there
-// is no other copy of them.  The float64 arithmetic rounds every product, quotient, root and sum on its own
+// checks, the half-widths of the clearance disc and the widening of one mask word, the pull relaxation of one cell, the field
+// at a pose, and the sampling of one row with its carrot walk.  Plain C++ with no HIP in it: goal_field_kernel and
+// goal_sample_kernel (bcp_goal.h) and mppi_kernel's terminal read (bcp_mppi.h) call these functions on the device,
+// tests/c_abi/goal_field_main.cpp and tests/c_abi/mppi_field_main.cpp call the same ones on the host, and there is no other
+// copy of them.  The float64 arithmetic rounds every product, quotient, root and sum on its own
 // (-ffp-contract=off).
 //
 // A field is a uint16 plane [rows][cols]: kGoalNone where no route exists (blocked, outside the valid shape, not connected
@@ -169,6 +170,33 @@ BCP_HD inline GoalSample goal_no_sample(double max_dist)
     return s;
 }
 
+// The field at a pose: (col, row) = half-to-even of ((x - ox) * inv_res, (y - oy) * inv_res) on a field with origin
+// (ox, oy) and valid shape (vr, vc); kGoalNone where `finite` is false (the caller's word on x and y) or the cell lies
+// outside the valid shape -- get is then not called.  (r, c): the cell, set whenever it lies inside.  The one statement of
+// the rule: goal_sample_row (below) and mppi_kernel's terminal read (bcp_mppi.h) both go through it.
+template <typename Get>
+BCP_HD inline int32_t goal_value_at(const Get& get, int32_t vr, int32_t vc, double x, double y, bool finite, double ox,
+                                    double oy, double inv_res, int32_t& r, int32_t& c)
+{
+    if (!finite) return kGoalNone;
+    const double fc = __builtin_rint((x - ox) * inv_res), fr = __builtin_rint((y - oy) * inv_res);   // half to even
+    if (!(fc >= 0.0 && fc < (double)vc && fr >= 0.0 && fr < (double)vr)) return kGoalNone;
+    r = (int32_t)fr;
+    c = (int32_t)fc;
+    return (int32_t)get(r, c);
+}
+
+template <typename Get>
+BCP_HD inline int32_t goal_value_at(const Get& get, int32_t vr, int32_t vc, double x, double y, bool finite, double ox,
+                                    double oy, double inv_res)
+{
+    int32_t r = 0, c = 0;
+    return goal_value_at(get, vr, vc, x, y, finite, ox, oy, inv_res, r, c);
+}
+
+// metres to go of a cell value, float64, the product and the quotient rounded on their own
+BCP_HD inline double goal_metres(int32_t v, double resolution) { return ((double)v * resolution) / 12.0; }
+
 // One row of bcp_goal_field_sample: pose (x, y) with heading (cos, sin) = (ct, st) on a field with origin (ox, oy) and valid
 // shape (vr, vc); `finite`: x, y and the heading are finite numbers.
 template <typename Get>
@@ -176,15 +204,12 @@ BCP_HD inline GoalSample goal_sample_row(const Get& get, int32_t vr, int32_t vc,
                                          bool finite, double ox, double oy, double inv_res, double resolution,
                                          int32_t carrot_cells, double max_dist)
 {
-    if (!finite) return goal_no_sample(max_dist);
-    const double fc = __builtin_rint((x - ox) * inv_res), fr = __builtin_rint((y - oy) * inv_res);   // half to even
-    if (!(fc >= 0.0 && fc < (double)vc && fr >= 0.0 && fr < (double)vr)) return goal_no_sample(max_dist);
-    int32_t r = (int32_t)fr, c = (int32_t)fc;
-    const int32_t r0 = r, c0 = c;
-    int32_t v = (int32_t)get(r, c);
+    int32_t r = 0, c = 0;
+    int32_t v = goal_value_at(get, vr, vc, x, y, finite, ox, oy, inv_res, r, c);
     if (v == kGoalNone) return goal_no_sample(max_dist);
+    const int32_t r0 = r, c0 = c;
     GoalSample s;
-    const double dist = ((double)v * resolution) / 12.0;
+    const double dist = goal_metres(v, resolution);
     s.out3[0] = (float)(dist < max_dist ? dist : max_dist);
     s.cell_value = v;
     for (int32_t step = 0; step < carrot_cells && v != 0; ++step) {

@@ -3,8 +3,11 @@
 // plan_trip) takes the trips: a candidate is rolled out by the very code lookahead_kernel runs.  Candidate actions are not
 // read from memory but made in registers: mean + sigma * eps, clipped to the action box.
 // Nothing of the handle is written; the only global stores are the caller's outputs (bcp_mppi_io).
+// bcp_mppi_field() is the same launch with one read more per candidate: the goal field (bcp_goal_field) at the pose the
+// candidate ended on, taken off its score as a distance to go (mppi_kernel<.., FIELD>; the cell rule is bcp_goal_cell.h's).
 #pragma once
 
+#include "bcp_goal_cell.h"
 #include "bcp_lookahead.h"
 
 // Launch arguments: the handle's parameter block, the caller's pointers and bcp_mppi_params by value -- nothing that the
@@ -26,6 +29,55 @@ struct MppiArgs {
     int32_t score_word;          // where the score area starts in the dynamic LDS (32-bit words, even), behind collides_wave's
     uint32_t flags;              // BCP_STEP_ACTIONS_F32
 };
+
+// What bcp_mppi_field adds to a launch: a finished goal field (bcp_goal_field) and the map binding's frame as
+// goal_sample_kernel takes it (bcp_goal.h), so that a candidate's final pose reads the cell bcp_goal_field_sample would read.
+struct MppiTerminal {
+    const uint16_t* field;       // [n_fields][rows][cols]
+    int64_t field_stride;        // rows * cols, or 0 when n_fields == 1: every env reads field 0
+    int64_t n_entries;           // pool entries, or n_envs without a pool: a slot outside [0, n_entries) reads nothing
+    const int32_t* valid_rows;   // per entry, or nullptr: the allocated shape
+    const int32_t* valid_cols;
+    const double* origins;       // per entry, or nullptr: (ox, oy)
+    double ox, oy, inv_res, resolution;
+    double weight;               // reward per metre of distance to go
+    int32_t* iter_value;         // nullptr or [I][N][K]
+    double* iter_score;          // nullptr or [I][N][K]
+    int32_t rows, cols, shared;
+};
+
+// The kernel's argument: MppiArgs as it is, and behind it the terminal part for the FIELD kernels only -- the plain ones
+// take what they always took.
+template <bool FIELD> struct MppiKernelArgs;
+template <> struct MppiKernelArgs<false> {
+    MppiArgs m;
+};
+template <> struct MppiKernelArgs<true> {
+    MppiArgs m;
+    MppiTerminal t;
+};
+
+struct MppiFieldGet {
+    GlobalPtr<const uint16_t> p;
+    int32_t cols;
+    __device__ __forceinline__ uint16_t operator()(int32_t r, int32_t c) const { return p[r * cols + c]; }
+};
+
+// The field value at a candidate's final pose (x, y) of an env on slot g: the rule of goal_sample_kernel -- the map frame is
+// entry 0's when the map is shared, the field is the slot's unless there is only one -- through goal_value_at.  One global
+// 2-byte load at most.
+__device__ __forceinline__ int32_t mppi_terminal_value(const MppiTerminal& t, int64_t g, double x, double y)
+{
+    if (g < 0 || g >= t.n_entries) return kGoalNone;
+    const int64_t e = t.shared ? 0 : g;
+    const double ox = t.origins ? as_global(t.origins)[2 * e] : t.ox, oy = t.origins ? as_global(t.origins)[2 * e + 1] : t.oy;
+    const int32_t vr = t.valid_rows ? max(0, min(as_global(t.valid_rows)[e], t.rows)) : t.rows;
+    const int32_t vc = t.valid_cols ? max(0, min(as_global(t.valid_cols)[e], t.cols)) : t.cols;
+    const double lim = 1.7976931348623157e308;
+    const bool finite = x >= -lim && x <= lim && y >= -lim && y <= lim;
+    const MppiFieldGet get = {as_global(t.field) + g * t.field_stride, t.cols};
+    return goal_value_at(get, vr, vc, x, y, finite, ox, oy, t.inv_res);
+}
 
 // The two perturbations of (env, draw, iteration j, candidate k, step t): Philox4x32-10 keyed by the seed on the counter
 //   c0 = env (low word), c1 = k | env (high bits) << 10 | draw (bits 32..51) << 12, c2 = j * H + t, c3 = draw (low word)
@@ -66,10 +118,14 @@ __device__ __forceinline__ double mppi_command(double mean, double sigma, float 
 // Scores: one double per (lane, chunk) in LDS behind the collision area (K >= 64: K * 8 bytes; K < 64: 512), written
 // and read by the same lane; they turn into the weights in place.  The update needs every u[t] again after the weights
 // are known: the perturbation is drawn again from its counter (or read again from eps_in).
+// FIELD (bcp_mppi_field): after its last trip a live lane reads the goal field at the pose it ended on -- the rolled-back
+// pose where it collided, bcp_lookahead's final_pose -- and its score loses weight * metres to go, a pose without a route
+// counting as kGoalFar cells.  Nothing else differs: iter_ret and iter_reason stay the pure return and reason.
 // Loops are bounded by I, H and K / 64; no atomics, no waits on other workgroups.
-template <bool PLAIN>
-__global__ void __launch_bounds__(kBlock) mppi_kernel(const MppiArgs a)
+template <bool PLAIN, bool FIELD>
+__global__ void __launch_bounds__(kBlock) mppi_kernel(const MppiKernelArgs<FIELD> ka)
 {
+    const MppiArgs& a = ka.m;
     typedef __attribute__((address_space(3))) double* LdsScore;
     const StepStatic* S = a.S;
     const DevParams& P = S->P;
@@ -138,7 +194,16 @@ __global__ void __launch_bounds__(kBlock) mppi_kernel(const MppiArgs a)
                 if (a.iter_ret) as_global(a.iter_ret)[c] = ret;
                 if (a.iter_reason) as_global(a.iter_reason)[c] = (uint8_t)reason;
             }
-            const double s = (reason & BCP_DONE_COLLIDED) ? ret - a.p.collision_penalty : ret;
+            double s = (reason & BCP_DONE_COLLIDED) ? ret - a.p.collision_penalty : ret;
+            if constexpr (FIELD) {
+                const MppiTerminal& T = ka.t;
+                const int32_t v = live ? mppi_terminal_value(T, g, st.r.p.x, st.r.p.y) : kGoalNone;
+                s = s - T.weight * goal_metres(v == kGoalNone ? kGoalFar : v, T.resolution);
+                if (live) {
+                    if (T.iter_value) as_global(T.iter_value)[c] = v;
+                    if (T.iter_score) as_global(T.iter_score)[c] = s;
+                }
+            }
             score[ch * kBlock] = s;
             best = s > best ? s : best;
         }

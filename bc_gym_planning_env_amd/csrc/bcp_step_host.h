@@ -1,6 +1,6 @@
 // bcp_step_host.h -- the host side of the step: which form a step takes, the device-resident parameter block, the launcher,
 // the methods of Parking and WaitWatchdog, and the entry points built on them (bcp_step, bcp_rollout, bcp_lookahead, bcp_mppi,
-// the timing calls).
+// bcp_mppi_field, the timing calls).
 // The kernels are in bcp_step.h, bcp_lookahead.h and bcp_mppi.h.  Included by bcplan.hip after bcp_field.h.
 #pragma once
 
@@ -436,35 +436,38 @@ extern "C" int bcp_lookahead(bcp_handle* h, const bcp_lookahead_io* io, uint32_t
 }
 
 // Sampling-based refinement of one plan per env (bcp_mppi.h): I iterations of sample, roll out, weight and update in one
-// launch.  Like bcp_lookahead it reads the handle and writes only the caller's arrays.
-extern "C" int bcp_mppi(bcp_handle* h, const bcp_mppi_params* p, const bcp_mppi_io* io, uint32_t flags, void* stream)
+// launch.  Like bcp_lookahead it reads the handle and writes only the caller's arrays.  The one launcher of bcp_mppi and
+// bcp_mppi_field (`who`; term == nullptr: the kernels without the terminal read): the checks of what the two have in common
+// are written here, once.
+static int launch_mppi(bcp_handle* h, const bcp_mppi_params* p, const bcp_mppi_io* io, const bcp_mppi_terminal* term,
+                       uint32_t flags, hipStream_t s, const char* who)
 {
-    if (!h || !p || !io) return fail(BCP_E_INVALID, "bcp_mppi: null argument");
-    if (flags & ~(uint32_t)BCP_STEP_ACTIONS_F32) return fail(BCP_E_INVALID, "bcp_mppi: undefined flag bits 0x%x", flags & ~(uint32_t)BCP_STEP_ACTIONS_F32);
-    hipStream_t s = (hipStream_t)stream;
-    BCP_TRY(plan_ready(h, "bcp_mppi", s));
+    if (flags & ~(uint32_t)BCP_STEP_ACTIONS_F32) return fail(BCP_E_INVALID, "%s: undefined flag bits 0x%x", who, flags & ~(uint32_t)BCP_STEP_ACTIONS_F32);
+    BCP_TRY(plan_ready(h, who, s));
     const bcp_params& hp = h->params;
-    if (p->horizon < 1 || p->iterations < 1) return fail(BCP_E_INVALID, "bcp_mppi: horizon and iterations must be at least 1");
+    if (p->horizon < 1 || p->iterations < 1) return fail(BCP_E_INVALID, "%s: horizon and iterations must be at least 1", who);
     const int32_t K = p->n_candidates;
     if (K < 8 || K > 1024 || (K & (K - 1)) != 0)
-        return fail(BCP_E_INVALID, "bcp_mppi: n_candidates must be a power of two in [8, 1024], got %d", K);
-    if (!(p->lambda_ > 0.0) || !std::isfinite(p->lambda_)) return fail(BCP_E_INVALID, "bcp_mppi: lambda_ must be positive and finite");
-    if (!std::isfinite(p->collision_penalty)) return fail(BCP_E_INVALID, "bcp_mppi: collision_penalty must be finite");
+        return fail(BCP_E_INVALID, "%s: n_candidates must be a power of two in [8, 1024], got %d", who, K);
+    if (!(p->lambda_ > 0.0) || !std::isfinite(p->lambda_)) return fail(BCP_E_INVALID, "%s: lambda_ must be positive and finite", who);
+    if (!std::isfinite(p->collision_penalty)) return fail(BCP_E_INVALID, "%s: collision_penalty must be finite", who);
     for (int d = 0; d < 2; ++d) {
         if (!(p->sigma[d] >= 0.0) || !std::isfinite(p->sigma[d]))
-            return fail(BCP_E_INVALID, "bcp_mppi: sigma[%d] must be finite and not negative", d);
-        if (!std::isfinite(p->low[d]) || !std::isfinite(p->high[d])) return fail(BCP_E_INVALID, "bcp_mppi: the action box must be finite");
-        if (p->low[d] > p->high[d]) return fail(BCP_E_INVALID, "bcp_mppi: low[%d] > high[%d]", d, d);
+            return fail(BCP_E_INVALID, "%s: sigma[%d] must be finite and not negative", who, d);
+        if (!std::isfinite(p->low[d]) || !std::isfinite(p->high[d])) return fail(BCP_E_INVALID, "%s: the action box must be finite", who);
+        if (p->low[d] > p->high[d]) return fail(BCP_E_INVALID, "%s: low[%d] > high[%d]", who, d, d);
     }
-    if (!io->mean || !io->action) return fail(BCP_E_INVALID, "bcp_mppi: mean and action are required");
+    if (!io->mean || !io->action) return fail(BCP_E_INVALID, "%s: mean and action are required", who);
     // element offsets are int64: the largest is 2 * I * N * K * H (eps); the bound leaves the room the header promises
     const int64_t limit = (int64_t)1 << 62;
     if (h->n > limit / 5 / p->iterations / K / p->horizon)
-        return fail(BCP_E_INVALID, "bcp_mppi: iterations * n_envs * n_candidates * horizon is too large for 64-bit element offsets");
+        return fail(BCP_E_INVALID, "%s: iterations * n_envs * n_candidates * horizon is too large for 64-bit element offsets", who);
     const int group = K < kBlock ? K : kBlock;
     const int64_t blocks = (h->n * group + kBlock - 1) / kBlock;
-    if (blocks > 0x7FFFFFFF) return fail(BCP_E_INVALID, "bcp_mppi: n_envs exceeds the largest grid");
-    MppiArgs a;
+    if (blocks > 0x7FFFFFFF) return fail(BCP_E_INVALID, "%s: n_envs exceeds the largest grid", who);
+    MppiKernelArgs<true> ka;   // (its head is all the plain kernels take)
+    memset(&ka, 0, sizeof(ka));
+    MppiArgs& a = ka.m;
     a.S = h->dev_static.get();
     a.p = *p;
     a.mean = io->mean;
@@ -484,9 +487,58 @@ extern "C" int bcp_mppi(bcp_handle* h, const bcp_mppi_params* p, const bcp_mppi_
     a.score_word = (int32_t)(collision / sizeof(uint32_t));
     const size_t lds = collision + (size_t)(K / group) * kBlock * sizeof(double);
     const bool plain = hp.reward_provider == BCP_REWARD_CONTINUOUS;
-    const void* fn = plain ? (const void*)mppi_kernel<true> : (const void*)mppi_kernel<false>;
     // (the LDS can pass 64 KiB: a staged map of nearly that plus the scores)
-    return launch_variant(h, fn, dim3((unsigned)blocks), dim3(kBlock), lds, s, a);
+    if (!term) {
+        const void* fn = plain ? (const void*)mppi_kernel<true, false> : (const void*)mppi_kernel<false, false>;
+        const MppiKernelArgs<false> plain_args = {ka.m};
+        return launch_variant(h, fn, dim3((unsigned)blocks), dim3(kBlock), lds, s, plain_args);
+    }
+    if (!(term->weight >= 0.0) || !std::isfinite(term->weight))
+        return fail(BCP_E_INVALID, "%s: weight must be finite and not negative", who);
+    // the field's shape and count against the binding: bcp_goal_field_sample's rules (the other arguments are made to pass)
+    const int64_t n_entries = n_slots(h);
+    switch (goal_sample_check_args(true, true, true, 1, 1.0, h->n, h->n, false, false, false, term->rows, term->cols, h->map.rows,
+                                   h->map.cols, term->n_fields, n_entries)) {
+    case kGoalSampleOk: break;
+    case kGoalSampleShape: return fail(BCP_E_INVALID, "%s: the field's shape %d x %d is not the bound maps' %d x %d", who, term->rows,
+                                       term->cols, h->map.rows, h->map.cols);
+    default: return fail(BCP_E_INVALID, "%s: n_fields %lld is neither 1 nor the %lld entries bound", who, (long long)term->n_fields,
+                         (long long)n_entries);
+    }
+    MppiTerminal& t = ka.t;
+    t.field = term->field;
+    t.field_stride = term->n_fields == 1 ? 0 : (int64_t)term->rows * term->cols;
+    t.n_entries = n_entries;
+    t.valid_rows = h->map_valid_rows;
+    t.valid_cols = h->map_valid_cols;
+    t.origins = h->map.origins;
+    t.ox = h->map.ox;
+    t.oy = h->map.oy;
+    t.inv_res = h->map.inv_res;
+    t.resolution = h->resolution;
+    t.weight = term->weight;
+    t.iter_value = term->iter_value;
+    t.iter_score = term->iter_score;
+    t.rows = term->rows;
+    t.cols = term->cols;
+    t.shared = h->map.shared;
+    const void* fn = plain ? (const void*)mppi_kernel<true, true> : (const void*)mppi_kernel<false, true>;
+    return launch_variant(h, fn, dim3((unsigned)blocks), dim3(kBlock), lds, s, ka);
+}
+
+extern "C" int bcp_mppi(bcp_handle* h, const bcp_mppi_params* p, const bcp_mppi_io* io, uint32_t flags, void* stream)
+{
+    if (!h || !p || !io) return fail(BCP_E_INVALID, "bcp_mppi: null argument");
+    return launch_mppi(h, p, io, nullptr, flags, (hipStream_t)stream, "bcp_mppi");
+}
+
+// bcp_mppi with a goal field as the terminal cost of a candidate (bcp_mppi.h, FIELD): the same launch, one 2-byte read more
+// per candidate and iteration.
+extern "C" int bcp_mppi_field(bcp_handle* h, const bcp_mppi_params* p, const bcp_mppi_io* io, const bcp_mppi_terminal* term,
+                              uint32_t flags, void* stream)
+{
+    if (!h || !p || !io || !term || !term->field) return fail(BCP_E_INVALID, "bcp_mppi_field: null argument");
+    return launch_mppi(h, p, io, term, flags, (hipStream_t)stream, "bcp_mppi_field");
 }
 
 extern "C" int bcp_expired_waits(bcp_handle* h, int64_t* count, void* stream)

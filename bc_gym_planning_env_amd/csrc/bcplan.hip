@@ -10,7 +10,7 @@
 //   bcp_field_plan.h   footprint geometry and the plan of a map binding: every shape and size, no HIP in it
 //   bcp_field.h        distance field and tiles: kernels, DistanceField, the launchers of what is derived from maps and paths
 //   bcp_step_host.h    step forms, the step's parameter block and launcher, Parking, WaitWatchdog, bcp_step / bcp_rollout /
-//                      bcp_lookahead / bcp_mppi
+//                      bcp_lookahead / bcp_mppi / bcp_mppi_field
 //   bcp_ego_host.h     egocentric costmaps (routed by bcp_ego_route.h, which has no HIP in it), goal-state vectors, the
 //                      episode record and its final observations
 //   bcp_worlds_host.h  mini-world and aisle-world entry points

@@ -38,9 +38,12 @@ class Mppi(object):
     """What BatchedPlanEnv.mppi() returns (device tensors, no sync): `mean` [N, H, 2] float64, the refined plan; `action`
     [N, 2] = mean[:, 0], ready for step(); optional, None unless asked for: `eps` [I, N, K, H, 2] float32 (the
     perturbations used), `iter_mean` [I, N, H, 2] (the mean going into each iteration), `iter_ret` / `iter_reason`
-    [I, N, K], `err` int32 [N].  Everything but `mean` is a cached buffer of the env for this (H, K, I)."""
+    [I, N, K], `err` int32 [N]; with a goal field (bcp_mppi_field) also `iter_value` int32 [I, N, K], the field value read at
+    each candidate's final pose (GOAL_NONE = none), and `iter_score` float64 [I, N, K], the scores as weighted.  Everything
+    but `mean` is a cached buffer of the env for this (H, K, I)."""
 
-    FIELDS = ("eps", "iter_mean", "iter_ret", "iter_reason", "err")
+    FIELDS = ("eps", "iter_mean", "iter_ret", "iter_reason", "err", "iter_value", "iter_score")
+    TERMINAL_FIELDS = ("iter_value", "iter_score")   # need a goal field
 
     def __init__(self, horizon, n_candidates, iterations, mean, action, **tensors):
         self.horizon, self.n_candidates, self.iterations = horizon, n_candidates, iterations
@@ -128,12 +131,18 @@ class MPPIPlanner(object):
     :param lam: temperature of the weights softmax(score / lam)
     :param collision_penalty: subtracted from the return of a candidate that collides within the horizon
     :param seed: of the perturbation stream (tick j uses draw index j; the env's noise stream is not involved)
+    :param goal_field: optional goal_field.GoalField of the env (env.goal_field()): every candidate's score then loses
+        terminal_weight * its final pose's distance to go through free space, inside the same launch (bcp_mppi_field) --
+        what the H steps of the roll-out cannot see.  A final pose without a route counts as GOAL_FAR cells
+    :param terminal_weight: reward per metre of that distance, finite and >= 0; 0 plans exactly as without a field
 
     A new plan -- at the start, and for the envs named by reset_plans() -- holds the centre of the action box,
     (low + high) / 2, at every step."""
 
-    def __init__(self, env, horizon, n_candidates, iterations, sigma, lam, collision_penalty, seed=0):
+    def __init__(self, env, horizon, n_candidates, iterations, sigma, lam, collision_penalty, seed=0, goal_field=None,
+                 terminal_weight=0.0):
         self.env = env
+        self.goal_field, self.terminal_weight = goal_field, float(terminal_weight)
         base = env
         while not hasattr(base, "n_envs"):   # wrappers forward mppi(); the sizes and the device are the batched env's
             base = base.unwrapped() if callable(base.unwrapped) else base.unwrapped
@@ -161,7 +170,8 @@ class MPPIPlanner(object):
         if not self._fresh:   # receding horizon: drop the step just taken, repeat the last row
             self.mean.copy_(torch.cat([self.mean[:, 1:], self.mean[:, -1:]], dim=1))
         self._fresh = False
+        terminal = {} if self.goal_field is None else dict(goal_field=self.goal_field, terminal_weight=self.terminal_weight)
         self.last = self.env.mppi(self.mean, self.sigma, self.iterations, self.n_candidates, self.lam, self.collision_penalty,
-                                  seed=self.seed, draw_index=self.draw_index)
+                                  seed=self.seed, draw_index=self.draw_index, **terminal)
         self.draw_index += 1
         return self.last.action

@@ -716,6 +716,35 @@ typedef struct bcp_mppi_io {
  *   - flag bits other than BCP_STEP_ACTIONS_F32; mean or action NULL. */
 int bcp_mppi(bcp_handle *h, const bcp_mppi_params *p, const bcp_mppi_io *io, uint32_t flags, void *stream);
 
+/* The terminal cost of bcp_mppi_field: a goal field of the handle's map binding (bcp_goal_field, below) and what a metre
+ * of distance to go costs.  Host struct of device pointers, caller-owned. */
+typedef struct bcp_mppi_terminal {
+    const uint16_t *field;   /* [n_fields][rows][cols], as bcp_goal_field wrote it */
+    int64_t n_fields;        /* 1, or the handle's entry count (pool entries, else n_envs) */
+    int32_t rows, cols;      /* must equal the map binding's */
+    double  weight;          /* reward per metre of distance to go, finite, >= 0 */
+    int32_t *iter_value;     /* optional [I][N][K]: the field value read for the candidate (65535 = none) */
+    double  *iter_score;     /* optional [I][N][K]: s_k as weighted */
+} bcp_mppi_terminal;
+
+/* bcp_mppi with the distance to go at a candidate's final pose in its score: what the H steps of the roll-out cannot see.
+ * Everything bcp_mppi specifies holds unchanged -- sampling, roll-outs, iter_ret / iter_reason (the pure return and reason),
+ * the weights and the update from the scores, one launch, nothing of the handle written, capture into a HIP graph, every
+ * refusal -- and only s_k differs.  For candidate k let (x, y) be its pose after the last step taken (after the roll-back
+ * where it collided: bcp_lookahead's final_pose) and g its env's slot (geom_of_env[i], else i):
+ *     (col, row) = half-to-even of ((x - ox) * inv_res, (y - oy) * inv_res), with the origin, inv_res and valid shape that
+ *                  bcp_goal_field_sample uses for that env's entry (entry 0 when the map is shared)
+ *     v   = field[n_fields == 1 ? 0 : g][row][col], or BCP_GOAL_NONE if x or y is not finite or the cell is outside the
+ *           valid shape
+ *     d   = ((double)(v == BCP_GOAL_NONE ? BCP_GOAL_FAR : v) * resolution) / 12.0      (float64, never through float32)
+ *     s_k = ret_k; if reason_k & BCP_DONE_COLLIDED: s_k = s_k - collision_penalty; then s_k = s_k - weight * d
+ * every product and sum rounded on its own, in that order.  With weight == 0 every output of bcp_mppi is the same bit for
+ * bit (d is always finite).  The read is one 2-byte load per live candidate and iteration.
+ * Refused with BCP_E_INVALID (messages prefixed "bcp_mppi_field: "): everything bcp_mppi refuses; term or term->field NULL;
+ * weight negative or not finite; rows / cols other than the binding's; n_fields neither 1 nor the entry count. */
+int bcp_mppi_field(bcp_handle *h, const bcp_mppi_params *p, const bcp_mppi_io *io, const bcp_mppi_terminal *term,
+                   uint32_t flags, void *stream);
+
 /* ---- costmap inflation ------------------------------------------------------------------------------------ */
 /* inflate_costmap (utilities/costmap_inflation.py:73-92) for n_maps maps in one call: the ROS inflation layer.  Per map
  * `data` [rows][cols] with valid shape (vr, vc) = (valid_rows[m], valid_cols[m]) clamped to [0, rows] x [0, cols], or the
