@@ -199,6 +199,9 @@ SYMBOLS = {
                                        C.c_void_p]),
     "bcp_goal_field": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bcp_goal_field_bound": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]),
+    "bcp_refresh_goal_fields": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bcp_goal_field_sample": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
                                         C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bcp_final_goal_field_sample": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_double,

@@ -7,6 +7,7 @@ raw pointers (tensor.data_ptr()); all arithmetic happens in libbcplan.so.
 """
 import ctypes as C
 import functools
+import weakref
 from collections import OrderedDict
 
 import attr
@@ -116,6 +117,7 @@ class BatchedPlanEnv(Handle):
         # what only some modes or subclasses change, at its neutral value
         self.endless = False       # BatchedRandomMiniEnv(endless=True)
         self._inflated = False     # inflate_costmaps()
+        self._goal_followers = []  # weak references to the GoalFields a refresh() keeps current (goal_field(follow_refresh=True))
         self._rollout_buffers, self._lookahead_buffers, self._mppi_buffers = OrderedDict(), OrderedDict(), OrderedDict()
         self._range_scan_buffers = OrderedDict()
 
@@ -715,7 +717,12 @@ class BatchedPlanEnv(Handle):
                                 lambda n, b, shapes, names: self._cached_outputs(self._range_scan_buffers, (n, b), shapes,
                                                                                  names, SCAN_CACHE_ENTRIES))
 
-    def goal_field(self, clearance=None, seeds="goal", max_passes=0):
+    def _follow_goal_fields(self, fields):
+        """Keep `fields` (a goal_field.GoalField built with follow_refresh=True) current across refresh(): by weak
+        reference, so a field nobody holds any more costs nothing."""
+        self._goal_followers.append(weakref.ref(fields))
+
+    def goal_field(self, clearance=None, seeds="goal", max_passes=0, follow_refresh=False):
         """The geodesic cost-to-go of every bound map to its path's goal (bcp_goal_field, one launch): for each free cell
         the length of the cheapest route through free space to the nearest seed, as a goal_field.GoalField whose sample()
         gives distance to go and route direction at any pose.  clearance: how far in metres a route keeps from every
@@ -724,10 +731,15 @@ class BatchedPlanEnv(Handle):
         every way point (the field is then the distance to the path).  max_passes: 0 = as many as it takes.
         Fields: one for a shared map with a shared path, one per pool entry, one per env for private maps -- and one per env
         for a shared map with private paths, the one map read n_envs times: n_envs * rows * cols * 2 bytes of fields.
-        Only cells == 254 are obstacles, so inflated maps give the same fields.  Refused on endless=True pools: a
-        refresh() would leave stale fields."""
+        Only cells == 254 are obstacles, so inflated maps give the same fields.
+        follow_refresh=True: the fields are built from the handle's own binding with the seeds derived on the device
+        (bcp_goal_field_bound: private maps with private paths, seeds="goal" only -- ValueError otherwise; the same
+        bytes).  On an endless=True pool the call first completes a refresh in flight (finish_refresh()), and from then
+        on every refresh() rebuilds, behind the re-sampled worlds and in the same stream order, the fields of exactly the
+        entries it re-sampled (bcp_refresh_goal_fields): the GoalField stays current for as long as it is alive.  With
+        follow_refresh=False an endless=True pool is refused (RuntimeError): a refresh() would leave stale fields."""
         from . import goal_field
-        return goal_field.build(self, clearance, seeds, max_passes)
+        return goal_field.build(self, clearance, seeds, max_passes, follow_refresh)
 
     def enable_episode_record(self, capacity=None):
         """Keep what every episode end leaves behind (bcp_bind_episode_record): from now on step() returns

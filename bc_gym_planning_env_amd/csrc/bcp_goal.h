@@ -20,10 +20,16 @@
 // The masks and the plane live in LDS when they fit (kLds); otherwise the masks are a slice of handle-owned scratch per
 // workgroup and the plane IS the map's slab of `out`.  A workgroup runs on one CU and its barriers order its own global
 // stores and loads (workgroup scope); no workgroup touches another's map.  The code is one template: the bytes are the same.
+// kBound (bcp_goal_field_bound / bcp_refresh_goal_fields): the same phases on the handle's own binding.  The trip counter
+// walks a selection of entries (EntrySelect: all of them, or a device-side list with a device-side count) instead of
+// 0 .. n_maps - 1, and phase 3 takes the entry's one seed from the last way point of its bound path.  Entries that are not
+// worked on keep their slab of `out` and their row of `info`.  The grid never depends on the count: a workgroup without a
+// trip leaves at once.
 #pragma once
 
 #include "bcp_device.h"
 #include "bcp_goal_cell.h"
+#include "bcp_step.h"   // EntrySelect
 
 namespace bcp {
 
@@ -40,6 +46,29 @@ struct GoalArgs {
     int64_t n_maps;
     int32_t rows, cols, wpr, shared;
     int32_t n_seeds, clearance_d2, reach, max_passes;   // reach = floor(sqrt(clearance_d2)); max_passes >= 1
+};
+
+// The bound form (bcp_goal_field_bound, bcp_refresh_goal_fields): the extra words behind GoalArgs.  The maps, valid shapes,
+// `out` and `info` are GoalArgs' (the handle's own binding, shared = 0, n_maps = the entry count); the entries worked on are
+// a selection, and each entry's one seed is the last way point of its bound path.
+struct GoalBound {
+    EntrySelect sel;             // {list, count, n_list}: list == nullptr = entries 0 .. n_list - 1
+    const double* paths;         // [n_maps][max_len][3], as given to bcp_set_paths
+    const int32_t* lens;         // [n_maps]
+    const double* origins;       // [n_maps][2], or nullptr: (ox, oy)
+    double ox, oy, inv_res;
+    int32_t max_len, pad;
+};
+
+// The kernel's argument: GoalArgs as it is, and behind it the bound part for the kBound kernels only -- the others take
+// what they always took.
+template <bool kBound> struct GoalKernelArgs;
+template <> struct GoalKernelArgs<false> {
+    GoalArgs g;
+};
+template <> struct GoalKernelArgs<true> {
+    GoalArgs g;
+    GoalBound b;
 };
 
 constexpr int kGoalFixedWords = 128 + 4;   // half-widths [128], pass flags [3], counter
@@ -68,9 +97,10 @@ __host__ __device__ inline size_t goal_lds_bytes(int rows, int cols, int wpr, bo
     return in_lds ? fixed + (size_t)2 * rows * wpr * 4 + (((size_t)rows * cols * 2 + 3) & ~(size_t)3) : fixed;
 }
 
-template <bool kLds>
-__global__ void __launch_bounds__(1024) goal_field_kernel(GoalArgs a)
+template <bool kLds, bool kBound>
+__global__ void __launch_bounds__(1024) goal_field_kernel(const GoalKernelArgs<kBound> ka)
 {
+    const GoalArgs& a = ka.g;
     typedef typename GoalMem<kLds>::Words Words;
     typedef typename GoalMem<kLds>::Plane Plane;
     const int rows = a.rows, cols = a.cols, wpr = a.wpr, cells = rows * cols, n_words = rows * wpr;
@@ -91,7 +121,16 @@ __global__ void __launch_bounds__(1024) goal_field_kernel(GoalArgs a)
     }
     for (int dr = tid; dr <= a.reach; dr += nthr) half_width[dr] = (uint32_t)goal_half_width(a.clearance_d2, dr);
 
-    for (int64_t m = blockIdx.x; m < a.n_maps; m += gridDim.x) {
+    // trips: the maps 0 .. n_maps - 1, or (kBound) the selection's entries -- *count clamped to [0, n_list], so the loop is
+    // bounded by n_list whatever the word holds; an id outside [0, n_maps) is skipped by the whole workgroup
+    int64_t trips = a.n_maps;
+    if constexpr (kBound) trips = ka.b.sel.list && ka.b.sel.count ? min(max(ka.b.sel.size(), (int64_t)0), ka.b.sel.n) : ka.b.sel.n;
+    for (int64_t trip = blockIdx.x; trip < trips; trip += gridDim.x) {
+        int64_t m = trip;
+        if constexpr (kBound) {
+            m = ka.b.sel.entry(trip);
+            if (m < 0 || m >= a.n_maps) continue;
+        }
         uint16_t* const dst = a.out + m * (int64_t)cells;
         if constexpr (!kLds) plane = dst;
         int vr = rows, vc = cols;
@@ -141,13 +180,27 @@ __global__ void __launch_bounds__(1024) goal_field_kernel(GoalArgs a)
         // ---- 3: the plane and the seeds
         for (int i = tid; i < cells; i += nthr) plane[i] = (uint16_t)kGoalNone;
         __syncthreads();
-        for (int s = tid; s < a.n_seeds; s += nthr) {
-            const int32_t* seed = a.seeds + (m * a.n_seeds + s) * 2;
-            const int sr = seed[0], sc = seed[1];
-            if ((uint32_t)sr < (uint32_t)vr && (uint32_t)sc < (uint32_t)vc) {
-                plane[sr * cols + sc] = (uint16_t)0;
-                __hip_atomic_fetch_and(closed + sr * wpr + (sc >> 5), ~(1u << (sc & 31)), __ATOMIC_RELAXED,
-                                       __HIP_MEMORY_SCOPE_WORKGROUP);
+        if constexpr (kBound) {   // one seed: the goal of the entry's path, on the entry's origin (goal_seed_of_path)
+            const GoalBound& b = ka.b;
+            const int32_t len = min(b.lens[m], b.max_len);
+            if (tid == 0 && len >= 1) {
+                const double* goal = b.paths + (m * b.max_len + (len - 1)) * 3;
+                const double ox = b.origins ? b.origins[2 * m] : b.ox, oy = b.origins ? b.origins[2 * m + 1] : b.oy;
+                int32_t sr = 0, sc = 0;
+                if (goal_seed_of_path(goal[0], goal[1], ox, oy, b.inv_res, vr, vc, sr, sc)) {
+                    plane[sr * cols + sc] = (uint16_t)0;
+                    closed[sr * wpr + (sc >> 5)] &= ~(1u << (sc & 31));   // (thread 0 alone, between two barriers)
+                }
+            }
+        } else {
+            for (int s = tid; s < a.n_seeds; s += nthr) {
+                const int32_t* seed = a.seeds + (m * a.n_seeds + s) * 2;
+                const int sr = seed[0], sc = seed[1];
+                if ((uint32_t)sr < (uint32_t)vr && (uint32_t)sc < (uint32_t)vc) {
+                    plane[sr * cols + sc] = (uint16_t)0;
+                    __hip_atomic_fetch_and(closed + sr * wpr + (sc >> 5), ~(1u << (sc & 31)), __ATOMIC_RELAXED,
+                                           __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
             }
         }
         __syncthreads();

@@ -1,6 +1,6 @@
 // bcp_goal_cell.h -- the goal field's arithmetic (bcp_goal_field, bcp_goal_field_sample; include/bcplan.h): the argument
 // checks, the half-widths of the clearance disc and the widening of one mask word, the pull relaxation of one cell, the field
-// at a pose, and the sampling of one row with its carrot walk.  Plain C++ with no HIP in it: goal_field_kernel and
+// at a pose, the seed cell of a bound path (bcp_goal_field_bound), and the sampling of one row with its carrot walk.  Plain C++ with no HIP in it: goal_field_kernel and
 // goal_sample_kernel (bcp_goal.h) and mppi_kernel's terminal read (bcp_mppi.h) call these functions on the device,
 // tests/c_abi/goal_field_main.cpp and tests/c_abi/mppi_field_main.cpp call the same ones on the host, and there is no other
 // copy of them.  The float64 arithmetic rounds every product, quotient, root and sum on its own
@@ -192,6 +192,49 @@ BCP_HD inline int32_t goal_value_at(const Get& get, int32_t vr, int32_t vc, doub
 {
     int32_t r = 0, c = 0;
     return goal_value_at(get, vr, vc, x, y, finite, ox, oy, inv_res, r, c);
+}
+
+// The seed of a bound path's last way point (x, y) on an entry with origin (ox, oy) and valid shape (vr, vc): the cell of
+// goal_value_at, by the same statement of the rule.  false -- and (row, col) untouched -- where x or y is not finite or the
+// cell lies outside the valid shape.  The range test is made on the rounded float64, before anything is converted: 1e300
+// is merely "outside".
+struct GoalAnyCell {
+    BCP_HD uint16_t operator()(int32_t, int32_t) const { return (uint16_t)0; }
+};
+
+BCP_HD inline bool goal_seed_of_path(double x, double y, double ox, double oy, double inv_res, int32_t vr, int32_t vc,
+                                     int32_t& row, int32_t& col)
+{
+    const double lim = 1.7976931348623157e308;
+    const bool finite = x >= -lim && x <= lim && y >= -lim && y <= lim;   // (a NaN fails every comparison)
+    return goal_value_at(GoalAnyCell(), vr, vc, x, y, finite, ox, oy, inv_res, row, col) != kGoalNone;
+}
+
+// what bcp_goal_field_bound and bcp_refresh_goal_fields refuse, in the order they look: 1 .. 6 with BCP_E_INVALID, 7 .. 10
+// with BCP_E_STATE.  refresh_form: bcp_refresh_goal_fields -- the list is the ring's, not the caller's, and a refresh must
+// be pending.  n_entries: the handle's entry count (pool entries, or n_envs without a pool).
+enum GoalBoundRefusal {
+    kGoalBoundOk = 0, kGoalBoundHandle = 1, kGoalBoundField = 2, kGoalBoundList = 3, kGoalBoundCount = 4,
+    kGoalBoundClearance = 5, kGoalBoundPasses = 6, kGoalBoundUnbound = 7, kGoalBoundShared = 8, kGoalBoundShape = 9,
+    kGoalBoundNoRefresh = 10
+};
+
+BCP_HD inline int goal_bound_check_args(bool have_handle, bool have_field, int64_t n_list, int64_t n_entries, bool have_entries,
+                                        bool have_count, int32_t clearance_d2, int32_t max_passes, bool have_map,
+                                        bool have_path, bool shared_map, bool shared_path, int32_t rows, int32_t cols,
+                                        bool refresh_form, bool refresh_pending)
+{
+    if (!have_handle) return kGoalBoundHandle;
+    if (!have_field) return kGoalBoundField;
+    if (!refresh_form && (n_list < 0 || n_list > n_entries)) return kGoalBoundList;
+    if (!refresh_form && have_count && !have_entries) return kGoalBoundCount;
+    if (clearance_d2 < 0 || clearance_d2 > kGoalMaxClearance) return kGoalBoundClearance;
+    if (max_passes < 0) return kGoalBoundPasses;
+    if (!have_map || !have_path) return kGoalBoundUnbound;
+    if (shared_map || shared_path) return kGoalBoundShared;
+    if (rows < 1 || rows > kGoalMaxSide || cols < 1 || cols > kGoalMaxSide) return kGoalBoundShape;
+    if (refresh_form && !refresh_pending) return kGoalBoundNoRefresh;
+    return kGoalBoundOk;
 }
 
 // metres to go of a cell value, float64, the product and the quotient rounded on their own

@@ -1,5 +1,6 @@
 // bcp_goal_host.h -- the host side of the goal field: bcp_goal_field (checks, the choice of where masks and plane live, the
-// launch), bcp_goal_field_sample / bcp_final_goal_field_sample over the rows of obs_rows() (bcp_ego_host.h), and the value
+// launch), bcp_goal_field_bound / bcp_refresh_goal_fields (the same launch on the handle's own binding, for all entries or a
+// device-side list of them), bcp_goal_field_sample / bcp_final_goal_field_sample over the rows of obs_rows() (bcp_ego_host.h), and the value
 // check of BCP_TUNE_GOAL_ROUTE.  The refusals are the checks of bcp_goal_cell.h, which the host tests run too; the kernels are
 // in bcp_goal.h.  Included by bcplan.hip after bcp_ego_host.h.
 // Capture: the launch arguments depend only on what the caller passes and nothing is uploaded, but a field kernel whose
@@ -59,10 +60,11 @@ extern "C" int bcp_goal_field(bcp_handle* h, const uint8_t* data, int64_t n_maps
     const bool in_lds = goal_lds_bytes(rows, cols, a.wpr, true) <= kMaxDynamicLds && h->tune.goal_route != 2;
     // a workgroup's threads: enough cells each to be worth their barriers
     const unsigned threads = cells >= 128 * 128 ? 1024u : 256u;
+    GoalKernelArgs<false> ka = {a};
     if (in_lds) {
         const unsigned grid = (unsigned)std::min<int64_t>(n_maps, 16384);
-        return launch_variant(h, reinterpret_cast<const void*>(goal_field_kernel<true>), dim3(grid), dim3(threads),
-                              goal_lds_bytes(rows, cols, a.wpr, true), s, a);
+        return launch_variant(h, reinterpret_cast<const void*>(goal_field_kernel<true, false>), dim3(grid), dim3(threads),
+                              goal_lds_bytes(rows, cols, a.wpr, true), s, ka);
     }
     const int64_t mask_words = (int64_t)2 * rows * a.wpr;
     const int64_t fit = std::max<int64_t>(1, kGoalScratchBytes / (mask_words * (int64_t)sizeof(uint32_t)));
@@ -71,9 +73,109 @@ extern "C" int bcp_goal_field(bcp_handle* h, const uint8_t* data, int64_t n_maps
         (void)hipGetLastError();
         return fail(BCP_E_HIP, "bcp_goal_field: cannot allocate %lld bytes of scratch", (long long)(grid * mask_words * 4));
     }
-    a.scratch = h->goal_scratch.get();
-    return launch_variant(h, reinterpret_cast<const void*>(goal_field_kernel<false>), dim3((unsigned)grid), dim3(threads),
-                          goal_lds_bytes(rows, cols, a.wpr, false), s, a);
+    ka.g.scratch = h->goal_scratch.get();
+    return launch_variant(h, reinterpret_cast<const void*>(goal_field_kernel<false, false>), dim3((unsigned)grid), dim3(threads),
+                          goal_lds_bytes(rows, cols, a.wpr, false), s, ka);
+}
+
+// ---- fields of the handle's own binding ---------------------------------------------------------------------------
+// bcp_goal_field_bound and bcp_refresh_goal_fields: the checks (goal_bound_check_args), the arguments from the binding, the
+// route as bcp_goal_field chooses it, and a grid that never depends on the device-side count.  refresh_form: the list is the
+// ring's `dirty` and the count its tally[0], as bcp_refresh_mini_worlds used them (bcp_worlds_host.h).
+constexpr int64_t kGoalBoundGrid = 1024;
+
+static int goal_field_bound(bcp_handle* h, const int32_t* entries, const int32_t* count, int64_t n_list, int32_t clearance_d2,
+                            int32_t max_passes, uint16_t* field, int32_t* info, void* stream, bool refresh_form, const char* who)
+{
+    const int64_t n_entries = h ? n_slots(h) : 0;
+    switch (goal_bound_check_args(h != nullptr, field != nullptr, n_list, n_entries, entries != nullptr, count != nullptr,
+                                  clearance_d2, max_passes, h && h->have_map, h && h->have_path, h && h->map.shared,
+                                  h && h->path.shared, h ? h->map.rows : 0, h ? h->map.cols : 0, refresh_form,
+                                  h && h->ring_refreshed && h->ring.get() && (int64_t)h->n_geoms == h->n * h->ring_episodes)) {
+    case kGoalBoundOk: break;
+    case kGoalBoundHandle: return fail(BCP_E_INVALID, "%s: null handle", who);
+    case kGoalBoundField: return fail(BCP_E_INVALID, "%s: null field", who);
+    case kGoalBoundList: return fail(BCP_E_INVALID, "%s: n_list %lld outside [0, %lld], the entries bound", who, (long long)n_list,
+                                     (long long)n_entries);
+    case kGoalBoundCount: return fail(BCP_E_INVALID, "%s: count needs entries", who);
+    case kGoalBoundClearance: return fail(BCP_E_INVALID, "%s: clearance_d2 %d outside [0, %d]", who, clearance_d2, kGoalMaxClearance);
+    case kGoalBoundPasses: return fail(BCP_E_INVALID, "%s: max_passes %d is negative", who, max_passes);
+    case kGoalBoundUnbound: return fail(BCP_E_STATE, "%s: costmaps and paths must be bound first", who);
+    case kGoalBoundShared: return fail(BCP_E_STATE, "%s: a shared map or a shared path has no per-entry goal here -- bcp_goal_field "
+                                                    "serves those", who);
+    case kGoalBoundShape: return fail(BCP_E_STATE, "%s: the bound maps' shape %d x %d is outside [1, 2048] x [1, 2048]", who,
+                                      h->map.rows, h->map.cols);
+    default: return fail(BCP_E_STATE, "%s: no refresh pending (between bcp_refresh_mini_worlds and bcp_release_mini_worlds)", who);
+    }
+    if (refresh_form) {   // the ring's arrays as bcp_plan_mini_worlds laid them out
+        const int64_t* first_world = (const int64_t*)h->ring.get();
+        const int32_t* counts = (const int32_t*)(first_world + h->n);
+        entries = counts + h->n;
+        count = entries + n_entries;
+        n_list = n_entries;
+    }
+    if (n_list == 0) return BCP_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    const int32_t rows = h->map.rows, cols = h->map.cols;
+
+    GoalKernelArgs<true> ka;
+    memset(&ka, 0, sizeof(ka));
+    GoalArgs& a = ka.g;
+    a.data = h->map_data;
+    a.valid_rows = h->map_valid_rows && h->map_valid_cols ? h->map_valid_rows : nullptr;
+    a.valid_cols = a.valid_rows ? h->map_valid_cols : nullptr;
+    a.out = field;
+    a.info = info;
+    a.n_maps = n_entries;
+    a.rows = rows;
+    a.cols = cols;
+    a.wpr = (cols + 31) / 32;
+    a.n_seeds = 1;
+    a.clearance_d2 = clearance_d2;
+    a.reach = goal_isqrt(clearance_d2);
+    a.max_passes = max_passes > 0 ? max_passes : rows * cols;
+    GoalBound& b = ka.b;
+    b.sel.list = entries;
+    b.sel.count = entries ? count : nullptr;
+    b.sel.n = n_list;
+    b.paths = h->path_src;
+    b.lens = h->path.lens;
+    b.origins = h->map.origins;
+    b.ox = h->map.ox;
+    b.oy = h->map.oy;
+    b.inv_res = h->map.inv_res;
+    b.max_len = h->path.max_len;
+    const int64_t cells = (int64_t)rows * cols;
+    const bool in_lds = goal_lds_bytes(rows, cols, a.wpr, true) <= kMaxDynamicLds && h->tune.goal_route != 2;
+    const unsigned threads = cells >= 128 * 128 ? 1024u : 256u;
+    if (in_lds) {
+        const unsigned grid = (unsigned)std::min(n_list, kGoalBoundGrid);
+        return launch_variant(h, reinterpret_cast<const void*>(goal_field_kernel<true, true>), dim3(grid), dim3(threads),
+                              goal_lds_bytes(rows, cols, a.wpr, true), s, ka);
+    }
+    const int64_t mask_words = (int64_t)2 * rows * a.wpr;
+    const int64_t fit = std::max<int64_t>(1, kGoalScratchBytes / (mask_words * (int64_t)sizeof(uint32_t)));
+    const int64_t grid = std::min(std::min(n_list, kGoalGlobalGrid), fit);
+    if (h->goal_bound_scratch.reserve((size_t)(grid * mask_words)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(BCP_E_HIP, "%s: cannot allocate %lld bytes of scratch", who, (long long)(grid * mask_words * 4));
+    }
+    a.scratch = h->goal_bound_scratch.get();
+    return launch_variant(h, reinterpret_cast<const void*>(goal_field_kernel<false, true>), dim3((unsigned)grid), dim3(threads),
+                          goal_lds_bytes(rows, cols, a.wpr, false), s, ka);
+}
+
+extern "C" int bcp_goal_field_bound(bcp_handle* h, const int32_t* entries, const int32_t* count, int64_t n_list,
+                                    int32_t clearance_d2, int32_t max_passes, uint16_t* field, int32_t* info, void* stream)
+{
+    return goal_field_bound(h, entries, count, n_list, clearance_d2, max_passes, field, info, stream, false, "bcp_goal_field_bound");
+}
+
+extern "C" int bcp_refresh_goal_fields(bcp_handle* h, int32_t clearance_d2, int32_t max_passes, uint16_t* field, int32_t* info,
+                                       void* stream)
+{
+    return goal_field_bound(h, nullptr, nullptr, 0, clearance_d2, max_passes, field, info, stream, true, "bcp_refresh_goal_fields");
 }
 
 // rec != nullptr: the final states of the episode record, n = capacity, rows j < min(*count, capacity)

@@ -249,6 +249,9 @@ struct bcp_handle {
     DevBuf<uint16_t> inflate_scratch;
     // ---- bcp_goal_field: the two bit masks of maps beyond LDS, a slice per workgroup; grown on demand, never shrunk
     DevBuf<uint32_t> goal_scratch;
+    // ---- bcp_goal_field_bound / bcp_refresh_goal_fields: the same, of their own -- a refresh on a side stream may run
+    // beside a bcp_goal_field on the steps' stream, and the two must not share mask slices
+    DevBuf<uint32_t> goal_bound_scratch;
 };
 
 // number of entries of a non-shared map / path / initial-state array

@@ -1,7 +1,9 @@
 """Goal fields for the whole batch: the geodesic cost-to-go of every bound map to its path's goal (bcp_goal_field, one
 launch per build) and what it says at a pose -- distance to go and the direction of the route -- per env and step
 (bcp_goal_field_sample, one tiny launch).  The terminal cost of a sampling planner, the dense shaping term and the
-"direction to goal" feature of a navigation policy.  The reference has no counterpart; the shape of the wrapper follows
+"direction to goal" feature of a navigation policy.  follow_refresh=True builds the fields from the handle's own binding
+(bcp_goal_field_bound) and, on an endless pool, has every refresh() rebuild the fields of the entries it re-samples
+(bcp_refresh_goal_fields).  The reference has no counterpart; the shape of the wrapper follows
 BatchedRangeScan (range_scan.py)."""
 from collections import OrderedDict
 
@@ -29,6 +31,7 @@ class GoalField(object):
         assert field.dtype == torch.uint16 and field.dim() == 3 and field.is_contiguous()
         self.owner, self.field, self.clearance_d2, self.info = owner, field, int(clearance_d2), info
         self.resolution = float(owner.resolution if resolution is None else resolution)
+        self.max_passes = 0         # of the build: what a following refresh() rebuilds with (build_bound)
         self._keep = keep           # the inputs of the build, alive until the stream has consumed them
         self._buffers = OrderedDict()
 
@@ -103,14 +106,42 @@ def path_seeds(env, which):
     return torch.where(beyond[..., None], torch.full((), -1, dtype=torch.int32, device=dev), rc).contiguous()
 
 
-def build(env, clearance=None, seeds="goal", max_passes=0):
-    """BatchedPlanEnv.goal_field: see there."""
+def build_bound(env, d2, max_passes):
+    """The fields of every entry of the env's own binding, seeds derived on the device (bcp_goal_field_bound); on an
+    endless env the GoalField is registered with it, and every refresh() rebuilds the fields of the entries it re-samples."""
     if env.endless:
-        raise RuntimeError("goal_field: not supported on endless=True pools -- refresh() re-samples worlds into the pool, "
-                           "which would leave stale fields")
+        env.finish_refresh()
+    data = env._keep["map"]
+    if env._shared_map or data.dim() != 3:
+        raise _lib.BcpError("goal_field(follow_refresh=True): needs private maps with private paths (a pool, or a map "
+                            "and a path per env); a shared map is served by the default build")
+    n, rows, cols = (int(v) for v in data.shape)
+    field = torch.empty((n, rows, cols), dtype=torch.uint16, device=env.device)
+    info = torch.zeros((n, 2), dtype=torch.int32, device=env.device)
+    _lib.check(env._lib.bcp_goal_field_bound(env._h, None, None, n, d2, int(max_passes), field.data_ptr(), info.data_ptr(),
+                                             env._stream()))
+    fields = GoalField(env, field, d2, info, keep=(data,))
+    fields.max_passes = int(max_passes)
+    if env.endless:
+        env._follow_goal_fields(fields)
+    return fields
+
+
+def build(env, clearance=None, seeds="goal", max_passes=0, follow_refresh=False):
+    """BatchedPlanEnv.goal_field: see there."""
+    if env.endless and not follow_refresh:
+        raise RuntimeError("goal_field: refused on endless=True pools unless follow_refresh=True -- refresh() re-samples "
+                           "worlds into the pool, which would leave stale fields")
+    if follow_refresh and seeds != "goal":
+        if seeds not in ("goal", "path"):
+            raise ValueError('seeds must be "goal" or "path", got %r' % (seeds,))
+        raise ValueError('goal_field(follow_refresh=True) needs seeds="goal": the way-point seed set is not derived on the '
+                         'device')
     if clearance is None:
         clearance = robots.inscribed_radius(env.footprint())
     d2 = clearance_cells_squared(clearance, env.resolution)
+    if follow_refresh:
+        return build_bound(env, d2, max_passes)
     s = path_seeds(env, seeds)
     data = env._keep["map"]
     n = int(s.shape[0])
@@ -137,13 +168,16 @@ class BatchedGoalField(BatchedObservationWrapper):
     unit vector, in the robot frame, towards the cell carrot_cells steps down the field.  The fields are built once, in the
     constructor (env.goal_field(clearance)); an observation costs two launches.  goal_n_state is the egocentric wrapper's
     vector with world size (max_dist, max_dist).
+    follow_refresh=True: the fields are built by env.goal_field(clearance, follow_refresh=True) -- on an endless=True env
+    every refresh() then rebuilds the fields of the entries it re-samples, and the observation follows worlds that never
+    repeat.
     final_observation=True: step() adds info["final_observation"] (BatchedObservationWrapper), sampled at every ended
     episode's final pose on the field of the map it ran on."""
 
-    def __init__(self, env, carrot_cells=8, clearance=None, max_dist=10.0, final_observation=False):
+    def __init__(self, env, carrot_cells=8, clearance=None, max_dist=10.0, final_observation=False, follow_refresh=False):
         super(BatchedGoalField, self).__init__(env)
         self.carrot_cells, self.max_dist = int(carrot_cells), float(max_dist)
-        self.fields = env.goal_field(clearance)
+        self.fields = env.goal_field(clearance, follow_refresh=True) if follow_refresh else env.goal_field(clearance)
         self._world = np.array([self.max_dist, self.max_dist], dtype=np.float64)
         self.goal_field = self._vector(env.n_envs)
         self.goal_n_state = self._goal_vector(env.n_envs)

@@ -515,6 +515,7 @@ class BatchedRandomMiniEnv(BatchedPlanEnv):
             self._ring_info = torch.zeros(4, dtype=torch.int32, device=dev)
             self._ring_info_done = torch.zeros(4, dtype=torch.int32, device=dev)
             self._ring_side, self._ring_pending = None, False
+            self._ring_fields = []
 
     def refresh(self, check=False, overlap=False):
         """endless=True: re-sample, on the GPU and in stream order, the pool entries of the worlds every env has left
@@ -531,6 +532,12 @@ class BatchedRandomMiniEnv(BatchedPlanEnv):
         (a refresh takes 2 .. 10 ms) and size `episodes` so that no env gets through `episodes - 1` worlds during two
         such periods.  Stepping on a high-priority stream (torch.cuda.Stream(priority=-1)) keeps the refresh kernels
         from delaying the steps (5 % in tools/bench_endless.py).
+
+        Goal fields that follow (goal_field(follow_refresh=True), BatchedGoalField(follow_refresh=True)): right behind
+        the new worlds, on the same stream, the refresh rebuilds the fields of exactly the re-sampled entries, one launch
+        per GoalField still alive (bcp_refresh_goal_fields) -- about 20 us of GPU time per re-sampled world and field.
+        The steps wait for the fields exactly as they wait for the worlds: an entry comes into reach with its field
+        already current.  A refresh with no field following is what it always was.
 
         Snapshots (get_state / set_state) hold pool ENTRIES, not worlds: one taken before a refresh can be restored only
         as long as the entries it points to have not been re-sampled.
@@ -582,6 +589,17 @@ class BatchedRandomMiniEnv(BatchedPlanEnv):
             pool.maps.data_ptr(), pool.path_points.data_ptr(), pool.lens.data_ptr(), pool.init.data_ptr(),
             float(ep.path_delta), self._ring_status.data_ptr(), self._ring_path_status.data_ptr(),
             C.c_void_p(stream.cuda_stream)))
+        # the goal fields that follow (goal_field(follow_refresh=True)): the same entries, right behind their new worlds
+        self._goal_followers = [ref for ref in self._goal_followers if ref() is not None]   # (dead references are dropped)
+        self._ring_fields = []   # the tensors the refresh writes, alive until finish_refresh() has waited for it
+        for fields in (ref() for ref in self._goal_followers):
+            if fields is None:
+                continue
+            field, info = fields.field, fields.info
+            self._ring_fields.append((field, info))
+            _lib.check(self._lib.bcp_refresh_goal_fields(self._h, fields.clearance_d2, fields.max_passes, field.data_ptr(),
+                                                         info.data_ptr() if info is not None else None,
+                                                         C.c_void_p(stream.cuda_stream)))
 
     def finish_refresh(self, check=False):
         """Complete the refresh in flight, if any: wait (on the current stream) for its side stream and open the ring to
@@ -594,6 +612,7 @@ class BatchedRandomMiniEnv(BatchedPlanEnv):
         _lib.check(self._lib.bcp_release_mini_worlds(self._h, C.c_void_p(main.cuda_stream)))
         self._ring_info_done.copy_(self._ring_info)   # (the plan's tally: the next plan overwrites _ring_info)
         self._ring_pending = False
+        self._ring_fields = []
         if not check:
             return self._ring_info_done
         if int(self._ring_status.sum()):

@@ -818,6 +818,45 @@ int bcp_goal_field(bcp_handle *h, const uint8_t *data, int64_t n_maps, int32_t r
                    int32_t *info,                                             /* optional [n_maps][2] */
                    void *stream);
 
+/* bcp_goal_field_bound: fields of the handle's OWN map / path binding, seeds derived on the device (the goal of each
+ * entry's path).  For private maps with private paths -- a geometry pool, or one map and one path per env -- and n_entries
+ * = the handle's entry count (the pool's entries, else n_envs).  One launch, asynchronous on `stream`, no host
+ * synchronisation, no upload; it allocates nothing after first use (the scratch of the global route is the handle's, one of
+ * its own beside bcp_goal_field's, grown only when a re-bind needs more).  A field kernel whose LDS passes 64 KB has its
+ * limit raised on first use, which is not a stream operation: one ordinary call must precede a capture.
+ * Data: the raw costmaps given to bcp_set_costmaps, entry m, with the binding's valid_rows / valid_cols when present,
+ * clamped as bcp_goal_field clamps them.
+ * Seed, one per entry: the last way point (x, y) = paths[m][lens[m] - 1] of the path given to bcp_set_paths (lens[m] above
+ * max_len counts as max_len), at
+ *   (col, row) = half-to-even of ((x - ox) * inv_res, (y - oy) * inv_res)        the rule of bcp_goal_field_sample
+ * on entry m's origin.  lens[m] < 1, an x or y that is not finite, or a cell outside the valid shape: no seed, the field is
+ * all BCP_GOAL_NONE and info = (0, 0).  A usable seed is free, whatever stood there.
+ * Result: field[m] and info[m] are byte for byte what bcp_goal_field writes for map m of the binding with that one seed.
+ * Entries: entries == NULL = entries 0 .. n_list - 1.  Otherwise `entries` is device int32 [n_list] -- room for n_list ids,
+ * which cannot be checked -- and the first min(max(*count, 0), n_list) of them are worked on (count == NULL = n_list); both
+ * are read on the device, in stream order, and the grid never depends on *count.  An id outside [0, n_entries) is skipped:
+ * nothing is read or written for it.  Listed ids are expected to be distinct.  field[m] and info[m] of every entry that is
+ * not worked on are left untouched.
+ * field: [n_entries][rows][cols] of the binding; info: optional [n_entries][2].  max_passes and clearance_d2: as above.
+ * BCP_E_INVALID: NULL h or field; n_list < 0 or above the entry count; count without entries; clearance_d2 outside
+ * [0, 16129]; max_passes < 0.  n_list == 0 succeeds and does nothing.  BCP_E_STATE: costmaps or paths not bound; a shared
+ * map or a shared path (bcp_goal_field serves those); bound maps beyond 2048 x 2048.  Refusals carry the entry point's name
+ * as a prefix.  Calls of the two entry points on different streams must not run beside each other (they share the scratch);
+ * either may run beside a bcp_goal_field. */
+int bcp_goal_field_bound(bcp_handle *h, const int32_t *entries /*device [n_list], or NULL = entries 0..n_list-1*/,
+                         const int32_t *count /*device word, or NULL = n_list*/, int64_t n_list,
+                         int32_t clearance_d2, int32_t max_passes,
+                         uint16_t *field /*[n_entries][rows][cols] of the binding*/, int32_t *info /*optional [n_entries][2]*/,
+                         void *stream);
+/* bcp_refresh_goal_fields: the same for exactly the entries the pending bcp_refresh_mini_worlds re-sampled -- the list
+ * bcp_plan_mini_worlds made, and the count the refresh used, both still in the handle.  A refresh is pending after
+ * bcp_refresh_mini_worlds and before bcp_release_mini_worlds; otherwise BCP_E_STATE.  The call belongs on the refresh's
+ * stream, or one ordered after it, and must be ordered before the bcp_release_mini_worlds that opens those entries to the
+ * envs: whoever waits for the worlds then waits for the fields too.  It may be called once per field tensor while the
+ * refresh is pending.  Everything else -- contract, refusals, capture -- as bcp_goal_field_bound. */
+int bcp_refresh_goal_fields(bcp_handle *h, int32_t clearance_d2, int32_t max_passes, uint16_t *field, int32_t *info,
+                            void *stream);
+
 /* bcp_goal_field_sample: what the fields say at a pose, per row -- distance to go, and the direction of the route.
  * One launch, asynchronous on `stream`, no allocation, no host synchronisation; the launch arguments depend only on the
  * pointers and numbers given, so a call can be captured into a HIP graph after one ordinary call.

@@ -1,0 +1,190 @@
+"""The host half of the goal fields that follow a refreshed pool (bcp_goal_field_bound, bcp_refresh_goal_fields):
+goal_seed_of_path and goal_bound_check_args of csrc/bcp_goal_cell.h as a stand-alone program under AddressSanitizer and
+UBSan, against their restatement in numpy (tests/goal_field_refresh_ref.py); and the two symbols in the header, the built
+library and the binding.  tests/c_abi/goal_seed_main.cpp includes the header alone and calls the very functions the bound
+form of goal_field_kernel and the entry points call; a conversion of a huge coordinate to an integer would be UBSan's."""
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import goal_field_refresh_ref as RR
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW_SYMBOLS = ["bcp_goal_field_bound", "bcp_refresh_goal_fields"]
+
+
+def _compiler():
+    for cand in ("g++", "/opt/rocm/llvm/bin/clang++", "clang++"):
+        path = shutil.which(cand)
+        if path:
+            return path
+    raise AssertionError("no host C++ compiler found (g++ or ROCm's clang++)")
+
+
+@pytest.fixture(scope="module")
+def program(tmp_path_factory):
+    exe = str(tmp_path_factory.mktemp("goal_seed") / "goal_seed_main")
+    cxx = _compiler()
+    static_runtime = ["-static-libasan", "-static-libubsan"] if cxx.endswith("g++") else []   # (clang's is static already)
+    cmd = [cxx] + static_runtime + ["-std=c++17", "-Wall", "-Werror", "-g", "-O1", "-ffp-contract=off",
+                                    "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                                    "-I" + os.path.join(ROOT, "bc_gym_planning_env_amd", "csrc"),
+                                    os.path.join(ROOT, "tests", "c_abi", "goal_seed_main.cpp"), "-o", exe]
+    built = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=300)
+    assert built.returncode == 0, built.stdout
+    return exe
+
+
+def _run(exe, *args):
+    ran = subprocess.run([exe] + list(args), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=120)
+    assert ran.returncode == 0, ran.stdout[-4000:]
+    assert "goal seed ok" in ran.stdout
+    for word in ("Sanitizer", "runtime error"):
+        assert word not in ran.stdout, ran.stdout[-4000:]
+    return ran.stdout.split("\n")
+
+
+def _word(v):
+    v = float(v)
+    return v.hex() if np.isfinite(v) else repr(v)       # 'nan', 'inf', '-inf': strtod reads them
+
+
+def _seeds(exe, tmp_path, cases):
+    path = str(tmp_path / "seeds.txt")
+    with open(path, "w") as f:
+        for x, y, ox, oy, inv_res, vr, vc in cases:
+            f.write(" ".join(_word(v) for v in (x, y, ox, oy, inv_res)) + " %d %d\n" % (vr, vc))
+    return [tuple(int(w) for w in ln.split()) for ln in _run(exe, "seeds", path)[:len(cases)]]
+
+
+def test_seed_cells_ties_edges_and_unusable_way_points(program, tmp_path):
+    inf, nan = float("inf"), float("nan")
+    vr, vc = 20, 24
+    res = 0.25                       # (a power of two: k + 1/2 cells are exact, the ties are real ties)
+    inv = 1.0 / res
+    ox, oy = -1.0, 0.5
+    at = lambda col, row: (ox + col * res, oy + row * res)   # noqa: E731
+    cases, want = [], []
+
+    def add(x, y, expect=None, shape=(vr, vc), origin=(ox, oy), inv_res=inv):
+        cases.append((x, y, origin[0], origin[1], inv_res, shape[0], shape[1]))
+        want.append(expect)
+
+    # ties go to the even cell
+    add(*at(0.5, 0.5), expect=(1, 0, 0))
+    add(*at(1.5, 2.5), expect=(1, 2, 2))
+    add(*at(2.5, 3.5), expect=(1, 4, 2))
+    add(*at(22.5, 18.5), expect=(1, 18, 22))
+    add(*at(-0.5, -0.5), expect=(1, 0, 0))                  # -0.5 -> -0.0: cell 0
+    add(*at(-0.5000001, 3.0), expect=(0, RR.NO_CELL, RR.NO_CELL))
+    # the last valid row / column, and one beyond
+    add(*at(23, 19), expect=(1, 19, 23))
+    add(*at(23.49, 19.49), expect=(1, 19, 23))
+    add(*at(23.5, 19), expect=(0, RR.NO_CELL, RR.NO_CELL))   # 23.5 -> 24: outside
+    add(*at(23, 19.5), expect=(0, RR.NO_CELL, RR.NO_CELL))
+    add(*at(24, 19), expect=(0, RR.NO_CELL, RR.NO_CELL))
+    add(*at(23, 20), expect=(0, RR.NO_CELL, RR.NO_CELL))
+    # negative cells
+    add(*at(-1, 5), expect=(0, RR.NO_CELL, RR.NO_CELL))
+    add(*at(5, -1), expect=(0, RR.NO_CELL, RR.NO_CELL))
+    add(*at(-300, -300), expect=(0, RR.NO_CELL, RR.NO_CELL))
+    # way points that are no numbers, and numbers no integer holds
+    for bad in (nan, inf, -inf, 1e300, -1e300, 3e9, -3e9):
+        add(bad, oy + res, expect=(0, RR.NO_CELL, RR.NO_CELL))
+        add(ox + res, bad, expect=(0, RR.NO_CELL, RR.NO_CELL))
+        add(bad, bad, expect=(0, RR.NO_CELL, RR.NO_CELL))
+    add(1e300, 1e300, expect=(0, RR.NO_CELL, RR.NO_CELL), inv_res=1e300)      # the product overflows to inf
+    # empty and one-cell valid shapes
+    add(*at(0, 0), expect=(0, RR.NO_CELL, RR.NO_CELL), shape=(0, 24))
+    add(*at(0, 0), expect=(0, RR.NO_CELL, RR.NO_CELL), shape=(20, 0))
+    add(*at(0, 0), expect=(1, 0, 0), shape=(1, 1))
+    add(*at(1, 0), expect=(0, RR.NO_CELL, RR.NO_CELL), shape=(1, 1))
+    # the largest shape
+    add(2047 * 0.03, 2047 * 0.03, shape=(2048, 2048), origin=(0.0, 0.0), inv_res=1.0 / 0.03)
+    # a spread of ordinary way points at the library's usual resolution
+    rng = np.random.RandomState(3)
+    for _ in range(400):
+        x, y = rng.uniform(-3.5, 3.5, size=2)
+        add(x, y, shape=(183, 183), origin=(-2.745, -2.745), inv_res=1.0 / 0.03)
+    got = _seeds(program, tmp_path, cases)
+    restated = [RR.seed_of_path(*c) for c in cases]
+    assert got == restated
+    for k, expect in enumerate(want):
+        if expect is not None:
+            assert got[k] == expect, (k, cases[k], got[k], expect)
+    usable = sum(g[0] for g in got[-400:])
+    assert 100 < usable < 400          # (the spread covers both outcomes)
+
+
+def test_every_refusal_of_the_bound_entry_points(program, tmp_path):
+    # handle field n_list n_entries entries count clearance_d2 max_passes map path shared_map shared_path rows cols refresh pending
+    ok = (1, 1, 16, 16, 0, 0, 151, 0, 1, 1, 0, 0, 183, 183, 0, 0)
+    rf = ok[:14] + (1, 1)
+    table = [
+        (ok, 0),
+        (ok[:2] + (0, 16, 0, 0) + ok[6:], 0),                      # n_list == 0
+        (ok[:2] + (3, 16, 1, 1) + ok[6:], 0),
+        (ok[:2] + (3, 16, 1, 0) + ok[6:], 0),                      # entries without count: all n_list of them
+        (ok[:6] + (0, 7) + ok[8:], 0), (ok[:6] + (16129, 0) + ok[8:], 0),
+        (ok[:12] + (1, 1, 0, 0), 0), (ok[:12] + (2048, 2048, 0, 0), 0),
+        (rf, 0),
+        (rf[:2] + (-5, 0, 0, 1) + rf[6:], 0),                      # the refresh form brings its own list
+        ((0,) + ok[1:], 1), ((0, 0) + ok[2:], 1),
+        ((1, 0) + ok[2:], 2),
+        (ok[:2] + (-1,) + ok[3:], 3), (ok[:2] + (17,) + ok[3:], 3), (ok[:2] + (1, 0) + ok[4:], 3),
+        (ok[:4] + (0, 1) + ok[6:], 4),
+        (ok[:6] + (-1,) + ok[7:], 5), (ok[:6] + (16130,) + ok[7:], 5),
+        (ok[:7] + (-1,) + ok[8:], 6),
+        (ok[:8] + (0, 1) + ok[10:], 7), (ok[:8] + (1, 0) + ok[10:], 7), (ok[:8] + (0, 0) + ok[10:], 7),
+        (ok[:10] + (1, 0) + ok[12:], 8), (ok[:10] + (0, 1) + ok[12:], 8),
+        (ok[:12] + (0, 183) + ok[14:], 9), (ok[:12] + (183, 2049) + ok[14:], 9),
+        (ok[:14] + (1, 0), 10),
+        # the order: arguments before state, the pending refresh last
+        ((0, 0, -1, 16, 0, 1, -1, -1, 0, 0, 1, 1, 0, 0, 1, 0), 1),
+        ((1, 0, -1, 16, 0, 1, -1, -1, 0, 0, 1, 1, 0, 0, 0, 0), 2),
+        ((1, 1, -1, 16, 0, 1, -1, -1, 0, 0, 1, 1, 0, 0, 0, 0), 3),
+        ((1, 1, 4, 16, 0, 1, -1, -1, 0, 0, 1, 1, 0, 0, 0, 0), 4),
+        ((1, 1, 4, 16, 1, 1, -1, -1, 0, 0, 1, 1, 0, 0, 0, 0), 5),
+        ((1, 1, 4, 16, 1, 1, 0, -1, 0, 0, 1, 1, 0, 0, 0, 0), 6),
+        ((1, 1, 4, 16, 1, 1, 0, 0, 0, 0, 1, 1, 0, 0, 0, 0), 7),
+        ((1, 1, 4, 16, 1, 1, 0, 0, 1, 1, 1, 1, 0, 0, 0, 0), 8),
+        ((1, 1, 4, 16, 1, 1, 0, 0, 1, 1, 0, 0, 0, 0, 1, 0), 9),
+        ((1, 1, -1, 16, 0, 1, -1, 0, 1, 1, 0, 0, 5, 5, 1, 0), 5),  # the refresh form skips the list's refusals
+        ((1, 1, -1, 16, 0, 1, 0, 0, 1, 1, 0, 0, 5, 5, 1, 0), 10),
+    ]
+    path = str(tmp_path / "args.txt")
+    with open(path, "w") as f:
+        for args, _want in table:
+            assert len(args) == 16
+            f.write(" ".join(str(a) for a in args) + "\n")
+    got = [int(ln) for ln in _run(program, "args", path)[:len(table)]]
+    assert got == [want for _args, want in table]
+    assert [RR.check_bound_args(*args) for args, _want in table] == got
+    assert set(got) == set(range(11))                 # every refusal, and none
+
+
+def test_header_library_and_binding_have_the_two_symbols():
+    import ctypes as C
+    from bc_gym_planning_env_amd import _lib, build
+    header = open(os.path.join(ROOT, "include", "bcplan.h")).read()
+    declared = set(re.findall(r"\b(bcp_[a-z_0-9]+)\s*\(", header))
+    build.build()
+    raw = C.CDLL(_lib.LIB_PATH)
+    for name in NEW_SYMBOLS:
+        assert name in declared, name
+        assert hasattr(raw, name), name
+        assert name in _lib.SYMBOLS, name
+    lib = _lib.load()
+    bound, refresh = lib.bcp_goal_field_bound.argtypes, lib.bcp_refresh_goal_fields.argtypes
+    assert len(bound) == 9 and bound[3] is C.c_int64 and bound[4:6] == [C.c_int32, C.c_int32]
+    assert len(refresh) == 6 and refresh[1:3] == [C.c_int32, C.c_int32]
+    assert _lib.ABI_VERSION == 2 and "#define BCP_ABI_VERSION 2" in header.replace("  ", " ")
+    # the refusals that need no device: a NULL handle comes first, with the entry point's name in front
+    assert lib.bcp_goal_field_bound(None, None, None, 0, 0, 0, None, None, None) == -1
+    assert lib.bcp_last_error().startswith(b"bcp_goal_field_bound: ")
+    assert lib.bcp_refresh_goal_fields(None, 0, 0, None, None, None) == -1
+    assert lib.bcp_last_error().startswith(b"bcp_refresh_goal_fields: ")

@@ -1,0 +1,454 @@
+"""Goal fields of the handle's own binding (bcp_goal_field_bound) and their rebuild behind a refreshed pool
+(bcp_refresh_goal_fields, goal_field(follow_refresh=True)) on the GPU.  Everything is compared with torch.equal: the
+reference is the existing path -- bcp_goal_field on the same maps with goal_field.path_seeds -- and, for a few entries,
+Dijkstra's field (tests/goal_field_ref.py).  Outputs start from a sentinel (0xABCD / -7), so an entry that was not worked
+on shows.  Shapes are the smallest at which each mechanism can go wrong: 16 .. 64 entries of the 183 x 183 mini worlds (the
+only worlds a refresh samples), and 1 100 entries of 20 x 24 for the second trips of both routes' grids (1 024 and 512)."""
+import gc
+
+import numpy as np
+import pytest
+
+import goal_field_ref as GR
+import mppi_field_ref as FR
+import mppi_ref as MR
+
+pytestmark = pytest.mark.gpu
+
+E_INVALID, E_STATE = -1, -4
+SENTINEL, SENTINEL_I = 0xABCD, -7
+
+
+# ---- helpers ---------------------------------------------------------------------------------------------------------------
+def _mini(n, timeout, endless=False, seeds=(1, 2, 3, 4), episodes=4):
+    from bc_gym_planning_env_amd import EnvParams, mini_env
+    params = mini_env.RandomMiniEnvParams(
+        env_params=EnvParams(goal_ang_dist=np.pi / 8., goal_spat_dist=0.2, iteration_timeout=timeout))
+    if endless:
+        return mini_env.BatchedRandomMiniEnv(n, params, episodes=episodes, auto_reset=True, seed=4, endless=True)
+    pool = mini_env.sample_pool(params, list(seeds), episodes)
+    return mini_env.BatchedRandomMiniEnv(n, params, pool=pool, auto_reset=True, seed=2)
+
+
+def _i16(t):
+    """a uint16 device tensor seen as int16: comparisons, indexing and torch.equal then run on a type every backend has"""
+    import torch
+    return t.view(torch.int16) if t.dtype == torch.uint16 else t
+
+
+def _same(a, b):
+    import torch
+    return torch.equal(_i16(a), _i16(b))
+
+
+def _all(t, value):
+    """every element holds `value` (a uint16 value for a field, an int32 one for info)"""
+    import torch
+    return bool((_i16(t) == (value - 65536 if t.dtype == torch.uint16 and value >= 32768 else value)).all())
+
+
+def _sentinels(torch, n, rows, cols):
+    field = torch.from_numpy(np.full((n, rows, cols), SENTINEL, dtype=np.uint16)).cuda()
+    info = torch.full((n, 2), SENTINEL_I, dtype=torch.int32, device="cuda")
+    return field, info
+
+
+def _bound(env, field, info, d2, entries=None, count=None, n_list=None, passes=0, stream=None):
+    """bcp_goal_field_bound through the C ABI -> the return code"""
+    n_list = int(field.shape[0]) if n_list is None else n_list
+    return env._lib.bcp_goal_field_bound(env._h, entries.data_ptr() if entries is not None else None,
+                                         count.data_ptr() if count is not None else None, n_list, int(d2), int(passes),
+                                         field.data_ptr() if field is not None else None,
+                                         info.data_ptr() if info is not None else None, stream)
+
+
+def _bound_all(torch, env, d2):
+    n, rows, cols = env.costmap_tensor.shape
+    field, info = _sentinels(torch, n, rows, cols)
+    assert _bound(env, field, info, d2) == 0, env._lib.bcp_last_error()
+    return field, info
+
+
+def _scratch_build(torch, env, d2):
+    """the existing path, from scratch: one bcp_goal_field call on the maps as they are now, seeds from path_seeds"""
+    from bc_gym_planning_env_amd import _lib
+    from bc_gym_planning_env_amd.goal_field import path_seeds
+    data = env.costmap_tensor
+    n, rows, cols = (int(v) for v in data.shape)
+    seeds = path_seeds(env, "goal")
+    vr, vc = env._keep.get("vr"), env._keep.get("vc")
+    field, info = _sentinels(torch, n, rows, cols)
+    _lib.check(env._lib.bcp_goal_field(env._h, data.data_ptr(), n, rows, cols, 0, vr.data_ptr() if vr is not None else None,
+                                       vc.data_ptr() if vc is not None else None, seeds.data_ptr(), 1, int(d2), 0,
+                                       field.data_ptr(), info.data_ptr(), None))
+    torch.cuda.synchronize()
+    return field, info
+
+
+def _dijkstra_of_entry(env, entry, d2):
+    """Dijkstra's field of one entry of the binding, the goal cell by numpy's own arithmetic"""
+    data = env.costmap_tensor[entry].cpu().numpy()
+    k = env._keep
+    valid = None if k.get("vr") is None else (int(k["vr"][entry]), int(k["vc"][entry]))
+    origin = k["origins"][entry].cpu().numpy()
+    goal = k["path"][entry, int(k["lens"][entry]) - 1].cpu().numpy()
+    inv = 1.0 / env.resolution
+    cell = (int(np.rint((goal[1] - origin[1]) * inv)), int(np.rint((goal[0] - origin[0]) * inv)))
+    return GR.dijkstra(data, [cell], d2, valid)
+
+
+def _equal_to_dijkstra(torch, env, field, entry, d2):
+    want = _dijkstra_of_entry(env, entry, d2)
+    assert (want != GR.NONE).sum() > 100, entry
+    assert _same(field[entry].cpu(), torch.from_numpy(want.copy())), entry
+
+
+def _drive(env, rng, steps):
+    for _ in range(steps):
+        env.step(env.action_space.sample_batch(env.n_envs, rng))
+
+
+# ---- 1. all entries = the existing path ------------------------------------------------------------------------------------
+@pytest.mark.parametrize("d2", [0, 151])
+def test_all_entries_equal_the_existing_path(torch_cuda, d2):
+    torch = torch_cuda
+    env = _mini(16, timeout=12)
+    want = env.goal_field(clearance=0.0) if d2 == 0 else env.goal_field()
+    assert want.clearance_d2 == d2 and want.field.shape == (16, 183, 183)
+    field, info = _bound_all(torch, env, d2)
+    torch.cuda.synchronize()
+    assert _same(field, want.field) and _same(info, want.info)
+    assert (info[:, 0] > 100).all() and (info[:, 1] == 0).all()
+    for entry in (0, 5):
+        _equal_to_dijkstra(torch, env, field, entry, d2)
+    # the Python surface on a pool that is not endless: follow_refresh only selects the bound build
+    again = env.goal_field(clearance=0.0 if d2 == 0 else None, follow_refresh=True)
+    assert again.clearance_d2 == d2 and _same(again.field, want.field) and _same(again.info, want.info)
+    assert env._goal_followers == []
+
+
+# ---- 2. padded shapes ------------------------------------------------------------------------------------------------------
+def test_padded_shapes_of_an_aisle_pool(torch_cuda):
+    torch = torch_cuda
+    from bc_gym_planning_env_amd import EnvParams, aisle_env
+    ranges = aisle_env.TurnRanges(main_corridor_length=(3., 4.), turn_corridor_length=(2., 3.), main_corridor_width=(1.2, 1.8),
+                                  turn_corridor_width=(1.2, 1.8), margin=0.5)
+    env = aisle_env.BatchedRandomAisleTurnEnv(16, EnvParams(iteration_timeout=40, resolution=0.05), n_chains=2, episodes=4,
+                                              sampler="device_resident", auto_reset=True, ranges=ranges)
+    want = env.goal_field(clearance=0.2)
+    vr, vc = env._keep["vr"].cpu().numpy(), env._keep["vc"].cpu().numpy()
+    assert want.field.shape[0] == 8 and len({(int(a), int(b)) for a, b in zip(vr, vc)}) > 1
+    field, info = _bound_all(torch, env, want.clearance_d2)
+    torch.cuda.synchronize()
+    assert _same(field, want.field) and _same(info, want.info)
+    got = field.cpu().numpy()
+    for f in range(8):
+        assert (got[f, vr[f]:] == GR.NONE).all() and (got[f, :, vc[f]:] == GR.NONE).all(), f
+    assert (info[:, 0] > 100).all()
+    _equal_to_dijkstra(torch, env, field, 3, want.clearance_d2)
+
+
+# ---- 3. selection ------------------------------------------------------------------------------------------------------------
+def test_selection_by_a_device_side_list_and_count(torch_cuda):
+    torch = torch_cuda
+    env = _mini(16, timeout=12)
+    want = env.goal_field()
+    listed = torch.tensor([5, 2, 11, -1, 16], dtype=torch.int32, device="cuda")
+    count = torch.zeros(1, dtype=torch.int32, device="cuda")
+
+    def run(c, n_list, entries=listed, with_count=True):
+        count.fill_(c)
+        field, info = _sentinels(torch, 16, 183, 183)
+        assert _bound(env, field, info, 151, entries, count if with_count else None, n_list) == 0, env._lib.bcp_last_error()
+        torch.cuda.synchronize()
+        return field, info
+
+    def rewritten(field, info, which):
+        for e in range(16):
+            if e in which:
+                assert _same(field[e], want.field[e]) and _same(info[e], want.info[e]), e
+            else:
+                assert _all(field[e], SENTINEL) and _all(info[e], SENTINEL_I), e
+
+    rewritten(*run(2, 5), which=(5, 2))
+    rewritten(*run(5, 5), which=(5, 2, 11))          # -1 and 16 are skipped
+    rewritten(*run(0, 5), which=())
+    rewritten(*run(-3, 5), which=())
+    rewritten(*run(99, 3), which=(5, 2, 11))         # clamped to n_list
+    rewritten(*run(1, 3, with_count=False), which=(5, 2, 11))     # no count: all n_list of them
+    rewritten(*run(0, 7, entries=None, with_count=False), which=range(7))     # no list: entries 0 .. n_list - 1
+
+
+# ---- 4. second trips ---------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def many_private(torch_cuda):
+    """1 100 envs, each with a private map inside a 20 x 24 allocation (valid shapes down to 1 x 1) and a private path"""
+    torch = torch_cuda
+    from bc_gym_planning_env_amd import BatchedPlanEnv, CostMap2D, EnvParams
+    n, res = 1100, 0.05
+    rng = np.random.RandomState(77)
+    shapes = [(20, 24), (1, 1), (20, 1), (1, 24), (7, 24), (20, 9), (13, 17)]
+    maps, paths, special = [], [], {}
+    for i in range(n):
+        rows, cols = shapes[i % len(shapes)] if i % 3 else (20, 24)
+        data = np.where(rng.uniform(size=(rows, cols)) < 0.12, 254, 0).astype(np.uint8)
+        origin = rng.uniform(-1.0, 0.0, 2)
+        goal_rc = (rng.randint(rows), rng.randint(cols))
+        kind = {40: "outside", 41: "lethal", 1030: "outside", 1031: "lethal", 1050: "nan", 1090: "beyond"}.get(i, "")
+        if kind == "outside":
+            goal_rc = (rows + 1, cols // 2)              # outside the valid shape, inside the allocation where it is padded
+        elif kind == "beyond":
+            goal_rc = (-3, 400)
+        elif kind == "lethal":
+            data[goal_rc] = 254
+        if kind:
+            special[i] = kind
+        goal = [origin[0] + goal_rc[1] * res, origin[1] + goal_rc[0] * res, 3.0]   # (facing back: not reached at the start)
+        n_points = 2 + i % 3                               # (paths of different lengths: the LAST way point is the seed)
+        points = [[origin[0] + 0.1 * j, origin[1] + 0.05 * j, 0.0] for j in range(n_points - 1)] + [goal]
+        maps.append(CostMap2D(data, res, origin))
+        paths.append(np.array(points))
+    env = BatchedPlanEnv(maps, paths, EnvParams(resolution=res, refine_path=False), n_envs=n, map_storage=(20, 24))
+    nan_env = [i for i, kind in special.items() if kind == "nan"][0]
+    env._keep["path"][nan_env, int(env._keep["lens"][nan_env]) - 1, 0] = float("nan")      # (behind the set-up: not stepped)
+    torch.cuda.synchronize()
+    return env, special
+
+
+@pytest.mark.parametrize("route", [0, 2])
+def test_second_trips_on_both_routes(torch_cuda, many_private, route):
+    torch = torch_cuda
+    from bc_gym_planning_env_amd import _lib
+    env, special = many_private
+    assert tuple(env.costmap_tensor.shape) == (1100, 20, 24) and env._keep["vr"] is not None
+    for d2 in (0, 2):
+        want, want_info = _scratch_build(torch, env, d2)
+        assert env._lib.bcp_set_tuning(env._h, _lib.TUNE_GOAL_ROUTE, route) == 0
+        try:
+            field, info = _bound_all(torch, env, d2)
+            torch.cuda.synchronize()
+        finally:
+            assert env._lib.bcp_set_tuning(env._h, _lib.TUNE_GOAL_ROUTE, 0) == 0
+        assert _same(field, want) and _same(info, want_info), (route, d2)
+        for i, kind in special.items():
+            if kind == "lethal":
+                assert int(info[i, 0]) >= 1 and bool((_i16(field[i]) == 0).any()), (i, kind)      # a usable seed is free
+            else:
+                assert _all(field[i], GR.NONE) and info[i].tolist() == [0, 0], (i, kind)
+        assert (info[1024:, 0] > 0).sum() > 40 and (info[512:1024, 0] > 0).sum() > 300      # the later trips did work
+    _equal_to_dijkstra_small(torch, env, field, 1099, 2)
+
+
+def _equal_to_dijkstra_small(torch, env, field, entry, d2):
+    want = _dijkstra_of_entry(env, entry, d2)
+    assert _same(field[entry].cpu(), torch.from_numpy(want.copy())), entry
+
+
+# ---- 5. .. 8.: an endless env ---------------------------------------------------------------------------------------------
+def _endless():
+    return _mini(16, timeout=6, endless=True)
+
+
+def test_refresh_in_order_rebuilds_the_resampled_entries(torch_cuda):
+    torch = torch_cuda
+    env = _endless()
+    fields = env.goal_field(follow_refresh=True)
+    assert fields.field.shape == (64, 183, 183) and fields.clearance_d2 == 151 and len(env._goal_followers) == 1
+    first, _ = _scratch_build(torch, env, 151)
+    assert _same(fields.field, first)
+    before, maps_before = fields.field.clone(), env.costmap_tensor.clone()
+    _drive(env, np.random.RandomState(3), 13)
+    done = env.refresh().clone()
+    torch.cuda.synchronize()
+    assert int(done[0]) >= 16, done.tolist()
+    want, want_info = _scratch_build(torch, env, 151)
+    assert _same(fields.field, want) and _same(fields.info, want_info)
+    assert (fields.info[:, 1] == 0).all()
+    changed = (env.costmap_tensor != maps_before).reshape(64, -1).any(dim=1).cpu().numpy()
+    assert changed.sum() >= 16
+    differs = [e for e in np.nonzero(changed)[0] if not _same(fields.field[e], before[e])]
+    assert differs, "no re-sampled entry's field differs from the one before"
+    assert all(_same(fields.field[e], before[e]) for e in np.nonzero(~changed)[0])
+    for entry in np.nonzero(changed)[0][[0, -1]]:
+        _equal_to_dijkstra(torch, env, fields.field, int(entry), 151)
+
+
+def test_refresh_overlapped_keeps_the_fields_of_the_entries_in_use(torch_cuda):
+    torch = torch_cuda
+    from bc_gym_planning_env_amd.goal_field import GoalField
+    env = _endless()
+    fields = env.goal_field(follow_refresh=True)
+    rng = np.random.RandomState(5)
+    resampled = 0
+    for rnd in range(6):
+        _drive(env, rng, 20)
+        done = env.refresh(overlap=True)
+        torch.cuda.synchronize()
+        if done is not None:
+            resampled += int(done[0])
+        want, _ = _scratch_build(torch, env, 151)
+        on = env.geom_of_env.to(torch.int64)
+        assert _same(_i16(fields.field)[on], _i16(want)[on]), rnd
+        mine = fields.sample(want=("cell_value", "carrot"))
+        ref = GoalField(env, want, 151).sample(want=("cell_value", "carrot"))
+        torch.cuda.synchronize()
+        assert all(_same(a, b) for a, b in zip(mine, ref)), rnd
+    assert resampled >= 5 * 16
+    env.finish_refresh()
+    torch.cuda.synchronize()
+    want, want_info = _scratch_build(torch, env, 151)
+    assert _same(fields.field, want) and _same(fields.info, want_info) and (fields.info[:, 1] == 0).all()
+
+
+def test_two_fields_follow_and_a_dropped_one_is_forgotten(torch_cuda):
+    torch = torch_cuda
+    env = _endless()
+    wide, tight = env.goal_field(follow_refresh=True), env.goal_field(clearance=0.0, follow_refresh=True)
+    assert (wide.clearance_d2, tight.clearance_d2) == (151, 0) and len(env._goal_followers) == 2
+    rng = np.random.RandomState(9)
+    _drive(env, rng, 13)
+    assert int(env.refresh()[0]) >= 16
+    for f in (wide, tight):
+        want, want_info = _scratch_build(torch, env, f.clearance_d2)
+        assert _same(f.field, want) and _same(f.info, want_info), f.clearance_d2
+    assert not _same(wide.field, tight.field)
+    del wide, f
+    gc.collect()
+    assert sum(ref() is not None for ref in env._goal_followers) == 1
+    _drive(env, rng, 13)
+    assert int(env.refresh()[0]) >= 16
+    assert len(env._goal_followers) == 1 and env._goal_followers[0]() is tight
+    want, _ = _scratch_build(torch, env, 0)
+    assert _same(tight.field, want)
+
+
+def test_consumers_follow_the_refreshed_fields(torch_cuda):
+    torch = torch_cuda
+    from bc_gym_planning_env_amd import BatchedGoalField, MPPIPlanner
+    from bc_gym_planning_env_amd.goal_field import GoalField
+    env = _endless()
+    wrap = BatchedGoalField(env, carrot_cells=6, max_dist=4.0, follow_refresh=True)
+    fields = wrap.fields
+    assert len(env._goal_followers) == 1
+    rng = np.random.RandomState(2)
+    _drive(env, rng, 13)
+    assert int(env.refresh()[0]) >= 16
+    want, _ = _scratch_build(torch, env, 151)
+    reference = GoalField(env, want, 151)
+    # the observation
+    obs = wrap.observation()
+    assert _same(obs["goal_field"][..., 0], fields.sample(carrot_cells=6, max_dist=4.0))
+    assert _same(obs["goal_field"][..., 0], reference.sample(carrot_cells=6, max_dist=4.0))
+    assert (obs["goal_field"][:, 0, 0] < 4.0).any()
+    # the terminal cost inside the MPPI launch: the reference field read at the look-ahead's final poses, teacher-forced
+    n, k, h, it = env.n_envs, 16, 8, 2
+    sigma = (0.2, 0.8)
+    res = env.mppi(FR.random_mean(env, rng, n, h), sigma, it, k, 0.4, 2.0, seed=11, want=("eps", "iter_mean", "iter_value"),
+                   goal_field=fields, terminal_weight=4.0)
+    low, high = FR.box(env)
+    row_env = torch.arange(n, dtype=torch.int32, device="cuda").repeat_interleave(k)
+    for j in range(it):
+        u = MR.candidates(res.iter_mean[j].cpu().numpy(), sigma, res.eps[j].cpu().numpy(), low, high)
+        la = env.lookahead(torch.from_numpy(MR.as_lookahead_actions(u)).cuda(), want=("final_pose",))
+        _out3, cell = reference.sample(la.final_pose.reshape(n * k, 3), row_env=row_env, carrot_cells=1, want=("cell_value",))
+        assert _same(cell.reshape(n, k), res.iter_value[j]), j
+    assert bool((res.iter_value != GR.NONE).any())
+    # a planner over a refresh
+    planner = MPPIPlanner(env, 8, 16, 2, sigma, 0.4, 2.0, seed=3, goal_field=fields, terminal_weight=4.0)
+    for tick in range(20):
+        _o, _r, done, _i = env.step(planner.act())
+        planner.reset_plans(done)
+        assert int(env.err.abs().sum()) == 0, tick
+        if tick == 12:
+            assert int(env.refresh()[0]) >= 16
+    env.check_errors()
+    want, _ = _scratch_build(torch, env, 151)
+    assert _same(fields.field, want)
+
+
+# ---- 9. refusals -------------------------------------------------------------------------------------------------------------
+def test_refusals(torch_cuda):
+    torch = torch_cuda
+    from bc_gym_planning_env_amd import BatchedPlanEnv, CostMap2D, EnvParams
+    env = _endless()
+    L = env._lib
+    with pytest.raises(RuntimeError, match="follow_refresh"):
+        env.goal_field()
+    with pytest.raises(ValueError, match="seeds"):
+        env.goal_field(seeds="path", follow_refresh=True)
+    with pytest.raises(ValueError):
+        env.goal_field(seeds="start", follow_refresh=True)
+    field, info = _sentinels(torch, 64, 183, 183)
+    # no refresh pending
+    assert L.bcp_refresh_goal_fields(env._h, 151, 0, field.data_ptr(), info.data_ptr(), None) == E_STATE
+    assert L.bcp_last_error().startswith(b"bcp_refresh_goal_fields: ") and b"pending" in L.bcp_last_error()
+    assert L.bcp_refresh_goal_fields(env._h, 151, 0, None, None, None) == E_INVALID
+    assert L.bcp_refresh_goal_fields(None, 151, 0, field.data_ptr(), None, None) == E_INVALID
+    assert L.bcp_refresh_goal_fields(env._h, -1, 0, field.data_ptr(), None, None) == E_INVALID
+    assert L.bcp_refresh_goal_fields(env._h, 151, -1, field.data_ptr(), None, None) == E_INVALID
+    # every BCP_E_INVALID of bcp_goal_field_bound
+    listed = torch.zeros(64, dtype=torch.int32, device="cuda")
+    count = torch.ones(1, dtype=torch.int32, device="cuda")
+    assert _bound(env, field, info, 151, n_list=0) == 0 and _bound(env, field, None, 16129, listed, count, 64, passes=3) == 0
+    assert L.bcp_goal_field_bound(None, None, None, 64, 151, 0, field.data_ptr(), None, None) == E_INVALID
+    assert _bound(env, None, info, 151, n_list=64) == E_INVALID and b"field" in L.bcp_last_error()
+    assert _bound(env, field, info, 151, n_list=-1) == E_INVALID and b"n_list" in L.bcp_last_error()
+    assert _bound(env, field, info, 151, n_list=65) == E_INVALID
+    assert _bound(env, field, info, 151, None, count, 64) == E_INVALID and b"count" in L.bcp_last_error()
+    for bad in (-1, 16130):
+        assert _bound(env, field, info, bad) == E_INVALID and b"clearance_d2" in L.bcp_last_error()
+    assert _bound(env, field, info, 151, passes=-1) == E_INVALID and b"max_passes" in L.bcp_last_error()
+    assert L.bcp_last_error().startswith(b"bcp_goal_field_bound: ")
+    torch.cuda.synchronize()
+    assert _all(field[1:], SENTINEL)           # (the one call that ran listed entry 0 alone)
+    # a shared map: BCP_E_STATE, and the message points to bcp_goal_field
+    data = np.zeros((30, 40), dtype=np.uint8)
+    path = np.array([[0.2, 0.2, 0.0], [1.0, 1.0, 0.0]])
+    shared = BatchedPlanEnv(CostMap2D(data, 0.05, np.zeros(2)), path, EnvParams(resolution=0.05, refine_path=False), n_envs=3)
+    out, _ = _sentinels(torch, 3, 30, 40)
+    assert _bound(shared, out, None, 4) == E_STATE
+    assert L.bcp_last_error().startswith(b"bcp_goal_field_bound: ") and b"bcp_goal_field serves" in L.bcp_last_error()
+    with pytest.raises(RuntimeError):
+        shared.goal_field(follow_refresh=True)
+    # nothing bound yet
+    from bc_gym_planning_env_amd.ops import NativeOps
+    bare = NativeOps()
+    assert _bound(bare, out, None, 4, n_list=1) == E_STATE and b"bound first" in L.bcp_last_error()
+    torch.cuda.synchronize()
+    assert _all(out, SENTINEL)
+
+
+# ---- 10. capture ------------------------------------------------------------------------------------------------------------
+def test_captured_call_replays_the_same_bytes(torch_cuda):
+    torch = torch_cuda
+    from bc_gym_planning_env_amd import _lib
+    env = _mini(16, timeout=12)
+    want = env.goal_field()
+    field, info = _sentinels(torch, 16, 183, 183)
+    listed = torch.tensor([3, 9, 14, 0], dtype=torch.int32, device="cuda")
+    count = torch.full((1,), 3, dtype=torch.int32, device="cuda")
+    stream = torch.cuda.Stream()
+    stream.wait_stream(torch.cuda.current_stream())
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.stream(stream):
+        s = stream.cuda_stream
+        _lib.check(_bound(env, field, info, 151, listed, count, 4, stream=s))       # one ordinary call
+        torch.cuda.synchronize()
+        with torch.cuda.graph(graph, stream=stream):
+            _lib.check(_bound(env, field, info, 151, listed, count, 4, stream=s))
+    torch.cuda.synchronize()
+    for _ in range(2):
+        field.copy_(torch.from_numpy(np.full((16, 183, 183), SENTINEL, dtype=np.uint16)).cuda())
+        info.fill_(SENTINEL_I)
+        graph.replay()
+        torch.cuda.synchronize()
+        for e in range(16):
+            if e in (3, 9, 14):
+                assert _same(field[e], want.field[e]) and _same(info[e], want.info[e]), e
+            else:
+                assert _all(field[e], SENTINEL) and _all(info[e], SENTINEL_I), e
+    # the count is read on the device when the graph runs
+    count.fill_(4)
+    graph.replay()
+    torch.cuda.synchronize()
+    assert _same(field[0], want.field[0])
