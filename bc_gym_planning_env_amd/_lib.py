@@ -113,6 +113,17 @@ class BcpMppiTerminal(C.Structure):
     ]
 
 
+class BcpMppiWidths(C.Structure):
+    """bcp_mppi_widths: the widths of bcp_mppi_adapt"""
+    _fields_ = [
+        ("sigma", C.c_void_p), ("sigma_min", C.c_double * 2), ("sigma_max", C.c_double * 2), ("rate", C.c_double),
+        ("iter_sigma", C.c_void_p),
+    ]
+
+
+BcpMppiAdapt = BcpMppiWidths   # (the argument of bcp_mppi_adapt, by the function's name)
+
+
 # every symbol include/bcplan.h declares: (restype, argtypes)
 _H = C.c_void_p
 SYMBOLS = {
@@ -136,6 +147,8 @@ SYMBOLS = {
     "bcp_mppi": (C.c_int, [_H, C.POINTER(BcpMppiParams), C.POINTER(BcpMppiIO), C.c_uint32, C.c_void_p]),
     "bcp_mppi_field": (C.c_int, [_H, C.POINTER(BcpMppiParams), C.POINTER(BcpMppiIO), C.POINTER(BcpMppiTerminal), C.c_uint32,
                                  C.c_void_p]),
+    "bcp_mppi_adapt": (C.c_int, [_H, C.POINTER(BcpMppiParams), C.POINTER(BcpMppiIO), C.POINTER(BcpMppiWidths),
+                                 C.POINTER(BcpMppiTerminal), C.c_uint32, C.c_void_p]),
     "bcp_expired_waits": (C.c_int, [_H, C.POINTER(C.c_int64), C.c_void_p]),
     "bcp_parked_poses": (C.c_int, [_H, C.POINTER(C.c_int64), C.c_void_p]),
     "bcp_side_stream": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_void_p)]),

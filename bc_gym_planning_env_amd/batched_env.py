@@ -614,7 +614,7 @@ class BatchedPlanEnv(Handle):
         return Lookahead(h, k, **out)
 
     def mppi(self, mean, sigma, iterations, n_candidates, lam, collision_penalty, seed=0, draw_index=0, mask=None, eps=None,
-             want=(), action_dtype=None, goal_field=None, terminal_weight=0.0):
+             want=(), action_dtype=None, goal_field=None, terminal_weight=0.0, adapt=None):
         """Refine one plan per env by sampling around it (bcp_mppi, one kernel launch, nothing of the env changes): for each
         of `iterations` rounds, n_candidates plans u = clip(mean + sigma * eps, action box) -- candidate 0 is the mean itself
         -- are rolled out with the noise-free forward model as lookahead() rolls them out, scored ret - collision_penalty *
@@ -630,8 +630,14 @@ class BatchedPlanEnv(Handle):
         the distance to go from its final pose through free space, read from the field inside the same launch
         (bcp_mppi_field); a pose without a route counts as GOAL_FAR cells.  want then also takes "iter_value" (int32
         [I, N, K], the field value read, GOAL_NONE = none) and "iter_score" (float64 [I, N, K], the scores as weighted).
-        Without a field the call is bcp_mppi as ever.  Returns an Mppi; buffers are cached per (H, K, I).  Delays > 0 are
-        refused."""
+        Without a field the call is bcp_mppi as ever.
+        adapt: None, or a dict(sigma=, rate=, sigma_min=, sigma_max=) -- the sampling widths then follow the weights
+        (bcp_mppi_adapt, the same launch).  sigma: [N, H, 2], a width per env, step and component in place of the two of
+        `sigma` (which is still checked); a contiguous float64 tensor on the env's device is refined IN PLACE, as `mean` is.
+        Every iteration moves a width by `rate` (in [0, 1]) of the way to the weighted standard deviation of its commands
+        about the new mean, inside [sigma_min, sigma_max] (two values each).  want then also takes "iter_sigma" (float64
+        [I, N, H, 2], the widths going into each iteration), and the result carries `sigma`.
+        Returns an Mppi; buffers are cached per (H, K, I).  Delays > 0 are refused."""
         n = self.n_envs
         mean = self._device_tensor(mean, torch.float64)   # (a contiguous float64 tensor on the device: itself)
         if mean.dim() != 3 or mean.shape[0] != n or mean.shape[2] != 2:
@@ -645,6 +651,15 @@ class BatchedPlanEnv(Handle):
             raise ValueError("mppi: iter_value / iter_score / terminal_weight need a goal_field")
         if goal_field is not None and goal_field.owner is not self:
             raise ValueError("mppi: goal_field belongs to another env")
+        if adapt is None and "iter_sigma" in want:
+            raise ValueError("mppi: iter_sigma needs adapt")
+        widths = None
+        if adapt is not None:
+            if set(adapt) != {"sigma", "rate", "sigma_min", "sigma_max"}:
+                raise ValueError("mppi: adapt takes exactly sigma, rate, sigma_min and sigma_max, got %s" % sorted(adapt))
+            widths = self._device_tensor(adapt["sigma"], torch.float64)   # (as for mean: itself where it can be)
+            if tuple(widths.shape) != tuple(mean.shape):
+                raise ValueError("adapt['sigma'] must have shape %s, got %s" % (tuple(mean.shape), tuple(widths.shape)))
         action_dtype = torch.float64 if action_dtype is None else action_dtype
         if action_dtype not in (torch.float32, torch.float64):
             raise ValueError("action_dtype must be torch.float32 or torch.float64")
@@ -677,23 +692,34 @@ class BatchedPlanEnv(Handle):
         shapes = {"action": ((n, 2), action_dtype), "eps": ((it, n, k, h, 2), torch.float32),
                   "iter_mean": ((it, n, h, 2), torch.float64), "iter_ret": ((it, n, k), torch.float64),
                   "iter_reason": ((it, n, k), torch.uint8), "err": ((n,), torch.int32),
-                  "iter_value": ((it, n, k), torch.int32), "iter_score": ((it, n, k), torch.float64)}
+                  "iter_value": ((it, n, k), torch.int32), "iter_score": ((it, n, k), torch.float64),
+                  "iter_sigma": ((it, n, h, 2), torch.float64)}
         out = self._cached_outputs(self._mppi_buffers, (h, k, it), shapes,
                                    ["action"] + [name for name in Mppi.FIELDS if name in want])
-        term = _lib.BcpMppiTerminal()
+        term, ad = _lib.BcpMppiTerminal(), _lib.BcpMppiWidths()
         for name, t in out.items():
-            setattr(term if name in Mppi.TERMINAL_FIELDS else io, "eps_out" if name == "eps" else name, t.data_ptr())
+            owner = term if name in Mppi.TERMINAL_FIELDS else ad if name == "iter_sigma" else io
+            setattr(owner, "eps_out" if name == "eps" else name, t.data_ptr())
         flags = _lib.STEP_ACTIONS_F32 if action_dtype == torch.float32 else 0
-        if goal_field is None:
-            _lib.check(self._lib.bcp_mppi(self._h, C.byref(p), C.byref(io), flags, self._stream()))
-        else:
+        if goal_field is not None:
             f = goal_field.field
             term.field, term.n_fields, term.rows, term.cols = f.data_ptr(), int(f.shape[0]), int(f.shape[1]), int(f.shape[2])
             term.weight = float(terminal_weight)
             keep.append(f)
+        if adapt is not None:
+            ad.sigma, ad.rate = widths.data_ptr(), float(adapt["rate"])
+            lo, hi = (np.asarray(adapt[name], dtype=np.float64).reshape(2) for name in ("sigma_min", "sigma_max"))
+            for d in range(2):
+                ad.sigma_min[d], ad.sigma_max[d] = lo[d], hi[d]
+            keep.append(widths)
+            _lib.check(self._lib.bcp_mppi_adapt(self._h, C.byref(p), C.byref(io), C.byref(ad),
+                                                None if goal_field is None else C.byref(term), flags, self._stream()))
+        elif goal_field is None:
+            _lib.check(self._lib.bcp_mppi(self._h, C.byref(p), C.byref(io), flags, self._stream()))
+        else:
             _lib.check(self._lib.bcp_mppi_field(self._h, C.byref(p), C.byref(io), C.byref(term), flags, self._stream()))
         self._alive["mppi"] = tuple(keep)   # alive until the stream has consumed them
-        return Mppi(h, k, it, mean, **out)
+        return Mppi(h, k, it, mean, sigma=widths, **out)
 
     def _beam_table(self, beam_angles):
         """The device table [B, 2] of (cos, sin) of the beam angles (beam_table_cached)."""

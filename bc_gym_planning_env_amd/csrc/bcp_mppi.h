@@ -5,10 +5,14 @@
 // Nothing of the handle is written; the only global stores are the caller's outputs (bcp_mppi_io).
 // bcp_mppi_field() is the same launch with one read more per candidate: the goal field (bcp_goal_field) at the pose the
 // candidate ended on, taken off its score as a distance to go (mppi_kernel<.., FIELD>; the cell rule is bcp_goal_cell.h's).
+// bcp_mppi_adapt() is the same launch again with a width per (env, step, component) in the caller's `sigma` array in place
+// of the two of bcp_mppi_params, each moved towards the weighted spread of its commands after every iteration
+// (mppi_kernel<.., ADAPT>; the clamp and the move are bcp_mppi_widths.h's).
 #pragma once
 
 #include "bcp_goal_cell.h"
 #include "bcp_lookahead.h"
+#include "bcp_mppi_widths.h"
 
 // Launch arguments: the handle's parameter block, the caller's pointers and bcp_mppi_params by value -- nothing that the
 // library changes from call to call, so a captured call replays (fresh perturbations come from *draw_index).
@@ -46,15 +50,32 @@ struct MppiTerminal {
     int32_t rows, cols, shared;
 };
 
-// The kernel's argument: MppiArgs as it is, and behind it the terminal part for the FIELD kernels only -- the plain ones
-// take what they always took.
-template <bool FIELD> struct MppiKernelArgs;
-template <> struct MppiKernelArgs<false> {
+// What bcp_mppi_adapt adds to a launch: the widths, their clamps and the rate.
+struct MppiWidths {
+    double* sigma;               // [N][H][2], in / out
+    double* iter_sigma;          // nullptr or [I][N][H][2]
+    double lo[2], hi[2];         // sigma_min, sigma_max
+    double rate;
+};
+
+// The kernel's argument: MppiArgs as it is, and behind it the terminal part for the FIELD kernels and the widths for the
+// ADAPT kernels only -- the plain ones take what they always took.
+template <bool FIELD, bool ADAPT> struct MppiKernelArgs;
+template <> struct MppiKernelArgs<false, false> {
     MppiArgs m;
 };
-template <> struct MppiKernelArgs<true> {
+template <> struct MppiKernelArgs<true, false> {
     MppiArgs m;
     MppiTerminal t;
+};
+template <> struct MppiKernelArgs<false, true> {
+    MppiArgs m;
+    MppiWidths w;
+};
+template <> struct MppiKernelArgs<true, true> {
+    MppiArgs m;
+    MppiTerminal t;
+    MppiWidths w;
 };
 
 struct MppiFieldGet {
@@ -105,6 +126,28 @@ __device__ __forceinline__ double mppi_command(double mean, double sigma, float 
     return u > high ? high : u;
 }
 
+// The width of component d at element `row` = env * H + t of the caller's array, clamped as it is read (ADAPT).
+__device__ __forceinline__ double mppi_width(const MppiWidths& w, int64_t row, int d)
+{
+    return mppi_clamp_width(as_global(w.sigma)[row * 2 + d], w.lo[d], w.hi[d]);
+}
+
+// The two perturbations of candidate k at step t of iteration j (c = (j * N + env) * K + k): read from eps_in or drawn;
+// candidate 0 has none.  What the update's second walk (ADAPT) makes again.
+__device__ __forceinline__ void mppi_eps(const MppiArgs& a, int64_t env, uint64_t draw, int j, int t, int k, float& e0, float& e1)
+{
+    const int H = a.p.horizon;
+    e0 = e1 = 0.0f;
+    if (k == 0) return;
+    if (a.eps_in) {
+        const int64_t c = ((int64_t)j * a.n + env) * a.p.n_candidates + k;
+        e0 = as_global(a.eps_in)[(c * H + t) * 2 + 0];
+        e1 = as_global(a.eps_in)[(c * H + t) * 2 + 1];
+    } else {
+        mppi_draw(a.p.seed, (uint64_t)env, draw, (uint32_t)j * (uint32_t)H + (uint32_t)t, k, e0, e1);
+    }
+}
+
 // One wavefront per workgroup (collides_wave is wave-wide and owns the dynamic LDS up to score_word).  With K >= 64 the
 // workgroup is ONE env: its K / 64 chunks of candidates are rolled out one after another by the same lanes (lane l holds
 // k = chunk * 64 + l), so the env's state is loaded once and everything the update needs stays in the wave.  With K < 64
@@ -121,9 +164,18 @@ __device__ __forceinline__ double mppi_command(double mean, double sigma, float 
 // FIELD (bcp_mppi_field): after its last trip a live lane reads the goal field at the pose it ended on -- the rolled-back
 // pose where it collided, bcp_lookahead's final_pose -- and its score loses weight * metres to go, a pose without a route
 // counting as kGoalFar cells.  Nothing else differs: iter_ret and iter_reason stay the pure return and reason.
+// ADAPT (bcp_mppi_adapt): the widths live in the caller's `sigma` array as the mean lives in `mean` -- row t is one broadcast
+// load per trip, clamped as it is read (a row the kernel wrote is inside the clamps already, so only what the caller passed
+// in changes under it).  The variance of row t needs the new mean of row t, so the update walks the lane's chunks a second
+// time for that row: the commands of every chunk but the last are made again from their counters (or read again from
+// eps_in), the last chunk's are still in registers -- the same bits either way, mppi_command is a function of its arguments.
+// The same butterflies reduce the two sums, the lane with kl == 0 replaces the row in place, and the barrier that ends the
+// iteration orders it like the mean's.  No LDS beyond the scores, no atomics.  (The second walk fetches through mppi_eps; the
+// roll-out and the first walk keep the text they had, under which the kernels without ADAPT compile to the instructions
+// they compiled to before there was an ADAPT.)
 // Loops are bounded by I, H and K / 64; no atomics, no waits on other workgroups.
-template <bool PLAIN, bool FIELD>
-__global__ void __launch_bounds__(kBlock) mppi_kernel(const MppiKernelArgs<FIELD> ka)
+template <bool PLAIN, bool FIELD, bool ADAPT>
+__global__ void __launch_bounds__(kBlock) mppi_kernel(const MppiKernelArgs<FIELD, ADAPT> ka)
 {
     const MppiArgs& a = ka.m;
     typedef __attribute__((address_space(3))) double* LdsScore;
@@ -157,6 +209,11 @@ __global__ void __launch_bounds__(kBlock) mppi_kernel(const MppiKernelArgs<FIELD
     for (int j = 0; j < a.p.iterations; ++j) {
         if (a.iter_mean && live)
             for (int e = kl; e < 2 * H; e += group) as_global(a.iter_mean)[((int64_t)j * a.n + i) * H * 2 + e] = mean[e];
+        if constexpr (ADAPT) {
+            if (ka.w.iter_sigma && live)
+                for (int e = kl; e < 2 * H; e += group)
+                    as_global(ka.w.iter_sigma)[((int64_t)j * a.n + i) * H * 2 + e] = mppi_width(ka.w, i * H + (e >> 1), e & 1);
+        }
         // ---- roll-outs: plan_trip on a copy of the state, one chunk of candidates at a time
         double best = -INFINITY;
         for (int ch = 0; ch < chunks; ++ch) {
@@ -186,8 +243,13 @@ __global__ void __launch_bounds__(kBlock) mppi_kernel(const MppiKernelArgs<FIELD
                     break;
                 }
                 const bool active = !finished;
-                const double cmd0 = mppi_command(mean[2 * t + 0], a.p.sigma[0], e0, a.p.low[0], a.p.high[0]);
-                const double cmd1 = mppi_command(mean[2 * t + 1], a.p.sigma[1], e1, a.p.low[1], a.p.high[1]);
+                double s0 = a.p.sigma[0], s1 = a.p.sigma[1];
+                if constexpr (ADAPT) {
+                    s0 = mppi_width(ka.w, i * H + t, 0);
+                    s1 = mppi_width(ka.w, i * H + t, 1);
+                }
+                const double cmd0 = mppi_command(mean[2 * t + 0], s0, e0, a.p.low[0], a.p.high[0]);
+                const double cmd1 = mppi_command(mean[2 * t + 1], s1, e1, a.p.low[1], a.p.high[1]);
                 plan_trip<PLAIN>(S, L, g, pts, m, cmd0, cmd1, zero3, false, active, st, ret, errs, reason, finished);
             }
             if (live) {
@@ -223,7 +285,13 @@ __global__ void __launch_bounds__(kBlock) mppi_kernel(const MppiKernelArgs<FIELD
         // ---- update: mean[t] = sum_k w_k u_k[t], the commands made again from their counters
         for (int t = 0; t < H; ++t) {
             const double m0 = mean[2 * t + 0], m1 = mean[2 * t + 1];
+            double s0 = a.p.sigma[0], s1 = a.p.sigma[1];
+            if constexpr (ADAPT) {
+                s0 = mppi_width(ka.w, i * H + t, 0);
+                s1 = mppi_width(ka.w, i * H + t, 1);
+            }
             double acc0 = 0.0, acc1 = 0.0;
+            double u0 = 0.0, u1 = 0.0;   // (after the loop: the last chunk's commands)
             for (int ch = 0; ch < chunks; ++ch) {
                 const int k = ch * kBlock + kl;
                 float e0 = 0.0f, e1 = 0.0f;
@@ -237,8 +305,10 @@ __global__ void __launch_bounds__(kBlock) mppi_kernel(const MppiKernelArgs<FIELD
                     mppi_draw(a.p.seed, (uint64_t)i, draw, (uint32_t)j * (uint32_t)H + (uint32_t)t, k, e0, e1);
                 }
                 const double w = score[ch * kBlock];
-                acc0 += w * mppi_command(m0, a.p.sigma[0], e0, a.p.low[0], a.p.high[0]);
-                acc1 += w * mppi_command(m1, a.p.sigma[1], e1, a.p.low[1], a.p.high[1]);
+                u0 = mppi_command(m0, s0, e0, a.p.low[0], a.p.high[0]);
+                u1 = mppi_command(m1, s1, e1, a.p.low[1], a.p.high[1]);
+                acc0 += w * u0;
+                acc1 += w * u1;
             }
             for (int off = group >> 1; off > 0; off >>= 1) {
                 acc0 += __shfl_xor(acc0, off);
@@ -247,6 +317,33 @@ __global__ void __launch_bounds__(kBlock) mppi_kernel(const MppiKernelArgs<FIELD
             if (live && kl == 0) {
                 mean[2 * t + 0] = acc0;
                 mean[2 * t + 1] = acc1;
+            }
+            if constexpr (ADAPT) {
+                // ---- widths: sd = sqrt(sum_k w_k (u_k - m')^2) about the row's new mean, then the move towards it.  The
+                // last chunk's commands are still in u0, u1; the others are made again
+                double v0 = 0.0, v1 = 0.0;
+                for (int ch = 0; ch < chunks; ++ch) {
+                    double x0 = u0, x1 = u1;
+                    if (ch != chunks - 1) {
+                        float e0, e1;
+                        mppi_eps(a, i, draw, j, t, ch * kBlock + kl, e0, e1);
+                        x0 = mppi_command(m0, s0, e0, a.p.low[0], a.p.high[0]);
+                        x1 = mppi_command(m1, s1, e1, a.p.low[1], a.p.high[1]);
+                    }
+                    const double w = score[ch * kBlock];
+                    const double d0 = x0 - acc0, d1 = x1 - acc1;
+                    v0 += w * (d0 * d0);
+                    v1 += w * (d1 * d1);
+                }
+                for (int off = group >> 1; off > 0; off >>= 1) {
+                    v0 += __shfl_xor(v0, off);
+                    v1 += __shfl_xor(v1, off);
+                }
+                if (live && kl == 0) {
+                    const GlobalPtr<double> sg = as_global(ka.w.sigma) + (i * H + t) * 2;
+                    sg[0] = mppi_next_width(s0, sqrt(v0), ka.w.rate, ka.w.lo[0], ka.w.hi[0]);
+                    sg[1] = mppi_next_width(s1, sqrt(v1), ka.w.rate, ka.w.lo[1], ka.w.hi[1]);
+                }
             }
             if (t == 0) {
                 first0 = acc0;

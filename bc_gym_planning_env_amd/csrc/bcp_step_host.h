@@ -436,11 +436,11 @@ extern "C" int bcp_lookahead(bcp_handle* h, const bcp_lookahead_io* io, uint32_t
 }
 
 // Sampling-based refinement of one plan per env (bcp_mppi.h): I iterations of sample, roll out, weight and update in one
-// launch.  Like bcp_lookahead it reads the handle and writes only the caller's arrays.  The one launcher of bcp_mppi and
-// bcp_mppi_field (`who`; term == nullptr: the kernels without the terminal read): the checks of what the two have in common
-// are written here, once.
+// launch.  Like bcp_lookahead it reads the handle and writes only the caller's arrays.  The one launcher of bcp_mppi,
+// bcp_mppi_field and bcp_mppi_adapt (`who`; term == nullptr: the kernels without the terminal read; ad == nullptr: the
+// kernels with the two widths of *p): the checks of what the three have in common are written here, once.
 static int launch_mppi(bcp_handle* h, const bcp_mppi_params* p, const bcp_mppi_io* io, const bcp_mppi_terminal* term,
-                       uint32_t flags, hipStream_t s, const char* who)
+                       const bcp_mppi_widths* ad, uint32_t flags, hipStream_t s, const char* who)
 {
     if (flags & ~(uint32_t)BCP_STEP_ACTIONS_F32) return fail(BCP_E_INVALID, "%s: undefined flag bits 0x%x", who, flags & ~(uint32_t)BCP_STEP_ACTIONS_F32);
     BCP_TRY(plan_ready(h, who, s));
@@ -465,7 +465,7 @@ static int launch_mppi(bcp_handle* h, const bcp_mppi_params* p, const bcp_mppi_i
     const int group = K < kBlock ? K : kBlock;
     const int64_t blocks = (h->n * group + kBlock - 1) / kBlock;
     if (blocks > 0x7FFFFFFF) return fail(BCP_E_INVALID, "%s: n_envs exceeds the largest grid", who);
-    MppiKernelArgs<true> ka;   // (its head is all the plain kernels take)
+    MppiKernelArgs<true, true> ka;   // (its head is all the plain kernels take)
     memset(&ka, 0, sizeof(ka));
     MppiArgs& a = ka.m;
     a.S = h->dev_static.get();
@@ -487,10 +487,25 @@ static int launch_mppi(bcp_handle* h, const bcp_mppi_params* p, const bcp_mppi_i
     a.score_word = (int32_t)(collision / sizeof(uint32_t));
     const size_t lds = collision + (size_t)(K / group) * kBlock * sizeof(double);
     const bool plain = hp.reward_provider == BCP_REWARD_CONTINUOUS;
+    if (ad) {   // (checked by bcp_mppi_adapt: mppi_adapt_check_args)
+        MppiWidths& w = ka.w;
+        w.sigma = ad->sigma;
+        w.iter_sigma = ad->iter_sigma;
+        for (int d = 0; d < 2; ++d) {
+            w.lo[d] = ad->sigma_min[d];
+            w.hi[d] = ad->sigma_max[d];
+        }
+        w.rate = ad->rate;
+    }
     // (the LDS can pass 64 KiB: a staged map of nearly that plus the scores)
     if (!term) {
-        const void* fn = plain ? (const void*)mppi_kernel<true, false> : (const void*)mppi_kernel<false, false>;
-        const MppiKernelArgs<false> plain_args = {ka.m};
+        if (ad) {
+            const void* fn = plain ? (const void*)mppi_kernel<true, false, true> : (const void*)mppi_kernel<false, false, true>;
+            const MppiKernelArgs<false, true> adapt_args = {ka.m, ka.w};
+            return launch_variant(h, fn, dim3((unsigned)blocks), dim3(kBlock), lds, s, adapt_args);
+        }
+        const void* fn = plain ? (const void*)mppi_kernel<true, false, false> : (const void*)mppi_kernel<false, false, false>;
+        const MppiKernelArgs<false, false> plain_args = {ka.m};
         return launch_variant(h, fn, dim3((unsigned)blocks), dim3(kBlock), lds, s, plain_args);
     }
     if (!(term->weight >= 0.0) || !std::isfinite(term->weight))
@@ -522,14 +537,19 @@ static int launch_mppi(bcp_handle* h, const bcp_mppi_params* p, const bcp_mppi_i
     t.rows = term->rows;
     t.cols = term->cols;
     t.shared = h->map.shared;
-    const void* fn = plain ? (const void*)mppi_kernel<true, true> : (const void*)mppi_kernel<false, true>;
-    return launch_variant(h, fn, dim3((unsigned)blocks), dim3(kBlock), lds, s, ka);
+    if (ad) {
+        const void* fn = plain ? (const void*)mppi_kernel<true, true, true> : (const void*)mppi_kernel<false, true, true>;
+        return launch_variant(h, fn, dim3((unsigned)blocks), dim3(kBlock), lds, s, ka);
+    }
+    const void* fn = plain ? (const void*)mppi_kernel<true, true, false> : (const void*)mppi_kernel<false, true, false>;
+    const MppiKernelArgs<true, false> field_args = {ka.m, ka.t};
+    return launch_variant(h, fn, dim3((unsigned)blocks), dim3(kBlock), lds, s, field_args);
 }
 
 extern "C" int bcp_mppi(bcp_handle* h, const bcp_mppi_params* p, const bcp_mppi_io* io, uint32_t flags, void* stream)
 {
     if (!h || !p || !io) return fail(BCP_E_INVALID, "bcp_mppi: null argument");
-    return launch_mppi(h, p, io, nullptr, flags, (hipStream_t)stream, "bcp_mppi");
+    return launch_mppi(h, p, io, nullptr, nullptr, flags, (hipStream_t)stream, "bcp_mppi");
 }
 
 // bcp_mppi with a goal field as the terminal cost of a candidate (bcp_mppi.h, FIELD): the same launch, one 2-byte read more
@@ -538,7 +558,29 @@ extern "C" int bcp_mppi_field(bcp_handle* h, const bcp_mppi_params* p, const bcp
                               uint32_t flags, void* stream)
 {
     if (!h || !p || !io || !term || !term->field) return fail(BCP_E_INVALID, "bcp_mppi_field: null argument");
-    return launch_mppi(h, p, io, term, flags, (hipStream_t)stream, "bcp_mppi_field");
+    return launch_mppi(h, p, io, term, nullptr, flags, (hipStream_t)stream, "bcp_mppi_field");
+}
+
+// bcp_mppi (or, with term, bcp_mppi_field) with a width per env, step and component that follows the weights (bcp_mppi.h,
+// ADAPT): the same launch, a second walk over the candidates of a row for its variance.  The checks of `ad` are
+// bcp_mppi_widths.h's, in its order; everything else is launch_mppi's.
+extern "C" int bcp_mppi_adapt(bcp_handle* h, const bcp_mppi_params* p, const bcp_mppi_io* io, const bcp_mppi_widths* ad,
+                              const bcp_mppi_terminal* term, uint32_t flags, void* stream)
+{
+    const char* who = "bcp_mppi_adapt";
+    if (!h || !p || !io) return fail(BCP_E_INVALID, "%s: null argument", who);
+    int d = 0;
+    switch (mppi_adapt_check_args(ad != nullptr, ad && ad->sigma, ad ? ad->rate : 0.0, ad ? ad->sigma_min : nullptr,
+                                  ad ? ad->sigma_max : nullptr, &d)) {
+    case kMppiAdaptOk: break;
+    case kMppiAdaptNull: return fail(BCP_E_INVALID, "%s: null argument (ad and ad->sigma are required)", who);
+    case kMppiAdaptRate: return fail(BCP_E_INVALID, "%s: rate must lie in [0, 1]", who);
+    case kMppiAdaptMin: return fail(BCP_E_INVALID, "%s: sigma_min[%d] must be finite and not negative", who, d);
+    case kMppiAdaptMax: return fail(BCP_E_INVALID, "%s: sigma_max[%d] must be finite and not negative", who, d);
+    default: return fail(BCP_E_INVALID, "%s: sigma_min[%d] > sigma_max[%d]", who, d, d);
+    }
+    if (term && !term->field) return fail(BCP_E_INVALID, "%s: null argument (term->field)", who);
+    return launch_mppi(h, p, io, term, ad, flags, (hipStream_t)stream, who);
 }
 
 extern "C" int bcp_expired_waits(bcp_handle* h, int64_t* count, void* stream)

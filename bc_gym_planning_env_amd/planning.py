@@ -39,15 +39,16 @@ class Mppi(object):
     [N, 2] = mean[:, 0], ready for step(); optional, None unless asked for: `eps` [I, N, K, H, 2] float32 (the
     perturbations used), `iter_mean` [I, N, H, 2] (the mean going into each iteration), `iter_ret` / `iter_reason`
     [I, N, K], `err` int32 [N]; with a goal field (bcp_mppi_field) also `iter_value` int32 [I, N, K], the field value read at
-    each candidate's final pose (GOAL_NONE = none), and `iter_score` float64 [I, N, K], the scores as weighted.  Everything
-    but `mean` is a cached buffer of the env for this (H, K, I)."""
+    each candidate's final pose (GOAL_NONE = none), and `iter_score` float64 [I, N, K], the scores as weighted; with
+    adapt (bcp_mppi_adapt) `sigma` [N, H, 2] float64, the refined widths, and optionally `iter_sigma` [I, N, H, 2], the widths
+    going into each iteration.  Everything but `mean` and `sigma` is a cached buffer of the env for this (H, K, I)."""
 
-    FIELDS = ("eps", "iter_mean", "iter_ret", "iter_reason", "err", "iter_value", "iter_score")
+    FIELDS = ("eps", "iter_mean", "iter_ret", "iter_reason", "err", "iter_sigma", "iter_value", "iter_score")
     TERMINAL_FIELDS = ("iter_value", "iter_score")   # need a goal field
 
-    def __init__(self, horizon, n_candidates, iterations, mean, action, **tensors):
+    def __init__(self, horizon, n_candidates, iterations, mean, action, sigma=None, **tensors):
         self.horizon, self.n_candidates, self.iterations = horizon, n_candidates, iterations
-        self.mean, self.action = mean, action
+        self.mean, self.action, self.sigma = mean, action, sigma
         for name in self.FIELDS:
             setattr(self, name, tensors.get(name))
 
@@ -135,12 +136,17 @@ class MPPIPlanner(object):
         terminal_weight * its final pose's distance to go through free space, inside the same launch (bcp_mppi_field) --
         what the H steps of the roll-out cannot see.  A final pose without a route counts as GOAL_FAR cells
     :param terminal_weight: reward per metre of that distance, finite and >= 0; 0 plans exactly as without a field
+    :param adapt_rate: None: every step of every plan is sampled with `sigma`, tick after tick.  A rate in [0, 1]: the planner
+        owns a width per env, step and component, `self.sigma` [N, H, 2], which every iteration moves by that share of the
+        way to the weighted spread of the commands (bcp_mppi_adapt, the same launch) and which shifts with the plan
+    :param sigma_min, sigma_max: the clamps of the widths, two values each; default sigma / 8 and 2 * sigma
+    :param sigma_recover: after the shift every width relaxes towards `sigma` by this share of the difference
 
     A new plan -- at the start, and for the envs named by reset_plans() -- holds the centre of the action box,
-    (low + high) / 2, at every step."""
+    (low + high) / 2, at every step, and with adapt_rate `sigma` as its widths."""
 
     def __init__(self, env, horizon, n_candidates, iterations, sigma, lam, collision_penalty, seed=0, goal_field=None,
-                 terminal_weight=0.0):
+                 terminal_weight=0.0, adapt_rate=None, sigma_min=None, sigma_max=None, sigma_recover=0.0):
         self.env = env
         self.goal_field, self.terminal_weight = goal_field, float(terminal_weight)
         base = env
@@ -153,6 +159,14 @@ class MPPIPlanner(object):
         centre = 0.5 * (np.asarray(space.low, np.float64) + np.asarray(space.high, np.float64))
         self.default = torch.from_numpy(centre).to(device)
         self.mean = self.default.expand(base.n_envs, self.horizon, 2).contiguous()
+        self.adapt_rate, self.sigma_recover = adapt_rate, float(sigma_recover)
+        if adapt_rate is not None:   # self.sigma becomes the widths [N, H, 2]; the two they start from stay in sigma0
+            width = np.asarray(sigma, np.float64).reshape(2)
+            self.sigma_min = tuple(width / 8 if sigma_min is None else np.asarray(sigma_min, np.float64).reshape(2))
+            self.sigma_max = tuple(2 * width if sigma_max is None else np.asarray(sigma_max, np.float64).reshape(2))
+            self.sigma0 = torch.from_numpy(width).to(device)
+            self._sigma_call = tuple(width)
+            self.sigma = self.sigma0.expand(base.n_envs, self.horizon, 2).contiguous()
         self.draw_index = 0
         self._fresh = True    # nothing to shift yet
         self.last = None      # the Mppi of the latest act()
@@ -163,15 +177,24 @@ class MPPIPlanner(object):
         mask = mask if isinstance(mask, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(mask))
         mask = mask.to(self.mean.device) != 0
         self.mean.copy_(torch.where(mask[:, None, None], self.default, self.mean))
+        if self.adapt_rate is not None:
+            self.sigma.copy_(torch.where(mask[:, None, None], self.sigma0, self.sigma))
 
     def act(self, observation=None):
         """actions [N, 2] (float64 device tensor) for env.step().  The observation is not needed (as for ShootingPlanner):
         the roll-outs start from the env's own state."""
         if not self._fresh:   # receding horizon: drop the step just taken, repeat the last row
             self.mean.copy_(torch.cat([self.mean[:, 1:], self.mean[:, -1:]], dim=1))
+            if self.adapt_rate is not None:   # the widths go with their steps; the new last step starts from sigma0
+                shifted = torch.cat([self.sigma[:, 1:], self.sigma0.expand(self.sigma.shape[0], 1, 2)], dim=1)
+                self.sigma.copy_(shifted + self.sigma_recover * (self.sigma0 - shifted))
         self._fresh = False
-        terminal = {} if self.goal_field is None else dict(goal_field=self.goal_field, terminal_weight=self.terminal_weight)
-        self.last = self.env.mppi(self.mean, self.sigma, self.iterations, self.n_candidates, self.lam, self.collision_penalty,
-                                  seed=self.seed, draw_index=self.draw_index, **terminal)
+        extra = {} if self.goal_field is None else dict(goal_field=self.goal_field, terminal_weight=self.terminal_weight)
+        sigma = self.sigma
+        if self.adapt_rate is not None:
+            sigma = self._sigma_call
+            extra["adapt"] = dict(sigma=self.sigma, rate=self.adapt_rate, sigma_min=self.sigma_min, sigma_max=self.sigma_max)
+        self.last = self.env.mppi(self.mean, sigma, self.iterations, self.n_candidates, self.lam, self.collision_penalty,
+                                  seed=self.seed, draw_index=self.draw_index, **extra)
         self.draw_index += 1
         return self.last.action

@@ -745,6 +745,41 @@ typedef struct bcp_mppi_terminal {
 int bcp_mppi_field(bcp_handle *h, const bcp_mppi_params *p, const bcp_mppi_io *io, const bcp_mppi_terminal *term,
                    uint32_t flags, void *stream);
 
+/* The widths of bcp_mppi_adapt.  Host struct of device pointers, caller-owned.  (Named for what it holds: a C tag may share
+ * its name with a function, a typedef name may not.) */
+typedef struct bcp_mppi_widths {
+    double *sigma;          /* [N][H][2] in / out: std of the perturbation per env, step and component */
+    double sigma_min[2];    /* finite, >= 0 */
+    double sigma_max[2];    /* finite, >= sigma_min */
+    double rate;            /* in [0, 1]: how far a width moves towards the weighted spread per iteration */
+    double *iter_sigma;     /* optional [I][N][H][2]: the widths going INTO iteration j (after the entry clamp) */
+} bcp_mppi_widths;
+
+/* bcp_mppi (term == NULL) or bcp_mppi_field (term given) with a sampling width per env, step and component that follows the
+ * weights, CEM-style: a plan the weights agree on is perturbed less the next time, one they spread over keeps its width.
+ * Everything bcp_mppi specifies holds -- the sampling stream, eps_in / eps_out, candidate 0, the roll-outs, iter_ret /
+ * iter_reason, the scores (with term exactly bcp_mppi_field's, iter_value / iter_score included), the weights and the mean
+ * update, one launch, nothing of the handle written, capture into a HIP graph with io->draw_index -- and two things differ.
+ * The width used.  Let clampd(s) = !(s >= sigma_min[d]) ? sigma_min[d] : (s > sigma_max[d] ? sigma_max[d] : s): a NaN goes
+ * to the minimum.  On entry sigma_0[i][t][d] = clampd(sigma[i][t][d]), and for iteration j
+ *     u = min(max(mean_j[i][t][d] + sigma_j[i][t][d] * (double)eps_j[i][k][t][d], low[d]), high[d])
+ * p->sigma is checked as bcp_mppi checks it and is otherwise not read.
+ * The width update.  With the weights w_k and the new mean row m' = mean_{j+1}[i][t][d], in float64, every difference,
+ * product, root and sum rounded on its own (the order of the sum over k unspecified, as for the mean):
+ *     v  = sum_k w_k * ((u_k - m') * (u_k - m'))
+ *     sd = sqrt(v)
+ *     sigma_{j+1}[i][t][d] = clampd(sigma_j + rate * (sd - sigma_j))
+ * After the last iteration `sigma` holds sigma_I.  Rows of envs with mask 0 are untouched, in sigma and iter_sigma as
+ * everywhere else.
+ * With rate == 0 and every sigma[i][t][d] == p->sigma[d] inside the clamps, every output that bcp_mppi has (bcp_mppi_field,
+ * when term is given) is the same bit for bit, and the bytes of sigma do not change.
+ * Refused with BCP_E_INVALID (messages prefixed "bcp_mppi_adapt: "), in this order: h, p or io NULL; ad or ad->sigma NULL;
+ * rate NaN or outside [0, 1]; per component d = 0, 1 a negative or non-finite sigma_min[d], the same of sigma_max[d],
+ * sigma_min[d] > sigma_max[d]; term given with term->field NULL; then everything bcp_mppi refuses and, with term,
+ * everything bcp_mppi_field refuses. */
+int bcp_mppi_adapt(bcp_handle *h, const bcp_mppi_params *p, const bcp_mppi_io *io, const bcp_mppi_widths *ad,
+                   const bcp_mppi_terminal *term /* NULL = no goal field */, uint32_t flags, void *stream);
+
 /* ---- costmap inflation ------------------------------------------------------------------------------------ */
 /* inflate_costmap (utilities/costmap_inflation.py:73-92) for n_maps maps in one call: the ROS inflation layer.  Per map
  * `data` [rows][cols] with valid shape (vr, vc) = (valid_rows[m], valid_cols[m]) clamped to [0, rows] x [0, cols], or the

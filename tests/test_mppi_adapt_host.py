@@ -1,0 +1,189 @@
+"""Host-side checks of the adaptive widths of the plan refinement (bcp_mppi_adapt): the C struct and its ctypes mirror, the
+width rule on hand-made tables (tests/mppi_adapt_ref.py, weights and sums in np.longdouble), the checks of the struct as a
+stand-alone program under AddressSanitizer and UBSan (csrc/bcp_mppi_widths.h, no HIP in it), and -- on the restatement and the
+CPU oracle alone -- that in the scenarios the GPU tests run the widths move without sitting on their clamps, and that a
+greedy rate does put them there."""
+import os
+import shutil
+import subprocess
+import tempfile
+
+import numpy as np
+import pytest
+
+import lookahead_ref as LR
+import mppi_adapt_ref as AR
+import mppi_ref as MR
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+WIDTH_FIELDS = ["sigma", "sigma_min", "sigma_max", "rate", "iter_sigma"]
+
+
+def test_widths_struct_matches_header_and_symbol_is_bound():
+    """sizeof / offsetof of bcp_mppi_widths as the C compiler lays it out from include/bcplan.h == the ctypes mirror; the
+    symbol is declared in the header, exported by the library and typed in _lib.py; the ABI version did not move"""
+    import ctypes as C
+    from bc_gym_planning_env_amd import _lib, build
+    assert [f[0] for f in _lib.BcpMppiWidths._fields_] == WIDTH_FIELDS and _lib.BcpMppiAdapt is _lib.BcpMppiWidths
+    src = ['#include <stddef.h>', '#include <stdio.h>', '#include "bcplan.h"',
+           'int main(void) {', '  /* the prototype of the header, type-checked and never called */',
+           '  size_t declared = sizeof(bcp_mppi_adapt((bcp_handle *)0, (const bcp_mppi_params *)0, (const bcp_mppi_io *)0,',
+           '                                          (const bcp_mppi_widths *)0, (const bcp_mppi_terminal *)0, 0u, (void *)0));',
+           '  printf("%zu", sizeof(bcp_mppi_widths));']
+    src += ['  printf(" %%zu", offsetof(bcp_mppi_widths, %s));' % f for f in WIDTH_FIELDS]
+    src += ['  printf(" %zu %d %d\\n", sizeof(((bcp_mppi_widths*)0)->sigma_min), BCP_ABI_VERSION, (int)declared);', '  return 0; }']
+    build.build()
+    with tempfile.TemporaryDirectory() as d:
+        c_file, exe = os.path.join(d, "probe.c"), os.path.join(d, "probe")
+        open(c_file, "w").write("\n".join(src))
+        subprocess.check_call([os.environ.get("CC", "gcc"), "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), c_file, "-o", exe])
+        got = [int(v) for v in subprocess.check_output([exe]).split()]
+    want = [C.sizeof(_lib.BcpMppiWidths)] + [getattr(_lib.BcpMppiWidths, f).offset for f in WIDTH_FIELDS]
+    assert got[:-3] == want and want == [56, 0, 8, 24, 40, 48]
+    assert got[-3:] == [16, _lib.ABI_VERSION, 4] and _lib.ABI_VERSION == 2
+    raw = C.CDLL(_lib.LIB_PATH)
+    assert hasattr(raw, "bcp_mppi_adapt") and "bcp_mppi_adapt" in _lib.SYMBOLS
+    args = _lib.load().bcp_mppi_adapt.argtypes
+    assert len(args) == 7 and args[1]._type_ is _lib.BcpMppiParams and args[2]._type_ is _lib.BcpMppiIO
+    assert args[3]._type_ is _lib.BcpMppiWidths and args[4]._type_ is _lib.BcpMppiTerminal and args[5] is C.c_uint32
+
+
+def test_python_surface_carries_the_names():
+    import inspect
+    from bc_gym_planning_env_amd import BatchedPlanEnv, MPPIPlanner, Mppi
+    assert "iter_sigma" in Mppi.FIELDS and "iter_sigma" not in Mppi.TERMINAL_FIELDS
+    assert inspect.signature(BatchedPlanEnv.mppi).parameters["adapt"].default is None
+    p = inspect.signature(MPPIPlanner.__init__).parameters
+    assert p["adapt_rate"].default is None and p["sigma_min"].default is None and p["sigma_max"].default is None
+    assert p["sigma_recover"].default == 0.0
+    m = Mppi(4, 8, 1, "mean", "action")
+    assert m.sigma is None and m.iter_sigma is None
+
+
+# ---------------------------------------------------------------------------------------------- the width rule
+LO, HI = np.array([0.02, 0.1]), np.array([0.5, 1.5])
+
+
+def _table(n, k, h, seed=0):
+    rng = np.random.RandomState(seed)
+    return rng.uniform(-1.0, 1.0, (n, k, h, 2)), rng.uniform(LO, HI, (n, h, 2))
+
+
+def test_one_hot_weights_shrink_a_width_by_the_rate():
+    """gaps of >= 20 000 lambda: one weight is 1 and the others exp(<= -20 000) = 0 even in np.longdouble (whose smallest
+    number is 1e-4951) -- sd = 0 exactly and sigma' = clampd(sigma (1 - rate))"""
+    u, sigma = _table(3, 8, 5)
+    score = np.array([[0.0, 1.0, 5.0, 2.0, 3.0, 1.5, 4.0, 0.5], [9.0, 1.0, 5.0, 2.0, 3.0, 1.5, 4.0, 0.5],
+                      [0.0, 1.0, 5.0, 2.0, 3.0, 1.5, 4.0, 6.0]])
+    for rate in (0.25, 0.5, 1.0):
+        mean, new, w = AR.update(u, score, 1.0 / 40000, sigma, rate, LO, HI)
+        assert (w.max(axis=1) == 1.0).all() and (w.sum(axis=1) == 1.0).all()
+        np.testing.assert_array_equal(mean, u[np.arange(3), [2, 0, 7]])
+        np.testing.assert_array_equal(AR.spread(u, w, mean), 0.0)
+        np.testing.assert_array_equal(new, AR.clampd(sigma + rate * (0.0 - sigma), LO, HI))
+        np.testing.assert_allclose(new, np.maximum(sigma * (1 - rate), LO), rtol=0, atol=1e-16)
+    assert (AR.update(u, score, 1.0 / 40000, sigma, 1.0, LO, HI)[1] == LO).all(), "rate 1 on a one-hot weight: the lower clamp"
+
+
+def test_equal_scores_give_the_population_standard_deviation():
+    u, sigma = _table(2, 16, 4, seed=1)
+    mean, new, w = AR.update(u, np.full((2, 16), 3.25), 0.1, sigma, 1.0, (0.0, 0.0), (10.0, 10.0))
+    assert (w == np.longdouble(1) / 16).all()
+    np.testing.assert_allclose(mean, u.mean(axis=1), rtol=0, atol=1e-15)
+    np.testing.assert_allclose(AR.spread(u, w, mean), u.std(axis=1), rtol=0, atol=1e-15)
+    np.testing.assert_allclose(new, u.std(axis=1), rtol=0, atol=1e-15)    # (rate 1, clamps out of reach)
+    half = AR.update(u, np.full((2, 16), 3.25), 0.1, sigma, 0.5, (0.0, 0.0), (10.0, 10.0))[1]
+    np.testing.assert_allclose(half, 0.5 * (sigma + u.std(axis=1)), rtol=0, atol=1e-15)
+    # about another mean the spread is the root of the mean square about THAT mean
+    other = mean + 0.125
+    np.testing.assert_allclose(AR.spread(u, w, other), np.sqrt(u.var(axis=1) + 0.125 ** 2), rtol=0, atol=1e-15)
+
+
+def test_rate_zero_leaves_the_widths_alone():
+    u, sigma = _table(4, 8, 6, seed=2)
+    score = np.random.RandomState(3).uniform(0, 3, (4, 8))
+    _, new, _ = AR.update(u, score, 0.3, sigma, 0.0, LO, HI)
+    np.testing.assert_array_equal(new.view(np.uint64), sigma.view(np.uint64))
+
+
+def test_entry_values_go_through_the_clamp():
+    s = np.array([[np.nan, np.nan], [-1.0, -1.0], [np.inf, np.inf], [1e300, 1e300], [-np.inf, 0.3], [0.02, 1.5], [0.1, 0.1]])
+    got = AR.clampd(s, LO, HI)
+    np.testing.assert_array_equal(got, [[0.02, 0.1], [0.02, 0.1], [0.5, 1.5], [0.5, 1.5], [0.02, 0.3], [0.02, 1.5], [0.1, 0.1]])
+    # and the candidates are made with the clamped width: a NaN width never reaches a command
+    mean = np.zeros((1, 7, 2))
+    eps = np.ones((1, 2, 7, 2), np.float32)
+    u = AR.candidates(mean, got[None], eps, [-9, -9], [9, 9])
+    np.testing.assert_array_equal(u[0, 1], got)
+    # with one width for all rows the candidates are mppi_ref's, bit for bit
+    rng = np.random.RandomState(5)
+    mean, eps = rng.uniform(-1, 1, (3, 4, 2)), MR.host_eps(1, 1, 3, 8, 4)[0]
+    a = AR.candidates(mean, np.broadcast_to(np.array([0.2, 0.6]), (3, 4, 2)), eps, MR.ACTION_LOW, MR.ACTION_HIGH)
+    np.testing.assert_array_equal(a, MR.candidates(mean, (0.2, 0.6), eps, MR.ACTION_LOW, MR.ACTION_HIGH))
+
+
+# ---------------------------------------------------------------------------------------------- the checks, sanitized
+def _compiler():
+    for cand in ("g++", "/opt/rocm/llvm/bin/clang++", "clang++"):
+        path = shutil.which(cand)
+        if path:
+            return path
+    raise AssertionError("no host C++ compiler found (g++ or ROCm's clang++)")
+
+
+def test_checks_of_the_struct_under_sanitizers(tmp_path):
+    """tests/c_abi/mppi_adapt_main.cpp, compiled with -fsanitize=address,undefined and run as its own process: every refusal
+    of mppi_adapt_check_args and their order, NaN and +-inf in every field, the clamp and the move"""
+    exe = str(tmp_path / "mppi_adapt_main")
+    cxx = _compiler()
+    static_runtime = ["-static-libasan", "-static-libubsan"] if cxx.endswith("g++") else []   # (clang's is static already)
+    cmd = [cxx] + static_runtime + ["-std=c++17", "-Wall", "-Werror", "-g", "-O1", "-ffp-contract=off",
+                                    "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                                    "-I" + os.path.join(ROOT, "bc_gym_planning_env_amd", "csrc"),
+                                    os.path.join(ROOT, "tests", "c_abi", "mppi_adapt_main.cpp"), "-o", exe]
+    built = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=300)
+    assert built.returncode == 0, built.stdout
+    ran = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=120)
+    assert ran.returncode == 0, ran.stdout[-4000:]
+    assert "mppi adapt ok" in ran.stdout
+    for word in ("Sanitizer", "runtime error"):
+        assert word not in ran.stdout, ran.stdout[-4000:]
+
+
+# ---------------------------------------------------------------------------------------------- non-vacuity
+def _run(oracle, kind, iterations, rate):
+    (n, k, h), _, _sigma, lam, penalty = MR.SCENARIOS[kind]
+    g, name, start = MR.scenario_world(kind, n)
+    sigma, lo, hi = AR.scenario_widths(kind, n, h)
+    eps = MR.host_eps(MR.EPS_SEED, 5, n, k, h)[:iterations]
+    run = AR.mppi_adapt_ref(oracle, MR.scenario_oracle_params(oracle, name), LR.shared_world(g), start, MR.initial_mean(kind, n, h),
+                            sigma, rate, lo, hi, MR.ACTION_LOW, MR.ACTION_HIGH, lam, penalty, eps)
+    return run, lo, hi
+
+
+@pytest.mark.parametrize("kind", ["goal", "aisle", "scatter"])
+def test_widths_move_and_stay_off_the_clamps(oracle, kind):
+    """I = 4, rate = 0.5, clamps [s0 / 8, 2 s0], on the restatement and the oracle alone: after every iteration fewer than
+    1 % of the widths lie on a clamp, and after four the median of sigma / s0 is below 0.95 in both components.
+    Measured: nothing on a clamp in 'goal' and 'aisle', in 'scatter' 0.07 % / 0.26 % (v / w) after the last iteration only;
+    medians (v, w) 0.60, 0.88 ('goal'), 0.45, 0.77 ('aisle'), 0.58, 0.49 ('scatter')."""
+    run, lo, hi = _run(oracle, kind, 4, 0.5)
+    s0 = np.asarray(MR.SCENARIOS[kind][2], np.float64)
+    after = list(run["iter_sigma"][1:]) + [run["sigma"]]
+    for j, s in enumerate(after):
+        at_lo, at_hi = AR.on_clamp(s, lo, hi)
+        print("%s after iteration %d: on sigma_min %s %%, on sigma_max %s %%" % (kind, j, 100 * at_lo, 100 * at_hi))
+        assert (at_lo + at_hi < 0.01).all(), (kind, j)
+    median = np.median((run["sigma"] / s0).reshape(-1, 2), axis=0)
+    print("%s: median sigma / s0 after 4 iterations (v, w) = %.2f, %.2f" % (kind, median[0], median[1]))
+    assert (median < 0.95).all()
+    np.testing.assert_array_equal(run["iter_sigma"][0], np.broadcast_to(s0, run["sigma"].shape))
+
+
+def test_a_greedy_rate_puts_widths_on_the_lower_clamp(oracle):
+    """'scatter' with rate = 1.0: at least 5 % of the widths equal sigma_min after the first iteration (measured 14.6 % (v)
+    and 14.2 % (w)) -- the clamp branch is really taken"""
+    run, lo, hi = _run(oracle, "scatter", 1, 1.0)
+    at_lo, _ = AR.on_clamp(run["sigma"], lo, hi)
+    print("scatter, rate 1: %.1f %% (v) and %.1f %% (w) of the widths on sigma_min after one iteration" % (100 * at_lo[0], 100 * at_lo[1]))
+    assert (at_lo >= 0.05).all()

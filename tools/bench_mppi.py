@@ -38,8 +38,9 @@ from bc_gym_planning_env_amd import _lib
 if args.lib:
     _lib.LIB_PATH = args.lib
 have_field = hasattr(ctypes.CDLL(_lib.LIB_PATH), "bcp_mppi_field")
-if not have_field:
-    _lib.SYMBOLS.pop("bcp_mppi_field")   # an older build: everything else binds as it is
+for younger in ("bcp_mppi_field", "bcp_mppi_adapt"):
+    if not hasattr(ctypes.CDLL(_lib.LIB_PATH), younger):
+        _lib.SYMBOLS.pop(younger)   # an older build: everything else binds as it is
 
 
 def record(rec):
