@@ -1,6 +1,6 @@
 // bcp_host.h -- what every host-side piece of libbcplan shares: the error record, the handle with the owners of its state,
 // and the few helpers that launch kernels.  Included by bcplan.hip after the device headers and before the subsystems (bcp_field.h,
-// bcp_step_host.h, bcp_seams.h + bcp_seams_host.h, bcp_ego_host.h, bcp_worlds_host.h, bcp_inflate_host.h, bcp_scan_host.h,
+// bcp_step_host.h, bcp_plan_host.h, bcp_seams.h + bcp_seams_host.h, bcp_ego_host.h, bcp_worlds_host.h, bcp_inflate_host.h, bcp_scan_host.h,
 // bcp_goal_host.h).
 #pragma once
 

@@ -170,9 +170,13 @@ __device__ __forceinline__ void mppi_eps(const MppiArgs& a, int64_t env, uint64_
 // time for that row: the commands of every chunk but the last are made again from their counters (or read again from
 // eps_in), the last chunk's are still in registers -- the same bits either way, mppi_command is a function of its arguments.
 // The same butterflies reduce the two sums, the lane with kl == 0 replaces the row in place, and the barrier that ends the
-// iteration orders it like the mean's.  No LDS beyond the scores, no atomics.  (The second walk fetches through mppi_eps; the
-// roll-out and the first walk keep the text they had, under which the kernels without ADAPT compile to the instructions
-// they compiled to before there was an ADAPT.)
+// iteration orders it like the mean's.  No LDS beyond the scores, no atomics.
+// The second walk fetches through mppi_eps; the roll-out and the first walk carry the same fetch inline, and the choice of
+// s0, s1 is written out in both.  That is measured, not taste (profiles/mppi_one_path.txt): with all three fetches through
+// mppi_eps and one mppi_widths_at, bcp_mppi at N = 4096, K = 64, H = 16, I = 4 took 3.97 ms against 3.93 ms and
+// bcp_mppi_adapt 4.21 against 4.13; with only the roll-out's block back 4.04, with only the first walk's 4.08; with both
+// back and only the widths in a function 4.05.  These ~14 k-instruction kernels change their schedule with any edit of the
+// body, so a change to the [I][N][K][H][2] layout has three places to find: here (mppi_eps) and the two blocks below.
 // Loops are bounded by I, H and K / 64; no atomics, no waits on other workgroups.
 template <bool PLAIN, bool FIELD, bool ADAPT>
 __global__ void __launch_bounds__(kBlock) mppi_kernel(const MppiKernelArgs<FIELD, ADAPT> ka)
@@ -294,7 +298,7 @@ __global__ void __launch_bounds__(kBlock) mppi_kernel(const MppiKernelArgs<FIELD
             double u0 = 0.0, u1 = 0.0;   // (after the loop: the last chunk's commands)
             for (int ch = 0; ch < chunks; ++ch) {
                 const int k = ch * kBlock + kl;
-                float e0 = 0.0f, e1 = 0.0f;
+                float e0 = 0.0f, e1 = 0.0f;   // (mppi_eps written out, as in the roll-out: see above the kernel)
                 if (a.eps_in) {
                     if (k != 0) {
                         const int64_t c = ((int64_t)j * a.n + i) * K + k;

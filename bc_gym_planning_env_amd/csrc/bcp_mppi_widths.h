@@ -1,7 +1,7 @@
 // bcp_mppi_widths.h -- what bcp_mppi_adapt decides about its widths before and inside the launch, as plain functions: the
 // checks of the bcp_mppi_adapt struct (mppi_adapt_check_args, the refusals in the order the header lists them), the clamp
 // every width goes through (mppi_clamp_width) and the move of a width towards the weighted spread (mppi_next_width).
-// No HIP in here: bcp_mppi.h and bcp_step_host.h include it, and so does a stand-alone host program
+// No HIP in here: bcp_mppi.h includes it for the kernel and bcp_plan_host.h's checks, and so does a stand-alone host program
 // (tests/c_abi/mppi_adapt_main.cpp) that drives the checks through every refusal without a GPU.
 #pragma once
 

@@ -9,8 +9,8 @@
 //                      bcp_devbuf.h), EgoCells, the launch helpers
 //   bcp_field_plan.h   footprint geometry and the plan of a map binding: every shape and size, no HIP in it
 //   bcp_field.h        distance field and tiles: kernels, DistanceField, the launchers of what is derived from maps and paths
-//   bcp_step_host.h    step forms, the step's parameter block and launcher, Parking, WaitWatchdog, bcp_step / bcp_rollout /
-//                      bcp_lookahead / bcp_mppi / bcp_mppi_field
+//   bcp_step_host.h    step forms, the step's parameter block and launcher, Parking, WaitWatchdog, bcp_step / bcp_rollout
+//   bcp_plan_host.h    the planners: bcp_lookahead / bcp_mppi / bcp_mppi_field / bcp_mppi_adapt
 //   bcp_ego_host.h     egocentric costmaps (routed by bcp_ego_route.h, which has no HIP in it), goal-state vectors, the
 //                      episode record and its final observations
 //   bcp_worlds_host.h  mini-world and aisle-world entry points
@@ -96,6 +96,7 @@ static void fill_dev_params(bcp_handle* h)
 // (each needs the ones before it, and the helpers above)
 #include "bcp_field.h"
 #include "bcp_step_host.h"
+#include "bcp_plan_host.h"
 #include "bcp_seams.h"
 #include "bcp_seams_host.h"
 #include "bcp_ego_host.h"

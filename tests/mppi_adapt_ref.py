@@ -15,13 +15,7 @@ def clampd(s, lo, hi):
         return np.where(~(s >= lo), lo, np.where(s > hi, hi, s))
 
 
-def candidates(mean, sigma, eps, low, high):
-    """u [N, K, H, 2] = min(max(mean + sigma * (double)eps, low), high) with sigma [N, H, 2] (already clamped): IEEE float64
-    operations, each rounded on its own"""
-    low, high = (np.asarray(v, np.float64).reshape(2) for v in (low, high))
-    e = np.asarray(eps, np.float32).astype(np.float64)
-    u = np.asarray(mean, np.float64)[:, None] + np.asarray(sigma, np.float64)[:, None] * e
-    return np.minimum(np.maximum(u, low), high)
+candidates = MR.candidates    # (with sigma [N, H, 2], already clamped)
 
 
 def spread(u, w, new_mean):
@@ -41,8 +35,7 @@ def next_sigma(sigma, sd, rate, lo, hi):
 def update(u, score, lam, sigma, rate, lo, hi, new_mean=None):
     """(new mean [N, H, 2], new sigma [N, H, 2], weights [N, K]) from the scores [N, K]; new_mean given: the spread is taken
     about that mean (the kernel's own), not about the restatement's"""
-    w = MR.weights(score, lam)
-    mean = (w[:, :, None, None] * np.asarray(u, np.float64).astype(np.longdouble)).sum(axis=1).astype(np.float64)
+    mean, w = MR.update_from_scores(u, score, lam)
     about = mean if new_mean is None else np.asarray(new_mean, np.float64)
     return mean, next_sigma(sigma, spread(u, w, about), rate, lo, hi), w
 

@@ -13,10 +13,12 @@ DONE_COLLIDED = LR.DONE_COLLIDED
 
 def candidates(mean, sigma, eps, low, high):
     """u [N, K, H, 2] float64 = min(max(mean + sigma * (double)eps, low), high): one product, one sum, two comparisons,
-    each an IEEE float64 operation (numpy rounds every ufunc on its own).  mean [N, H, 2], eps [N, K, H, 2] float32."""
-    sigma, low, high = (np.asarray(v, np.float64).reshape(2) for v in (sigma, low, high))
+    each an IEEE float64 operation (numpy rounds every ufunc on its own).  mean [N, H, 2], eps [N, K, H, 2] float32; sigma
+    one pair (2,), or a width per env, step and component [N, H, 2] (bcp_mppi_adapt's, already clamped)."""
+    low, high = (np.asarray(v, np.float64).reshape(2) for v in (low, high))
+    sigma = np.asarray(sigma, np.float64)
     e = np.asarray(eps, np.float32).astype(np.float64)
-    u = np.asarray(mean, np.float64)[:, None] + sigma * e
+    u = np.asarray(mean, np.float64)[:, None] + (sigma if sigma.ndim == 1 else sigma[:, None]) * e
     return np.minimum(np.maximum(u, low), high)
 
 
@@ -32,11 +34,16 @@ def weights(score, lam):
     return e / e.sum(axis=1, keepdims=True)
 
 
-def update(u, ret, reason, lam, collision_penalty):
-    """the new mean [N, H, 2] (longdouble sum, rounded once to float64) and the weights [N, K] (longdouble)"""
-    w = weights(scores(ret, reason, collision_penalty), lam)
+def update_from_scores(u, score, lam):
+    """the new mean [N, H, 2] (longdouble sum, rounded once to float64) and the weights [N, K] (longdouble) from scores
+    taken as given bits"""
+    w = weights(score, lam)
     new = (w[:, :, None, None] * np.asarray(u, np.float64).astype(np.longdouble)).sum(axis=1)
     return new.astype(np.float64), w
+
+
+def update(u, ret, reason, lam, collision_penalty):
+    return update_from_scores(u, scores(ret, reason, collision_penalty), lam)
 
 
 def effective_sample_size(w):

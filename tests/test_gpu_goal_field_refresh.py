@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 import goal_field_ref as GR
-import mppi_field_ref as FR
+import mppi_check as MC
 import mppi_ref as MR
 
 pytestmark = pytest.mark.gpu
@@ -343,9 +343,9 @@ def test_consumers_follow_the_refreshed_fields(torch_cuda):
     # the terminal cost inside the MPPI launch: the reference field read at the look-ahead's final poses, teacher-forced
     n, k, h, it = env.n_envs, 16, 8, 2
     sigma = (0.2, 0.8)
-    res = env.mppi(FR.random_mean(env, rng, n, h), sigma, it, k, 0.4, 2.0, seed=11, want=("eps", "iter_mean", "iter_value"),
+    res = env.mppi(MC.random_mean(env, rng, n, h), sigma, it, k, 0.4, 2.0, seed=11, want=("eps", "iter_mean", "iter_value"),
                    goal_field=fields, terminal_weight=4.0)
-    low, high = FR.box(env)
+    low, high = MC.box(env)
     row_env = torch.arange(n, dtype=torch.int32, device="cuda").repeat_interleave(k)
     for j in range(it):
         u = MR.candidates(res.iter_mean[j].cpu().numpy(), sigma, res.eps[j].cpu().numpy(), low, high)

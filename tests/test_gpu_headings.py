@@ -218,7 +218,7 @@ def test_mppi_flags_an_env_for_a_single_candidate(torch_cuda, oracle, world, row
     """the same start states, a plan that steers away from the edge: few candidates cross it -- in some envs none, in some one,
     in some only odd-numbered ones.  err per env is the reference's: the OR over iterations and candidates; returns and
     reasons of every iteration as the MPPI tests compare them"""
-    from test_gpu_mppi import _teacher_forced
+    import mppi_check as MC
     torch = torch_cuda
     b, env, start, world_d, p, cat = _planning_case(torch, oracle, world, row)
     m = HD.MPPI
@@ -226,7 +226,8 @@ def test_mppi_flags_an_env_for_a_single_candidate(torch_cuda, oracle, world, row
     res = env.mppi(HD.plan_mean(start), m["sigma"], m["iterations"], k, m["lam"], m["penalty"], eps=eps,
                    want=("eps", "iter_mean", "iter_ret", "iter_reason", "err"))
     assert torch.equal(res.eps, torch.from_numpy(eps).cuda())
-    _teacher_forced(torch, env, res, m["sigma"], m["lam"], m["penalty"], (oracle, p, world_d, start), tag="%s K=%d" % (world, k))
+    MC.teacher_forced(torch, env, res, m["sigma"], m["lam"], m["penalty"], oracle_args=(oracle, p, world_d, start),
+                      tag="%s K=%d" % (world, k))
     # the reference's word, teacher-forced like the rest: each iteration's candidates made from the GPU's own mean of that iteration
     low, high = (np.asarray(v, np.float64) for v in (env.action_space.low, env.action_space.high))
     iter_err = []

@@ -2,6 +2,8 @@
 iteration and teacher-forced: iteration j is judged from the mean the kernel itself took into it (iter_mean[j]) and the
 perturbations it used (eps), so a last-bit difference in one weight cannot cascade into another trajectory.
 
+The checker is tests/mppi_check.teacher_forced; the bound it applies to the mean is derived here.
+
 Roll-outs: u_j is rebuilt in numpy (exact IEEE operations, tests/mppi_ref.candidates); env.lookahead(u_j) must give
 iter_ret[j] and iter_reason[j] bit for bit (the same arithmetic), and the CPU oracle the same reasons and ret within 1e-9.
 
@@ -21,6 +23,7 @@ import numpy as np
 import pytest
 
 import lookahead_ref as LR
+import mppi_check as MC
 import mppi_ref as MR
 from util import GOLDEN, env_from_traj
 
@@ -30,106 +33,23 @@ ALL = ("eps", "iter_mean", "iter_ret", "iter_reason", "err")
 OUT = ("mean", "action") + ALL
 
 
-def _set_start(torch, env, start):
-    env.state.robot.copy_(torch.from_numpy(start.robot))
-    env.state.min_spat_dist_so_far.copy_(torch.from_numpy(start.min_dist))
-    env.state.target_idx.copy_(torch.from_numpy(start.target_idx))
-    env.state.current_iter.copy_(torch.from_numpy(start.cur_iter))
-    env.state.robot_collided.copy_(torch.from_numpy(start.collided))
-    if start.geom is not None:
-        env.geom_of_env.copy_(torch.from_numpy(start.geom))
-
-
-def _read_start(env):
-    s = env.state
-    return LR.StartState(s.robot.cpu().numpy(), s.min_spat_dist_so_far.cpu().numpy(), s.target_idx.cpu().numpy(),
-                         s.current_iter.cpu().numpy(), s.robot_collided.cpu().numpy(),
-                         None if env.geom_of_env is None else env.geom_of_env.cpu().numpy())
-
-
-def _box(env):
-    return np.asarray(env.action_space.low, np.float64), np.asarray(env.action_space.high, np.float64)
-
-
-def _tolerance(env, k):
-    low, high = _box(env)
-    return 4.0 * (k + 16) * 2.0 ** -53 * max(np.abs(low).max(), np.abs(high).max())
-
-
-def _random_mean(env, rng, n, h):
-    """a plan that is not constant over the horizon, inside the box"""
-    low, high = _box(env)
-    return np.ascontiguousarray(rng.uniform(low, high, (n, h, 2)))
-
-
-def _snapshot(res):
-    return {f: getattr(res, f).clone() for f in OUT if getattr(res, f) is not None}
-
-
-def _teacher_forced(torch, env, res, sigma, lam, penalty, oracle_args=None, rows=None, tag=""):
-    """res: Mppi with all optional outputs.  oracle_args: (oracle, params, world, start) or None.  rows: envs to compare"""
-    low, high = _box(env)
-    it, n, k = res.iter_ret.shape
-    sel = slice(None) if rows is None else rows
-    tsel = slice(None) if rows is None else torch.from_numpy(np.asarray(rows)).cuda()
-    tol = _tolerance(env, k)
-    worst_update, worst_ret, hits = 0.0, 0.0, 0
-    for j in range(it):
-        mean_j = res.iter_mean[j].cpu().numpy()
-        eps_j = res.eps[j].cpu().numpy()
-        assert (eps_j[sel][:, 0] == 0).all(), "candidate 0 is the unperturbed mean"
-        u = MR.candidates(mean_j, sigma, eps_j, low, high)
-        la = env.lookahead(torch.from_numpy(MR.as_lookahead_actions(u)).cuda(), want=())
-        ret, reason = res.iter_ret[j].cpu().numpy(), res.iter_reason[j].cpu().numpy()
-        assert torch.equal(la.ret[tsel], res.iter_ret[j][tsel]), "%s iteration %d: ret differs from lookahead's by %g" % (
-            tag, j, (la.ret[tsel] - res.iter_ret[j][tsel]).abs().max())
-        assert torch.equal(la.reason[tsel], res.iter_reason[j][tsel]), "%s iteration %d: reason" % (tag, j)
-        if oracle_args is not None:
-            oracle, params, world, start = oracle_args
-            exp = LR.oracle_lookahead(oracle, params, world, start, MR.as_lookahead_actions(u), threads=16)
-            np.testing.assert_array_equal(reason[sel], exp["reason"][sel], err_msg="%s iteration %d reason" % (tag, j))
-            worst_ret = max(worst_ret, np.abs(ret[sel] - exp["ret"][sel]).max())
-        want, _ = MR.update(u, ret, reason, lam, penalty)
-        got = (res.iter_mean[j + 1] if j + 1 < it else res.mean).cpu().numpy()
-        worst_update = max(worst_update, np.abs(got[sel] - want[sel]).max())
-        hits += int(((reason[sel] & LR.DONE_COLLIDED) != 0).sum())
-    print("%s: max |mean - restatement| = %.3g (bound %.3g), max |ret - oracle| = %.3g, %d collided candidates"
-          % (tag, worst_update, tol, worst_ret, hits))
-    assert worst_ret <= 1e-9, tag
-    assert worst_update <= tol, tag
-    assert torch.equal(res.action[tsel], res.mean[:, 0][tsel]), tag
-    return hits
-
-
-def _scenario_env(torch, kind, n):
-    """'scatter' / 'goal' on a handle that has noise on (the refinement must not care), 'aisle' as recorded"""
-    g, name, start = MR.scenario_world(kind, n)
-    env = env_from_traj(g, "mini_with_noise" if "mini" in name else name, n_envs=n)
-    assert env.noise_parameters is not None
-    low, high = _box(env)
-    np.testing.assert_array_equal(low, MR.ACTION_LOW)
-    np.testing.assert_array_equal(high, MR.ACTION_HIGH)
-    _set_start(torch, env, start)
-    return g, name, start, env
-
-
 # ---------------------------------------------------------------------------------------------- 1. scenarios and shapes
 @pytest.mark.parametrize("kind", ["scatter", "goal", "aisle"])
 def test_scenarios_teacher_forced(torch_cuda, oracle, kind):
     """the scenarios tests/test_mppi_host.py shows to be non-vacuous, with its perturbations (parity mode) and I = 4"""
     torch = torch_cuda
     (n, k, h), _, sigma, lam, penalty = MR.SCENARIOS[kind]
-    g, name, start, env = _scenario_env(torch, kind, n)
+    g, name, start, env = MC.scenario_env(torch, kind, n)
     eps = MR.host_eps(MR.EPS_SEED, 5, n, k, h)[:4]
     res = env.mppi(MR.initial_mean(kind, n, h), sigma, 4, k, lam, penalty, eps=eps, want=ALL)
     assert torch.equal(res.eps, torch.from_numpy(eps).cuda()), "parity mode: the perturbations used are the ones given"
-    hits = _teacher_forced(torch, env, res, sigma, lam, penalty,
-                           (oracle, MR.scenario_oracle_params(oracle, name), LR.shared_world(g), start), tag=kind)
+    hits = MC.teacher_forced(torch, env, res, sigma, lam, penalty, tag=kind,
+                             oracle_args=(oracle, MR.scenario_oracle_params(oracle, name), LR.shared_world(g), start)).hits
     assert (res.err == 0).all()
     if kind != "goal":
         assert hits >= 100
     # the first iteration is the restatement's, reasons exactly and returns within the oracle's 1e-9
-    u0 = MR.candidates(MR.initial_mean(kind, n, h), sigma, eps[0], *_box(env))
+    u0 = MR.candidates(MR.initial_mean(kind, n, h), sigma, eps[0], *MC.box(env))
     exp = LR.oracle_lookahead(oracle, MR.scenario_oracle_params(oracle, name), LR.shared_world(g), start,
                               MR.as_lookahead_actions(u0), threads=16)
     np.testing.assert_array_equal(res.iter_reason[0].cpu().numpy(), exp["reason"])
@@ -143,10 +63,10 @@ def test_shapes_teacher_forced_with_device_perturbations(torch_cuda, oracle, kin
     device; the inputs of the 'scatter' and 'aisle' scenarios at other shapes"""
     torch = torch_cuda
     _, _, sigma, lam, penalty = MR.SCENARIOS[kind]
-    g, name, start, env = _scenario_env(torch, kind, n)
+    g, name, start, env = MC.scenario_env(torch, kind, n)
     res = env.mppi(MR.initial_mean(kind, n, h), sigma, it, k, lam, penalty, seed=7, draw_index=3, want=ALL)
-    _teacher_forced(torch, env, res, sigma, lam, penalty,
-                    (oracle, MR.scenario_oracle_params(oracle, name), LR.shared_world(g), start), tag="%dx%dx%dx%d" % (n, k, h, it))
+    MC.teacher_forced(torch, env, res, sigma, lam, penalty, tag="%dx%dx%dx%d" % (n, k, h, it),
+                      oracle_args=(oracle, MR.scenario_oracle_params(oracle, name), LR.shared_world(g), start))
     assert (res.eps[:, :, 1:] != 0).any() and bool(torch.isfinite(res.eps).all())
 
 
@@ -155,16 +75,16 @@ def test_odd_env_count_and_mask(torch_cuda, oracle):
     torch = torch_cuda
     n, k, h, it = 37, 16, 12, 2
     _, _, sigma, lam, penalty = MR.SCENARIOS["scatter"]
-    g, name, start, env = _scenario_env(torch, "scatter", n)
+    g, name, start, env = MC.scenario_env(torch, "scatter", n)
     rng = np.random.RandomState(1)
-    mean0 = _random_mean(env, rng, n, h)
+    mean0 = MC.random_mean(env, rng, n, h)
     res = env.mppi(mean0, sigma, it, k, lam, penalty, seed=1, want=ALL)
     args = (oracle, MR.scenario_oracle_params(oracle, name), LR.shared_world(g), start)
-    _teacher_forced(torch, env, res, sigma, lam, penalty, args, tag="N=37")
-    first = _snapshot(res)
+    MC.teacher_forced(torch, env, res, sigma, lam, penalty, oracle_args=args, tag="N=37")
+    first = MC.snapshot(res, OUT)
     mask = (np.arange(n) % 3 != 1).astype(np.uint8)
     off = torch.from_numpy(mask == 0).cuda()
-    mean1 = torch.from_numpy(_random_mean(env, rng, n, h)).cuda()
+    mean1 = torch.from_numpy(MC.random_mean(env, rng, n, h)).cuda()
     before = mean1.clone()
     res2 = env.mppi(mean1, sigma, it, k, lam, penalty, seed=2, mask=mask, want=ALL)
     assert res2.mean.data_ptr() == mean1.data_ptr(), "a float64 device tensor is refined in place"
@@ -172,25 +92,18 @@ def test_odd_env_count_and_mask(torch_cuda, oracle):
     for f in ("action", "err", "eps", "iter_mean", "iter_ret", "iter_reason"):
         a, b = getattr(res2, f), first[f]
         assert torch.equal(a[off] if a.shape[0] == n else a[:, off], b[off] if b.shape[0] == n else b[:, off]), f
-    _teacher_forced(torch, env, res2, sigma, lam, penalty, args, rows=np.nonzero(mask)[0], tag="masked")
+    MC.teacher_forced(torch, env, res2, sigma, lam, penalty, oracle_args=args, rows=np.nonzero(mask)[0], tag="masked")
     assert not torch.equal(res2.mean[~off], before[~off])
 
 
 # ---------------------------------------------------------------------------------------------- 2. configurations
-def _drive(env, rng, steps, gain):
-    for _ in range(steps):
-        a = env.action_space.sample_batch(env.n_envs, rng)
-        a[:, 0] *= gain
-        env.step(a)
-
-
 def _configuration(torch, oracle, env, params, world, k, h, it, tag, sigma=(0.2, 0.8), lam=0.3, penalty=2.0, min_hits=0):
     rng = np.random.RandomState(17)
-    start = _read_start(env)
-    res = env.mppi(_random_mean(env, rng, env.n_envs, h), sigma, it, k, lam, penalty, seed=11, draw_index=5, want=ALL)
-    hits = _teacher_forced(torch, env, res, sigma, lam, penalty, (oracle, params, world, start), tag=tag)
+    start = MC.read_start(env)
+    res = env.mppi(MC.random_mean(env, rng, env.n_envs, h), sigma, it, k, lam, penalty, seed=11, draw_index=5, want=ALL)
+    hits = MC.teacher_forced(torch, env, res, sigma, lam, penalty, oracle_args=(oracle, params, world, start), tag=tag).hits
     assert hits >= min_hits, tag
-    after = _read_start(env)
+    after = MC.read_start(env)
     for f in ("robot", "min_dist", "target_idx", "cur_iter", "collided"):
         np.testing.assert_array_equal(getattr(start, f), getattr(after, f))
 
@@ -207,7 +120,7 @@ def test_diffdrive(torch_cuda, oracle):
     robot = np.zeros((7, n))
     robot[:] = g["start_state"][:, None]
     robot[0:3] += np.concatenate([rng.normal(0, 0.05, (2, n)), rng.normal(0, 0.4, (1, n))])
-    _set_start(torch, env, LR.StartState(robot, np.full(n, float(g["init_min_dist"])), np.full(n, int(g["init_target_idx"])),
+    MC.set_start(torch, env, LR.StartState(robot, np.full(n, float(g["init_min_dist"])), np.full(n, int(g["init_target_idx"])),
                                          np.zeros(n)))
     p = oracle.make_params("diffdrive", noise=None, spatial_precision=0.2, angular_precision=np.pi / 8)
     _configuration(torch, oracle, env, p, LR.shared_world(g), 32, 24, 2, "diffdrive")
@@ -220,7 +133,7 @@ def test_pure_pursuit(torch_cuda, oracle):
     res, n = float(g["resolution"]), 64
     params = EnvParams(resolution=res, refine_path=False, reward_provider_name='continuous_reward_pure_pursuit')
     env = BatchedPlanEnv(CostMap2D(g["costmap"], res, g["origin"]), g["path"], params, n_envs=n)
-    _drive(env, np.random.RandomState(4), 30, 2.0)
+    MC.drive(env, np.random.RandomState(4), 30, 2.0)
     p = oracle.make_params("tricycle", noise=None, reward_provider=oracle.REWARD_PURE_PURSUIT)
     _configuration(torch, oracle, env, p, LR.shared_world(g), 64, 24, 2, "pure pursuit", lam=0.05)
 
@@ -250,32 +163,21 @@ def test_private_maps_and_paths(torch_cuda, oracle):
         pbuf[i, :len(p_)] = p_
     env.set_costmap_tensors(torch.from_numpy(maps).cuda(), torch.from_numpy(origins).cuda(), res,
                             torch.from_numpy(vr).cuda(), torch.from_numpy(vc).cuda())
-    _drive(env, np.random.RandomState(9), 25, 2.0)
+    MC.drive(env, np.random.RandomState(9), 25, 2.0)
     world = dict(costmaps=maps, origins=origins, resolution=res, paths=pbuf, lens=np.array([len(p_) for p_ in paths]),
                  rows=vr, cols=vc)
     _configuration(torch, oracle, env, oracle.make_params("tricycle", noise=None), world, 16, 24, 2, "private maps")
 
 
 def _mini_pool_env(n, **kw):
-    from bc_gym_planning_env_amd import EnvParams, mini_env
-    params = mini_env.RandomMiniEnvParams(env_params=EnvParams(goal_ang_dist=np.pi / 8., goal_spat_dist=0.2,
-                                                               iteration_timeout=60))
-    pool = mini_env.sample_pool(params, list(range(100, 107)), 3)
-    env = mini_env.BatchedRandomMiniEnv(n, params, pool=pool, seed=11, noise_parameters="planenv", **kw)
-    paths = env._paths
-    pbuf = np.zeros((len(paths), max(len(p) for p in paths), 3))
-    for j, p in enumerate(paths):
-        pbuf[j, :len(p)] = p
-    world = dict(costmaps=np.stack([c.get_data() for c in pool.costmaps]), origins=np.stack([c.get_origin() for c in pool.costmaps]),
-                 resolution=params.env_params.resolution, paths=pbuf, lens=np.array([len(q) for q in paths]))
-    return env, world
+    return MC.mini_pool(n, 60, seeds=range(100, 107), episodes=3, seed=11, with_world=True, noise_parameters="planenv", **kw)
 
 
 def test_mini_pool_with_envs_on_different_entries(torch_cuda, oracle):
     torch = torch_cuda
     n = 96
     env, world = _mini_pool_env(n, auto_reset=True)
-    _drive(env, np.random.RandomState(4), 75, 3.0)
+    MC.drive(env, np.random.RandomState(4), 75, 3.0)
     assert len(np.unique(env.geom_of_env.cpu().numpy())) >= 16
     p = oracle.make_params("tricycle", noise=None, spatial_precision=0.2, angular_precision=np.pi / 8, iteration_timeout=60)
     _configuration(torch, oracle, env, p, world, 32, 32, 2, "mini pool")
@@ -297,7 +199,7 @@ def test_aisle_pool_with_envs_on_different_entries(torch_cuda, oracle):
         maps[g_].reshape(-1)[:vr[g_] * vc[g_]] = padded[g_, :vr[g_], :vc[g_]].ravel()
     world = dict(costmaps=maps, origins=dp.origins.cpu().numpy(), resolution=ep.resolution,
                  paths=dp.path_points.cpu().numpy(), lens=dp.lens.cpu().numpy(), rows=vr, cols=vc)
-    _drive(env, np.random.RandomState(21), 90, 3.0)
+    MC.drive(env, np.random.RandomState(21), 90, 3.0)
     assert len(np.unique(env.geom_of_env.cpu().numpy())) >= 16
     p = oracle.make_params("tricycle", noise=None, spatial_precision=ep.goal_spat_dist, angular_precision=ep.goal_ang_dist,
                            iteration_timeout=60)
@@ -312,14 +214,14 @@ def test_one_hot_limit_is_bit_exact(torch_cuda):
     n, k, h = 64, 8, 32
     _, _, sigma, _, penalty = MR.SCENARIOS["scatter"]
     lam = 1.0 / 1024
-    g, name, start, env = _scenario_env(torch, "scatter", n)
+    g, name, start, env = MC.scenario_env(torch, "scatter", n)
     res = env.mppi(MR.initial_mean("scatter", n, h), sigma, 1, k, lam, penalty, seed=5, want=ALL)
     score = MR.scores(res.iter_ret[0].cpu().numpy(), res.iter_reason[0].cpu().numpy(), penalty)
     order = np.sort(score, axis=1)
     unique = np.nonzero(order[:, -1] - order[:, -2] >= 800 * lam)[0]
     print("%d of %d envs have a unique best candidate" % (len(unique), n))
     assert len(unique) >= 4
-    u = MR.candidates(res.iter_mean[0].cpu().numpy(), sigma, res.eps[0].cpu().numpy(), *_box(env))
+    u = MR.candidates(res.iter_mean[0].cpu().numpy(), sigma, res.eps[0].cpu().numpy(), *MC.box(env))
     best = score.argmax(axis=1)
     assert len(set(best[unique].tolist())) >= 2
     np.testing.assert_array_equal(res.mean.cpu().numpy()[unique], u[unique, best[unique]])
@@ -330,11 +232,11 @@ def test_device_stream_replays_and_is_standard_normal(torch_cuda):
     torch = torch_cuda
     n, k, h, it = 256, 64, 16, 2
     _, _, sigma, lam, penalty = MR.SCENARIOS["goal"]
-    g, name, start, env = _scenario_env(torch, "goal", n)
+    g, name, start, env = MC.scenario_env(torch, "goal", n)
     mean0 = MR.initial_mean("goal", n, h)
 
     def call(**kw):
-        return _snapshot(env.mppi(mean0, sigma, it, k, lam, penalty, want=ALL, **kw))
+        return MC.snapshot(env.mppi(mean0, sigma, it, k, lam, penalty, want=ALL, **kw), OUT)
 
     a = call(seed=9, draw_index=4)
     replay = call(eps=a["eps"])
@@ -366,12 +268,22 @@ def test_device_stream_replays_and_is_standard_normal(torch_cuda):
     assert abs((pairs[:, :, :, :-1] * pairs[:, :, :, 1:]).mean()) <= 5 / np.sqrt(m * (h - 1) / h)
 
 
+@pytest.mark.parametrize("n,k,h,it", [(9, 8, 3, 2), (3, 128, 3, 2)])
+def test_replayed_perturbations_below_and_above_a_wave(torch_cuda, n, k, h, it):
+    """eps_in where its index takes the env (K = 8: eight envs per wave, a second workgroup of one env and seven shadows)
+    and the chunk (K = 128: two): a call fed the perturbations another drew gives every output of that call"""
+    torch = torch_cuda
+    _, _, sigma, lam, penalty = MR.SCENARIOS["scatter"]
+    g, name, start, env = MC.scenario_env(torch, "scatter", n)
+    mean0 = MR.initial_mean("scatter", n, h)
+    a = MC.snapshot(env.mppi(mean0, sigma, it, k, lam, penalty, want=ALL, seed=9, draw_index=4), OUT)
+    replay = MC.snapshot(env.mppi(mean0, sigma, it, k, lam, penalty, want=ALL, eps=a["eps"]), OUT)
+    assert (a["eps"][:, :, 1:] != 0).any()
+    for f in OUT:
+        assert torch.equal(a[f], replay[f]), "eps_out fed back as eps_in: " + f
+
+
 # ---------------------------------------------------------------------------------------------- 5. nothing moved
-def _state_tensors(env):
-    s = env.state
-    return [s.robot, s.min_spat_dist_so_far, s.target_idx, s.current_iter, s.robot_collided, env.geom_of_env]
-
-
 def test_mppi_leaves_the_handle_untouched(torch_cuda):
     """on-device noise, a pool, auto-reset and a bound episode record: state, geom_of_env and the record are bit-identical
     after each of 50 calls, and the steps in between -- rewards, dones, drawn normals (the tick words key them), episode
@@ -385,15 +297,15 @@ def test_mppi_leaves_the_handle_untouched(torch_cuda):
         envs.append((env, env.enable_episode_record()))
     (env, ends), (twin, twin_ends) = envs
     zout, zout_twin = (torch.zeros(n, 3, dtype=torch.float64, device="cuda") for _ in range(2))
-    mean = torch.from_numpy(_random_mean(env, rng, n, h)).cuda()
+    mean = torch.from_numpy(MC.random_mean(env, rng, n, h)).cuda()
     n_ends = 0
     for t in range(60):
         a = env.action_space.sample_batch(n, rng)
         a[:, 0] *= 3.0
         if t >= 10:
-            before = [x.clone() for x in _state_tensors(env)] + [ends.ret.clone(), ends.count.clone(), ends.reason.clone()]
+            before = [x.clone() for x in MC.state_tensors(env)] + [ends.ret.clone(), ends.count.clone(), ends.reason.clone()]
             res = env.mppi(mean, (0.2, 0.6), 2, k, 0.3, 2.0, seed=1, draw_index=t, want=ALL)
-            after = _state_tensors(env) + [ends.ret, ends.count, ends.reason]
+            after = MC.state_tensors(env) + [ends.ret, ends.count, ends.reason]
             for b, x in zip(before, after):
                 assert torch.equal(b, x), "step %d" % t
             assert bool(torch.isfinite(res.mean).all())
@@ -401,7 +313,7 @@ def test_mppi_leaves_the_handle_untouched(torch_cuda):
         _, r2, d2, _ = twin.step(a, noise_z_out=zout_twin)
         assert torch.equal(r1, r2) and torch.equal(d1, d2), t
         assert torch.equal(torch.nan_to_num(zout, nan=7.0), torch.nan_to_num(zout_twin, nan=7.0)), t
-        for x, y in zip(_state_tensors(env), _state_tensors(twin)):
+        for x, y in zip(MC.state_tensors(env), MC.state_tensors(twin)):
             assert torch.equal(x, y), t
         m = int(ends.count[0])
         assert m == int(twin_ends.count[0]) and m <= n and torch.equal(ends.reason, twin_ends.reason), t
@@ -421,17 +333,17 @@ def test_action_is_step_zero_of_the_mean_and_steps(torch_cuda):
     torch = torch_cuda
     n, k, h = 64, 16, 8
     _, _, sigma, lam, penalty = MR.SCENARIOS["goal"]
-    g, name, start, env = _scenario_env(torch, "goal", n)
-    r64 = _snapshot(env.mppi(MR.initial_mean("goal", n, h), sigma, 2, k, lam, penalty, seed=3))
-    r32 = _snapshot(env.mppi(MR.initial_mean("goal", n, h), sigma, 2, k, lam, penalty, seed=3, action_dtype=torch.float32))
+    g, name, start, env = MC.scenario_env(torch, "goal", n)
+    r64 = MC.snapshot(env.mppi(MR.initial_mean("goal", n, h), sigma, 2, k, lam, penalty, seed=3), OUT)
+    r32 = MC.snapshot(env.mppi(MR.initial_mean("goal", n, h), sigma, 2, k, lam, penalty, seed=3, action_dtype=torch.float32), OUT)
     assert r64["action"].dtype == torch.float64 and torch.equal(r64["action"], r64["mean"][:, 0])
     assert r32["action"].dtype == torch.float32 and torch.equal(r32["mean"], r64["mean"])
     assert torch.equal(r32["action"], r64["mean"][:, 0].to(torch.float32))
-    low, high = _box(env)
+    low, high = MC.box(env)
     a = r64["action"].cpu().numpy()
     assert (a >= low).all() and (a <= high).all() and len(np.unique(a[:, 1])) > n // 2
     _, rew, done, _ = env.step(r32["action"])
-    _set_start(torch, env, start)
+    MC.set_start(torch, env, start)
     _, rew64, _, _ = env.step(r64["action"])
     env.check_errors()
     assert bool(torch.isfinite(rew).all()) and bool(torch.isfinite(rew64).all())
@@ -439,7 +351,7 @@ def test_action_is_step_zero_of_the_mean_and_steps(torch_cuda):
 
 def _raw(env, mean, action, **over):
     from bc_gym_planning_env_amd import _lib
-    low, high = _box(env)
+    low, high = MC.box(env)
     p, io = _lib.BcpMppiParams(), _lib.BcpMppiIO()
     p.horizon, p.n_candidates, p.iterations = int(mean.shape[1]), 16, 1
     for d in range(2):
@@ -483,7 +395,7 @@ def test_refusals(torch_cuda):
         rc, msg = _raw(env, mean, action, **over)
         assert rc == -1 and msg.startswith(b"bcp_mppi"), (over, rc, msg)
     assert b"too large" in _raw(env, mean, action, horizon=2 ** 31 - 1, iterations=2 ** 31 - 1, n_candidates=1024)[1]
-    for ok in (dict(n_candidates=8), dict(n_candidates=1024), dict(sigma=(0, 0.0)), dict(low=(0, float(_box(env)[1][0])))):
+    for ok in (dict(n_candidates=8), dict(n_candidates=1024), dict(sigma=(0, 0.0)), dict(low=(0, float(MC.box(env)[1][0])))):
         assert _raw(env, mean, action, **ok)[0] == 0, ok
     torch.cuda.synchronize()
     with pytest.raises(ValueError):
@@ -500,12 +412,12 @@ def test_captured_call_draws_afresh_from_a_device_word(torch_cuda):
     torch = torch_cuda
     n, k, h, it = 128, 32, 12, 2
     _, _, sigma, lam, penalty = MR.SCENARIOS["goal"]
-    g, name, start, env = _scenario_env(torch, "goal", n)
+    g, name, start, env = MC.scenario_env(torch, "goal", n)
     mean0 = torch.from_numpy(MR.initial_mean("goal", n, h)).cuda()
     direct = []
     mean = mean0.clone()
     for d in range(3):
-        direct.append(_snapshot(env.mppi(mean, sigma, it, k, lam, penalty, seed=4, draw_index=d, want=ALL)))
+        direct.append(MC.snapshot(env.mppi(mean, sigma, it, k, lam, penalty, seed=4, draw_index=d, want=ALL), OUT))
     assert not torch.equal(direct[0]["eps"], direct[1]["eps"]) and not torch.equal(direct[0]["mean"], direct[1]["mean"])
     word = torch.zeros(1, dtype=torch.int64, device="cuda")
     mean = mean0.clone()

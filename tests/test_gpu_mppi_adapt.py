@@ -2,7 +2,10 @@
 weights.  Every check is per iteration and teacher-forced, as in tests/test_gpu_mppi.py: iteration j is judged from the mean
 and the widths the kernel itself took into it (iter_mean[j], iter_sigma[j]) and the perturbations it used (eps).
 
-Roll-outs: u_j is rebuilt in numpy (mppi_adapt_ref.candidates, exact IEEE operations); env.lookahead(u_j) must give iter_ret[j]
+The checker is tests/mppi_check.teacher_forced with `widths`; the bound it applies to them (mppi_check.sigma_tolerance) is
+derived here.
+
+Roll-outs: u_j is rebuilt in numpy (mppi_ref.candidates, exact IEEE operations); env.lookahead(u_j) must give iter_ret[j]
 and iter_reason[j] bit for bit; in the scenarios the CPU oracle gives the same reasons and the returns within 1e-9.
 Mean: within 4 (K + 16) 2^-53 U of the longdouble restatement, U = max(|low|, |high|) (tests/test_gpu_mppi.py derives it).
 
@@ -31,23 +34,22 @@ import pytest
 import goal_field_ref as GR
 import lookahead_ref as LR
 import mppi_adapt_ref as AR
-import mppi_field_ref as FR
+import mppi_check as MC
 import mppi_ref as MR
-from util import GOLDEN, env_from_traj
+from util import GOLDEN
 
 pytestmark = pytest.mark.gpu
 
 PLAIN = ("eps", "iter_mean", "iter_ret", "iter_reason", "err")
 ALL = PLAIN + ("iter_sigma",)
 FIELD = ALL + ("iter_value", "iter_score")
-EPS = 2.0 ** -53
 SENTINEL = -777.25
 SIGMA, LAM, PENALTY, WEIGHT = (0.2, 0.8), 0.4, 2.0, 4.0
 LO, HI = (0.025, 0.1), (0.4, 1.6)     # SIGMA / 8 and 2 SIGMA
 
 
 def _snapshot(res, names):
-    return {f: getattr(res, f).clone() for f in ("mean", "action", "sigma") + tuple(names)}
+    return MC.snapshot(res, ("mean", "action", "sigma") + tuple(names))
 
 
 def _call(torch, env, mean0, sigma0, rate, lo, hi, it, k, lam, penalty, want=ALL, sigma_call=SIGMA, **kw):
@@ -67,74 +69,11 @@ def _call(torch, env, mean0, sigma0, rate, lo, hi, it, k, lam, penalty, want=ALL
     return res
 
 
-def _sigma_tolerance(env, k, rate, hi, sd_ref):
-    low, high = FR.box(env)
-    u_max = max(np.abs(low).max(), np.abs(high).max())
-    v = 4.0 * (k + 17) * EPS * 4.0 * u_max * u_max
-    with np.errstate(divide="ignore"):
-        root = np.minimum(np.sqrt(v), v / sd_ref)
-    return rate * (root + 3 * EPS * u_max) + 3 * EPS * max(2 * u_max, float(np.max(hi)))
-
-
 def _teacher_forced(torch, env, res, sigma_in, rate, lo, hi, lam, penalty, oracle_args=None, rows=None, fields=None, weight=0.0,
                     tag=""):
-    """res: Mppi of an adapt call with all optional outputs (and iter_value / iter_score with fields).  sigma_in: the widths
-    passed in.  rows: the envs to compare (None: all).  -> number of collided candidates"""
-    low, high = FR.box(env)
-    it, n, k = res.iter_ret.shape
-    sel = slice(None) if rows is None else rows
-    tsel = slice(None) if rows is None else torch.from_numpy(np.asarray(rows)).cuda()
-    tol = FR.tolerance(env, k)
-    np.testing.assert_array_equal(res.iter_sigma[0].cpu().numpy()[sel], AR.clampd(sigma_in, lo, hi)[sel],
-                                  err_msg="%s: iter_sigma[0] is the input through the clamp" % tag)
-    worst_mean, worst_sigma, worst_ratio, worst_ret, hits = 0.0, 0.0, 0.0, 0.0, 0
-    for j in range(it):
-        mean_j, sigma_j, eps_j = (t[j].cpu().numpy() for t in (res.iter_mean, res.iter_sigma, res.eps))
-        assert (eps_j[sel][:, 0] == 0).all(), "candidate 0 is the unperturbed mean"
-        assert ((sigma_j[sel] >= lo) & (sigma_j[sel] <= hi)).all(), "%s iteration %d: a width outside the clamps" % (tag, j)
-        u = AR.candidates(mean_j, sigma_j, eps_j, low, high)
-        la = env.lookahead(torch.from_numpy(MR.as_lookahead_actions(u)).cuda(), want=("final_pose",) if fields is not None else ())
-        assert torch.equal(la.ret[tsel], res.iter_ret[j][tsel]), "%s iteration %d: ret differs from lookahead's by %g" % (
-            tag, j, (la.ret[tsel] - res.iter_ret[j][tsel]).abs().max())
-        assert torch.equal(la.reason[tsel], res.iter_reason[j][tsel]), "%s iteration %d: reason" % (tag, j)
-        ret, reason = res.iter_ret[j].cpu().numpy(), res.iter_reason[j].cpu().numpy()
-        if oracle_args is not None:
-            oracle, params, world, start = oracle_args
-            exp = LR.oracle_lookahead(oracle, params, world, start, MR.as_lookahead_actions(u), threads=16)
-            np.testing.assert_array_equal(reason[sel], exp["reason"][sel], err_msg="%s iteration %d reason" % (tag, j))
-            worst_ret = max(worst_ret, np.abs(ret[sel] - exp["ret"][sel]).max())
-        score = MR.scores(ret, reason, penalty)
-        if fields is not None:
-            row_env = torch.arange(n, dtype=torch.int32, device="cuda").repeat_interleave(k)
-            _o, cell = fields.sample(la.final_pose.reshape(n * k, 3), row_env=row_env, carrot_cells=1, want=("cell_value",))
-            assert torch.equal(cell.reshape(n, k)[tsel], res.iter_value[j][tsel]), "%s iteration %d: value" % (tag, j)
-            score = FR.scores(ret, reason, penalty, res.iter_value[j].cpu().numpy(), env.resolution, weight)
-            assert torch.equal(torch.from_numpy(score).cuda()[tsel], res.iter_score[j][tsel]), "%s iteration %d: score" % (tag, j)
-        got_mean = (res.iter_mean[j + 1] if j + 1 < it else res.mean).cpu().numpy()
-        got_sigma = (res.iter_sigma[j + 1] if j + 1 < it else res.sigma).cpu().numpy()
-        want_mean, want_sigma, w = AR.update(u, score, lam, sigma_j, rate, lo, hi, new_mean=got_mean)
-        worst_mean = max(worst_mean, np.abs(got_mean[sel] - want_mean[sel]).max())
-        bound = _sigma_tolerance(env, k, rate, hi, AR.spread(u, w, got_mean))
-        err = np.abs(got_sigma - want_sigma)
-        worst_sigma = max(worst_sigma, err[sel].max())
-        worst_ratio = max(worst_ratio, (err / bound)[sel].max())
-        hits += int(((reason[sel] & LR.DONE_COLLIDED) != 0).sum())
-    print("%s: max |mean - restatement| = %.3g (bound %.3g), max |sigma - restatement| = %.3g (%.3g of its bound, which is >= "
-          "%.3g), max |ret - oracle| = %.3g, %d collided candidates"
-          % (tag, worst_mean, tol, worst_sigma, worst_ratio, 3 * EPS * max(2 * np.abs(high).max(), float(np.max(hi))), worst_ret, hits))
-    assert worst_ret <= 1e-9, tag
-    assert worst_mean <= tol, tag
-    assert worst_ratio <= 1.0, tag
-    assert torch.equal(res.action[tsel], res.mean[:, 0][tsel]), tag
-    return hits
-
-
-def _scenario_env(torch, kind, n):
-    """'scatter' / 'goal' on a handle that has noise on (the refinement must not care), 'aisle' as recorded"""
-    g, name, start = MR.scenario_world(kind, n)
-    env = env_from_traj(g, "mini_with_noise" if "mini" in name else name, n_envs=n)
-    FR.set_start(torch, env, start)
-    return g, name, start, env
+    """sigma_in: the widths passed in.  -> number of collided candidates"""
+    return MC.teacher_forced(torch, env, res, None, lam, penalty, oracle_args=oracle_args, rows=rows, fields=fields, weight=weight,
+                             widths=MC.Widths(sigma_in, rate, lo, hi), tag=tag).hits
 
 
 def _random_widths(rng, n, h, lo=LO, hi=HI):
@@ -148,7 +87,7 @@ def test_scenarios_teacher_forced(torch_cuda, oracle, kind):
     """the scenarios tests/test_mppi_adapt_host.py shows to be non-vacuous, with its perturbations, I = 3 and rate = 0.5"""
     torch = torch_cuda
     (n, k, h), _, sigma, lam, penalty = MR.SCENARIOS[kind]
-    g, name, start, env = _scenario_env(torch, kind, n)
+    g, name, start, env = MC.scenario_env(torch, kind, n)
     widths, lo, hi = AR.scenario_widths(kind, n, h)
     eps = MR.host_eps(MR.EPS_SEED, 5, n, k, h)[:3]
     res = _call(torch, env, MR.initial_mean(kind, n, h), widths, 0.5, lo, hi, 3, k, lam, penalty, sigma_call=sigma, eps=eps)
@@ -166,9 +105,9 @@ def test_shapes_with_device_perturbations(torch_cuda, n, k, h, it, masked):
     """eight envs per wave with a ragged last wave and reductions over 8 lanes; one env per wave; four and sixteen chunks per
     lane (the second walk makes the commands of all chunks but the last again).  Rows masked out keep what they held"""
     torch = torch_cuda
-    g, name, start, env = _scenario_env(torch, "scatter", n)
+    g, name, start, env = MC.scenario_env(torch, "scatter", n)
     rng = np.random.RandomState(n + k)
-    mean0, widths = FR.random_mean(env, rng, n, h), _random_widths(rng, n, h)
+    mean0, widths = MC.random_mean(env, rng, n, h), _random_widths(rng, n, h)
     kw, rows = {}, None
     if masked:
         mask = (np.arange(n) % 3 != 1).astype(np.uint8)
@@ -191,7 +130,7 @@ def test_shapes_with_device_perturbations(torch_cuda, n, k, h, it, masked):
 def test_rate_zero_with_constant_widths_is_plain_mppi_bit_for_bit(torch_cuda):
     torch = torch_cuda
     n, k, h, it = 32, 32, 16, 2
-    g, name, start, env = _scenario_env(torch, "scatter", n)
+    g, name, start, env = MC.scenario_env(torch, "scatter", n)
     mean0 = MR.initial_mean("scatter", n, h)
     widths = np.ascontiguousarray(np.broadcast_to(np.array(SIGMA), (n, h, 2)))
     plain = env.mppi(mean0, SIGMA, it, k, LAM, PENALTY, seed=9, draw_index=4, want=PLAIN)
@@ -222,7 +161,7 @@ def test_a_greedy_rate_puts_widths_on_the_lower_clamp(torch_cuda):
     """'scatter' at rate = 1.0 with the host test's perturbations: at least 5 % of iter_sigma[1] equals sigma_min"""
     torch = torch_cuda
     (n, k, h), _, sigma, lam, penalty = MR.SCENARIOS["scatter"]
-    g, name, start, env = _scenario_env(torch, "scatter", n)
+    g, name, start, env = MC.scenario_env(torch, "scatter", n)
     widths, lo, hi = AR.scenario_widths("scatter", n, h)
     eps = MR.host_eps(MR.EPS_SEED, 5, n, k, h)[:2]
     res = _call(torch, env, MR.initial_mean("scatter", n, h), widths, 1.0, lo, hi, 2, k, lam, penalty, sigma_call=sigma, eps=eps)
@@ -237,9 +176,9 @@ def test_poisoned_widths_go_through_the_entry_clamp(torch_cuda):
     those of a run without the poison"""
     torch = torch_cuda
     n, k, h, it = 12, 16, 4, 2
-    g, name, start, env = _scenario_env(torch, "scatter", n)
+    g, name, start, env = MC.scenario_env(torch, "scatter", n)
     rng = np.random.RandomState(4)
-    mean0, clean = FR.random_mean(env, rng, n, h), _random_widths(rng, n, h)
+    mean0, clean = MC.random_mean(env, rng, n, h), _random_widths(rng, n, h)
     poisoned = clean.copy()
     poisoned[3] = np.array([[np.nan, -1.0], [np.inf, 1e9], [-1.0, np.nan], [1e9, np.inf]])
     poisoned[8, 1:3] = np.array([[np.nan, np.nan], [np.inf, -np.inf]])
@@ -260,12 +199,12 @@ def test_poisoned_widths_go_through_the_entry_clamp(torch_cuda):
 def _configuration(torch, env, k, h, it, tag, lam=0.3, **kw):
     rng = np.random.RandomState(17)
     n = env.n_envs
-    before = FR.read_start(env)
+    before = MC.read_start(env)
     widths = _random_widths(rng, n, h)
-    res = _call(torch, env, FR.random_mean(env, rng, n, h), widths, 0.5, LO, HI, it, k, lam, PENALTY, seed=11, draw_index=5, **kw)
+    res = _call(torch, env, MC.random_mean(env, rng, n, h), widths, 0.5, LO, HI, it, k, lam, PENALTY, seed=11, draw_index=5, **kw)
     hits = _teacher_forced(torch, env, res, widths, 0.5, LO, HI, lam, PENALTY, tag=tag, fields=kw.get("goal_field"),
                            weight=kw.get("terminal_weight", 0.0))
-    after = FR.read_start(env)
+    after = MC.read_start(env)
     for f in ("robot", "min_dist", "target_idx", "cur_iter", "collided"):
         np.testing.assert_array_equal(getattr(before, f), getattr(after, f))
     return res, hits
@@ -283,7 +222,7 @@ def test_diffdrive(torch_cuda):
     robot = np.zeros((7, n))
     robot[:] = g["start_state"][:, None]
     robot[0:3] += np.concatenate([rng.normal(0, 0.05, (2, n)), rng.normal(0, 0.4, (1, n))])
-    FR.set_start(torch, env, LR.StartState(robot, np.full(n, float(g["init_min_dist"])), np.full(n, int(g["init_target_idx"])),
+    MC.set_start(torch, env, LR.StartState(robot, np.full(n, float(g["init_min_dist"])), np.full(n, int(g["init_target_idx"])),
                                            np.zeros(n)))
     _configuration(torch, env, 32, 12, 2, "diffdrive")
 
@@ -296,24 +235,17 @@ def test_pure_pursuit(torch_cuda):
     res, n = float(g["resolution"]), 16
     params = EnvParams(resolution=res, refine_path=False, reward_provider_name='continuous_reward_pure_pursuit')
     env = BatchedPlanEnv(CostMap2D(g["costmap"], res, g["origin"]), g["path"], params, n_envs=n)
-    FR.drive(env, np.random.RandomState(4), 30, 2.0)
+    MC.drive(env, np.random.RandomState(4), 30, 2.0)
     _configuration(torch, env, 64, 12, 2, "pure pursuit", lam=0.05)
     fields = env.goal_field()
     _configuration(torch, env, 16, 8, 2, "pure pursuit with a goal field", lam=0.05, want=FIELD, goal_field=fields,
                    terminal_weight=WEIGHT)
 
 
-def _mini_pool(n, timeout, **kw):
-    from bc_gym_planning_env_amd import EnvParams, mini_env
-    params = mini_env.RandomMiniEnvParams(env_params=EnvParams(goal_ang_dist=np.pi / 8., goal_spat_dist=0.2, iteration_timeout=timeout))
-    pool = mini_env.sample_pool(params, [1, 2, 3, 4], 4)
-    return mini_env.BatchedRandomMiniEnv(n, params, pool=pool, auto_reset=True, seed=2, **kw)
-
-
 def test_mini_pool_with_envs_on_different_entries(torch_cuda):
     torch = torch_cuda
-    env = _mini_pool(48, timeout=12)
-    FR.drive(env, np.random.RandomState(1), 60, 1.0)
+    env = MC.mini_pool(48, timeout=12)
+    MC.drive(env, np.random.RandomState(1), 60, 1.0)
     assert len(np.unique(env.geom_of_env.cpu().numpy())) >= 4
     _configuration(torch, env, 16, 8, 2, "mini pool")
 
@@ -328,7 +260,7 @@ def test_private_maps_and_paths(torch_cuda):
     costmaps = [CostMap2D(gs[i % 4]["costmap"], res, gs[i % 4]["origin"]) for i in range(n)]
     paths = [gs[i % 4]["path"][:len(gs[i % 4]["path"]) - (i % 3)] for i in range(n)]
     env = BatchedPlanEnv(costmaps, paths, EnvParams(resolution=res, refine_path=False), n_envs=n, seed=5)
-    FR.drive(env, np.random.RandomState(9), 25, 2.0)
+    MC.drive(env, np.random.RandomState(9), 25, 2.0)
     _configuration(torch, env, 16, 8, 2, "private maps")
 
 
@@ -336,7 +268,7 @@ def test_goal_field_teacher_forced(torch_cuda):
     """the FIELD kernels: values, scores (tests/mppi_field_ref.py) and, from those scores, the mean and the widths"""
     torch = torch_cuda
     n, k, h, it = 16, 64, 8, 2
-    g, name, start, env = _scenario_env(torch, "scatter", n)
+    g, name, start, env = MC.scenario_env(torch, "scatter", n)
     fields = env.goal_field()
     res, _ = _configuration(torch, env, k, h, it, "goal field", lam=LAM, want=FIELD, goal_field=fields, terminal_weight=WEIGHT)
     values = res.iter_value.cpu().numpy()
@@ -349,9 +281,9 @@ def test_goal_field_teacher_forced(torch_cuda):
 def test_replay_and_same_draw_reproduce_everything(torch_cuda):
     torch = torch_cuda
     n, k, h, it = 24, 128, 6, 2
-    g, name, start, env = _scenario_env(torch, "goal", n)
+    g, name, start, env = MC.scenario_env(torch, "goal", n)
     rng = np.random.RandomState(6)
-    mean0, widths = FR.random_mean(env, rng, n, h), _random_widths(rng, n, h)
+    mean0, widths = MC.random_mean(env, rng, n, h), _random_widths(rng, n, h)
 
     def call(**kw):
         return _snapshot(_call(torch, env, mean0, widths, 0.5, LO, HI, it, k, LAM, PENALTY, **kw), ALL)
@@ -366,33 +298,28 @@ def test_replay_and_same_draw_reproduce_everything(torch_cuda):
 
 
 # ---------------------------------------------------------------------------------------------- 7. nothing moved
-def _state_tensors(env):
-    s = env.state
-    return [s.robot, s.min_spat_dist_so_far, s.target_idx, s.current_iter, s.robot_collided, env.geom_of_env]
-
-
 def test_the_handle_is_untouched(torch_cuda):
     """a pool with auto-reset and on-device noise: state and geom_of_env are bit-identical after each of 10 calls, and the
     steps in between equal those of a twin that never called it"""
     torch = torch_cuda
     n, k, h = 64, 16, 8
-    env, twin = (_mini_pool(n, timeout=12, noise_parameters="planenv") for _ in range(2))
+    env, twin = (MC.mini_pool(n, timeout=12, noise_parameters="planenv") for _ in range(2))
     rng = np.random.RandomState(2)
-    mean = torch.from_numpy(FR.random_mean(env, rng, n, h)).cuda()
+    mean = torch.from_numpy(MC.random_mean(env, rng, n, h)).cuda()
     widths = torch.from_numpy(_random_widths(rng, n, h)).cuda()
     adapt = dict(sigma=widths, rate=0.5, sigma_min=LO, sigma_max=HI)
     for t in range(20):
         a = env.action_space.sample_batch(n, rng)
         if t % 2 == 0:
-            before = [x.clone() for x in _state_tensors(env)]
+            before = [x.clone() for x in MC.state_tensors(env)]
             res = env.mppi(mean, SIGMA, 2, k, LAM, PENALTY, seed=1, draw_index=t, want=ALL, adapt=adapt)
-            for b, x in zip(before, _state_tensors(env)):
+            for b, x in zip(before, MC.state_tensors(env)):
                 assert torch.equal(b, x), "call at step %d" % t
             assert res.sigma.data_ptr() == widths.data_ptr() and bool(torch.isfinite(res.mean).all())
         _, r1, d1, _ = env.step(a)
         _, r2, d2, _ = twin.step(a)
         assert torch.equal(r1, r2) and torch.equal(d1, d2), t
-        for x, y in zip(_state_tensors(env), _state_tensors(twin)):
+        for x, y in zip(MC.state_tensors(env), MC.state_tensors(twin)):
             assert torch.equal(x, y), t
     lo, hi = (torch.tensor(v, dtype=torch.float64, device="cuda") for v in (LO, HI))
     assert bool(((widths >= lo) & (widths <= hi)).all())
@@ -405,7 +332,7 @@ def test_captured_call_replayed_twice_equals_two_direct_calls(torch_cuda):
     """captured with draw_index on the device; each replay refines, in place, the mean and the widths the one before left"""
     torch = torch_cuda
     n, k, h, it = 32, 32, 8, 2
-    g, name, start, env = _scenario_env(torch, "scatter", n)
+    g, name, start, env = MC.scenario_env(torch, "scatter", n)
     rng = np.random.RandomState(8)
     mean0 = torch.from_numpy(MR.initial_mean("scatter", n, h)).cuda()
     widths0 = torch.from_numpy(_random_widths(rng, n, h)).cuda()
@@ -445,7 +372,7 @@ def test_captured_call_replayed_twice_equals_two_direct_calls(torch_cuda):
 # ---------------------------------------------------------------------------------------------- 9. refusals, Python surface
 def _raw(env, mean, action, ad, term=None, flags=0, **over):
     from bc_gym_planning_env_amd import _lib
-    low, high = FR.box(env)
+    low, high = MC.box(env)
     p, io = _lib.BcpMppiParams(), _lib.BcpMppiIO()
     p.horizon, p.n_candidates, p.iterations = int(mean.shape[1]), 16, 1
     for d in range(2):
@@ -466,7 +393,7 @@ def test_refusals(torch_cuda):
     torch = torch_cuda
     from bc_gym_planning_env_amd import _lib
     n = 8
-    g, name, start, env = _scenario_env(torch, "scatter", n)
+    g, name, start, env = MC.scenario_env(torch, "scatter", n)
     fields = env.goal_field()
     rows, cols = int(fields.field.shape[1]), int(fields.field.shape[2])
     mean = torch.zeros(n, 4, 2, dtype=torch.float64, device="cuda") + 0.3

@@ -5,6 +5,7 @@ from the mean the kernel took into it (iter_mean[j]) and the perturbations it us
 Parity at iteration j, all bit for bit: u_j is rebuilt in numpy (mppi_ref.candidates); env.lookahead(u_j) gives iter_ret[j]
 and iter_reason[j] and the final poses; fields.sample(final poses, row_env) gives iter_value[j]; the numpy score
 (mppi_field_ref.scores) of (ret, reason, value) gives iter_score[j].
+The checker is tests/mppi_check.teacher_forced with `fields`.
 Update: the next mean lies within 4 (K + 16) 2^-53 max(|low|, |high|) of the longdouble restatement applied to the kernel's
 own scores -- the derivation of tests/test_gpu_mppi.py carries over as it stands, the scores enter it as given bits."""
 import ctypes as C
@@ -15,9 +16,10 @@ import pytest
 
 import goal_field_ref as GR
 import lookahead_ref as LR
+import mppi_check as MC
 import mppi_field_ref as FR
 import mppi_ref as MR
-from util import GOLDEN, env_from_traj
+from util import GOLDEN
 
 pytestmark = pytest.mark.gpu
 
@@ -27,51 +29,15 @@ OUT = ("mean", "action") + ALL
 SIGMA, LAM, PENALTY, WEIGHT = (0.2, 0.8), 0.4, 2.0, 4.0
 
 
-def _snapshot(res, names=OUT):
-    return {f: getattr(res, f).clone() for f in names if getattr(res, f) is not None}
-
-
 def _teacher_forced(torch, env, fields, res, sigma, lam, penalty, weight, rows=None, tag=""):
-    """res: Mppi with all optional outputs, from env.mppi(..., goal_field=fields, terminal_weight=weight).  rows: the envs to
-    compare (None: all).  -> (values [I, N, K], reasons [I, N, K]) as numpy"""
-    low, high = FR.box(env)
-    it, n, k = res.iter_ret.shape
-    sel = slice(None) if rows is None else rows
-    tsel = slice(None) if rows is None else torch.from_numpy(np.asarray(rows)).cuda()
-    tol = FR.tolerance(env, k)
-    row_env = torch.arange(n, dtype=torch.int32, device="cuda").repeat_interleave(k)
-    worst = 0.0
-    for j in range(it):
-        mean_j = res.iter_mean[j].cpu().numpy()
-        eps_j = res.eps[j].cpu().numpy()
-        assert (eps_j[sel][:, 0] == 0).all(), "candidate 0 is the unperturbed mean"
-        u = MR.candidates(mean_j, sigma, eps_j, low, high)
-        la = env.lookahead(torch.from_numpy(MR.as_lookahead_actions(u)).cuda(), want=("final_pose",))
-        assert torch.equal(la.ret[tsel], res.iter_ret[j][tsel]), "%s iteration %d: ret is not lookahead's" % (tag, j)
-        assert torch.equal(la.reason[tsel], res.iter_reason[j][tsel]), "%s iteration %d: reason" % (tag, j)
-        _out3, cell = fields.sample(la.final_pose.reshape(n * k, 3), row_env=row_env, carrot_cells=1, want=("cell_value",))
-        assert torch.equal(cell.reshape(n, k)[tsel], res.iter_value[j][tsel]), "%s iteration %d: value is not the sampler's" % (tag, j)
-        ret, reason, value = (t[j].cpu().numpy() for t in (res.iter_ret, res.iter_reason, res.iter_value))
-        score = FR.scores(ret, reason, penalty, value, env.resolution, weight)
-        assert torch.equal(torch.from_numpy(score).cuda()[tsel], res.iter_score[j][tsel]), "%s iteration %d: score differs by %g" % (
-            tag, j, np.abs(score - res.iter_score[j].cpu().numpy())[sel].max())
-        want, _ = FR.update(u, res.iter_score[j].cpu().numpy(), lam)
-        got = (res.iter_mean[j + 1] if j + 1 < it else res.mean).cpu().numpy()
-        worst = max(worst, np.abs(got[sel] - want[sel]).max())
-    values, reasons = res.iter_value.cpu().numpy()[:, sel], res.iter_reason.cpu().numpy()[:, sel]
-    print("%s: max |mean - restatement| = %.3g (bound %.3g), values %d .. %d, %d of %d without a route, %d collided"
-          % (tag, worst, tol, values.min(), values[values != GR.NONE].max() if (values != GR.NONE).any() else -1,
-             (values == GR.NONE).sum(), values.size, ((reasons & LR.DONE_COLLIDED) != 0).sum()))
-    assert worst <= tol, tag
-    assert torch.equal(res.action[tsel], res.mean[:, 0][tsel]), tag
-    return values, reasons
+    """-> (values [I, N, K], reasons [I, N, K]) of the rows compared, as numpy"""
+    c = MC.teacher_forced(torch, env, res, sigma, lam, penalty, rows=rows, fields=fields, weight=weight, tag=tag)
+    return c.values, c.reasons
 
 
 def _scatter_env(torch, n):
     """the 'scatter' scenario of tests/mppi_ref.py: one map and one path for all envs, the handle with noise on"""
-    g, name, start = MR.scenario_world("scatter", n)
-    env = env_from_traj(g, "mini_with_noise", n_envs=n)
-    FR.set_start(torch, env, start)
+    g, _name, start, env = MC.scenario_env(torch, "scatter", n)
     return g, start, env
 
 
@@ -102,13 +68,13 @@ def test_odd_env_count_and_mask(torch_cuda):
     g, _start, env = _scatter_env(torch, n)
     fields = env.goal_field()
     rng = np.random.RandomState(1)
-    res = env.mppi(FR.random_mean(env, rng, n, h), SIGMA, it, k, LAM, PENALTY, seed=1, want=ALL, goal_field=fields,
+    res = env.mppi(MC.random_mean(env, rng, n, h), SIGMA, it, k, LAM, PENALTY, seed=1, want=ALL, goal_field=fields,
                    terminal_weight=WEIGHT)
     _teacher_forced(torch, env, fields, res, SIGMA, LAM, PENALTY, WEIGHT, tag="N=37")
-    first = _snapshot(res)
+    first = MC.snapshot(res, OUT)
     mask = (np.arange(n) % 3 != 1).astype(np.uint8)
     off = torch.from_numpy(mask == 0).cuda()
-    mean1 = torch.from_numpy(FR.random_mean(env, rng, n, h)).cuda()
+    mean1 = torch.from_numpy(MC.random_mean(env, rng, n, h)).cuda()
     before = mean1.clone()
     res2 = env.mppi(mean1, SIGMA, it, k, LAM, PENALTY, seed=2, mask=mask, want=ALL, goal_field=fields, terminal_weight=WEIGHT)
     assert res2.mean.data_ptr() == mean1.data_ptr() and torch.equal(res2.mean[off], before[off])
@@ -119,17 +85,26 @@ def test_odd_env_count_and_mask(torch_cuda):
     assert not torch.equal(res2.mean[~off], before[~off])
 
 
+@pytest.mark.parametrize("n,k,h,it", [(9, 8, 3, 2), (3, 128, 3, 2)])
+def test_replayed_perturbations_below_and_above_a_wave(torch_cuda, n, k, h, it):
+    """eps_in where its index takes the env (K = 8: eight envs per wave, a second workgroup of one env and seven shadows)
+    and the chunk (K = 128: two): a call fed the perturbations another drew gives every output of that call"""
+    torch = torch_cuda
+    g, _start, env = _scatter_env(torch, n)
+    fields = env.goal_field()
+    mean0 = MR.initial_mean("scatter", n, h)
+    kw = dict(want=ALL, goal_field=fields, terminal_weight=WEIGHT)
+    a = MC.snapshot(env.mppi(mean0, SIGMA, it, k, LAM, PENALTY, seed=9, draw_index=4, **kw), OUT)
+    replay = MC.snapshot(env.mppi(mean0, SIGMA, it, k, LAM, PENALTY, eps=a["eps"], **kw), OUT)
+    assert (a["eps"][:, :, 1:] != 0).any()
+    for f in OUT:
+        assert torch.equal(a[f], replay[f]), "eps_out fed back as eps_in: " + f
+
+
 # ---------------------------------------------------------------------------------------------- 2. bindings
-def _mini_pool(n, timeout, seeds=(1, 2, 3, 4), episodes=4, **kw):
-    from bc_gym_planning_env_amd import EnvParams, mini_env
-    params = mini_env.RandomMiniEnvParams(env_params=EnvParams(goal_ang_dist=np.pi / 8., goal_spat_dist=0.2, iteration_timeout=timeout))
-    pool = mini_env.sample_pool(params, list(seeds), episodes)
-    return mini_env.BatchedRandomMiniEnv(n, params, pool=pool, auto_reset=True, seed=2, **kw)
-
-
 def _binding(torch, env, fields, k, h, it, tag, seed=11):
     rng = np.random.RandomState(17)
-    res = env.mppi(FR.random_mean(env, rng, env.n_envs, h), SIGMA, it, k, LAM, PENALTY, seed=seed, draw_index=5, want=ALL,
+    res = env.mppi(MC.random_mean(env, rng, env.n_envs, h), SIGMA, it, k, LAM, PENALTY, seed=seed, draw_index=5, want=ALL,
                    goal_field=fields, terminal_weight=WEIGHT)
     return _teacher_forced(torch, env, fields, res, SIGMA, LAM, PENALTY, WEIGHT, tag=tag)
 
@@ -138,10 +113,10 @@ def test_mini_pool_with_envs_on_different_entries(torch_cuda):
     """16 entries, 64 envs after auto-resets: an env reads the field of the entry it is on"""
     torch = torch_cuda
     n = 64
-    env = _mini_pool(n, timeout=12)
+    env = MC.mini_pool(n, timeout=12)
     fields = env.goal_field()
     assert fields.field.shape[0] == 16
-    FR.drive(env, np.random.RandomState(1), 60, 1.0)
+    MC.drive(env, np.random.RandomState(1), 60, 1.0)
     geom = env.geom_of_env.cpu().numpy()
     assert len(np.unique(geom)) >= 4
     values, _ = _binding(torch, env, fields, 16, 8, 2, "mini pool")
@@ -165,7 +140,7 @@ def test_aisle_pool_with_padded_valid_shapes(torch_cuda):
     assert env._keep.get("vr") is not None, "the pool's entries are padded to one shape"
     vr, vc = env._keep["vr"].cpu().numpy(), env._keep["vc"].cpu().numpy()
     assert fields.field.shape[0] == 8 and len(set(zip(vr.tolist(), vc.tolist()))) > 1
-    FR.drive(env, np.random.RandomState(2), 50, 1.0)
+    MC.drive(env, np.random.RandomState(2), 50, 1.0)
     assert len(np.unique(env.geom_of_env.cpu().numpy())) > 1
     values, _ = _binding(torch, env, fields, 32, 8, 2, "aisle pool")
     assert (values != GR.NONE).mean() > 0.5
@@ -184,7 +159,7 @@ def test_private_maps(torch_cuda):
     env = BatchedPlanEnv(costmaps, paths, EnvParams(resolution=res, refine_path=False), n_envs=n, seed=5)
     fields = env.goal_field()
     assert fields.field.shape[0] == n
-    FR.drive(env, np.random.RandomState(9), 25, 2.0)
+    MC.drive(env, np.random.RandomState(9), 25, 2.0)
     values, _ = _binding(torch, env, fields, 16, 8, 2, "private maps")
     assert (values != GR.NONE).mean() > 0.5
 
@@ -231,7 +206,7 @@ def test_poses_without_a_route_and_a_first_step_collision(torch_cuda):
     robot[0:2, 0] = origin - 0.5
     robot[0:2, 1] = origin + np.array([c1, r1]) * res
     robot[0:2, 2] = origin + np.array([c2, r2]) * res
-    FR.set_start(torch, env, LR.StartState(robot, start.min_dist, start.target_idx, start.cur_iter))
+    MC.set_start(torch, env, LR.StartState(robot, start.min_dist, start.target_idx, start.cur_iter))
     fields = env.goal_field(clearance=0.0)
     assert fields.clearance_d2 == 0
     res_ = env.mppi(MR.initial_mean("scatter", n, h), SIGMA, it, k, LAM, PENALTY, seed=3, want=ALL, goal_field=fields,
@@ -256,15 +231,15 @@ def test_weight_zero_and_no_field_equal_plain_mppi_and_float32_actions(torch_cud
     g, _start, env = _scatter_env(torch, n)
     fields = env.goal_field()
     mean0 = MR.initial_mean("scatter", n, h)
-    plain = _snapshot(env.mppi(mean0, SIGMA, it, k, LAM, PENALTY, seed=9, draw_index=4, want=PLAIN))
-    none = _snapshot(env.mppi(mean0, SIGMA, it, k, LAM, PENALTY, seed=9, draw_index=4, want=PLAIN, goal_field=None, terminal_weight=0.0))
-    zero = _snapshot(env.mppi(mean0, SIGMA, it, k, LAM, PENALTY, seed=9, draw_index=4, want=ALL, goal_field=fields, terminal_weight=0.0))
+    plain = MC.snapshot(env.mppi(mean0, SIGMA, it, k, LAM, PENALTY, seed=9, draw_index=4, want=PLAIN), OUT)
+    none = MC.snapshot(env.mppi(mean0, SIGMA, it, k, LAM, PENALTY, seed=9, draw_index=4, want=PLAIN, goal_field=None, terminal_weight=0.0), OUT)
+    zero = MC.snapshot(env.mppi(mean0, SIGMA, it, k, LAM, PENALTY, seed=9, draw_index=4, want=ALL, goal_field=fields, terminal_weight=0.0), OUT)
     for f in ("mean", "action") + PLAIN:
         assert torch.equal(plain[f], none[f]), "goal_field=None: " + f
         assert torch.equal(plain[f], zero[f]), "weight 0: " + f
     want = MR.scores(zero["iter_ret"].cpu().numpy(), zero["iter_reason"].cpu().numpy(), PENALTY)
     assert torch.equal(zero["iter_score"], torch.from_numpy(want).cuda()) and (zero["iter_value"] != GR.NONE).any()
-    some = _snapshot(env.mppi(mean0, SIGMA, it, k, LAM, PENALTY, seed=9, draw_index=4, want=ALL, goal_field=fields, terminal_weight=WEIGHT))
+    some = MC.snapshot(env.mppi(mean0, SIGMA, it, k, LAM, PENALTY, seed=9, draw_index=4, want=ALL, goal_field=fields, terminal_weight=WEIGHT), OUT)
     assert not torch.equal(some["mean"], plain["mean"]) and torch.equal(some["iter_ret"][0], plain["iter_ret"][0])
     f32 = env.mppi(mean0, SIGMA, it, k, LAM, PENALTY, seed=9, draw_index=4, goal_field=fields, terminal_weight=WEIGHT,
                    action_dtype=torch.float32)
@@ -274,32 +249,27 @@ def test_weight_zero_and_no_field_equal_plain_mppi_and_float32_actions(torch_cud
     env.check_errors()
 
 
-def _state_tensors(env):
-    s = env.state
-    return [s.robot, s.min_spat_dist_so_far, s.target_idx, s.current_iter, s.robot_collided, env.geom_of_env]
-
-
 def test_the_handle_is_untouched(torch_cuda):
     """a pool with auto-reset and on-device noise: state and geom_of_env are bit-identical after each of 10 calls, and the
     steps in between equal those of a twin that never called it"""
     torch = torch_cuda
     n, k, h = 64, 16, 8
-    env, twin = (_mini_pool(n, timeout=12, noise_parameters="planenv") for _ in range(2))
+    env, twin = (MC.mini_pool(n, timeout=12, noise_parameters="planenv") for _ in range(2))
     fields = env.goal_field()
     rng = np.random.RandomState(2)
-    mean = torch.from_numpy(FR.random_mean(env, rng, n, h)).cuda()
+    mean = torch.from_numpy(MC.random_mean(env, rng, n, h)).cuda()
     for t in range(20):
         a = env.action_space.sample_batch(n, rng)
         if t % 2 == 0:
-            before = [x.clone() for x in _state_tensors(env)]
+            before = [x.clone() for x in MC.state_tensors(env)]
             res = env.mppi(mean, SIGMA, 2, k, LAM, PENALTY, seed=1, draw_index=t, want=ALL, goal_field=fields, terminal_weight=WEIGHT)
-            for b, x in zip(before, _state_tensors(env)):
+            for b, x in zip(before, MC.state_tensors(env)):
                 assert torch.equal(b, x), "call at step %d" % t
             assert bool(torch.isfinite(res.mean).all())
         _, r1, d1, _ = env.step(a)
         _, r2, d2, _ = twin.step(a)
         assert torch.equal(r1, r2) and torch.equal(d1, d2), t
-        for x, y in zip(_state_tensors(env), _state_tensors(twin)):
+        for x, y in zip(MC.state_tensors(env), MC.state_tensors(twin)):
             assert torch.equal(x, y), t
     env.check_errors()
     twin.check_errors()
@@ -319,7 +289,7 @@ def test_captured_call_replayed_twice_equals_two_direct_calls(torch_cuda):
     direct = []
     mean = mean0.clone()
     for d in range(2):
-        direct.append(_snapshot(call(mean, d)))
+        direct.append(MC.snapshot(call(mean, d), OUT))
     assert not torch.equal(direct[0]["mean"], direct[1]["mean"])
     word = torch.zeros(1, dtype=torch.int64, device="cuda")
     mean = mean0.clone()
@@ -346,7 +316,7 @@ def test_captured_call_replayed_twice_equals_two_direct_calls(torch_cuda):
 # ---------------------------------------------------------------------------------------------- 5. refusals
 def _raw(env, mean, action, term, flags=0, **over):
     from bc_gym_planning_env_amd import _lib
-    low, high = FR.box(env)
+    low, high = MC.box(env)
     p, io = _lib.BcpMppiParams(), _lib.BcpMppiIO()
     p.horizon, p.n_candidates, p.iterations = int(mean.shape[1]), 16, 1
     for d in range(2):
@@ -414,7 +384,7 @@ def test_planner_with_a_goal_field(torch_cuda):
     n, ticks = 64, 20
     runs = {}
     for which, weight in (("plain", None), ("zero", 0.0), ("weighted", WEIGHT)):
-        env = _mini_pool(n, timeout=60)
+        env = MC.mini_pool(n, timeout=60)
         kw = {} if weight is None else dict(goal_field=env.goal_field(), terminal_weight=weight)
         planner = MPPIPlanner(env, horizon=12, n_candidates=32, iterations=2, sigma=(0.2, 0.6), lam=0.3, collision_penalty=2.0,
                               seed=0, **kw)

@@ -254,7 +254,8 @@ def test_lookahead_with_everything_moved(torch_cuda, oracle):
 
 
 def test_mppi_with_everything_moved(torch_cuda, oracle):
-    from test_gpu_mppi import ALL, _teacher_forced
+    import mppi_check as MC
+    from test_gpu_mppi import ALL
     torch = torch_cuda
     k, horizon, sigma, lam, penalty = 16, 8, (0.2, 0.8), 0.3, 2.0
     b, env, start, world, p = _planning_case(torch, oracle)
@@ -262,5 +263,5 @@ def test_mppi_with_everything_moved(torch_cuda, oracle):
     mean = np.ascontiguousarray(np.broadcast_to(np.array((0.4, 0.0)), (b.n, horizon, 2)))
     res = env.mppi(mean, sigma, 2, k, lam, penalty, eps=eps, want=ALL)
     assert torch.equal(res.eps, torch.from_numpy(eps).cuda())
-    hits = _teacher_forced(torch, env, res, sigma, lam, penalty, (oracle, p, world, start), tag="row 11")
+    hits = MC.teacher_forced(torch, env, res, sigma, lam, penalty, oracle_args=(oracle, p, world, start), tag="row 11").hits
     assert (res.err == 0).all() and hits >= 50
