@@ -16,6 +16,7 @@ ERR_ANGLE_JUMP, ERR_TIME_ORDER, ERR_INTERNAL = 1, 2, 4
 DONE_GOAL, DONE_TIMEOUT, DONE_COLLIDED = 1, 2, 4
 TUNE_EXACT_MODE, TUNE_DENSE_THRESHOLD, TUNE_CULL, TUNE_DEFER, TUNE_EDT_LDS, TUNE_FUSED, TUNE_EGO_SPARSE, TUNE_NEAR_DILATE = 0, 1, 2, 3, 4, 5, 6, 7
 TUNE_LOCAL_PAIRS, TUNE_EGO_LIST_STRIDE, TUNE_NEAR_SHIFT, TUNE_INFLATE_ROUTE, TUNE_GOAL_ROUTE = 8, 9, 10, 11, 12
+TUNE_LOCAL_SHARED = 13
 GOAL_ORTHO, GOAL_DIAG, GOAL_FAR, GOAL_NONE = 12, 17, 65534, 65535
 E_NO_DEVICE = -2
 OPT_DIFFDRIVE_NOISE = 1
@@ -195,6 +196,7 @@ SYMBOLS = {
                                         C.c_void_p, C.c_void_p, C.c_void_p]),
     "bcp_device_normals": (C.c_int, [_H, C.c_int64, C.c_int64, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p]),
     "bcp_step_form": (C.c_int, [_H]),
+    "bcp_step_shared_variant": (C.c_int, [_H]),
     "bcp_time_step_kernels": (C.c_int, [_H, C.POINTER(BcpStepIO), C.c_uint32, C.c_int32, C.c_void_p,
                                         C.POINTER(C.c_float)]),
     "bcp_time_steps": (C.c_int, [_H, C.POINTER(BcpStepIO), C.c_uint32, C.c_int32, C.c_void_p, C.POINTER(C.c_float)]),

@@ -848,6 +848,13 @@ class BatchedPlanEnv(Handle):
             _lib.check(form)
         return self.STEP_FORMS[form]
 
+    def step_shared_variant(self):
+        """True when the last step() ran step_local_kernel's shared-geometry variant (bcp_step_shared_variant)."""
+        rc = self._lib.bcp_step_shared_variant(self._h)
+        if rc < 0:
+            _lib.check(rc)
+        return rc == 1
+
     def time_steps(self, actions, steps, noise_z=None):
         """Average device time (ms) of one step over `steps` back-to-back steps, measured with HIP events on the
         launch stream."""

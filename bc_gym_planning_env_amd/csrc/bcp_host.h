@@ -84,6 +84,7 @@ struct Tuning {
     int32_t cull = 1;               // BCP_TUNE_CULL: build and use the distance field
     int32_t fused = 1;              // settle parked poses inside the step launch (step_local_kernel) instead of a second launch
     int32_t local_pairs = 0;        // BCP_TUNE_LOCAL_PAIRS: workgroup size of step_local_kernel (0 = default, 1, 2, 4 x 64 envs)
+    int32_t local_shared = 1;       // BCP_TUNE_LOCAL_SHARED: 1 = step_local_kernel's shared-geometry variant where the handle allows it, 0 = never
     int32_t near_shift = -1;        // BCP_NEAR_SHIFT / BCP_TUNE_NEAR_SHIFT: resolution of step_near for private maps (-1: the library's rule)
     int32_t near_dilate = 1;        // BCP_TUNE_NEAR_DILATE: 0 never, 1 pool refreshes (default), 2 every build (after the field: tests)
     int32_t edt_in_lds = 1;         // distance transform of maps that fit: the LDS-resident kernel (BCP_TUNE_EDT_LDS)
@@ -232,6 +233,7 @@ struct bcp_handle {
     Parking parking;
     DevBuf<uint64_t> parked_slots;  // a word per workgroup of step_local_kernel, its parked poses so far (bcp_parked_poses)
     WaitWatchdog watchdog;
+    int32_t last_local_shared = 0;  // the last step ran step_local_kernel's shared-geometry variant (bcp_step_shared_variant)
     // ---- egocentric views
     DevBuf<int32_t> ego_bins;       // [2][capacity / 2] image counts / first slots per map entry
     DevBuf<int32_t> ego_order;      // [2][capacity / 2] rank within the bin / images grouped by map entry

@@ -1062,7 +1062,9 @@ __device__ __forceinline__ int64_t slot_of(SP S, int64_t i, const Pending& q)
 // pure-pursuit branch out.
 // (A: StepArgs by value, or by reference into the kernel-argument segment -- only a.S, the output pointers and a.flags are used)
 // Returns the episode-record slot the env took (-1: none, or no record bound).
-template <bool PLAIN, typename A, typename SP>
+// SHARED (step_local_kernel's variant for one map, one path and no geometry pool, see step_local_body): the branches on
+// those properties are compiled out.
+template <bool PLAIN, bool SHARED = false, typename A, typename SP>
 __device__ __forceinline__ int finalize_env_from(const A& a, SP S, int64_t i, Pending& q, bool hit, LdsF64 lds_path = nullptr,
                                              const PathWindow* free_window = nullptr, bool have_score = false,
                                              ScoredFree score = ScoredFree(), int known_len = -1, bool score_fits_hit = false,
@@ -1098,9 +1100,9 @@ __device__ __forceinline__ int finalize_env_from(const A& a, SP S, int64_t i, Pe
     double rew = 0.0;
     int m;
     bool goal;
-    const int64_t g = slot_of(S, i, q);
-    const double* pts = S->path.pts + (S->path.shared ? 0 : g * (int64_t)S->path.max_len * 5);
-    m = known_len >= 0 ? known_len : (S->path.shared ? S->path.max_len : S->path.lens[g]);
+    const int64_t g = SHARED ? i : slot_of(S, i, q);
+    const double* pts = S->path.pts + ((SHARED || S->path.shared) ? 0 : g * (int64_t)S->path.max_len * 5);
+    m = known_len >= 0 ? known_len : ((SHARED || S->path.shared) ? S->path.max_len : S->path.lens[g]);
     if (pure_pursuit) {
         if (have_score && !hit) {   // the scorer wave has already done it (no collision: the flag it assumed stands)
             rew = score.rew;
@@ -1120,8 +1122,8 @@ __device__ __forceinline__ int finalize_env_from(const A& a, SP S, int64_t i, Pe
         } else if (!ABLATED(a, kAblateNoReward)) {
             // way-point window of the pose: the caller may have looked it up already for the un-rolled-back pose
             const PathWindow w =
-                (free_window && !hit && !pose_delay) ? *free_window : path_window_of(P, S->path.shared != 0, S->path.bbox, S->path.index, g, seen[0], seen[1]);
-            if (lds_path && S->path.shared)  // way points staged in LDS by the step kernel
+                (free_window && !hit && !pose_delay) ? *free_window : path_window_of(P, SHARED || S->path.shared != 0, S->path.bbox, S->path.index, g, seen[0], seen[1]);
+            if ((SHARED || lds_path) && (SHARED || S->path.shared))  // way points staged in LDS by the step kernel
                 rew = reward_step(P, lds_path, w, m, seen[0], seen[1], seen[2], min_dist, target);
             else
                 rew = reward_step<PLAIN ? 4 : 2>(P, pts, w, m, seen[0], seen[1], seen[2], min_dist, target);
@@ -1147,7 +1149,7 @@ __device__ __forceinline__ int finalize_env_from(const A& a, SP S, int64_t i, Pe
     InitAhead ahead = InitAhead();   // (initialised: left undefined outside the branch, it was kept in scratch memory)
     if (reset) {  // PlanEnv.reset(): set_state(initial_state) (env.py:293-303)
         int64_t k = i;
-        if (S->geom_of_env) {  // RandomMiniEnv.reset(): the env moves on to its next geometry (mini_env.py:469-481).
+        if (!SHARED && S->geom_of_env) {  // RandomMiniEnv.reset(): the env moves on to its next geometry (mini_env.py:469-481).
             // Computed from the entry the step started with, so kernel 2 redoing an env that kernel 1 already reset
             // lands on the same geometry (a hit always ends the episode, so both reset or neither does).
             k = S->next_geom ? as_global(S->next_geom)[g] : g;
@@ -1181,7 +1183,7 @@ __device__ __forceinline__ int finalize_env_from(const A& a, SP S, int64_t i, Pe
         if (done && rec_slot < R.capacity) {   // (beyond: overflow, only counted)
             const int64_t j = rec_slot, c = R.capacity;
             as_global(R.env_id)[j] = (int32_t)i;
-            as_global(R.geom)[j] = S->geom_of_env ? (int32_t)g : -1;
+            as_global(R.geom)[j] = (!SHARED && S->geom_of_env) ? (int32_t)g : -1;
             if (R.ret) as_global(R.final_ret)[j] = ret_sum;
             as_global(R.fin.x)[j] = r.p.x;
             as_global(R.fin.y)[j] = r.p.y;
@@ -1779,10 +1781,18 @@ constexpr uint32_t kDiagWithholdVerdicts = 1u << 23;   // -DBCP_DIAG builds: par
 // form is this code with the loop folded away.
 typedef const __attribute__((address_space(4))) StepArgs* KernArgPtr;
 
+// SHARED: the variant for handles whose geometry is one map and one path, both staged in LDS, with no geometry pool, no
+// per-env origins and the 1-bit `near` tiles (local_step_shared, bcp_step_host.h: C2, C3, the sharded C5, every replica
+// batch).  What the generic variant asks at run time is then known when the kernel is compiled, and the variant holds ONE
+// exact test (on the LDS map), the LDS list scan, classify_near and coop_last_reached for hits -- not both copies of the
+// exact test, the private-path scans and their speculative reward, and the branches between them.  SHARED = false is the
+// code as it was.
+//
 // one step of the workgroup's envs: the whole of the one-step kernel, and one trip (`rs`) of a rollout
-template <bool WIDE, bool PLAIN, int PAIRS, bool ROLL>
+template <bool WIDE, bool PLAIN, int PAIRS, bool ROLL, bool SHARED = false>
 __device__ __forceinline__ void step_local_body(KernArgPtr kernarg, const int rs)
 {
+    static_assert(!SHARED || (PAIRS == 4 && !ROLL), "the shared-geometry variant exists for the 16-wave one-step kernel");
     static_assert(PAIRS == 1 || PAIRS == 2 || PAIRS == 4, "a workgroup holds 1, 2 or 4 (mover, scorer, helper, helper) quartets");
     constexpr int kLocalPairs = PAIRS, kLocalWaves = 4 * PAIRS, kLocalEnvs = PAIRS * kBlock;
     constexpr int kPairShift = PAIRS == 4 ? 2 : (PAIRS == 2 ? 1 : 0);
@@ -1830,9 +1840,12 @@ __device__ __forceinline__ void step_local_body(KernArgPtr kernarg, const int rs
         }
     }
     const int64_t out_base = ROLL ? (int64_t)rs * L.hot.n : 0;
-    const int hot_n_verts = L.hot.n_verts, hot_npath = L.hot.lds_path_doubles, hot_path_shared = L.hot.path_shared;
+    const int hot_n_verts = L.hot.n_verts, hot_npath = L.hot.lds_path_doubles, hot_path_shared = SHARED ? 1 : L.hot.path_shared;
     const int hot_map_rows = L.hot.map_rows, hot_map_cols = L.hot.map_cols, hot_map_wpr = L.hot.map_wpr;
-    const int hot_map_shared = L.hot.map_shared, hot_noise_on = L.hot.noise_on, hot_max_len = L.hot.path_max_len;
+    const int hot_map_shared = SHARED ? 1 : L.hot.map_shared, hot_noise_on = L.hot.noise_on, hot_max_len = L.hot.path_max_len;
+    // (SHARED: no pool and no origins of their own -- the launcher has looked)
+    const int32_t* const hot_geom_of_env = SHARED ? nullptr : L.hot.geom_of_env;
+    const double* const hot_map_origins = SHARED ? nullptr : L.hot.map_origins;
     const int64_t hot_n = L.hot.n;
     // PLAIN (continuous reward, no delays): the backward scan for the last reached way point -- the longest stretch of
     // the reward provider -- is split three ways between the pair's scorer and its two helper waves (every third
@@ -1845,7 +1858,7 @@ __device__ __forceinline__ void step_local_body(KernArgPtr kernarg, const int rs
     __attribute__((address_space(3))) double* qv = (__attribute__((address_space(3))) double*)lds_dyn;
     const int nq = 2 * hot_n_verts;
     const int npath = hot_npath;
-    const LdsF64 lds_path = npath ? (LdsF64)(qv + nq) : (LdsF64) nullptr;
+    const LdsF64 lds_path = (SHARED || npath) ? (LdsF64)(qv + nq) : (LdsF64) nullptr;
     __attribute__((address_space(3))) double* hand_pose = qv + nq + npath + pair * kHandDoubles * kBlock;
     __attribute__((address_space(3))) double* hand_score = hand_pose + 3 * kBlock;
     __attribute__((address_space(3))) double* hand_heading = hand_pose + 6 * kBlock;
@@ -1858,7 +1871,7 @@ __device__ __forceinline__ void step_local_body(KernArgPtr kernarg, const int rs
         (__attribute__((address_space(3))) ParkedPose*)((__attribute__((address_space(3))) char*)lds_dyn + rec_off);
     const LdsU32 cell_list = (LdsU32)(rec + kLocalEnvs) + wave * kSparseLdsWords;
     const LdsU32 lds_map = (LdsU32)(rec + kLocalEnvs) + kLocalWaves * kSparseLdsWords;
-    const int map_words = ((hot_map_shared != 0) & (hot_map_rows * hot_map_wpr <= kLocalMapWords)) ? hot_map_rows * hot_map_wpr : 0;
+    const int map_words = (SHARED || ((hot_map_shared != 0) & (hot_map_rows * hot_map_wpr <= kLocalMapWords))) ? hot_map_rows * hot_map_wpr : 0;
     // the parameter block *S, copied into LDS by the prologue: behind barrier 0 every wave reads its parameters from there.
     // (Scalar fetches of *S take 1.3 - 2.2 k cycles at a kernel start, and a wave that holds the ~60 words it needs of the
     //  block in scalar registers from the start has none left for the launch arguments.)
@@ -1900,27 +1913,27 @@ __device__ __forceinline__ void step_local_body(KernArgPtr kernarg, const int rs
     double own_org_x = 0.0, own_org_y = 0.0;                  // (only ever written by the loads below: a later assignment
     uint64_t own_len_shift = 0;                                // (private path: way points | index shift << 32)
                                                                //  to a register a load is in flight to would wait for it)
-    const bool own_origin = !hot_path_shared || L.hot.map_origins != nullptr;
+    const bool own_origin = !hot_path_shared || hot_map_origins != nullptr;
     if (mover) {
         load_env<PLAIN>(L, 0, 0, i, active, q, cmd0, cmd1, false);
         if (!hot_path_shared) {   // private paths: origin and length of the entry share a line
-            const int64_t g = L.hot.geom_of_env ? (int64_t)q.geom : i;
+            const int64_t g = hot_geom_of_env ? (int64_t)q.geom : i;
             own_org_x = as_global(L.hot.path_bbox)[g * kBoxDoubles + kBoxOrigin];
             own_org_y = as_global(L.hot.path_bbox)[g * kBoxDoubles + kBoxOrigin + 1];
             own_len_shift = as_global(reinterpret_cast<const uint64_t*>(L.hot.path_bbox))[g * kBoxDoubles + kBoxLenWord / 2];
-        } else if (L.hot.map_origins) {   // (private maps with a shared path)
-            const int64_t g = L.hot.geom_of_env ? (int64_t)q.geom : i;
-            own_org_x = as_global(L.hot.map_origins)[2 * g + 0];
-            own_org_y = as_global(L.hot.map_origins)[2 * g + 1];
+        } else if (hot_map_origins) {   // (private maps with a shared path)
+            const int64_t g = hot_geom_of_env ? (int64_t)q.geom : i;
+            own_org_x = as_global(hot_map_origins)[2 * g + 0];
+            own_org_y = as_global(hot_map_origins)[2 * g + 1];
         }
     } else {
         if (scanner) {
             if (!PLAIN) q.min_dist = as_global(L.hot.st.min_dist)[i];   // (PLAIN: the scan only needs the target index)
             q.target = as_global(L.hot.st.target_idx)[i];
-            q.geom = L.hot.geom_of_env ? as_global(L.hot.geom_of_env)[i] : 0;
+            q.geom = hot_geom_of_env ? as_global(hot_geom_of_env)[i] : 0;
             q.collided = PLAIN ? 0 : (int32_t)(as_global(L.hot.st.collided)[i] != 0);
             if (!hot_path_shared) {
-                const int64_t g = L.hot.geom_of_env ? (int64_t)q.geom : i;
+                const int64_t g = hot_geom_of_env ? (int64_t)q.geom : i;
 #pragma unroll
                 for (int k = 0; k < 8; ++k) box[k] = as_global(reinterpret_cast<const float*>(L.hot.path_bbox + g * kBoxDoubles))[k];
                 quant_inv = as_global(reinterpret_cast<const float*>(L.hot.path_bbox + g * kBoxDoubles))[kBoxQuantStep + 1];
@@ -2107,20 +2120,20 @@ __device__ __forceinline__ void step_local_body(KernArgPtr kernarg, const int rs
         const double map_inv_res = SL->map.inv_res;
         const int64_t near_stride = SL->cull.step_near_stride;
         const double org_x = own_origin ? own_org_x : SL->map.ox, org_y = own_origin ? own_org_y : SL->map.oy;
-        const int64_t g = slot_of(SL, i, q);
+        const int64_t g = SHARED ? i : slot_of(SL, i, q);
         const int px = (int)rint((r.p.x - org_x) * map_inv_res);  // world_to_pixel, coordinate_transformations.py:185-205
         const int py = (int)rint((r.p.y - org_y) * map_inv_res);
         double c, s;
         cos_sin(r.p.th, c, s);
         DIAG_STAMP_U(0, 4);    // mover: cos / sin of the new heading
-        const int64_t map_env = a.hot.map_shared ? 0 : g;
+        const int64_t map_env = (SHARED || a.hot.map_shared) ? 0 : g;
         int cls = kFree;
 #ifdef BCP_DIAG
         if (!ABLATED(a, kAblateNoCollision | kAblateNoClassify))
 #endif
         {
             // (a shared field is 18 KB for the 183 x 183 map and stays in the CU's L1: a copy in LDS measured no faster)
-            if (a.hot.near) {
+            if (SHARED || a.hot.near) {
                 cls = classify_near(outer, as_global(a.hot.near) + map_env * near_stride, map_rows, map_cols, px, py, c, s);
             } else {
                 const OuterLookups look = outer_lookups_issue(*(const CullDesc*)&SL->cull, map_env, map_rows, map_cols, px, py, c, s);
@@ -2141,10 +2154,10 @@ __device__ __forceinline__ void step_local_body(KernArgPtr kernarg, const int rs
     } else if (scanner && !ABLATED(a, kAblateNoReward)) {
         // (3b) the reward provider for the pose as it stands if nothing collides
         const double x = hand_pose[lane], y = hand_pose[kBlock + lane], th = hand_pose[2 * kBlock + lane];
-        const int64_t g = slot_of(SL, i, q);
+        const int64_t g = SHARED ? i : slot_of(SL, i, q);
         const int m = my_len;
-        const double* gpath = a.hot.path_pts + (a.hot.path_shared ? 0 : g * (int64_t)a.hot.path_max_len * 5);
-        if (PLAIN && lds_path) {
+        const double* gpath = a.hot.path_pts + ((SHARED || a.hot.path_shared) ? 0 : g * (int64_t)a.hot.path_max_len * 5);
+        if (PLAIN && (SHARED || lds_path)) {
             // Shared path in LDS: the candidates of the pair's 64 envs as ONE list, shared out evenly between the three
             // scanning waves.  More than half of the envs of a rollout are nowhere near the path (no candidate at all) while
             // a few have ten: with a lane per env the waves ran as many trips as their unluckiest lane (four) for an average
@@ -2215,7 +2228,7 @@ __device__ __forceinline__ void step_local_body(KernArgPtr kernarg, const int rs
             DIAG_STAMP_U(kWHelper2, 8);    // helper 2 of pair 0: scanned
         } else {
         PathWindow win;
-        if (SL->path.shared)
+        if (SHARED || SL->path.shared)
             win = path_window(P, (LdsF64)lds_box, (const __attribute__((address_space(3))) int16_t*)lds_index, x, y);
         else
             win = path_window_compact(P, box, as_global(reinterpret_cast<const uint16_t*>(L.hot.path_bbox + g * kBoxDoubles)) + kBoxIndexU16,
@@ -2248,9 +2261,9 @@ __device__ __forceinline__ void step_local_body(KernArgPtr kernarg, const int rs
             int target = q.target;
             double rew;
             if (P.reward_provider == BCP_REWARD_PURE_PURSUIT) {
-                if (lds_path) rew = reward_pure_pursuit(lds_path, m, x, y, q.collided != 0, min_dist, target);
+                if (SHARED || lds_path) rew = reward_pure_pursuit(lds_path, m, x, y, q.collided != 0, min_dist, target);
                 else rew = reward_pure_pursuit(gpath, m, x, y, q.collided != 0, min_dist, target);
-            } else if (lds_path) {
+            } else if (SHARED || lds_path) {
                 rew = reward_step(P, lds_path, win, m, x, y, th, min_dist, target);
             } else {
                 rew = reward_step(P, gpath, win, m, x, y, th, min_dist, target);
@@ -2300,7 +2313,7 @@ __device__ __forceinline__ void step_local_body(KernArgPtr kernarg, const int rs
         // memory by one lane at the very end of the step, with the rest of the workgroup idle (C4: the workgroups that
         // end last all hold such an env).  The mover has nothing to do until its pair's scans are in, so it works that
         // reward out now for every pose it parked; the verdict then only picks between two finished results.
-        if (PLAIN && !lds_path && !hot_path_shared && a.hot.path_pre && park && !ABLATED(a, kAblateNoReward)) {
+        if (PLAIN && !(SHARED || lds_path) && !hot_path_shared && a.hot.path_pre && park && !ABLATED(a, kAblateNoReward)) {
             const int64_t g = slot_of(SL, i, q);
             const GlobalPtr<const float> bx = as_global(reinterpret_cast<const float*>(L.hot.path_bbox + g * kBoxDoubles));
             float obox[8];
@@ -2339,12 +2352,12 @@ __device__ __forceinline__ void step_local_body(KernArgPtr kernarg, const int rs
     if (mover) {
         if (PLAIN) {
             const __attribute__((address_space(3))) int32_t* found = (__attribute__((address_space(3))) int32_t*)hand_score;
-            const int last = lds_path ? found[lane] : max(max(found[lane], found[kBlock + lane]), found[2 * kBlock + lane]);
-            const int64_t g = slot_of(SL, i, q);
+            const int last = (SHARED || lds_path) ? found[lane] : max(max(found[lane], found[kBlock + lane]), found[2 * kBlock + lane]);
+            const int64_t g = SHARED ? i : slot_of(SL, i, q);
             const int m = my_len;
             sc.min_dist = q.min_dist;
             sc.target = q.target;
-            if (lds_path)
+            if (SHARED || lds_path)
                 sc.rew = reward_from_last(P, lds_path, m, last, r.p.x, r.p.y, sc.min_dist, sc.target);
             else
                 sc.rew = reward_from_last(P, SL->path.pts + (SL->path.shared ? 0 : g * (int64_t)SL->path.max_len * 5), m,
@@ -2384,7 +2397,7 @@ __device__ __forceinline__ void step_local_body(KernArgPtr kernarg, const int rs
         const double c = e->c, s = e->s;
         const int px = e->px, py = e->py;
         const int64_t env = ((int64_t)e->env_hi << 32) | (uint32_t)e->env_lo;
-        const int64_t g = a.hot.map_shared ? 0 : (a.hot.geom_of_env ? (int64_t)e->geom : env);
+        const int64_t g = (SHARED || a.hot.map_shared) ? 0 : (a.hot.geom_of_env ? (int64_t)e->geom : env);
         const uint32_t* words = a.hot.map_bits + g * a.hot.map_env_stride;
         const uint32_t* tiles = a.map_tiles + g * map_tile_words(a.hot.map_rows, a.hot.map_wpr);
         bool h = false;
@@ -2398,7 +2411,7 @@ __device__ __forceinline__ void step_local_body(KernArgPtr kernarg, const int rs
 #else
             unsigned long long* const phases = nullptr;
 #endif
-            const int verdict = map_words
+            const int verdict = (SHARED || map_words)
                 ? coop_collides_sparse<WIDE>(P, (LdsF64)qv, c, s, px, py, (LdsWords)lds_map, a.hot.map_rows, a.hot.map_cols,
                                              a.hot.map_wpr, cell_list, phases)
                 : coop_collides_sparse<WIDE, true>(P, (LdsF64)qv, c, s, px, py, as_global(tiles), a.hot.map_rows, a.hot.map_cols,
@@ -2449,7 +2462,7 @@ __device__ __forceinline__ void step_local_body(KernArgPtr kernarg, const int rs
         // reached way point by the whole wave, a candidate per lane (one lane walking the window alone took ~5 k cycles, and
         // the step ends with the workgroups that hold such an env).  Shared path in LDS, continuous provider without delays;
         // otherwise finalize_env_from computes it itself.
-        const bool hit_score = PLAIN && lds_path && a.hot.path_shared && !ABLATED(a, kAblateNoReward);
+        const bool hit_score = PLAIN && (SHARED || lds_path) && (SHARED || a.hot.path_shared) && !ABLATED(a, kAblateNoReward);
         int last_hit = -1;
         if (hit_score) {
             uint64_t hits = __ballot(park && verdict == 2);
@@ -2470,7 +2483,7 @@ __device__ __forceinline__ void step_local_body(KernArgPtr kernarg, const int rs
                 sc.min_dist = q.min_dist;
                 sc.target = q.target;
                 sc.rew = reward_from_last(P, lds_path, my_len, last_hit, q.old.x, q.old.y, sc.min_dist, sc.target);
-            } else if (PLAIN && hit_now && my_rec->spec_ok) {   // (private path: worked out ahead, see above)
+            } else if (!SHARED && PLAIN && hit_now && my_rec->spec_ok) {   // (private path: worked out ahead, see above)
                 sc.rew = my_rec->spec_rew;
                 sc.min_dist = my_rec->spec_min;
                 sc.target = my_rec->spec_target;
@@ -2482,7 +2495,7 @@ __device__ __forceinline__ void step_local_body(KernArgPtr kernarg, const int rs
 #pragma unroll
                 for (int k = 0; k < 7; ++k) q.popped_state[k] = fifo_stash[(3 + k) * kLocalEnvs];
             }
-            finalize_env_from<PLAIN>(a, SL, i, q, hit_now, lds_path, nullptr, !ABLATED(a, kAblateNoReward), sc, my_len, fits, out_base);
+            finalize_env_from<PLAIN, SHARED>(a, SL, i, q, hit_now, lds_path, nullptr, !ABLATED(a, kAblateNoReward), sc, my_len, fits, out_base);
         }
         // Episode record: the step's count can only be published once every mover has taken its slots, so with a record the
         // last mover of the workgroup (ctl[3], an LDS count) draws the step's ticket in place of the wave below -- one
@@ -2541,13 +2554,13 @@ __device__ __attribute__((noinline)) void step_local_trip(uint64_t kernarg_bits,
     step_local_body<WIDE, PLAIN, PAIRS, true>((KernArgPtr)(uintptr_t)(((uint64_t)hi << 32) | lo), __builtin_amdgcn_readfirstlane(rs));
 }
 
-template <bool WIDE, bool PLAIN, int PAIRS, bool ROLL = false>
+template <bool WIDE, bool PLAIN, int PAIRS, bool ROLL = false, bool SHARED = false>
 __global__ void __attribute__((amdgpu_flat_work_group_size(4 * PAIRS * kBlock, 4 * PAIRS * kBlock), amdgpu_waves_per_eu(4)))
 step_local_kernel(const StepArgs launch_args)
 {
     KernArgPtr kernarg = (KernArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
     if constexpr (!ROLL) {
-        step_local_body<WIDE, PLAIN, PAIRS, false>(kernarg, 0);
+        step_local_body<WIDE, PLAIN, PAIRS, false, SHARED>(kernarg, 0);
     } else {
         const int n_steps = kernarg->rollout_steps;
         for (int rs = 0; rs < n_steps; ++rs) {

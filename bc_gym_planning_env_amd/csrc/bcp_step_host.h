@@ -144,9 +144,28 @@ static const void* const kFastPairFn[4] = {(const void*)step_fast_pair_kernel<fa
 static const void* const kPendingFn[4] = {(const void*)step_pending_kernel<false, false>, (const void*)step_pending_kernel<false, true>,
                                           (const void*)step_pending_kernel<true, false>, (const void*)step_pending_kernel<true, true>};
 
-// step_local_kernel<WIDE, PLAIN, PAIRS, ROLL>: variant = WIDE << 1 | PLAIN; the rollout form exists for the 16-wave workgroup
-static const void* local_step_fn(int variant, int pairs, bool roll = false)
+// The shared-geometry variant of step_local_kernel (SHARED, bcp_step.h) takes for granted what this asks: one map for all
+// envs, staged in LDS; one path, staged in LDS; no geometry pool, no per-env origins; the 1-bit `near` tiles.  (C2, C3, the
+// sharded C5, every replica batch.)  BCP_TUNE_LOCAL_SHARED = 0 keeps a handle on the generic variant.
+static bool local_step_shared(const bcp_handle* h, const StepStatic& S)
 {
+    const int64_t bitmap_words = (int64_t)S.map.rows * S.map.wpr;
+    return h->tune.local_shared != 0 && S.map.shared && bitmap_words > 0 && bitmap_words <= kLocalMapWords && S.path.shared &&
+           S.lds_path_doubles > 0 && S.geom_of_env == nullptr && S.map.origins == nullptr && S.cull.on && S.cull.step_near != nullptr;
+}
+
+// step_local_kernel<WIDE, PLAIN, PAIRS, ROLL, SHARED>: variant = WIDE << 1 | PLAIN; the rollout form and the shared-geometry
+// variant exist for the 16-wave workgroup
+static const void* local_step_fn(int variant, int pairs, bool roll = false, bool shared = false)
+{
+    if (shared) {   // (the caller has looked: 16-wave workgroups, one step per launch)
+        switch (variant) {
+            case 3: return (const void*)step_local_kernel<true, true, 4, false, true>;
+            case 2: return (const void*)step_local_kernel<true, false, 4, false, true>;
+            case 1: return (const void*)step_local_kernel<false, true, 4, false, true>;
+            default: return (const void*)step_local_kernel<false, false, 4, false, true>;
+        }
+    }
     if (roll) {
         switch (variant) {
             case 3: return (const void*)step_local_kernel<true, true, 4, true>;
@@ -233,8 +252,11 @@ static int launch_step(bcp_handle* h, const bcp_step_io* io, uint32_t flags, hip
             HIP_TRY(hipMemsetAsync(h->parked_slots.get(), 0, h->parked_slots.capacity() * sizeof(uint64_t), s));
         }
         a.parked_slots = h->parked_slots.get();
-        return launch_variant(h, local_step_fn(variant, pairs, roll), grid, block, lds, s, a);
+        const bool shared = pairs == 4 && !roll && local_step_shared(h, S);
+        h->last_local_shared = shared ? 1 : 0;
+        return launch_variant(h, local_step_fn(variant, pairs, roll, shared), grid, block, lds, s, a);
     }
+    h->last_local_shared = 0;
     if (rollout_steps > 1) return fail(BCP_E_STATE, "launch_step: only the single-launch step form takes several steps per launch");
     if (form == 0) {
         const size_t lds = collision_lds_bytes(h->params.n_verts, h->map.in_lds, h->map.rows, h->map.wpr);
@@ -386,6 +408,12 @@ extern "C" int bcp_parked_poses(bcp_handle* h, int64_t* count, void* stream)
     for (uint64_t v : slots) sum += v;
     *count = (int64_t)sum;
     return BCP_OK;
+}
+
+extern "C" int bcp_step_shared_variant(bcp_handle* h)
+{
+    if (!h) return fail(BCP_E_INVALID, "bcp_step_shared_variant: null handle");
+    return h->last_local_shared;
 }
 
 extern "C" int bcp_step_form(bcp_handle* h)

@@ -246,6 +246,10 @@ extern "C" int bcp_set_tuning(bcp_handle* h, int32_t key, int32_t value)
                 return fail(BCP_E_INVALID, "bcp_set_tuning: BCP_TUNE_LOCAL_PAIRS takes 0 (default), 1, 2 or 4");
             h->tune.local_pairs = value;
             return BCP_OK;
+        case BCP_TUNE_LOCAL_SHARED:
+            if (value != 0 && value != 1) return fail(BCP_E_INVALID, "bcp_set_tuning: BCP_TUNE_LOCAL_SHARED takes 0 or 1");
+            h->tune.local_shared = value;
+            return BCP_OK;
         case BCP_TUNE_INFLATE_ROUTE:
             if (value != 0 && value != 2) return fail(BCP_E_INVALID, "bcp_set_tuning: BCP_TUNE_INFLATE_ROUTE takes 0 or 2");
             h->tune.inflate_route = value;

@@ -42,7 +42,7 @@ class Handle(object):
         ("defer", _lib.TUNE_DEFER), ("edt_lds", _lib.TUNE_EDT_LDS), ("fused", _lib.TUNE_FUSED),
         ("ego_sparse", _lib.TUNE_EGO_SPARSE), ("local_pairs", _lib.TUNE_LOCAL_PAIRS),
         ("ego_list_stride", _lib.TUNE_EGO_LIST_STRIDE), ("near_dilate", _lib.TUNE_NEAR_DILATE),
-        ("near_shift", _lib.TUNE_NEAR_SHIFT)))
+        ("near_shift", _lib.TUNE_NEAR_SHIFT), ("local_shared", _lib.TUNE_LOCAL_SHARED)))
     _h = None   # (close() may run on an object whose constructor raised)
 
     def __init__(self, bcp_params, n_envs, device, env_id_base=0, needs_gpu=None):

@@ -202,11 +202,16 @@ int bcp_seed(bcp_handle *h, uint64_t seed);
  *                             compare the two routes on one map; the bytes are the same)
  *   BCP_TUNE_GOAL_ROUTE       where bcp_goal_field keeps its bit masks and its 16-bit working plane: 0 (default) = in LDS
  *                             when they fit, else the masks in the handle's global scratch and the plane in `out` itself;
- *                             2 = always in global memory (the bytes are the same on both routes) */
+ *                             2 = always in global memory (the bytes are the same on both routes)
+ *   BCP_TUNE_LOCAL_SHARED     which variant of the single-launch step runs: 1 (default) = the library's choice -- a variant
+ *                             compiled for shared geometry where the handle has one costmap and one path for all envs, both
+ *                             small enough for LDS, no geometry pool, no per-env origins, and 16-wavefront workgroups; the
+ *                             generic variant otherwise; 0 = always the generic variant.  Same results bit for bit (the knob
+ *                             lets both run against each other on one handle). */
 enum { BCP_TUNE_EXACT_MODE = 0, BCP_TUNE_DENSE_THRESHOLD = 1, BCP_TUNE_CULL = 2, BCP_TUNE_DEFER = 3, BCP_TUNE_EDT_LDS = 4,
        BCP_TUNE_FUSED = 5, BCP_TUNE_EGO_SPARSE = 6, BCP_TUNE_NEAR_DILATE = 7, BCP_TUNE_LOCAL_PAIRS = 8,
        BCP_TUNE_EGO_LIST_STRIDE = 9, BCP_TUNE_NEAR_SHIFT = 10, BCP_TUNE_INFLATE_ROUTE = 11,
-       BCP_TUNE_GOAL_ROUTE = 12 };
+       BCP_TUNE_GOAL_ROUTE = 12, BCP_TUNE_LOCAL_SHARED = 13 };
 int bcp_set_tuning(bcp_handle *h, int32_t key, int32_t value);
 
 /* ---- static per-episode inputs ------------------------------------------------------------------------ */
@@ -938,6 +943,9 @@ int bcp_final_goal_field_sample(bcp_handle *h, const uint16_t *field, int64_t n_
  * forced mode), 1 = step_fast_pair_kernel alone (every undecided pose settled in place), 2 = step_fast_pair_kernel +
  * step_pending_kernel, 3 = step_local_kernel (one launch).  Negative: BCP_E_*. */
 int bcp_step_form(bcp_handle *h);
+/* 1 when the last step of this handle ran step_local_kernel's shared-geometry variant (BCP_TUNE_LOCAL_SHARED), 0 when it
+ * ran anything else or no step has run.  Negative: BCP_E_*. */
+int bcp_step_shared_variant(bcp_handle *h);
 /* Runs `steps` bcp_step() launches back to back on `stream` bracketed by HIP events recorded on that stream and
  * returns the average kernel-launch duration in milliseconds (synchronises).  Used by bench.py for
  * roofline.achieved. */

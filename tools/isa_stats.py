@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Per-kernel register / spill / scratch figures and instruction mix of libbcplan, from hipcc -save-temps.
+"""Per-kernel code size, register / spill / scratch figures and instruction mix of libbcplan, from hipcc -save-temps.
 
     python tools/isa_stats.py [name-filter] [--mix]
 
@@ -35,6 +35,8 @@ def kernels(path):
         m = re.search(r"^%s:\n(.*?)^\s*\.section|^%s:\n(.*?)\.Lfunc_end" % (re.escape(name), re.escape(name)), text, re.S | re.M)
         if m:
             bodies[name] = m.group(1) or m.group(2)
+        m = re.search(r"^%s:.*?; codeLenInByte = (\d+)" % re.escape(name), text, re.S | re.M)   # (the first one behind the label)
+        meta[name]["code_bytes"] = int(m.group(1)) if m else -1
     return meta, bodies
 
 
@@ -59,8 +61,8 @@ def main():
         if flt and not any(f in name for f in flt):
             continue
         k = meta[name]
-        print("%-58s vgpr %3d sgpr %3d  spills v %3d s %3d  scratch %4d B  lds %6d B"
-              % (name[:58], k.get("vgpr_count", -1), k.get("sgpr_count", -1), k.get("vgpr_spill_count", 0),
+        print("%-58s code %6d B  vgpr %3d sgpr %3d  spills v %3d s %3d  scratch %4d B  lds %6d B"
+              % (name[:58], k.get("code_bytes", -1), k.get("vgpr_count", -1), k.get("sgpr_count", -1), k.get("vgpr_spill_count", 0),
                  k.get("sgpr_spill_count", 0), k.get("private_segment_fixed_size", 0), k.get("group_segment_fixed_size", 0)))
         if "--mix" in sys.argv and name in bodies:
             print("    ", mix(bodies[name]))
