@@ -18,6 +18,7 @@ TUNE_EXACT_MODE, TUNE_DENSE_THRESHOLD, TUNE_CULL, TUNE_DEFER, TUNE_EDT_LDS, TUNE
 TUNE_LOCAL_PAIRS, TUNE_EGO_LIST_STRIDE, TUNE_NEAR_SHIFT, TUNE_INFLATE_ROUTE, TUNE_GOAL_ROUTE = 8, 9, 10, 11, 12
 TUNE_LOCAL_SHARED = 13
 GOAL_ORTHO, GOAL_DIAG, GOAL_FAR, GOAL_NONE = 12, 17, 65534, 65535
+ROUTE_LONG, ROUTE_TOO_CLOSE, ROUTE_NO_ROUTE, ROUTE_STUCK = 1, 2, 4, 8
 E_NO_DEVICE = -2
 OPT_DIFFDRIVE_NOISE = 1
 EGO_KERNELS = {0: "none", 1: "ego_sparse_kernel", 2: "ego_costmap_kernel<staged>", 3: "ego_costmap_binned_kernel",
@@ -221,6 +222,10 @@ SYMBOLS = {
                                         C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bcp_final_goal_field_sample": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_double,
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bcp_goal_route": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                 C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bcp_goal_route_bound": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

@@ -117,6 +117,7 @@ class BatchedPlanEnv(Handle):
         # what only some modes or subclasses change, at its neutral value
         self.endless = False       # BatchedRandomMiniEnv(endless=True)
         self._inflated = False     # inflate_costmaps()
+        self._path_per_env = False  # route_paths() on expanded templates: self._paths then holds a path per env
         self._goal_followers = []  # weak references to the GoalFields a refresh() keeps current (goal_field(follow_refresh=True))
         self._rollout_buffers, self._lookahead_buffers, self._mppi_buffers = OrderedDict(), OrderedDict(), OrderedDict()
         self._range_scan_buffers = OrderedDict()
@@ -406,7 +407,7 @@ class BatchedPlanEnv(Handle):
     def path_of(self, i):
         if self.geom_of_env is not None:
             return self._paths[int(self.geom_of_env[i])]
-        if self._template_of_env is not None:
+        if self._template_of_env is not None and not self._path_per_env:
             return self._paths[self._template_of_env[i]]
         return self._paths[0] if self._shared_path else self._paths[i]
 
@@ -766,6 +767,71 @@ class BatchedPlanEnv(Handle):
         follow_refresh=False an endless=True pool is refused (RuntimeError): a refresh() would leave stale fields."""
         from . import goal_field
         return goal_field.build(self, clearance, seeds, max_passes, follow_refresh)
+
+    def route_paths(self, fields=None, stride=2, max_len=None, clearance=None):
+        """Replace every entry's path by the route traced down its goal field (bcp_goal_route_bound, one launch): from the
+        entry's own start pose, through the centre of every stride-th cell of the cheapest route that keeps `clearance`
+        from the walls, to its own goal pose -- a path a robot can follow, where the straight path of a pool world may
+        cross a wall.  fields: a goal_field.GoalField of this env with one field per entry, None = built here
+        (self.goal_field(clearance); clearance None = the footprint's inscribed radius).  max_len: the slots a route may
+        take, None = the binding's; a route that needs more is ROUTE_LONG.
+        Entries whose status is 0 get the routed path, its length and the reward provider's initial state on it; every
+        other entry keeps what it had (merged on the device).  The paths and the initial state are bound again, path_of(i),
+        the per-env views and a device pool's path_points / lens / init follow, and the call ends with reset().  While
+        max_len does not exceed the binding's, the path and length tensors -- a device-resident pool's own -- are written
+        in place; a larger max_len replaces them (the pool's attributes then name the new tensors).  Either way another
+        env that holds the same device pool keeps stepping on what it bound (its derived path data and its initial
+        states are its own) until it binds the pool again, while the pool's `paths` already show the routes.
+        Starts and goals do not change: GoalFields of this env built before the call stay valid, and calling again
+        changes nothing.  clearance only applies when the fields are built here: with `fields` it is a ValueError.
+        Returns the int32 status [entries] (device tensor; _lib.ROUTE_* bits).
+        Refused on endless=True pools (refresh() would write straight paths back), on a shared map or path, and on fields
+        whose owner or shape is not this env's."""
+        if self.endless:
+            raise RuntimeError("route_paths: not supported on endless=True pools -- refresh() re-samples worlds with "
+                               "straight paths into the pool")
+        if self._shared_path or self._shared_map:
+            raise RuntimeError("route_paths: needs private maps with private paths (a pool, or a map and a path per env)")
+        if fields is not None and clearance is not None:
+            raise ValueError("route_paths: clearance belongs to the build of the fields; pass one of fields and clearance")
+        if fields is None:
+            fields = self.goal_field(clearance)
+        data, old_pts, old_lens = self._keep["map"], self._keep["path"], self._keep["lens"]
+        if fields.owner is not self or tuple(fields.field.shape) != tuple(data.shape):
+            raise ValueError("route_paths: fields must be this env's, one per entry: %s expected, got %s"
+                             % (tuple(data.shape), tuple(fields.field.shape)))
+        old_len = int(old_pts.shape[1])
+        max_len = old_len if max_len is None else int(max_len)
+        paths, lens, status, init = fields.route_bound(stride, max_len, want=("init",))
+        status = status.clone()
+        ok = status == 0
+        length = max(max_len, old_len)
+        new_pts = torch.zeros((int(old_pts.shape[0]), length, 3), dtype=torch.float64, device=self.device)
+        new_pts[:, :old_len] = old_pts
+        routed = torch.zeros_like(new_pts)
+        routed[:, :max_len] = paths
+        new_pts = torch.where(ok[:, None, None], routed, new_pts).contiguous()
+        new_lens = torch.where(ok, lens, old_lens).contiguous()
+        if length == old_len:   # nothing grows: the bound tensors themselves (a device pool's own) take the routes
+            new_pts, new_lens = old_pts.copy_(new_pts), old_lens.copy_(new_lens)
+        first = self._initial_state
+        first.min_spat_dist_so_far.copy_(torch.where(ok, init[:, 0], first.min_spat_dist_so_far))
+        first.target_idx.copy_(torch.where(ok, init[:, 1].to(torch.int32), first.target_idx))
+        self._bind_paths(new_pts, new_lens)
+        self._bind(first, self._lib.bcp_bind_initial_state)
+        dp = self._device_pool
+        if dp is not None:
+            dp.path_points, dp.lens = new_pts, new_lens
+            dp.init.copy_(torch.stack([first.min_spat_dist_so_far, first.target_idx.to(torch.float64)], dim=1))
+            self._paths = dp.paths
+        else:   # the host copies behind path_of(i): one per entry (per env where templates were expanded)
+            pts_host, lens_host, ok_host = new_pts.cpu().numpy(), new_lens.cpu().numpy(), ok.cpu().numpy()
+            per_template = self._template_of_env is not None and not self._path_per_env
+            old = [self._paths[int(t)] for t in self._template_of_env] if per_template else list(self._paths)
+            self._paths = [pts_host[k, :lens_host[k]].copy() if ok_host[k] else old[k] for k in range(len(old))]
+            self._path_per_env = self._template_of_env is not None
+        self.reset()
+        return status
 
     def enable_episode_record(self, capacity=None):
         """Keep what every episode end leaves behind (bcp_bind_episode_record): from now on step() returns

@@ -229,7 +229,7 @@ __global__ void aisle_world_paths_kernel(const double* __restrict__ worlds, int6
         lens[g] = m;
         double min_dist;
         int target;
-        path_initial_reward(p, m, sp, ap, pure_pursuit, min_dist, target, rc);
+        path_initial_reward(p, m, sp, ap, pure_pursuit, min_dist, target, rc, DeviceNormalizeAngle());
         init[2 * g] = min_dist;
         init[2 * g + 1] = (double)target;
         status[g] = rc;

@@ -85,6 +85,11 @@ constexpr double kInvPi = 1.0 / kPi;   // (constant expression: IEEE division, c
 // utilities/coordinate_transformations.py:28-36
 __device__ __forceinline__ double normalize_angle(double z) { return py_mod_two_pi(z + kPi) - kPi; }
 
+// ... as the functor that plain host / device code takes (path_initial_reward, bcp_path_init.h)
+struct DeviceNormalizeAngle {
+    __device__ __forceinline__ double operator()(double z) const { return normalize_angle(z); }
+};
+
 // np.clip == minimum(maximum(a, lo), hi)
 __device__ __forceinline__ double clipd(double a, double lo, double hi)
 {

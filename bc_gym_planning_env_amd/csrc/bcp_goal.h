@@ -258,20 +258,28 @@ __global__ void __launch_bounds__(1024) goal_field_kernel(const GoalKernelArgs<k
 }
 
 // ---- per-row reads of finished fields ---------------------------------------------------------------------------
-struct GoalSampleArgs {
+// Whose row reads what: the part of the arguments that goal_sample_kernel and goal_route_kernel share, and the one
+// statement of how a row finds its env, its entry, the entry's origin and valid shape, and its field (goal_row_entry).
+struct GoalRows {
     const uint16_t* field;       // [n_fields][rows][cols]
     int64_t n_fields, n_entries;   // n_entries: pool entries, or n_envs without a pool
-    int32_t rows, cols, shared, carrot_cells;
+    int32_t rows, cols, shared, pad;
     const int32_t* valid_rows;   // per entry, or nullptr: the allocated shape
     const int32_t* valid_cols;
     const double* origins;       // per entry, or nullptr: (ox, oy)
-    double ox, oy, inv_res, resolution, max_dist;
+    double ox, oy, inv_res, resolution;
     const double* poses;         // [n][3] or nullptr: sx, sy, sth
     const double *sx, *sy, *sth;
     const int32_t* entry;        // entry of an env (pool entry, or env of a record's slot), or nullptr: the env index itself
-    const int32_t* live;         // rows beyond min(*live, n) are left alone, or nullptr
     const int32_t* row_env;      // env of row i, or nullptr: i % n_envs
     int64_t n_envs, n;
+};
+
+struct GoalSampleArgs {
+    GoalRows src;
+    int32_t carrot_cells, pad;
+    double max_dist;
+    const int32_t* live;         // rows beyond min(*live, n) are left alone, or nullptr
     float* out3;
     int32_t* cell_value;         // or nullptr
     int32_t* carrot;             // or nullptr
@@ -283,30 +291,61 @@ struct GoalFieldGet {
     __device__ __forceinline__ uint16_t operator()(int32_t r, int32_t c) const { return p[r * cols + c]; }
 };
 
+// the entry a row stands on
+struct GoalRowEntry {
+    int64_t slot;                // the env's entry among the non-shared arrays: it picks the field and the bound path
+    double ox, oy;
+    int32_t vr, vc;
+    GoalFieldGet get;
+};
+
+// false: the row's env or its entry is out of range, and `e` is untouched
+__device__ __forceinline__ bool goal_row_entry(const GoalRows& a, int64_t i, GoalRowEntry& e)
+{
+    const int64_t me = a.row_env ? (int64_t)a.row_env[i] : i % a.n_envs;
+    if (me < 0 || me >= a.n_envs) return false;
+    // the env's entry among the non-shared arrays: it picks the field; the map it is read on is entry 0 when shared
+    const int64_t slot = a.entry ? (int64_t)a.entry[me] : me;
+    if (slot < 0 || slot >= a.n_entries) return false;
+    const int64_t g = a.shared ? 0 : slot;
+    e.slot = slot;
+    e.ox = a.origins ? a.origins[2 * g] : a.ox;
+    e.oy = a.origins ? a.origins[2 * g + 1] : a.oy;
+    e.vr = a.valid_rows ? max(0, min(a.valid_rows[g], a.rows)) : a.rows;
+    e.vc = a.valid_cols ? max(0, min(a.valid_cols[g], a.cols)) : a.cols;
+    e.get.p = a.field + (a.n_fields == 1 ? 0 : slot) * ((int64_t)a.rows * a.cols);
+    e.get.cols = a.cols;
+    return true;
+}
+
+__device__ __forceinline__ void goal_row_pose(const GoalRows& a, int64_t i, double pose[3])
+{
+    pose[0] = a.poses ? a.poses[3 * i] : a.sx[i];
+    pose[1] = a.poses ? a.poses[3 * i + 1] : a.sy[i];
+    pose[2] = a.poses ? a.poses[3 * i + 2] : a.sth[i];
+}
+
+__device__ __forceinline__ bool goal_pose_finite(const double pose[3])
+{
+    const double lim = 1.7976931348623157e308;   // (a NaN fails every comparison)
+    return pose[0] >= -lim && pose[0] <= lim && pose[1] >= -lim && pose[1] <= lim && pose[2] >= -lim && pose[2] <= lim;
+}
+
 __global__ void __launch_bounds__(256) goal_sample_kernel(GoalSampleArgs a)
 {
+    const GoalRows& R = a.src;
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t n_rows = a.live ? min(a.n, (int64_t)max(*a.live, 0)) : a.n;
+    const int64_t n_rows = a.live ? min(R.n, (int64_t)max(*a.live, 0)) : R.n;
     if (i >= n_rows) return;
     GoalSample s = goal_no_sample(a.max_dist);
-    const int64_t me = a.row_env ? (int64_t)a.row_env[i] : i % a.n_envs;
-    if (me >= 0 && me < a.n_envs) {
-        // the env's entry among the non-shared arrays: it picks the field; the map it is read on is entry 0 when shared
-        const int64_t slot = a.entry ? (int64_t)a.entry[me] : me;
-        if (slot >= 0 && slot < a.n_entries) {
-            const int64_t g = a.shared ? 0 : slot;
-            const double ox = a.origins ? a.origins[2 * g] : a.ox, oy = a.origins ? a.origins[2 * g + 1] : a.oy;
-            const double x = a.poses ? a.poses[3 * i] : a.sx[i];
-            const double y = a.poses ? a.poses[3 * i + 1] : a.sy[i];
-            const double th = a.poses ? a.poses[3 * i + 2] : a.sth[i];
-            const double lim = 1.7976931348623157e308;
-            const bool finite = x >= -lim && x <= lim && y >= -lim && y <= lim && th >= -lim && th <= lim;
-            const double ct = finite ? cos(th) : 0.0, st = finite ? sin(th) : 0.0;
-            const int32_t vr = a.valid_rows ? max(0, min(a.valid_rows[g], a.rows)) : a.rows;
-            const int32_t vc = a.valid_cols ? max(0, min(a.valid_cols[g], a.cols)) : a.cols;
-            const GoalFieldGet get = {a.field + (a.n_fields == 1 ? 0 : slot) * ((int64_t)a.rows * a.cols), a.cols};
-            s = goal_sample_row(get, vr, vc, x, y, ct, st, finite, ox, oy, a.inv_res, a.resolution, a.carrot_cells, a.max_dist);
-        }
+    GoalRowEntry e;
+    if (goal_row_entry(R, i, e)) {
+        double pose[3];
+        goal_row_pose(R, i, pose);
+        const bool finite = goal_pose_finite(pose);
+        const double ct = finite ? cos(pose[2]) : 0.0, st = finite ? sin(pose[2]) : 0.0;
+        s = goal_sample_row(e.get, e.vr, e.vc, pose[0], pose[1], ct, st, finite, e.ox, e.oy, R.inv_res, R.resolution,
+                            a.carrot_cells, a.max_dist);
     }
     a.out3[3 * i] = s.out3[0];
     a.out3[3 * i + 1] = s.out3[1];
@@ -315,6 +354,72 @@ __global__ void __launch_bounds__(256) goal_sample_kernel(GoalSampleArgs a)
     if (a.carrot) {
         a.carrot[2 * i] = s.carrot_row;
         a.carrot[2 * i + 1] = s.carrot_col;
+    }
+}
+
+// ---- routes -----------------------------------------------------------------------------------------------------------
+// goal_route_kernel: one lane per row.  A row's walk is a chain of dependent 3 x 3 reads of a plane that L2 holds; the
+// parallelism is the rows', and nothing is staged.  A row's way points are its own: it writes them with plain stores, reads
+// them back for the headings and the provider state (the same lane, program order), and nobody else touches them.
+struct GoalRouteArgs {
+    GoalRows src;
+    const double* goals;         // [n][3], or nullptr: the last way point of the bound path of the row's entry
+    const double* src_paths;     // the bound paths [.][src_max_len][3] (one [src_max_len][3] when src_lens is nullptr), or nullptr
+    const int32_t* src_lens;
+    int32_t src_max_len, bound;  // bound: row m is entry m and starts at its bound path[0]
+    int32_t stride, max_len, pure_pursuit, pad;
+    double sp, ap;
+    double* paths;               // [n][max_len][3]
+    int32_t* lens;               // [n]
+    double* init;                // [n][2], or nullptr
+    int32_t* status;             // [n]
+};
+
+__global__ void __launch_bounds__(256) goal_route_kernel(GoalRouteArgs a)
+{
+    const GoalRows& R = a.src;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= R.n) return;
+    double* const wp = a.paths + i * (int64_t)a.max_len * 3;
+    int32_t len = 0, status = kGoalRouteNoRoute;
+    double init[2] = {0.0, 0.0};
+    bool routed = false;
+    GoalRowEntry e;
+    if (goal_row_entry(R, i, e)) {
+        // the bound path of the row's entry: its last way point is the goal (and, in the bound form, its first the start)
+        const double* src = nullptr;
+        int32_t src_len = 0;
+        if (a.src_paths) {
+            src = a.src_paths + (a.src_lens ? e.slot : 0) * (int64_t)a.src_max_len * 3;
+            src_len = a.src_lens ? min(a.src_lens[e.slot], a.src_max_len) : a.src_max_len;
+        }
+        const bool need_src = a.bound || !a.goals;
+        if (!need_src || src_len >= 1) {
+            double start[3], goal[3];
+            if (a.bound) {
+                start[0] = src[0];
+                start[1] = src[1];
+                start[2] = src[2];
+            } else {
+                goal_row_pose(R, i, start);
+            }
+            const double* g = a.goals ? a.goals + 3 * i : src + 3 * (int64_t)(src_len - 1);
+            goal[0] = g[0];
+            goal[1] = g[1];
+            goal[2] = g[2];
+            const bool finite = goal_pose_finite(start) && goal_pose_finite(goal);
+            status = goal_route_row(e.get, e.vr, e.vc, start, goal, finite, e.ox, e.oy, R.inv_res, R.resolution, a.stride,
+                                    a.max_len, a.sp, a.ap, a.pure_pursuit, DeviceNormalizeAngle(), wp, len, init);
+            routed = true;
+        }
+    }
+    if (!routed)
+        for (int32_t j = 0; j < 3 * a.max_len; ++j) wp[j] = 0.0;
+    a.lens[i] = len;
+    a.status[i] = status;
+    if (a.init) {
+        a.init[2 * i] = init[0];
+        a.init[2 * i + 1] = init[1];
     }
 }
 

@@ -1,9 +1,10 @@
 // bcp_goal_cell.h -- the goal field's arithmetic (bcp_goal_field, bcp_goal_field_sample; include/bcplan.h): the argument
 // checks, the half-widths of the clearance disc and the widening of one mask word, the pull relaxation of one cell, the field
-// at a pose, the seed cell of a bound path (bcp_goal_field_bound), and the sampling of one row with its carrot walk.  Plain C++ with no HIP in it: goal_field_kernel and
-// goal_sample_kernel (bcp_goal.h) and mppi_kernel's terminal read (bcp_mppi.h) call these functions on the device,
-// tests/c_abi/goal_field_main.cpp and tests/c_abi/mppi_field_main.cpp call the same ones on the host, and there is no other
-// copy of them.  The float64 arithmetic rounds every product, quotient, root and sum on its own
+// at a pose, the seed cell of a bound path (bcp_goal_field_bound), the sampling of one row with its carrot walk, and the
+// route of one row (bcp_goal_route: the walk written out as a path).  Plain C++ with no HIP in it: goal_field_kernel,
+// goal_sample_kernel and goal_route_kernel (bcp_goal.h) and mppi_kernel's terminal read (bcp_mppi.h) call these functions on
+// the device, tests/c_abi/goal_field_main.cpp, tests/c_abi/goal_route_main.cpp and tests/c_abi/mppi_field_main.cpp call the
+// same ones on the host, and there is no other copy of them.  The float64 arithmetic rounds every product, quotient, root and sum on its own
 // (-ffp-contract=off).
 //
 // A field is a uint16 plane [rows][cols]: kGoalNone where no route exists (blocked, outside the valid shape, not connected
@@ -15,7 +16,10 @@
 // still the length of an admissible route.
 #pragma once
 
+#include <cmath>
 #include <cstdint>
+
+#include "bcp_path_init.h"   // path_initial_reward: the provider state of a routed path (goal_route_row)
 
 #if defined(__HIPCC__)
 #define BCP_HD __host__ __device__
@@ -274,6 +278,107 @@ BCP_HD inline GoalSample goal_sample_row(const Get& get, int32_t vr, int32_t vc,
     s.out3[1] = (float)(ux * ct + uy * st);
     s.out3[2] = (float)(uy * ct - ux * st);
     return s;
+}
+
+// ---- routes: the walk down a field written out as a path (bcp_goal_route, bcp_goal_route_bound) --------------------
+constexpr int32_t kGoalRouteMaxStride = 64;
+constexpr int32_t kGoalRouteMaxLen = 32766;   // bcp_set_paths' limit
+
+// the bits of a row's status
+constexpr int32_t kGoalRouteLong = 1;       // truncated: the first max_len - 1 way points, then the goal
+constexpr int32_t kGoalRouteTooClose = 2;   // path_initial_reward's "Goal pose too close to initial pose"
+constexpr int32_t kGoalRouteNoRoute = 4;    // no path at all: len 0, every slot zero, init (0, 0)
+constexpr int32_t kGoalRouteStuck = 8;      // the plane is not a goal field here: the walk could not descend
+
+// what bcp_goal_route and bcp_goal_route_bound refuse with BCP_E_INVALID, in the order they look.  bound_form: the rows are
+// the binding's entries -- n is not the caller's to choose, there are no poses, and every entry needs a field of its own.
+enum GoalRouteRefusal {
+    kGoalRouteOk = 0, kGoalRouteNull = 1, kGoalRouteStride = 2, kGoalRouteMaxLenRange = 3, kGoalRouteRows = 4,
+    kGoalRouteRowEnv = 5, kGoalRouteShape = 6, kGoalRouteFields = 7
+};
+
+BCP_HD inline int goal_route_check_args(bool have_handle, bool have_field, bool have_paths, bool have_lens, bool have_status,
+                                        int32_t stride, int32_t max_len, int64_t n, int64_t n_envs, bool have_poses,
+                                        bool have_row_env, bool bound_form, int32_t rows, int32_t cols, int32_t map_rows,
+                                        int32_t map_cols, int64_t n_fields, int64_t n_entries)
+{
+    if (!have_handle || !have_field || !have_paths || !have_lens || !have_status) return kGoalRouteNull;
+    if (stride < 1 || stride > kGoalRouteMaxStride) return kGoalRouteStride;
+    if (max_len < 2 || max_len > kGoalRouteMaxLen) return kGoalRouteMaxLenRange;
+    if (!bound_form && (n <= 0 || (!have_poses && n != n_envs))) return kGoalRouteRows;
+    if (!bound_form && !have_poses && have_row_env) return kGoalRouteRowEnv;
+    if (n_entries > 0 && (rows != map_rows || cols != map_cols)) return kGoalRouteShape;
+    if (n_entries > 0 && n_fields != n_entries && (bound_form || n_fields != 1)) return kGoalRouteFields;
+    return kGoalRouteOk;
+}
+
+// One row of bcp_goal_route: the route from the pose `start` (x, y, theta) down the field to a cell of value 0, written as
+// way points wp[0 .. len) of [max_len][3]: the start pose bit for bit, the centre of every stride-th cell the walk enters
+// before it arrives, the pose `goal` bit for bit.  Interior way points head for their successor; slots len .. max_len - 1
+// are zeros.  init = (min_spat_dist_so_far, target_idx) of the reward provider on that path (path_initial_reward).  Returns
+// the status bits.  `finite`: every number of start and goal is finite.  Every trip of the loop ends it or lowers v, which
+// a uint16 gave: at most 65534 trips whatever the plane holds.
+template <typename Get, typename Normalize>
+BCP_HD inline int32_t goal_route_row(const Get& get, int32_t vr, int32_t vc, const double start[3], const double goal[3],
+                                     bool finite, double ox, double oy, double inv_res, double resolution, int32_t stride,
+                                     int32_t max_len, double sp, double ap, int pure_pursuit, const Normalize& normalize,
+                                     double* wp, int32_t& len, double init[2])
+{
+    int32_t r = 0, c = 0;
+    int32_t v = goal_value_at(get, vr, vc, start[0], start[1], finite, ox, oy, inv_res, r, c);
+    if (v == kGoalNone) {
+        for (int32_t j = 0; j < 3 * max_len; ++j) wp[j] = 0.0;
+        len = 0;
+        init[0] = init[1] = 0.0;
+        return kGoalRouteNoRoute;
+    }
+    int32_t status = 0, k = 1, steps = 0;
+    wp[0] = start[0];
+    wp[1] = start[1];
+    wp[2] = start[2];
+    while (v != 0) {
+        const int q = goal_walk_step(get, vr, vc, r, c);
+        if (q < 0) {
+            status |= kGoalRouteStuck;
+            break;
+        }
+        const int32_t nr = r + goal_drow(q), nc = c + goal_dcol(q);
+        const int32_t nv = (int32_t)get(nr, nc);
+        if (nv >= v) {   // not a goal field
+            status |= kGoalRouteStuck;
+            break;
+        }
+        r = nr;
+        c = nc;
+        v = nv;
+        ++steps;
+        if (v != 0 && steps % stride == 0) {
+            if (k == max_len - 1) {   // the last slot is the goal's
+                status |= kGoalRouteLong;
+                break;
+            }
+            wp[3 * k] = ox + (double)c * resolution;
+            wp[3 * k + 1] = oy + (double)r * resolution;
+            ++k;
+        }
+    }
+    wp[3 * k] = goal[0];
+    wp[3 * k + 1] = goal[1];
+    wp[3 * k + 2] = goal[2];
+    ++k;
+    for (int32_t j = 1; j + 1 < k; ++j) {
+        const double dx = wp[3 * (j + 1)] - wp[3 * j], dy = wp[3 * (j + 1) + 1] - wp[3 * j + 1];
+        wp[3 * j + 2] = dx == 0.0 && dy == 0.0 ? goal[2] : atan2(dy, dx);
+    }
+    for (int32_t j = 3 * k; j < 3 * max_len; ++j) wp[j] = 0.0;
+    len = k;
+    double min_dist = 0.0;
+    int target = 0, rc = 0;
+    path_initial_reward(wp, k, sp, ap, pure_pursuit, min_dist, target, rc, normalize);
+    if (rc == 2) status |= kGoalRouteTooClose;
+    init[0] = min_dist;
+    init[1] = (double)target;
+    return status;
 }
 
 }  // namespace bcp

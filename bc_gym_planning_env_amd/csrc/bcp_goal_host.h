@@ -1,6 +1,7 @@
 // bcp_goal_host.h -- the host side of the goal field: bcp_goal_field (checks, the choice of where masks and plane live, the
 // launch), bcp_goal_field_bound / bcp_refresh_goal_fields (the same launch on the handle's own binding, for all entries or a
-// device-side list of them), bcp_goal_field_sample / bcp_final_goal_field_sample over the rows of obs_rows() (bcp_ego_host.h), and the value
+// device-side list of them), bcp_goal_field_sample / bcp_final_goal_field_sample over the rows of obs_rows() (bcp_ego_host.h),
+// bcp_goal_route / bcp_goal_route_bound over the same rows or the binding's entries, and the value
 // check of BCP_TUNE_GOAL_ROUTE.  The refusals are the checks of bcp_goal_cell.h, which the host tests run too; the kernels are
 // in bcp_goal.h.  Included by bcplan.hip after bcp_ego_host.h.
 // Capture: the launch arguments depend only on what the caller passes and nothing is uploaded, but a field kernel whose
@@ -178,6 +179,38 @@ extern "C" int bcp_refresh_goal_fields(bcp_handle* h, int32_t clearance_d2, int3
     return goal_field_bound(h, nullptr, nullptr, 0, clearance_d2, max_passes, field, info, stream, true, "bcp_refresh_goal_fields");
 }
 
+// Whose row reads what (GoalRows, bcp_goal.h), from the handle's map binding and the rows of obs_rows(): the one statement
+// for bcp_goal_field_sample and bcp_goal_route.
+static GoalRows goal_rows(const bcp_handle* h, const ObsRows& R, const uint16_t* field, int64_t n_fields, int32_t rows,
+                          int32_t cols, const double* poses, int64_t n, const int32_t* row_env)
+{
+    GoalRows a;
+    memset(&a, 0, sizeof(a));
+    a.field = field;
+    a.n_fields = n_fields;
+    a.n_entries = n_slots(h);   // (a shared map may go with private paths: a field per env)
+    a.rows = rows;
+    a.cols = cols;
+    a.shared = h->map.shared;
+    a.valid_rows = h->map_valid_rows;
+    a.valid_cols = h->map_valid_cols;
+    a.origins = h->map.origins;
+    a.ox = h->map.ox;
+    a.oy = h->map.oy;
+    a.inv_res = h->map.inv_res;
+    a.resolution = h->resolution;
+    a.poses = poses;
+    const bool delayed = h->params.pose_delay > 0 && R.st.pose_seen;   // the observation shows State.pose, i.e. the delayed pose
+    a.sx = delayed ? R.st.pose_seen : R.st.x;
+    a.sy = delayed ? R.st.pose_seen + R.n : R.st.y;
+    a.sth = delayed ? R.st.pose_seen + 2 * R.n : R.st.angle;
+    a.entry = h->n_geoms > 0 ? (R.entry ? R.entry : h->geom_of_env) : R.entry;
+    a.row_env = row_env;
+    a.n_envs = R.n;
+    a.n = n;
+    return a;
+}
+
 // rec != nullptr: the final states of the episode record, n = capacity, rows j < min(*count, capacity)
 static int goal_field_sample(bcp_handle* h, const uint16_t* field, int64_t n_fields, int32_t rows, int32_t cols,
                              const double* poses, int64_t n, const int32_t* row_env, int32_t carrot_cells, double max_dist,
@@ -206,31 +239,10 @@ static int goal_field_sample(bcp_handle* h, const uint16_t* field, int64_t n_fie
     const ObsRows R = obs_rows(h, rec);
     GoalSampleArgs a;
     memset(&a, 0, sizeof(a));
-    a.field = field;
-    a.n_fields = n_fields;
-    a.n_entries = n_entries;
-    a.rows = rows;
-    a.cols = cols;
-    a.shared = h->map.shared;
+    a.src = goal_rows(h, R, field, n_fields, rows, cols, poses, n, row_env);
     a.carrot_cells = carrot_cells;
-    a.valid_rows = h->map_valid_rows;
-    a.valid_cols = h->map_valid_cols;
-    a.origins = h->map.origins;
-    a.ox = h->map.ox;
-    a.oy = h->map.oy;
-    a.inv_res = h->map.inv_res;
-    a.resolution = h->resolution;
     a.max_dist = max_dist;
-    a.poses = poses;
-    const bool delayed = h->params.pose_delay > 0 && R.st.pose_seen;   // the observation shows State.pose, i.e. the delayed pose
-    a.sx = delayed ? R.st.pose_seen : R.st.x;
-    a.sy = delayed ? R.st.pose_seen + R.n : R.st.y;
-    a.sth = delayed ? R.st.pose_seen + 2 * R.n : R.st.angle;
-    a.entry = h->n_geoms > 0 ? (R.entry ? R.entry : h->geom_of_env) : R.entry;
     a.live = R.live;
-    a.row_env = row_env;
-    a.n_envs = R.n;
-    a.n = n;
     a.out3 = out3;
     a.cell_value = cell_value;
     a.carrot = carrot;
@@ -252,4 +264,79 @@ extern "C" int bcp_final_goal_field_sample(bcp_handle* h, const uint16_t* field,
     if (h && !h->have_rec) return fail(BCP_E_STATE, "bcp_final_goal_field_sample: no episode record bound");
     return goal_field_sample(h, field, n_fields, rows, cols, nullptr, h ? h->rec.capacity : 0, nullptr, carrot_cells, max_dist,
                              out3, cell_value, carrot, stream, h ? &h->rec : nullptr, "bcp_final_goal_field_sample");
+}
+
+// ---- routes -----------------------------------------------------------------------------------------------------------
+// bcp_goal_route and bcp_goal_route_bound: the checks (goal_route_check_args), the rows as bcp_goal_field_sample resolves
+// them -- or, bound_form, row m = entry m of the binding, from its bound path[0] to its last way point -- and one launch.
+// Nothing is uploaded or allocated and the kernel uses no LDS: a call can be captured after one ordinary call.
+static int goal_route(bcp_handle* h, const uint16_t* field, int64_t n_fields, int32_t rows, int32_t cols, const double* poses,
+                      int64_t n, const int32_t* row_env, const double* goals, int32_t stride, int32_t max_len, double* paths,
+                      int32_t* lens, double* init, int32_t* status, void* stream, bool bound_form, const char* who)
+{
+    const bool bound = h && h->have_map;
+    const int64_t n_entries = bound ? n_slots(h) : 0;
+    switch (goal_route_check_args(h != nullptr, field != nullptr, paths != nullptr, lens != nullptr, status != nullptr, stride,
+                                  max_len, n, h ? h->n : 0, poses != nullptr, row_env != nullptr, bound_form, rows, cols,
+                                  bound ? h->map.rows : 0, bound ? h->map.cols : 0, n_fields, n_entries)) {
+    case kGoalRouteOk: break;
+    case kGoalRouteNull: return fail(BCP_E_INVALID, "%s: null argument", who);
+    case kGoalRouteStride: return fail(BCP_E_INVALID, "%s: stride %d outside [1, %d]", who, stride, kGoalRouteMaxStride);
+    case kGoalRouteMaxLenRange: return fail(BCP_E_INVALID, "%s: max_len %d outside [2, %d]", who, max_len, kGoalRouteMaxLen);
+    case kGoalRouteRows: return fail(BCP_E_INVALID, "%s: n must be positive, and n_envs without poses", who);
+    case kGoalRouteRowEnv: return fail(BCP_E_INVALID, "%s: row_env needs poses", who);
+    case kGoalRouteShape: return fail(BCP_E_INVALID, "%s: the field's shape %d x %d is not the bound maps' %d x %d", who, rows, cols,
+                                      h->map.rows, h->map.cols);
+    default: return fail(BCP_E_INVALID, "%s: n_fields %lld is neither 1 nor the %lld entries bound", who, (long long)n_fields,
+                         (long long)n_entries);
+    }
+    if (!h->have_map) return fail(BCP_E_STATE, "%s: costmaps not set", who);
+    const bool reads_path = bound_form || !goals;
+    if (reads_path && !h->have_path) return fail(BCP_E_STATE, "%s: no goals given and no paths bound", who);
+    if (bound_form && (h->map.shared || h->path.shared))
+        return fail(BCP_E_STATE, "%s: a shared map or a shared path has no per-entry route here -- bcp_goal_route serves those", who);
+    if (!bound_form && !poses && !h->have_state) return fail(BCP_E_STATE, "%s: no poses given and no state bound", who);
+    if (reads_path && ((const void*)paths == (const void*)h->path_src || (const void*)lens == (const void*)h->path.lens))
+        return fail(BCP_E_STATE, "%s: paths / lens are the bound paths' own arrays, which the call reads", who);
+    HIP_TRY(hipSetDevice(h->device));
+    const ObsRows R = obs_rows(h, nullptr);
+    GoalRouteArgs a;
+    memset(&a, 0, sizeof(a));
+    a.src = goal_rows(h, R, field, n_fields, rows, cols, poses, bound_form ? n_entries : n, row_env);
+    if (bound_form) {   // row m is entry m: no env in between
+        a.src.entry = nullptr;
+        a.src.n_envs = n_entries;
+    }
+    a.goals = goals;
+    if (reads_path) {
+        a.src_paths = h->path_src;
+        a.src_lens = h->path.shared ? nullptr : h->path.lens;
+        a.src_max_len = h->path.max_len;
+    }
+    a.bound = bound_form ? 1 : 0;
+    a.stride = stride;
+    a.max_len = max_len;
+    a.pure_pursuit = h->params.reward_provider == BCP_REWARD_PURE_PURSUIT;
+    a.sp = h->params.spatial_precision;
+    a.ap = h->params.angular_precision;
+    a.paths = paths;
+    a.lens = lens;
+    a.init = init;
+    a.status = status;
+    return launch_fn((const void*)goal_route_kernel, dim3((unsigned)((a.src.n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+}
+
+extern "C" int bcp_goal_route(bcp_handle* h, const uint16_t* field, int64_t n_fields, int32_t rows, int32_t cols,
+                              const double* poses, int64_t n, const int32_t* row_env, const double* goals, int32_t stride,
+                              int32_t max_len, double* paths, int32_t* lens, double* init, int32_t* status, void* stream)
+{
+    return goal_route(h, field, n_fields, rows, cols, poses, n, row_env, goals, stride, max_len, paths, lens, init, status, stream,
+                      false, "bcp_goal_route");
+}
+
+extern "C" int bcp_goal_route_bound(bcp_handle* h, const uint16_t* field, int32_t rows, int32_t cols, int32_t stride,
+                                    int32_t max_len, double* paths, int32_t* lens, double* init, int32_t* status, void* stream)
+{
+    return goal_route(h, field, h && h->have_map ? n_slots(h) : 0, rows, cols, nullptr, 0, nullptr, nullptr, stride, max_len, paths,
+                      lens, init, status, stream, true, "bcp_goal_route_bound");
 }

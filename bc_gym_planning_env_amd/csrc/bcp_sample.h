@@ -15,6 +15,7 @@
 
 #include "bcp_device.h"
 #include "bcp_coop.h"
+#include "bcp_path_init.h"   // path_initial_reward
 
 namespace bcp {
 
@@ -464,32 +465,6 @@ __global__ void __launch_bounds__(64) mini_world_sample_kernel(DevParams P, Mini
     }
 }
 
-// The reward provider's initial state on a refined path p[0 .. m) that starts at the initial pose p[0]; rc becomes 2 for
-// "Goal pose too close to initial pose" (ValueError in the reference), else it is left as it is.
-__device__ __forceinline__ void path_initial_reward(const double* __restrict__ p, int m, double sp, double ap,
-                                                    int pure_pursuit, double& min_dist, int& target, int& rc)
-{
-    const double x0 = p[0], y0 = p[1], th0 = p[2];
-    const double x1 = p[3 * (m - 1)], y1 = p[3 * (m - 1) + 1];
-    if (pure_pursuit) {   // reward.py:355-371
-        target = 1;
-        min_dist = hypot(x1 - x0, y1 - y0);
-    } else {              // find_last_reached(path[0], path) (path_tools.py:408-448), reward.py:261-288
-        int last = -1;
-        for (int j = 0; j < m; ++j) {
-            const double xj = p[3 * j], yj = p[3 * j + 1], tj = p[3 * j + 2];
-            const bool near = hypot(xj - x0, yj - y0) < sp;
-            if (!near) continue;   // (three independent predicates: the other two cost a cos, a sin and an fmod per way point)
-            const bool aligned = fabs(normalize_angle(th0 - tj)) < ap;
-            const bool ahead = cos(tj) * (x0 - xj) + sin(tj) * (y0 - yj) >= -sp / 9;
-            if (aligned && ahead) last = j;
-        }
-        if (last == m - 1) rc = 2;
-        target = min(last + 1, m - 1);
-        min_dist = hypot(p[3 * target] - x0, p[3 * target + 1] - y0);
-    }
-}
-
 // ---- from sampled worlds to what a PlanEnv starts with -----------------------------------------------------------
 // make_initial_state (envs/base/env.py:179-214) for every world: refine_path of the coarse (start, end) path
 // (utilities/path_tools.py:178-240: points every path_delta, np.linspace arithmetic, inserted points carry the start
@@ -533,7 +508,7 @@ __device__ __forceinline__ void mini_world_path(const double* __restrict__ world
     lens[g] = m;
     double min_dist;
     int target;
-    path_initial_reward(p, m, sp, ap, pure_pursuit, min_dist, target, rc);
+    path_initial_reward(p, m, sp, ap, pure_pursuit, min_dist, target, rc, DeviceNormalizeAngle());
     init[2 * g] = min_dist;
     init[2 * g + 1] = (double)target;
     status[g] = rc;

@@ -34,6 +34,7 @@ class GoalField(object):
         self.max_passes = 0         # of the build: what a following refresh() rebuilds with (build_bound)
         self._keep = keep           # the inputs of the build, alive until the stream has consumed them
         self._buffers = OrderedDict()
+        self._route_cache = OrderedDict()   # route() / route_bound(): outputs per (n, max_len)
 
     def _call(self, final, poses, n, row_env, carrot_cells, max_dist, out3, cell_value, carrot):
         o, f = self.owner, self.field
@@ -72,6 +73,68 @@ class GoalField(object):
                    buf.get("carrot") if "carrot" in want else None)
         o._alive["goal_field_sample"] = (poses, row_env)
         return buf["out3"] if not want else (buf["out3"],) + tuple(buf[w] for w in want)
+
+    def _route_buffers(self, n, max_len, want):
+        shapes = {"paths": ((n, max_len, 3), torch.float64), "lens": ((n,), torch.int32), "status": ((n,), torch.int32),
+                  "init": ((n, 2), torch.float64)}
+        buf = cached(self._route_cache, (n, max_len), dict, SCAN_CACHE_ENTRIES)
+        for name in ["paths", "lens", "status"] + list(want):
+            if name not in buf:
+                buf[name] = torch.zeros(shapes[name][0], dtype=shapes[name][1], device=self.owner.device)
+        return buf
+
+    def _bound_max_len(self):
+        pts = self.owner._keep.get("path")
+        if pts is None:
+            raise ValueError("route: max_len=None needs an owner with paths bound")
+        return int(pts.shape[-2])
+
+    def route(self, poses=None, row_env=None, goals=None, stride=2, max_len=None, want=()):
+        """bcp_goal_route: the route down the field from each row's pose to its goal, as a path.  Rows as for sample():
+        poses None = every env's current pose, or [n, 3], row i on the map of env row_env[i] (or i % n_envs).  goals: [n, 3],
+        or None = the last way point of the path bound for the row's entry.  A way point is written for the pose, for every
+        stride-th cell of the walk, and for the goal; interior way points head for their successor.  max_len: the slots per
+        row, None = the binding's max_len.  -> (paths float64 [n, max_len, 3] with zeros behind each row's way points, lens
+        int32 [n], status int32 [n]: a mask of _lib.ROUTE_LONG / ROUTE_TOO_CLOSE / ROUTE_NO_ROUTE / ROUTE_STUCK), plus init
+        float64 [n, 2] = (min_spat_dist_so_far, target_idx) of the owner's reward provider on each path with want=("init",).
+        Device tensors, no sync; the outputs are cached per (n, max_len), so the next call with the same sizes overwrites
+        them."""
+        o, f = self.owner, self.field
+        unknown = set(want) - {"init"}
+        if unknown:
+            raise ValueError("route: unknown outputs %s" % sorted(unknown))
+        if poses is not None:
+            poses = o._device_tensor(poses, torch.float64)
+            assert poses.dim() == 2 and poses.shape[1] == 3
+        n = int(poses.shape[0]) if poses is not None else int(getattr(o, "n_envs", 1))
+        if row_env is not None:
+            row_env = o._device_tensor(row_env, torch.int32, (n,))
+        if goals is not None:
+            goals = o._device_tensor(goals, torch.float64, (n, 3))
+        max_len = self._bound_max_len() if max_len is None else int(max_len)
+        buf = self._route_buffers(n, min(max(max_len, 1), 32766), want)
+        opt = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+        _lib.check(o._lib.bcp_goal_route(o._h, f.data_ptr(), f.shape[0], f.shape[1], f.shape[2], opt(poses), n, opt(row_env),
+                                         opt(goals), int(stride), max_len, buf["paths"].data_ptr(), buf["lens"].data_ptr(),
+                                         buf["init"].data_ptr() if "init" in want else None, buf["status"].data_ptr(),
+                                         o._stream()))
+        o._alive["goal_route"] = (poses, row_env, goals)
+        return (buf["paths"], buf["lens"], buf["status"]) + tuple(buf[w] for w in want)
+
+    def route_bound(self, stride=2, max_len=None, want=()):
+        """bcp_goal_route_bound: row m is entry m of the owner's own binding, from its bound path's first way point to its
+        last.  Needs private maps with private paths and a field per entry.  Returns what route() returns."""
+        o, f = self.owner, self.field
+        unknown = set(want) - {"init"}
+        if unknown:
+            raise ValueError("route_bound: unknown outputs %s" % sorted(unknown))
+        max_len = self._bound_max_len() if max_len is None else int(max_len)
+        buf = self._route_buffers(int(f.shape[0]), min(max(max_len, 1), 32766), want)
+        _lib.check(o._lib.bcp_goal_route_bound(o._h, f.data_ptr(), f.shape[1], f.shape[2], int(stride), max_len,
+                                               buf["paths"].data_ptr(), buf["lens"].data_ptr(),
+                                               buf["init"].data_ptr() if "init" in want else None, buf["status"].data_ptr(),
+                                               o._stream()))
+        return (buf["paths"], buf["lens"], buf["status"]) + tuple(buf[w] for w in want)
 
     def metres(self):
         """float32 [entries, rows, cols]: the fields in metres, inf where there is no route."""

@@ -938,6 +938,65 @@ int bcp_final_goal_field_sample(bcp_handle *h, const uint16_t *field, int64_t n_
                                 int32_t carrot_cells, double max_dist, float *out3, int32_t *cell_value, int32_t *carrot,
                                 void *stream);
 
+/* bcp_goal_route: the route down a field from a pose to the goal, per row, written as a path that bcp_set_paths takes.
+ * One launch (one lane per row), asynchronous on `stream`, no allocation, no upload, no host synchronisation; the launch
+ * arguments depend only on the pointers and numbers given, so a call can be captured into a HIP graph after one ordinary
+ * call.  Nothing of the handle changes.
+ * Rows, fields and shapes: exactly those of bcp_goal_field_sample -- poses [n,3] or NULL (n == n_envs, row_env NULL: the
+ * bound state's pose, pose_seen when pose_delay > 0); row i belongs to env row_env[i], or i % n_envs; it stands on the map
+ * entry of its env and reads field 0 (n_fields == 1) or the field of its env's entry.
+ * goals: device [n][3], or NULL = the last way point paths_bound[e][min(lens_bound[e], max_len_bound) - 1] of the path given
+ * to bcp_set_paths for the row's entry e (a shared path: its last way point).
+ * Per row with start pose s and goal pose g on an entry with origin (ox, oy):
+ *   (col, row) = half-to-even of ((s.x - ox) * inv_res, (s.y - oy) * inv_res),  v = field[row][col]
+ *   way point 0 = s, bit for bit
+ *   while v != 0: one step of bcp_goal_field_sample's carrot walk (the admissible neighbour k that minimises field + w_k, ties
+ *     to the lowest k); STUCK if no neighbour is admissible or the neighbour's value is not below v (the plane is not a goal
+ *     field there) -- the walk then ends where it stands; otherwise move, and after every stride-th step that did not arrive
+ *     on a cell of value 0 append the centre (ox + col * resolution, oy + row * resolution) of the cell reached.  If that way
+ *     point would take the last slot, max_len - 1, it is not written and the walk ends: LONG.
+ *   the last way point = g, bit for bit
+ * Every trip ends the walk or lowers v, a uint16: the loop is bounded whatever the plane holds.
+ * Headings: way point 0 keeps s.theta, the last one g.theta; interior way point j gets atan2(y[j+1] - y[j], x[j+1] - x[j])
+ * over the written coordinates, or g.theta where both differences are zero.  float64, every operation rounded on its own.
+ * paths: [n][max_len][3]; slots lens[i] .. max_len - 1 of a row are written as zeros, so the output is a function of the
+ * input alone.  lens: [n], 2 <= lens[i] <= max_len for a row with a path.
+ * status: [n], a bit mask --
+ *   1 LONG       truncated: the first max_len - 1 way points, then the goal
+ *   2 TOO_CLOSE  the reward provider's "Goal pose too close to initial pose" on the written path (find_last_reached of way
+ *                point 0 is the last way point); evaluated for every row that has a path.  init is then (distance to the
+ *                goal, lens[i] - 1)
+ *   4 NO_ROUTE   the start or the goal pose is not finite, the start's cell is outside the valid shape, the field there is
+ *                BCP_GOAL_NONE, the row's env or entry is out of range, or (goals NULL) the entry's bound path has lens < 1:
+ *                lens[i] = 0, every slot zero, init = (0, 0)
+ *   8 STUCK
+ * init: optional [n][2] = (min_spat_dist_so_far, (double)target_idx) of this handle's reward provider on the written path
+ * (ContinuousRewardProvider.generate_initial_state, reward.py:261-288; :355-371 for pure pursuit), what
+ * bcp_bind_initial_state takes beside pose = way point 0.
+ * BCP_E_INVALID: NULL h, field, paths, lens or status; stride outside [1, 64]; max_len outside [2, 32766]; n <= 0, or
+ * n != n_envs without poses; row_env without poses; rows / cols other than the binding's; n_fields neither 1 nor the handle's
+ * entry count (the bound form: not the entry count) -- tested in that order.  BCP_E_STATE: no costmaps bound; no goals and
+ * no paths bound; no poses and no state bound; `paths` or `lens` being the arrays given to bcp_set_paths while the call
+ * reads them.  Refusals carry the entry point's name as a prefix.
+ *
+ * bcp_goal_route_bound: row m is entry m of the handle's own binding -- from its bound path[m][0] to its last way point
+ * (lens[m] above max_len_bound counts as max_len_bound; lens[m] < 1: NO_ROUTE), on map m and field m.  For private maps
+ * with private paths (a geometry pool, or a map and a path per env), as bcp_goal_field_bound; field is
+ * [n_entries][rows][cols], paths [n_entries][max_len][3], lens / status [n_entries], init optional [n_entries][2].  A shared
+ * map or path: BCP_E_STATE.  No state needs to be bound. */
+int bcp_goal_route(bcp_handle *h, const uint16_t *field, int64_t n_fields, int32_t rows, int32_t cols,
+                   const double *poses /*[n][3] or NULL*/, int64_t n, const int32_t *row_env /*or NULL*/,
+                   const double *goals /*[n][3] or NULL*/, int32_t stride, int32_t max_len,
+                   double *paths /*[n][max_len][3]*/, int32_t *lens /*[n]*/, double *init /*optional [n][2]*/,
+                   int32_t *status /*[n]*/, void *stream);
+int bcp_goal_route_bound(bcp_handle *h, const uint16_t *field, int32_t rows, int32_t cols, int32_t stride, int32_t max_len,
+                         double *paths /*[n_entries][max_len][3]*/, int32_t *lens, double *init /*optional*/, int32_t *status,
+                         void *stream);
+#define BCP_ROUTE_LONG      1
+#define BCP_ROUTE_TOO_CLOSE 2
+#define BCP_ROUTE_NO_ROUTE  4
+#define BCP_ROUTE_STUCK     8
+
 /* ---- measurement -------------------------------------------------------------------------------------- */
 /* Which kernels a bcp_step() of this handle launches, as configured now: 0 = step_kernel alone (no distance field, or a
  * forced mode), 1 = step_fast_pair_kernel alone (every undecided pose settled in place), 2 = step_fast_pair_kernel +

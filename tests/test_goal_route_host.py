@@ -1,0 +1,287 @@
+"""The route of one row (csrc/bcp_goal_cell.h: goal_route_row and goal_route_check_args, with csrc/bcp_path_init.h's
+path_initial_reward) as a stand-alone host program under AddressSanitizer and UBSan, against the contract restated in numpy
+(tests/goal_route_ref.py, on fields from goal_field_ref.dijkstra and the provider state of host_init).
+tests/c_abi/goal_route_main.cpp includes those headers alone -- they have no HIP in them -- and calls the very functions
+goal_route_kernel calls; it reads every plane through a bounds-checked accessor and keeps every row's way points in a heap
+block of exactly max_len slots, so a walk that left the map or a way point past the last slot fails here, without a GPU.
+Compared bit for bit: x, y, lens, status, target_idx and the zero tails; within 1e-9 (the project's bound on float64 state):
+headings and min_spat_dist_so_far -- atan2 and hypot are the host library's here, numpy's there.  Every case is checked to
+lie away from the knife edges of find_last_reached in the reference alone (goal_route_ref.away_from_knife_edges)."""
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import goal_field_ref as GR
+import goal_route_ref as RR
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW_SYMBOLS = ["bcp_goal_route", "bcp_goal_route_bound"]
+STRIDES = (1, 2, 4, 7)
+CLEARANCES = (151, 0)
+SP, AP = RR.REWARD_PARAMS.spatial_precision, RR.REWARD_PARAMS.angular_precision
+
+
+def _compiler():
+    for cand in ("g++", "/opt/rocm/llvm/bin/clang++", "clang++"):
+        path = shutil.which(cand)
+        if path:
+            return path
+    raise AssertionError("no host C++ compiler found (g++ or ROCm's clang++)")
+
+
+@pytest.fixture(scope="module")
+def program(tmp_path_factory):
+    exe = str(tmp_path_factory.mktemp("goal_route") / "goal_route_main")
+    cxx = _compiler()
+    static_runtime = ["-static-libasan", "-static-libubsan"] if cxx.endswith("g++") else []   # (clang's is static already)
+    cmd = [cxx] + static_runtime + ["-std=c++17", "-Wall", "-Werror", "-g", "-O1", "-ffp-contract=off",
+                                    "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                                    "-I" + os.path.join(ROOT, "bc_gym_planning_env_amd", "csrc"),
+                                    os.path.join(ROOT, "tests", "c_abi", "goal_route_main.cpp"), "-o", exe]
+    built = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=300)
+    assert built.returncode == 0, built.stdout
+    return exe
+
+
+def _run(exe, *args):
+    ran = subprocess.run([exe] + list(args), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=120)
+    assert ran.returncode == 0, ran.stdout[-4000:]
+    assert "goal route ok" in ran.stdout
+    for word in ("Sanitizer", "runtime error"):
+        assert word not in ran.stdout, ran.stdout[-4000:]
+    return ran.stdout.split("\n")
+
+
+def _route(exe, tmp_path, field, valid, origin, resolution, starts, goals, stride, max_len, pure_pursuit=False, knife=True):
+    """runs the program and the reference on the same rows, compares everything, -> (paths, lens, status, init)"""
+    rows, cols = field.shape
+    starts, goals = np.asarray(starts, dtype=np.float64).reshape(-1, 3), np.asarray(goals, dtype=np.float64).reshape(-1, 3)
+    n = len(starts)
+    path, out = str(tmp_path / "route.bin"), str(tmp_path / "route.out")
+    with open(path, "wb") as f:
+        f.write(np.array([rows, cols, valid[0], valid[1], n, stride, max_len, int(pure_pursuit)], dtype=np.int32).tobytes())
+        f.write(np.array([origin[0], origin[1], resolution, SP, AP], dtype=np.float64).tobytes())
+        f.write(np.ascontiguousarray(field, dtype=np.uint16).tobytes())
+        f.write(np.concatenate([starts, goals], axis=1).tobytes())
+    _run(exe, "route", path, out)
+    raw = np.fromfile(out, dtype=np.uint8)
+    n_p, n_i = n * max_len * 3 * 8, n * 2 * 8
+    assert len(raw) == n_p + n_i + 8 * n
+    paths = raw[:n_p].view(np.float64).reshape(n, max_len, 3)
+    init = raw[n_p:n_p + n_i].view(np.float64).reshape(n, 2)
+    lens = raw[n_p + n_i:n_p + n_i + 4 * n].view(np.int32)
+    status = raw[n_p + n_i + 4 * n:].view(np.int32)
+    want_p, want_l, want_s, want_i = RR.route(field[None], [valid], [origin], resolution, np.zeros(n, dtype=np.int64), starts, goals,
+                                              stride, max_len, pure_pursuit=pure_pursuit)
+    compare(paths, lens, status, init, want_p, want_l, want_s, want_i)
+    if knife and not pure_pursuit:
+        for i in range(n):
+            if want_l[i]:
+                assert RR.away_from_knife_edges(want_p[i, :want_l[i]]), i
+    return paths, lens, status, init
+
+
+compare = RR.compare
+
+
+@pytest.mark.parametrize("clearance_d2", CLEARANCES)
+def test_the_golden_worlds_route_bit_for_bit(program, tmp_path, clearance_d2):
+    steps_seen = []
+    for world in range(48):
+        _data, origin, res, _goal, _start = GR.mini_world(world)
+        field = GR.mini_field(world, clearance_d2)
+        start, goal = RR.mini_world_poses(world)
+        for stride in STRIDES:
+            paths, lens, status, _init = _route(program, tmp_path, field, field.shape, origin, res, [start], [goal], stride, 140)
+            assert status[0] == 0, (world, stride)
+            cells = RR.route_row(field, field.shape, origin, res, start, goal, stride, 140)[4]
+            steps = len(cells) - 1
+            assert lens[0] == 2 + (steps - 1) // stride
+            assert (paths[0, 0] == start).all() and (paths[0, lens[0] - 1] == goal).all()
+            assert all(field[r, c] != GR.NONE for r, c in cells)
+        steps_seen.append(steps)
+    if clearance_d2 == 151:
+        assert min(steps_seen) == 21 and max(steps_seen) == 128
+
+
+def test_a_max_len_that_fits_and_one_that_is_one_short(program, tmp_path):
+    _data, origin, res, _goal, _start = GR.mini_world(5)
+    field = GR.mini_field(5, 151)
+    start, goal = RR.mini_world_poses(5)
+    whole, lens, status, _ = _route(program, tmp_path, field, field.shape, origin, res, [start], [goal], 2, 200)
+    n = int(lens[0])
+    assert n == 59 and status[0] == 0
+    fits, lens, status, _ = _route(program, tmp_path, field, field.shape, origin, res, [start], [goal], 2, n)
+    assert lens[0] == n and status[0] == 0 and (fits[0] == whole[0, :n]).all()
+    short, lens, status, _ = _route(program, tmp_path, field, field.shape, origin, res, [start], [goal], 2, n - 1)
+    assert lens[0] == n - 1 and status[0] == RR.LONG
+    assert (short[0, :n - 2, :2] == whole[0, :n - 2, :2]).all() and (short[0, n - 2] == goal).all()
+    two, lens, status, _ = _route(program, tmp_path, field, field.shape, origin, res, [start], [goal], 2, 2)
+    assert lens[0] == 2 and status[0] & RR.LONG and (two[0, 0] == start).all() and (two[0, 1] == goal).all()
+
+
+def test_starts_on_and_beside_the_seed_and_rows_without_a_route(program, tmp_path):
+    _data, origin, res, goal_cell, _start = GR.mini_world(5)
+    field = GR.mini_field(5, 151)
+    _s, goal = RR.mini_world_poses(5)
+    centre = np.array([origin[0] + goal_cell[1] * res, origin[1] + goal_cell[0] * res])
+    none_r, none_c = np.nonzero(field == GR.NONE)
+    starts = np.array([
+        [centre[0] + 0.004, centre[1] - 0.003, goal[2] + 2.0],            # on the seed cell, turned away
+        [centre[0] + 0.004, centre[1] - 0.003, goal[2] + 0.01],           # ... and nearly the goal pose: too close
+        [centre[0] + res + 0.002, centre[1] + 0.001, 1.0],                # one step east of it
+        [centre[0] - res + 0.002, centre[1] - res + 0.001, 0.5],          # one diagonal step from it
+        [origin[0] + none_c[7] * res, origin[1] + none_r[7] * res, 0.0],  # a cell without a value
+        [origin[0] - 0.51 * res, origin[1], 0.0],                         # outside the shape
+        [origin[0] + 200 * res, origin[1] + 3 * res, 0.0],
+        [np.nan, 0.0, 0.0], [0.0, np.inf, 0.0], [0.0, 0.0, -np.inf], [1e300, -1e300, 0.0],
+    ])
+    goals = np.tile(goal, (len(starts), 1))
+    paths, lens, status, init = _route(program, tmp_path, field, field.shape, origin, res, starts, goals, 2, 9)
+    assert list(lens[:4]) == [2, 2, 2, 2] and status[0] == 0 and status[1] == RR.TOO_CLOSE and list(status[2:4]) == [0, 0]
+    assert init[1, 1] == 1
+    assert (status[4:] == RR.NO_ROUTE).all() and (lens[4:] == 0).all()
+    assert (paths[4:].view(np.uint64) == 0).all() and (init[4:].view(np.uint64) == 0).all()
+    # a goal that is not finite: no route either
+    bad_goal = goals[:1].copy()
+    bad_goal[0, 2] = np.nan
+    _p, lens, status, _i = _route(program, tmp_path, field, field.shape, origin, res, starts[:1], bad_goal, 2, 9)
+    assert lens[0] == 0 and status[0] == RR.NO_ROUTE
+    # a valid shape smaller than the plane: a start beyond it has no route, whatever the plane holds there
+    _p, lens, status, _i = _route(program, tmp_path, field, (goal_cell[0], field.shape[1]), origin, res, starts[:1], goals[:1], 2, 9)
+    assert lens[0] == 0 and status[0] == RR.NO_ROUTE
+
+
+def test_serpentine_and_diagonal_wall(program, tmp_path):
+    res, origin = 0.5, np.array([-0.2, 0.1])   # (cells of half a metre: the map is large against spatial_precision)
+    data = GR.serpentine(9)
+    field = GR.dijkstra(data, [(0, 0)], 0)
+    start = np.array([origin[0] + 8 * res + 0.01, origin[1] + 8 * res - 0.01, 0.3])     # the corridor's far end
+    goal = np.array([origin[0] + 0.003, origin[1] + 0.002, -1.0])
+    for stride in (1, 3):
+        paths, lens, status, _ = _route(program, tmp_path, field, field.shape, origin, res, [start], [goal], stride, 60)
+        steps = int(field[8, 8]) // 12
+        assert status[0] == 0 and steps == 48 and lens[0] == 2 + (steps - 1) // stride
+        cols = np.rint((paths[0, 1:lens[0] - 1, 0] - origin[0]) / res).astype(int)
+        rows = np.rint((paths[0, 1:lens[0] - 1, 1] - origin[1]) / res).astype(int)
+        assert (data[rows, cols] == 0).all()                   # never on a wall
+    data = GR.diagonal_wall(9)
+    field = GR.dijkstra(data, [(0, 0)], 0)
+    starts = np.array([[origin[0] + 3 * res + 0.01, origin[1] + 3 * res, 0.5],          # this side of the wall
+                       [origin[0] + 0 * res, origin[1] + 7 * res + 0.01, 0.5],          # beside the wall: no corner is cut
+                       [origin[0] + 6 * res, origin[1] + 6 * res, 0.5]])                # beyond it
+    _paths, lens, status, _ = _route(program, tmp_path, field, field.shape, origin, res, starts, np.tile(goal, (3, 1)), 1, 20)
+    assert list(status) == [0, 0, RR.NO_ROUTE] and lens[0] == 4 and lens[1] == 8 and lens[2] == 0
+
+
+def test_planes_that_are_not_goal_fields(program, tmp_path):
+    res, origin = 0.5, np.array([0.0, 0.0])
+    goal = np.array([0.013, 0.021, 0.4])
+    flat = np.full((9, 11), 7, dtype=np.uint16)
+    start = np.array([5 * res + 0.01, 4 * res, 2.0])
+    paths, lens, status, _ = _route(program, tmp_path, flat, flat.shape, origin, res, [start], [goal], 1, 12)
+    assert status[0] == RR.STUCK and lens[0] == 2 and (paths[0, 1] == goal).all()
+    alone = np.full((9, 11), GR.NONE, dtype=np.uint16)
+    alone[4, 5] = 30                                           # no admissible neighbour at all
+    _p, lens, status, _ = _route(program, tmp_path, alone, alone.shape, origin, res, [start], [goal], 1, 12)
+    assert status[0] == RR.STUCK and lens[0] == 2
+    pit = np.full((9, 11), 500, dtype=np.uint16)               # descends for two cells, then a minimum that is not 0
+    pit[4, 4], pit[4, 3] = 100, 50
+    paths, lens, status, _ = _route(program, tmp_path, pit, pit.shape, origin, res, [start], [goal], 1, 12)
+    assert status[0] == RR.STUCK and lens[0] == 4
+    # a field ended by max_passes: every value is an upper bound, and a walk either descends to the seed or is stuck
+    data = GR.serpentine(33)
+    capped, _passes, gave_up = GR.jacobi(data, [(32, 32)], 0, max_passes=60)
+    assert gave_up == 1
+    rr, cc = np.nonzero((capped != GR.NONE) & (capped != 0))
+    assert len(rr) >= 40
+    pick = np.random.RandomState(3).choice(len(rr), 40, replace=False)
+    starts = np.stack([cc[pick] * res + 0.004, rr[pick] * res - 0.006, np.linspace(-3, 3, 40)], axis=1)
+    seed_goal = np.array([32 * res + 0.002, 32 * res + 0.001, 0.2])
+    _p, lens, status, _ = _route(program, tmp_path, capped, capped.shape, origin, res, starts, np.tile(seed_goal, (40, 1)), 2, 400)
+    assert set(status.tolist()) <= {0, RR.STUCK, RR.TOO_CLOSE, RR.STUCK | RR.TOO_CLOSE} and (lens >= 2).all()
+
+
+def test_caller_goals_and_the_heading_that_falls_back(program, tmp_path):
+    _data, origin, res, _goal_cell, _start = GR.mini_world(17)
+    field = GR.mini_field(17, 151)
+    start, goal = RR.mini_world_poses(17)
+    cells = RR.route_row(field, field.shape, origin, res, start, goal, 1, 200)[4]
+    r, c = cells[-2]                                           # the last interior way point at stride 1
+    on_centre = np.array([np.float64(origin[0]) + np.float64(c) * np.float64(res),
+                          np.float64(origin[1]) + np.float64(r) * np.float64(res), 0.7])
+    goals = np.array([goal, on_centre, [goal[0] + 0.2, goal[1] - 0.1, -3.0]])
+    paths, lens, status, _ = _route(program, tmp_path, field, field.shape, origin, res, np.tile(start, (3, 1)), goals, 1, 200)
+    assert (status == 0).all() and lens[0] == lens[1] == lens[2] == len(cells)
+    k = lens[1]
+    assert (paths[1, k - 2, :2] == on_centre[:2]).all() and paths[1, k - 2, 2] == 0.7 and paths[1, k - 1, 2] == 0.7
+    assert paths[0, k - 2, 2] != goal[2]
+    assert (paths[0, :k - 1, :2] == paths[2, :k - 1, :2]).all() and (paths[2, k - 1] == goals[2]).all()
+
+
+def test_pure_pursuit(program, tmp_path):
+    for world in (0, 5):
+        _data, origin, res, _goal, _start = GR.mini_world(world)
+        field = GR.mini_field(world, 151)
+        start, goal = RR.mini_world_poses(world)
+        _p, _lens, status, init = _route(program, tmp_path, field, field.shape, origin, res, [start], [goal], 2, 140,
+                                         pure_pursuit=True)
+        assert status[0] == 0 and init[0, 1] == 1
+        assert abs(init[0, 0] - np.hypot(goal[0] - start[0], goal[1] - start[1])) <= 1e-9
+
+
+def test_argument_checks_and_their_order(program, tmp_path):
+    ok = (1, 1, 1, 1, 1, 2, 72, 16, 16, 0, 0, 0, 183, 183, 183, 183, 1, 16)
+    table = [
+        # handle field paths lens status stride max_len n n_envs poses row_env bound rows cols map_rows map_cols n_fields n_entries
+        (ok, 0),
+        (ok[:5] + (1, 2, 40, 16, 1, 1, 0) + ok[12:16] + (16, 16), 0),
+        (ok[:5] + (64, 32766, 0, 16, 0, 0, 1) + ok[12:16] + (16, 16), 0),     # the bound form: n is the binding's
+        (ok[:12] + (5, 5, 0, 0, 3, 0), 0),                                     # no costmaps bound yet: the caller's refusal
+        ((0,) + ok[1:], 1), ((1, 0) + ok[2:], 1), ((1, 1, 0) + ok[3:], 1), ((1, 1, 1, 0) + ok[4:], 1), ((1, 1, 1, 1, 0) + ok[5:], 1),
+        (ok[:5] + (0,) + ok[6:], 2), (ok[:5] + (65,) + ok[6:], 2), (ok[:5] + (-1,) + ok[6:], 2),
+        (ok[:6] + (1,) + ok[7:], 3), (ok[:6] + (32767,) + ok[7:], 3), (ok[:6] + (0,) + ok[7:], 3),
+        (ok[:7] + (0, 16, 1) + ok[10:], 4), (ok[:7] + (15, 16, 0) + ok[10:], 4), (ok[:7] + (-2, 16, 1) + ok[10:], 4),
+        (ok[:9] + (0, 1) + ok[11:], 5),
+        (ok[:12] + (183, 182) + ok[14:], 6), (ok[:12] + (184, 183) + ok[14:], 6),
+        (ok[:16] + (0, 16), 7), (ok[:16] + (2, 16), 7), (ok[:16] + (17, 16), 7),
+        (ok[:11] + (1,) + ok[12:16] + (1, 16), 7),                             # the bound form needs a field per entry
+        (ok[:9] + (0, 1, 1) + ok[12:], 7),                                     # ... and asks nothing of n and row_env
+        ((0, 0, 0, 0, 0, 0, 0, 0, 16, 0, 1, 0, 5, 5, 6, 6, 3, 16), 1),         # the order: null, stride, max_len, rows, ...
+        ((1, 1, 1, 1, 1, 0, 0, 0, 16, 0, 1, 0, 5, 5, 6, 6, 3, 16), 2),
+        ((1, 1, 1, 1, 1, 1, 0, 0, 16, 0, 1, 0, 5, 5, 6, 6, 3, 16), 3),
+        ((1, 1, 1, 1, 1, 1, 2, 0, 16, 0, 1, 0, 5, 5, 6, 6, 3, 16), 4),
+        ((1, 1, 1, 1, 1, 1, 2, 16, 16, 0, 1, 0, 5, 5, 6, 6, 3, 16), 5),
+        ((1, 1, 1, 1, 1, 1, 2, 16, 16, 0, 0, 0, 5, 5, 6, 6, 3, 16), 6),
+        ((1, 1, 1, 1, 1, 1, 2, 16, 16, 0, 0, 0, 6, 6, 6, 6, 3, 16), 7),
+    ]
+    path = str(tmp_path / "args.txt")
+    with open(path, "w") as f:
+        for args, _want in table:
+            f.write(" ".join(str(a) for a in args) + "\n")
+    got = [int(ln) for ln in _run(program, "args", path)[:len(table)]]
+    assert got == [want for _args, want in table]
+    assert [RR.check_route_args(*args) for args, _want in table] == got
+
+
+def test_header_library_and_binding_agree_and_the_abi_stays():
+    import ctypes as C
+    from bc_gym_planning_env_amd import _lib, build
+    build.build()
+    raw = C.CDLL(_lib.LIB_PATH)
+    header = open(os.path.join(ROOT, "include", "bcplan.h")).read()
+    for name in NEW_SYMBOLS:
+        assert hasattr(raw, name), name
+        assert name in _lib.SYMBOLS, name
+        assert "int %s(bcp_handle *h" % name in header, name
+    lib = _lib.load()
+    assert len(lib.bcp_goal_route.argtypes) == 16 and len(lib.bcp_goal_route_bound.argtypes) == 11
+    assert lib.bcp_goal_route.argtypes[2] is C.c_int64 and lib.bcp_goal_route.argtypes[9:11] == [C.c_int32, C.c_int32]
+    assert (_lib.ROUTE_LONG, _lib.ROUTE_TOO_CLOSE, _lib.ROUTE_NO_ROUTE, _lib.ROUTE_STUCK) == (1, 2, 4, 8)
+    for name, bit in (("LONG", 1), ("TOO_CLOSE", 2), ("NO_ROUTE", 4), ("STUCK", 8)):
+        assert "#define BCP_ROUTE_%s" % name in header and (RR.LONG, RR.TOO_CLOSE, RR.NO_ROUTE, RR.STUCK) == (1, 2, 4, 8)
+    assert _lib.ABI_VERSION == 2 and raw.bcp_abi_version() == 2
+    assert "#define BCP_ABI_VERSION 2" in header.replace("  ", " ")
