@@ -178,6 +178,43 @@ struct StepArgs {
     int32_t rollout_steps;     // step_local_kernel<.., ROLL = true> (bcp_rollout): steps per launch; actions / noise_z / outputs are [steps][N]..
     const uint32_t* map_tiles; // MapDesc::tiles: what step_local_kernel's exact tests read when the map is not staged in LDS
 };
+// The per-launch words finalize_env_from uses, as they lie in StepArgs (noise_z_out .. err), and the flags.  The shared-
+// geometry variant of step_local_kernel keeps this launch's copy in LDS, behind its copy of *S (kFinishSlotBytes).
+struct FinishWords {
+    double* noise_z_out;
+    double* reward;
+    uint8_t* done;
+    uint8_t* collided_now;
+    int32_t* err;
+    uint32_t flags, pad;
+};
+constexpr int kFinishPtrWords = 5 * 2;
+constexpr int kFinishSlotBytes = 64;
+static_assert(offsetof(StepArgs, err) + 8 - offsetof(StepArgs, noise_z_out) == kFinishPtrWords * 4 &&
+              offsetof(FinishWords, flags) == kFinishPtrWords * 4 && sizeof(FinishWords) <= kFinishSlotBytes, "noise_z_out .. err are adjacent");
+
+// What finalize_env_from takes from a launch, under StepArgs' member names, as VALUES: the movers of step_local_kernel's
+// shared-geometry variant read them from LDS in one batch (FinishWords and the state arrays of the LDS copy of *S), into vector
+// registers -- every store of the finishing pass has a per-lane 64-bit address anyway -- instead of fetching each from the
+// launch arguments where it is first used, one scalar round trip after the other at the very end of the workgroup.
+struct FinishArgs {
+    const __attribute__((address_space(4))) StepArgs* launch;   // (for the global block *S: the episode record)
+    struct {
+        DevState st;   // (x .. collided)
+    } hot;
+    double* noise_z_out;
+    double* reward;
+    uint8_t* done;
+    uint8_t* collided_now;
+    int32_t* err;
+    uint32_t flags;    // (wave-uniform, one scalar register)
+};
+
+// the parameter block in global memory (finalize_env_from: the episode record, which no LDS copy holds)
+template <typename A>
+__device__ __forceinline__ const StepStatic* global_block(const A& a) { return a.S; }
+__device__ __forceinline__ const StepStatic* global_block(const FinishArgs& a) { return a.launch->S; }
+
 constexpr int kTickWords = 16;
 constexpr int kTickLocalTicket = 8;   // step_local_kernel's ticket: not on the line the prologues read the counter and the seed from
 
@@ -854,6 +891,9 @@ __device__ unsigned long long g_diag[kDiagBlocks * 16];
 // lane 0 of EVERY wave: row (base + workgroup), slot = wave number (base = 1024, 1536: arrival at barrier 0 / 1)
 #define DIAG_STAMP_WAVES(base) do { if ((threadIdx.x & 63) == 0 && blockIdx.x < 256) g_diag[((base) + blockIdx.x) * 16 + (threadIdx.x >> 6)] = __builtin_amdgcn_s_memtime(); } while (0)
 // maximum over ALL lanes of the workgroup (not only lane 0 of each wave)
+/* the finishing pass (finalize_env_from) of wave 0, lane 0: rows 1792 .. 2047, slots 0 .. 3 -- arguments in hand, outputs stored, reset values in hand, state stored */
+#define DIAG_STAMP_FIN(k) do { if (threadIdx.x == 0 && blockIdx.x < 256) g_diag[(1792 + blockIdx.x) * 16 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
+#define DIAG_WAIT_LGKM() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
 #define DIAG_MAX_ALL(k, v) do { if (blockIdx.x < 2048) atomicMax(&g_diag[(2048 + blockIdx.x) * 16 + (k)], (unsigned long long)(v)); } while (0)
 extern "C" int bcp_diag_read(unsigned long long* out)
 {
@@ -876,6 +916,8 @@ extern "C" int bcp_diag_clear()
 #define DIAG_STAMP_U(w, k) do { } while (0)
 #define DIAG_WAIT_VMEM() do { } while (0)
 #define DIAG_STAMP_WAVES(base) do { } while (0)
+#define DIAG_STAMP_FIN(k) do { } while (0)
+#define DIAG_WAIT_LGKM() do { } while (0)
 #define DIAG_MAX_ALL(k, v) do { } while (0)
 #endif
 
@@ -1060,7 +1102,8 @@ __device__ __forceinline__ int64_t slot_of(SP S, int64_t i, const Pending& q)
 // (:377-396), reward (:352), done (:407-419), outputs, optional reset, state write-back.  Runs on one lane for env i.
 // PLAIN = true (no delays, continuous reward provider -- see step_is_plain) compiles the delay queues and the
 // pure-pursuit branch out.
-// (A: StepArgs by value, or by reference into the kernel-argument segment -- only a.S, the output pointers and a.flags are used)
+// (A: StepArgs by value, or by reference into the kernel-argument segment, or FinishArgs -- only the global block, the output
+//  pointers, a.hot.st and a.flags are used)
 // Returns the episode-record slot the env took (-1: none, or no record bound).
 // SHARED (step_local_kernel's variant for one map, one path and no geometry pool, see step_local_body): the branches on
 // those properties are compiled out.
@@ -1134,6 +1177,8 @@ __device__ __forceinline__ int finalize_env_from(const A& a, SP S, int64_t i, Pe
     const bool done = goal || timeout || collided;   // env.py:400-419
 
     const int64_t o = out_base + i;
+    DIAG_WAIT_LGKM();
+    DIAG_STAMP_FIN(0);   // arguments in hand (the shared-geometry variant: read from LDS ahead of the verdicts)
     as_global(a.reward)[o] = rew;
     as_global(a.done)[o] = (uint8_t)done;
     if (a.collided_now) as_global(a.collided_now)[o] = (uint8_t)hit;
@@ -1145,6 +1190,7 @@ __device__ __forceinline__ int finalize_env_from(const A& a, SP S, int64_t i, Pe
         as_global(a.noise_z_out)[3 * o + 2] = (q.drawn & 4) ? q.z[2] : nan;
     }
 
+    DIAG_STAMP_FIN(1);   // outputs stored
     const bool reset = done && (a.flags & BCP_STEP_AUTO_RESET);
     InitAhead ahead = InitAhead();   // (initialised: left undefined outside the branch, it was kept in scratch memory)
     if (reset) {  // PlanEnv.reset(): set_state(initial_state) (env.py:293-303)
@@ -1161,7 +1207,7 @@ __device__ __forceinline__ int finalize_env_from(const A& a, SP S, int64_t i, Pe
     // env holds after its last step goes to a slot while the initial-state loads above are in flight.
     int rec_slot = -1;
     if (a.flags & kStepRecord) {
-        const EpisodeRec& R = a.S->rec;   // (the global block: step_local_kernel's LDS copy ends before the record)
+        const EpisodeRec& R = global_block(a)->rec;   // (the global block: step_local_kernel's LDS copy ends before the record)
         double ret_sum = 0.0;             // the episode's return, summed in step order (reward.py:66-69, :144-153)
         if (R.ret) ret_sum = (redo.on ? redo.ret_before : as_global(R.ret)[i]) + rew;
         as_global(R.reason)[i] = done ? (uint8_t)((goal ? BCP_DONE_GOAL : 0) | (timeout ? BCP_DONE_TIMEOUT : 0) |
@@ -1235,8 +1281,13 @@ __device__ __forceinline__ int finalize_env_from(const A& a, SP S, int64_t i, Pe
         seen_rs[4] = r.w;
         seen_rs[5] = r.steer;
         seen_rs[6] = r.wheel;
+#ifdef BCP_DIAG
+        DIAG_WAIT_VMEM();
+        DIAG_STAMP_FIN(2);   // reset values in hand (diagnostic build only: the wait is not in the shipping kernel)
+#endif
     }
-    // (the state pointers come with the kernel arguments -- StepHot -- not through *S: one dependent load less per array)
+    // (the state pointers come with the kernel arguments -- StepHot -- not through *S: one dependent load less per array;
+    //  step_local_kernel's shared-geometry variant: with the rest of FinishArgs, from the LDS copy of *S)
     as_global(a.hot.st.x)[i] = r.p.x;
     as_global(a.hot.st.y)[i] = r.p.y;
     as_global(a.hot.st.angle)[i] = r.p.th;
@@ -1258,6 +1309,7 @@ __device__ __forceinline__ int finalize_env_from(const A& a, SP S, int64_t i, Pe
 #pragma unroll
         for (int c = 0; c < 7; ++c) S->st.state_seen[c * n + i] = seen_rs[c];
     }
+    DIAG_STAMP_FIN(3);   // state stored
     return rec_slot;
 }
 
@@ -1715,6 +1767,7 @@ static size_t local_step_lds_bytes(int n_verts, int lds_path_doubles, int staged
     bytes += (size_t)staged_map_words * sizeof(uint32_t);
     bytes = (bytes + 15) & ~(size_t)15;
     bytes += kStaticChunks * 16;   // the parameter block *S
+    bytes += kFinishSlotBytes;     // this launch's FinishWords (the shared-geometry variant)
     if (!plain) bytes += (size_t)10 * kLocalEnvs * sizeof(double);   // delay queues: what the step's pushes will hand back
     return bytes;
 }
@@ -1882,7 +1935,9 @@ __device__ __forceinline__ void step_local_body(KernArgPtr kernarg, const int rs
     // delay queues (PLAIN = false): the ten values this step's pushes into the pose / robot-state queues will hand back are
     // fetched with the state (fifo_peek) and needed when the env is finished; in between they wait in LDS, not in 20 vector
     // registers of a wave that has none to spare
-    __attribute__((address_space(3))) double* fifo_stash = (__attribute__((address_space(3))) double*)(lds_static + kStaticChunks) + pair * kBlock + lane;
+    __attribute__((address_space(3))) double* fifo_stash = (__attribute__((address_space(3))) double*)(lds_static + kStaticChunks + kFinishSlotBytes / 16) + pair * kBlock + lane;
+    // this launch's FinishWords, behind the parameter block (SHARED: written by the last wave ahead of barrier 0)
+    __attribute__((address_space(3))) uint32_t* const lds_finish_words = (__attribute__((address_space(3))) uint32_t*)(lds_static + kStaticChunks);
 
     DIAG_STAMP(0);
     DIAG_STAMP_WAVES(768);    // every wave: launch arguments fetched
@@ -1962,6 +2017,18 @@ __device__ __forceinline__ void step_local_body(KernArgPtr kernarg, const int rs
     u32x4 st_static = {0u, 0u, 0u, 0u};
     const bool first_trip = !ROLL || rs == 0;   // the staging data is copied into LDS once per launch
     if (first_trip && tid >= kStaticFrom && tid < kStaticFrom + kStaticChunks) st_static = as_global(reinterpret_cast<const u32x4*>(a.S))[tid - kStaticFrom];
+    // (2a) SHARED: the per-launch words of the finishing pass -- output pointers, flags -- go to LDS too.  They belong to this
+    //     launch (a caller may hand a different `done` row every step), so they are fetched from the launch arguments every
+    //     time, by the last wave, whose chain is not the movers': a word per lane, by a VECTOR load of the argument segment
+    //     that is in flight beside the wave's share of *S and stored with it, in front of barrier 0.  (As a scalar fetch the
+    //     two or three cold argument lines cost the wave a wait of ~1.2 k cycles of its own: without noise to draw it was then
+    //     the last to reach barrier 0, C2 +0.6 %.)  The flags are in the prologue's hands already.  The movers read the slot
+    //     back ahead of their verdict polls (FinishArgs).
+    uint32_t st_finish = 0;
+    const bool finish_stager = SHARED && tid >= kCtlFrom && tid < kCtlFrom + kFinishPtrWords;
+    if (finish_stager)
+        st_finish = as_global(reinterpret_cast<const uint32_t*>((uintptr_t)kernarg + offsetof(StepArgs, noise_z_out)))[tid - kCtlFrom];
+    if (SHARED && tid == kCtlFrom + kFinishPtrWords) lds_finish_words[kFinishPtrWords] = L.flags;
     DIAG_STAMP_U(0, 10);   // mover: own + staging loads issued
     DIAG_STAMP_U(kWScorer, 11);   // scorer: the same
     DIAG_STAMP_WAVES(1280);   // every wave: prologue loads issued
@@ -2029,6 +2096,7 @@ __device__ __forceinline__ void step_local_body(KernArgPtr kernarg, const int rs
     // (6) the parameter block into LDS
     if (tid >= kCtlFrom && tid < kCtlFrom + 16) ctl[tid - kCtlFrom] = 0;
     if (first_trip && tid >= kStaticFrom && tid < kStaticFrom + kStaticChunks) lds_static[tid - kStaticFrom] = st_static;
+    if (finish_stager) lds_finish_words[tid - kCtlFrom] = st_finish;
     DIAG_STAMP_WAVES(1024);
     __syncthreads();   // barrier 0: noise, old heading and the parameter block are in LDS
     const DevParams& P = *(const DevParams*)&SL->P;
@@ -2134,6 +2202,8 @@ __device__ __forceinline__ void step_local_body(KernArgPtr kernarg, const int rs
         {
             // (a shared field is 18 KB for the 183 x 183 map and stays in the CU's L1: a copy in LDS measured no faster)
             if (SHARED || a.hot.near) {
+                // (SHARED: `near` from the LDS copy of *S instead, SL->cull.step_near, one scalar fetch less in front of the
+                //  classification: measured, no difference -- profiles/step_finish_pass.txt)
                 cls = classify_near(outer, as_global(a.hot.near) + map_env * near_stride, map_rows, map_cols, px, py, c, s);
             } else {
                 const OuterLookups look = outer_lookups_issue(*(const CullDesc*)&SL->cull, map_env, map_rows, map_cols, px, py, c, s);
@@ -2442,6 +2512,32 @@ __device__ __forceinline__ void step_local_body(KernArgPtr kernarg, const int rs
     // (7) movers: the envs they parked are finished by the lane that holds their state, as soon as the verdicts are in
     //     (every parked pose has been claimed by now -- by this wave or by one that is working on it)
     if (mover) {
+        // SHARED: everything the finishing pass takes from the launch, read from LDS in one batch and issued HERE, ahead of
+        // the verdict polls, so that it has landed when the verdicts are in: this launch's FinishWords and the state arrays of
+        // the LDS copy of *S (the same pointers as StepHot's).  The generic variants fetch them from the launch arguments.
+        FinishArgs fin = FinishArgs();
+        uint32_t fin_flags = 0;
+        if (SHARED) {
+            const __attribute__((address_space(3))) FinishWords* fw = (const __attribute__((address_space(3))) FinishWords*)lds_finish_words;
+            fin.launch = kernarg;
+            fin.noise_z_out = fw->noise_z_out;
+            fin.reward = fw->reward;
+            fin.done = fw->done;
+            fin.collided_now = fw->collided_now;
+            fin.err = fw->err;
+            fin_flags = fw->flags;
+            fin.hot.st.x = SL->st.x;
+            fin.hot.st.y = SL->st.y;
+            fin.hot.st.angle = SL->st.angle;
+            fin.hot.st.v = SL->st.v;
+            fin.hot.st.w = SL->st.w;
+            fin.hot.st.steer = SL->st.steer;
+            fin.hot.st.wheel = SL->st.wheel;
+            fin.hot.st.min_dist = SL->st.min_dist;
+            fin.hot.st.target_idx = SL->st.target_idx;
+            fin.hot.st.cur_iter = SL->st.cur_iter;
+            fin.hot.st.collided = SL->st.collided;
+        }
         int verdict = park ? 0 : 1;
         {
             int trips = 0;
@@ -2463,6 +2559,7 @@ __device__ __forceinline__ void step_local_body(KernArgPtr kernarg, const int rs
         // the step ends with the workgroups that hold such an env).  Shared path in LDS, continuous provider without delays;
         // otherwise finalize_env_from computes it itself.
         const bool hit_score = PLAIN && (SHARED || lds_path) && (SHARED || a.hot.path_shared) && !ABLATED(a, kAblateNoReward);
+        fin.flags = (uint32_t)__builtin_amdgcn_readfirstlane((int)fin_flags);   // (one value for the pass's tests of the flags)
         int last_hit = -1;
         if (hit_score) {
             uint64_t hits = __ballot(park && verdict == 2);
@@ -2495,12 +2592,15 @@ __device__ __forceinline__ void step_local_body(KernArgPtr kernarg, const int rs
 #pragma unroll
                 for (int k = 0; k < 7; ++k) q.popped_state[k] = fifo_stash[(3 + k) * kLocalEnvs];
             }
-            finalize_env_from<PLAIN, SHARED>(a, SL, i, q, hit_now, lds_path, nullptr, !ABLATED(a, kAblateNoReward), sc, my_len, fits, out_base);
+            if constexpr (SHARED)
+                finalize_env_from<PLAIN, SHARED>(fin, SL, i, q, hit_now, lds_path, nullptr, !ABLATED(a, kAblateNoReward), sc, my_len, fits, out_base);
+            else
+                finalize_env_from<PLAIN, SHARED>(a, SL, i, q, hit_now, lds_path, nullptr, !ABLATED(a, kAblateNoReward), sc, my_len, fits, out_base);
         }
         // Episode record: the step's count can only be published once every mover has taken its slots, so with a record the
         // last mover of the workgroup (ctl[3], an LDS count) draws the step's ticket in place of the wave below -- one
         // global atomic per workgroup, as without a record; the last workgroup moves the counter on and publishes the count.
-        if ((a.flags & kStepRecord) && lane == 0 &&
+        if (((SHARED ? fin.flags : a.flags) & kStepRecord) && lane == 0 &&
             __hip_atomic_fetch_add(&ctl[3], 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP) == kLocalPairs - 1) {
             __threadfence();
             unsigned int* ticket = reinterpret_cast<unsigned int*>(a.tick + kTickLocalTicket);

@@ -4,6 +4,9 @@ import sys, os, ctypes as C, numpy as np, torch
 sys.path.insert(0, '.')
 from bc_gym_planning_env_amd import _lib
 _lib.LIB_PATH = os.path.join('tools', 'libbcplan_diag.so')
+for arg in sys.argv[1:]:    # (another -DBCP_DIAG build, e.g. the parent's beside this one's)
+    if arg.endswith('.so'):
+        _lib.LIB_PATH = arg
 import bench
 n = 65536
 pairs = int(os.environ.get("BCP_LOCAL_PAIRS", "4"))   # workgroup size of step_local_kernel (bcp_create reads the same variable)
@@ -83,6 +86,28 @@ endw = np.maximum(a[:, 13], a[:, 14]) - a[:, 0]
 for k in sorted(set(a[:, 15].tolist())):
     sel = a[:, 15] == k
     print("  parked %2d: %3d workgroups, done after median %6d  max %6d cycles" % (k, sel.sum(), np.median(endw[sel]), endw[sel].max()))
+# the finishing pass: from the mover's reward to the end of its envs, in workgroups where no verdict is waited for, and the
+# stamps inside finalize_env_from (wave 0, lane 0 of the first 256 workgroups; zero in builds from before the stamps)
+calm = a[:, 15] == 0
+if calm.any():
+    d = (a[:, 13] - a[:, 6])[calm]
+    print("  no parked pose: %d workgroups, reward provider done -> out of tickets: median %d  min %d  max %d cycles" % (calm.sum(), np.median(d), d.min(), d.max()))
+d = a[:, 13] - a[:, 6]
+print("  all workgroups: reward provider done -> out of tickets: median %d  p90 %d  max %d cycles" % (np.median(d), np.percentile(d, 90), d.max()))
+fin = raw[1792:1792 + min(groups, 256), :4]
+if fin[:, 0].any():
+    b = a[:len(fin)]
+    fnames = ("arguments in hand", "outputs stored", "reset values in hand (lane 0 resets)", "state stored")
+    for k in (0, 1, 2, 3):
+        sel = fin[:, k] > 0
+        if sel.any():
+            d = (fin[:, k] - b[:, 6])[sel]
+            print("  finishing pass, %-38s since reward provider done: %3d workgroups, median %5d  p90 %5d" % (fnames[k], sel.sum(), np.median(d), np.percentile(d, 90)))
+    d = fin[:, 3] - fin[:, 0]
+    print("  finishing pass, arguments in hand -> state stored: median %d  p90 %d  max %d cycles" % (np.median(d), np.percentile(d, 90), d.max()))
+    for label, sel in (("lane 0 resets", fin[:, 2] > 0), ("lane 0 does not reset", fin[:, 2] == 0)):
+        if sel.any():
+            print("     %-22s %3d workgroups: median %d cycles" % (label + ":", sel.sum(), np.median(d[sel])))
 # the longest exact test of each workgroup: cycles and kind (0 free, 1 hit, 2 too many cells -> row-by-row rasteriser)
 dur, kind = upper[:, 0] >> 4, upper[:, 0] & 15
 for k in (0, 1, 2):
