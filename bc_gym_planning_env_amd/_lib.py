@@ -19,6 +19,7 @@ TUNE_LOCAL_PAIRS, TUNE_EGO_LIST_STRIDE, TUNE_NEAR_SHIFT, TUNE_INFLATE_ROUTE, TUN
 TUNE_LOCAL_SHARED = 13
 GOAL_ORTHO, GOAL_DIAG, GOAL_FAR, GOAL_NONE = 12, 17, 65534, 65535
 ROUTE_LONG, ROUTE_TOO_CLOSE, ROUTE_NO_ROUTE, ROUTE_STUCK = 1, 2, 4, 8
+SCATTER_SHORT, SCATTER_REVERTED = 1, 2   # BatchedPlanEnv.scatter_obstacles' status bits
 E_NO_DEVICE = -2
 OPT_DIFFDRIVE_NOISE = 1
 EGO_KERNELS = {0: "none", 1: "ego_sparse_kernel", 2: "ego_costmap_kernel<staged>", 3: "ego_costmap_binned_kernel",
@@ -120,6 +121,14 @@ class BcpMppiWidths(C.Structure):
     _fields_ = [
         ("sigma", C.c_void_p), ("sigma_min", C.c_double * 2), ("sigma_max", C.c_double * 2), ("rate", C.c_double),
         ("iter_sigma", C.c_void_p),
+    ]
+
+
+class BcpScatterParams(C.Structure):
+    """bcp_scatter_params: what bcp_scatter_boxes draws from"""
+    _fields_ = [
+        ("n_boxes", C.c_int32), ("max_attempts", C.c_int32), ("n_yaws", C.c_int32), ("reserved", C.c_int32),
+        ("seed", C.c_uint64), ("along", C.c_double * 2), ("half_size", C.c_double * 2),
     ]
 
 
@@ -226,6 +235,9 @@ SYMBOLS = {
                                  C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bcp_goal_route_bound": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bcp_scatter_boxes": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_double, C.POINTER(BcpScatterParams), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

@@ -15,7 +15,7 @@ import attr
 import numpy as np
 import torch
 
-from . import _lib, host_init, robots
+from . import _lib, boxes, host_init, robots
 from .api import Action, Box, CONTINUOUS_REWARD_PURE_PURSUIT, CostMap2D, EnvParams, INDUSTRIAL_TRICYCLE_V1, State
 from .episode_record import EpisodeEnds
 from .geometry import DeviceGeometryPool, chain_layout, stack_costmaps, stack_paths
@@ -118,6 +118,7 @@ class BatchedPlanEnv(Handle):
         self.endless = False       # BatchedRandomMiniEnv(endless=True)
         self._inflated = False     # inflate_costmaps()
         self._path_per_env = False  # route_paths() on expanded templates: self._paths then holds a path per env
+        self._map_per_env = False   # scatter_obstacles() on expanded templates: self._costmaps then holds a map per env
         self._goal_followers = []  # weak references to the GoalFields a refresh() keeps current (goal_field(follow_refresh=True))
         self._rollout_buffers, self._lookahead_buffers, self._mppi_buffers = OrderedDict(), OrderedDict(), OrderedDict()
         self._range_scan_buffers = OrderedDict()
@@ -414,7 +415,7 @@ class BatchedPlanEnv(Handle):
     def costmap_of(self, i):
         if self.geom_of_env is not None:
             return self._costmaps[int(self.geom_of_env[i])]
-        if self._template_of_env is not None:
+        if self._template_of_env is not None and not self._map_per_env:
             return self._costmaps[self._template_of_env[i]]
         if self._shared_map or len(self._costmaps) == 1:
             return self._costmaps[0]
@@ -832,6 +833,75 @@ class BatchedPlanEnv(Handle):
             self._path_per_env = self._template_of_env is not None
         self.reset()
         return status
+
+    def scatter_obstacles(self, n_boxes, half_size, along=(0.2, 0.8), lateral=1.0, keep_clear=None, n_yaws=16, seed=0,
+                          max_attempts=32, ensure_route=True, clearance=None):
+        """Stamp up to n_boxes box obstacles into every entry's map, on the device and reproducibly (bcp_scatter_boxes, one
+        launch): boxes with half sizes uniform in half_size = (lo, hi) metres and one of n_yaws yaws (multiples of
+        2 pi / n_yaws), centred at start + t * (goal - start) + l * lateral * normal of the entry's bound path -- t uniform
+        in `along`, l in (-1, 1), `lateral` in metres.  Entry m tries attempts 0 .. max_attempts - 1, drawn from
+        (seed, m, attempt), and keeps the first n_boxes that stay inside its valid shape and clear of its start and goal
+        cells by keep_clear metres (None = the footprint's circumscribed radius R; d2 = (ceil(R / resolution) + 1)^2 cells),
+        so the start and goal poses of every entry stay collision-free.  Boxes may overlap walls and each other.
+        ensure_route: a goal field is then built on the new maps at `clearance` (None = the footprint's inscribed radius, as
+        in goal_field()); an entry whose start cell has no value -- its boxes cut the goal off -- gets its original map
+        back, on the device, and SCATTER_REVERTED in its status.  SCATTER_SHORT marks counts < n_boxes.
+        The maps are bound again with the arguments of the original binding, so that everything derived from them is
+        rebuilt; the host copies behind envs[i].get_state().costmap follow, a pool that lives on the device is changed
+        where it is (whoever else holds it sees the boxes), and the call ends with reset().  GoalFields of this env built
+        before the call are stale: build them again.  Scatter first, then inflate_costmaps().
+        Returns (status int32 [entries], counts int32 [entries], boxes int32 [entries, n_boxes, 9] = (attempt, four (x, y)
+        corners in cells), zeros behind counts) -- device tensors; counts and boxes of a reverted entry say what had been
+        placed.
+        Refused on endless=True pools (refresh() would write bare worlds back), on a shared map or path, and on maps that
+        are inflated already."""
+        if self.endless:
+            raise RuntimeError("scatter_obstacles: not supported on endless=True pools -- refresh() re-samples bare worlds "
+                               "into the pool")
+        if self._shared_path or self._shared_map:
+            raise RuntimeError("scatter_obstacles: needs private maps with private paths (a pool, or a map and a path per env)")
+        if self._inflated:
+            raise RuntimeError("scatter_obstacles: the costmaps of this env are inflated already -- scatter first, then inflate")
+        data, origins = self._keep["map"], self._keep["origins"]
+        vr, vc = self._keep.get("vr"), self._keep.get("vc")
+        pts, lens = self._keep["path"], self._keep["lens"]
+        n = int(data.shape[0])
+        last = (lens.to(torch.int64) - 1).clamp(min=0)
+        starts = pts[:, 0, :].cpu().numpy()
+        goals = pts[torch.arange(n, device=self.device), last].cpu().numpy()
+        org = origins.cpu().numpy()
+        start_cells, goal_cells = boxes.cells_of(starts, org, self.resolution), boxes.cells_of(goals, org, self.resolution)
+        if keep_clear is None:
+            keep_clear = float(np.linalg.norm(self.footprint(), axis=1).max())
+        d2 = (int(np.ceil(float(keep_clear) / self.resolution)) + 1) ** 2
+        original = data.clone()
+        bx, counts = boxes.scatter_boxes(self, data, origins, self.resolution, boxes.path_frames(starts, goals, lateral),
+                                         boxes.yaw_table(n_yaws), n_boxes, half_size, along,
+                                         boxes.keep_outs([start_cells, goal_cells], d2), (vr, vc), seed, max_attempts)
+        status = (counts < int(n_boxes)).to(torch.int32) * _lib.SCATTER_SHORT
+        if ensure_route:
+            fields = self.goal_field(clearance)
+            sc = torch.from_numpy(start_cells).to(self.device)
+            rows, cols = int(data.shape[1]), int(data.shape[2])
+            inside = (sc[:, 0] >= 0) & (sc[:, 0] < rows) & (sc[:, 1] >= 0) & (sc[:, 1] < cols)
+            # (uint16 planes cannot be indexed: as int16, GOAL_NONE reads -1)
+            at = fields.field.view(torch.int16)[torch.arange(n, device=self.device), sc[:, 0].clamp(0, rows - 1),
+                                                sc[:, 1].clamp(0, cols - 1)]
+            cut = ~inside | (at == _lib.GOAL_NONE - 65536)
+            data.copy_(torch.where(cut[:, None, None], original, data))
+            status = status | cut.to(torch.int32) * _lib.SCATTER_REVERTED
+        self.set_costmap_tensors(data, origins, self.resolution, vr, vc)
+        if self._device_pool is None:   # the host copies behind envs[i].get_state().costmap: one per entry
+            host = data.cpu().numpy()
+            shapes = (np.stack([vr.cpu().numpy(), vc.cpu().numpy()], axis=1) if vr is not None
+                      else np.tile(host.shape[1:], (n, 1)))
+            per_template = self._template_of_env is not None and not self._map_per_env
+            old = [self._costmaps[int(t)] for t in self._template_of_env] if per_template else list(self._costmaps)
+            self._costmaps = [CostMap2D(host[k, :shapes[k][0], :shapes[k][1]].copy(), c.get_resolution(), c.get_origin())
+                              for k, c in enumerate(old)]
+            self._map_per_env = self._template_of_env is not None
+        self.reset()
+        return status, counts, bx
 
     def enable_episode_record(self, capacity=None):
         """Keep what every episode end leaves behind (bcp_bind_episode_record): from now on step() returns

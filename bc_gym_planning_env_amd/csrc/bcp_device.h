@@ -10,6 +10,7 @@
 
 #include "../../include/bcplan.h"
 #include "bcp_desc.h"   // DevParams
+#include "bcp_philox.h"
 
 namespace bcp {
 
@@ -328,22 +329,7 @@ __device__ __forceinline__ int robot_step(const DevParams& P, Robot& r, double c
     return robot_step_end(P, r, d, z, drawn, old_heading);
 }
 
-// Philox4x32-10 (Salmon et al., SC'11), counter = (env_lo, env_hi, step_lo, step_hi), key = seed.
-__device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1)
-{
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        uint64_t p0 = (uint64_t)0xD2511F53u * c[0];
-        uint64_t p1 = (uint64_t)0xCD9E8D57u * c[2];
-        uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0;
-        uint32_t n1 = (uint32_t)p1;
-        uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-        uint32_t n3 = (uint32_t)p0;
-        c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-}
+// (philox4x32_10: bcp_philox.h)
 
 // Three standard normals for (seed, env, step): Box-Muller in float64 on 32-bit uniforms -- the stand-in for the float64
 // np.random.normal draws of robot_models/differential_drive.py:43-52 (parity runs replay exact values through noise_z).

@@ -4,7 +4,9 @@
 // collision classification / exact rasteriser -> rollback -> reward provider -> done -> optional reset -> state write-back),
 // bcp_lookahead.h and bcp_mppi.h (the planners), bcp_ego.h (egocentric views), bcp_sample.h and bcp_aisle.h (world samplers),
 // bcp_inflate.h (costmap inflation), bcp_scan.h (range scans; the walk: bcp_scan_march.h, no HIP in it), bcp_goal.h (goal
-// fields; a cell's arithmetic: bcp_goal_cell.h, no HIP in it).  The host side is split by subsystem:
+// fields; a cell's arithmetic: bcp_goal_cell.h, no HIP in it), bcp_boxes.h (box obstacles; the rule: bcp_boxes_cell.h, no HIP
+// in it; bcp_philox.h and bcp_outline.h hold the generator and the edge walk for host and device).  The host side is split by
+// subsystem:
 //   bcp_host.h         errors, the handle and the owners of its state (device buffers are DevBuf, events and streams Owned:
 //                      bcp_devbuf.h), EgoCells, the launch helpers
 //   bcp_field_plan.h   footprint geometry and the plan of a map binding: every shape and size, no HIP in it
@@ -17,6 +19,7 @@
 //   bcp_inflate_host.h bcp_inflate_costmaps (kernel: bcp_inflate.h)
 //   bcp_scan_host.h    bcp_range_scan / bcp_final_range_scan (kernel: bcp_scan.h)
 //   bcp_goal_host.h    bcp_goal_field / bcp_goal_field_sample / bcp_final_goal_field_sample (kernels: bcp_goal.h)
+//   bcp_boxes_host.h   bcp_scatter_boxes (kernel: bcp_boxes.h)
 //   bcp_seams_host.h   bind / reset / broadcast of the state and the operator seams (their small kernels: bcp_seams.h)
 // This file holds create / destroy / seed / pool / tuning / side stream, bcp_set_costmaps with the two reads of the distance
 // field, and bcp_set_paths.
@@ -47,6 +50,7 @@
 #include "bcp_inflate.h"
 #include "bcp_scan.h"
 #include "bcp_goal.h"
+#include "bcp_boxes.h"
 
 using namespace bcp;
 
@@ -104,6 +108,7 @@ static void fill_dev_params(bcp_handle* h)
 #include "bcp_inflate_host.h"
 #include "bcp_scan_host.h"
 #include "bcp_goal_host.h"
+#include "bcp_boxes_host.h"
 
 // ------------------------------------------------------------------------------------------------ host API
 extern "C" int bcp_create(const bcp_params* params, int64_t n_envs, int device, int64_t env_id_base, bcp_handle** out)

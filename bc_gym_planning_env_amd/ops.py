@@ -12,13 +12,14 @@ try/except ImportError), batched over many inputs.
   inflate_costmap       utilities/costmap_inflation.py:73-92 (cv2.distanceTransform + _pixel_distance_to_cost)
   range_scan            no counterpart: distances to the nearest lethal cell along beams (bcp_range_scan)
   goal_field            no counterpart: geodesic cost-to-go of a map to its seed cells (bcp_goal_field)
+  scatter_boxes         no counterpart: box obstacles stamped into a batch of maps (bcp_scatter_boxes)
 """
 import ctypes as C
 
 import numpy as np
 import torch
 
-from . import _lib, robots
+from . import _lib, boxes, robots
 from .api import EnvParams, INDUSTRIAL_TRICYCLE_V1
 from .handle import Handle
 
@@ -240,6 +241,24 @@ class NativeOps(Handle):
         self._alive["goal_field"] = (maps, s3, vr, vc)
         out = out[0] if d.dim() == 2 and s.dim() == 2 else out
         return (out, info) if want_info else out
+
+    def scatter_boxes(self, data, origins, resolution, frame, yaw_cs, n_boxes, half_size, along=(0.2, 0.8), keep=None,
+                      valid=None, seed=0, max_attempts=32):
+        """Box obstacles stamped into a batch of maps (bcp_scatter_boxes, one launch): data uint8 [n, rows, cols] -- a
+        contiguous tensor on the handle's device is written IN PLACE, anything else is copied there first -- with origins
+        [n, 2] at `resolution`.  Entry m tries attempts 0 .. max_attempts - 1 and keeps the first n_boxes that are not
+        rejected: a box with centre frame[m][0:2] + t * frame[m][2:4] + l * frame[m][4:6] (t uniform in `along`, l in
+        (-1, 1)), half sizes uniform in `half_size` (metres) and one of the yaws of yaw_cs [n_yaws, 2] = (cos, sin); rejected
+        when a corner leaves the entry's valid shape (valid = (valid_rows, valid_cols), None = the whole plane) or a cell of
+        it lies within squared distance d2 of a keep-out (row, col, d2) of keep int32 [n, K, 3] (d2 < 0: unused).  The
+        draws are Philox words of (seed, m, attempt): the same call gives the same boxes.
+        -> (data, boxes int32 [n, n_boxes, 9] = (attempt, four (x, y) corners in cells), counts int32 [n]); the slots
+        behind counts[m] are zeros.  Device tensors, no sync."""
+        d = self._device_tensor(data, torch.uint8)
+        assert d.dim() == 3
+        bx, counts = boxes.scatter_boxes(self, d, origins, resolution, frame, yaw_cs, n_boxes, half_size, along, keep, valid,
+                                         seed, max_attempts)
+        return d, bx, counts
 
     def robot_step(self, state7, actions, noise_z=None):
         """state7 [n,7] rows {x,y,angle,v,w,steering_motor_command,wheel_angle}, actions [n,2] -> (new [n,7], err)."""

@@ -997,6 +997,55 @@ int bcp_goal_route_bound(bcp_handle *h, const uint16_t *field, int32_t rows, int
 #define BCP_ROUTE_NO_ROUTE  4
 #define BCP_ROUTE_STUCK     8
 
+/* ---- box obstacles ------------------------------------------------------------------------------------ */
+/* bcp_scatter_boxes: rectangular obstacles stamped into every map of a batch, reproducibly.  One launch (one 256-thread
+ * workgroup per entry), asynchronous on `stream`, no allocation, no upload, no host synchronisation; the launch arguments
+ * depend only on the pointers and numbers given, so a call can be captured into a HIP graph after one ordinary call.
+ * Nothing of the handle changes: the maps are the caller's (bind them again if they are the ones bound).
+ * Everything below is float64 + - *, rint (half to even) and integers, every operation rounded on its own; there is no
+ * sin, cos, sqrt or division on the device.
+ * Draws: for entry m and attempt a, Philox4x32-10 with key (seed low word, seed high word): counter (m_lo, m_hi, a, 0) gives
+ * w0 .. w3 and counter (m_lo, m_hi, a, 1) gives v0;  u_i = ((double)w_i + 0.5) * 2^-32.
+ * Candidate box of (m, a), with frame[m] = (ax, ay, dx, dy, nx, ny) -- anchor, along-vector, lateral vector:
+ *   t = along[0] + u0 * (along[1] - along[0])        l = 2 * u1 - 1
+ *   hx = half_size[0] + u2 * (half_size[1] - half_size[0])      hy likewise from u3
+ *   k = ((uint64)v0 * n_yaws) >> 32      (c, s) = yaw_cs[k], the caller's table of cosines and sines
+ *   cx = (ax + t * dx) + l * nx          cy = (ay + t * dy) + l * ny
+ *   for the corner signs (sx, sy) = (+,+), (-,+), (-,-), (+,-):
+ *     wx = (cx + (sx * hx) * c) - (sy * hy) * s       wy = (cy + (sx * hx) * s) + (sy * hy) * c
+ *     px = rint((wx - ox) * inv_res)   py = rint((wy - oy) * inv_res)     (world_to_pixel; inv_res = 1.0 / resolution)
+ * The four integer vertices V are the candidate; its pixel set is exactly what cv2.fillPoly(img, [V], 254) writes for that
+ * contour: the four edges by the 8-connected LineIterator plus the even-odd spans in 16.16 fixed point.  Degenerate
+ * contours come out as fillPoly draws them: half sizes of 0 give a single pixel, one of them 0 a line.
+ * A candidate is rejected when a vertex lies outside [0, valid_cols[m]) x [0, valid_rows[m]) (NULL: cols, rows; a vertex
+ * that is not a finite number lies outside), or when a cell (r, c) of its pixel set has (r - kr)^2 + (c - kc)^2 <= d2 for
+ * a keep-out (kr, kc, d2) of keep[m]; d2 < 0 is an unused slot.
+ * The accepted boxes of an entry are the first n_boxes attempts, in attempt order, of 0 .. max_attempts - 1 that are not
+ * rejected.  Overlap with walls or with other boxes is allowed, so a verdict depends on its attempt alone.  Every cell of
+ * an accepted box becomes 254; no other byte of `data` changes.
+ * boxes: [n_maps][n_boxes][9] = (attempt, V0.x, V0.y, .. V3.x, V3.y) per accepted box, x a column and y a row; the slots
+ * behind counts[m] are zeros.  counts: [n_maps].
+ * BCP_E_INVALID, tested in this order: NULL h; NULL p; n_maps < 0; rows or cols outside [1, 2048]; resolution not a finite
+ * number > 0; n_boxes outside [1, 64]; max_attempts outside [1, 4096]; n_yaws outside [1, 4096]; n_keep outside [0, 16];
+ * along not finite or along[0] > along[1]; half_size not finite, negative or half_size[0] > half_size[1]; a largest box
+ * that need not fit the map, (4 * half_size[1]) * inv_res + 2 > min(rows, cols); one of valid_rows / valid_cols without
+ * the other; n_maps > 0 with a NULL data, origins, frame, yaw_cs, boxes or counts, or with n_keep > 0 and a NULL keep. */
+typedef struct bcp_scatter_params {
+    int32_t n_boxes;        /* boxes wanted per entry */
+    int32_t max_attempts;   /* attempts 0 .. max_attempts - 1 are tried */
+    int32_t n_yaws;         /* rows of yaw_cs */
+    int32_t reserved;       /* 0 */
+    uint64_t seed;
+    double along[2];        /* the range of t */
+    double half_size[2];    /* the range of hx and hy, in metres */
+} bcp_scatter_params;
+int bcp_scatter_boxes(bcp_handle *h, uint8_t *data /*[n_maps][rows][cols]*/, int64_t n_maps, int32_t rows, int32_t cols,
+                      const int32_t *valid_rows /*[n_maps] or NULL*/, const int32_t *valid_cols,
+                      const double *origins /*[n_maps][2]*/, double resolution, const bcp_scatter_params *p /*host*/,
+                      const double *frame /*[n_maps][6]*/, const int32_t *keep /*[n_maps][n_keep][3] or NULL*/, int32_t n_keep,
+                      const double *yaw_cs /*[n_yaws][2]*/, int32_t *boxes /*[n_maps][n_boxes][9]*/, int32_t *counts /*[n_maps]*/,
+                      void *stream);
+
 /* ---- measurement -------------------------------------------------------------------------------------- */
 /* Which kernels a bcp_step() of this handle launches, as configured now: 0 = step_kernel alone (no distance field, or a
  * forced mode), 1 = step_fast_pair_kernel alone (every undecided pose settled in place), 2 = step_fast_pair_kernel +
