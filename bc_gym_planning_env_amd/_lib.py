@@ -150,6 +150,7 @@ SYMBOLS = {
     "bcp_set_paths": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "bcp_bind_state": (C.c_int, [_H, C.POINTER(BcpState)]),
     "bcp_bind_initial_state": (C.c_int, [_H, C.POINTER(BcpState)]),
+    "bcp_declare_uniform_initial_state": (C.c_int, [_H, C.c_int, C.c_void_p]),
     "bcp_reset_masked": (C.c_int, [_H, C.c_void_p, C.c_void_p]),
     "bcp_broadcast_state": (C.c_int, [_H, C.c_int64, C.c_void_p, C.c_void_p]),
     "bcp_step": (C.c_int, [_H, C.POINTER(BcpStepIO), C.c_uint32, C.c_void_p]),
@@ -207,6 +208,7 @@ SYMBOLS = {
     "bcp_device_normals": (C.c_int, [_H, C.c_int64, C.c_int64, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p]),
     "bcp_step_form": (C.c_int, [_H]),
     "bcp_step_shared_variant": (C.c_int, [_H]),
+    "bcp_step_uniform_reset": (C.c_int, [_H]),
     "bcp_time_step_kernels": (C.c_int, [_H, C.POINTER(BcpStepIO), C.c_uint32, C.c_int32, C.c_void_p,
                                         C.POINTER(C.c_float)]),
     "bcp_time_steps": (C.c_int, [_H, C.POINTER(BcpStepIO), C.c_uint32, C.c_int32, C.c_void_p, C.POINTER(C.c_float)]),

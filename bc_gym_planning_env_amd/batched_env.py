@@ -146,7 +146,7 @@ class BatchedPlanEnv(Handle):
             self._set_paths(path)
         self._bind(self.state, self._lib.bcp_bind_state)
         self._initial_state = self._make_initial_state()
-        self._bind(self._initial_state, self._lib.bcp_bind_initial_state)
+        self._bind_initial_state()
         # per-step call state, built once (the step path itself should cost microseconds of host time)
         self._io = _lib.BcpStepIO()
         self._io.reward = self.reward.data_ptr()
@@ -176,6 +176,27 @@ class BatchedPlanEnv(Handle):
     # ------------------------------------------------------------------ construction helpers
     def _bind(self, s, fn):
         _lib.check(fn(self._h, C.byref(s.fill_pointers(_lib.BcpState()))))
+
+    def _bind_initial_state(self):
+        """Binds self._initial_state and, where one shared path gives every env the same initial state (no pool, no expanded
+        templates), declares it uniform (declare_uniform_initial_state): the library checks the arrays and refuses otherwise."""
+        self._bind(self._initial_state, self._lib.bcp_bind_initial_state)
+        if self._shared_path and self.geom_of_env is None and self._template_of_env is None:
+            self.declare_uniform_initial_state(True)
+
+    def declare_uniform_initial_state(self, on=True):
+        """bcp_declare_uniform_initial_state: on=True checks (on the host, synchronising) that every env's bound initial state
+        equals env 0's bit for bit and keeps that entry as a snapshot; auto-reset steps of the shared-geometry kernel then
+        reset from it without loading the arrays.  Raises _lib.BcpError where the arrays differ or the env has a geometry
+        pool.  The snapshot is a value: after writing the initial tensors in place, declare again.  on=False drops it."""
+        _lib.check(self._lib.bcp_declare_uniform_initial_state(self._h, 1 if on else 0, self._stream()))
+
+    def step_uniform_reset(self):
+        """True when the last step() took its resets from the declared uniform initial state (bcp_step_uniform_reset)."""
+        rc = self._lib.bcp_step_uniform_reset(self._h)
+        if rc < 0:
+            _lib.check(rc)
+        return rc == 1
 
     def _refine(self):
         """What every path given to the constructor goes through: refine_path at params.path_delta, or nothing."""

@@ -234,6 +234,10 @@ struct bcp_handle {
     DevBuf<uint64_t> parked_slots;  // a word per workgroup of step_local_kernel, its parked poses so far (bcp_parked_poses)
     WaitWatchdog watchdog;
     int32_t last_local_shared = 0;  // the last step ran step_local_kernel's shared-geometry variant (bcp_step_shared_variant)
+    // ---- a declared uniform initial state (bcp_declare_uniform_initial_state): entry 0 of the arrays as they were at the call
+    bool init_declared = false;
+    InitUniform init_snapshot = {};
+    int32_t last_uniform_reset = 0; // the last step took its resets from the snapshot (bcp_step_uniform_reset)
     // ---- egocentric views
     DevBuf<int32_t> ego_bins;       // [2][capacity / 2] image counts / first slots per map entry
     DevBuf<int32_t> ego_order;      // [2][capacity / 2] rank within the bin / images grouped by map entry

@@ -48,6 +48,58 @@ extern "C" int bcp_bind_initial_state(bcp_handle* h, const bcp_state* initial)
     // (the initial State exposes the initial pose / robot state themselves and has empty queues: nothing more to bind)
     h->init = to_dev_state(initial);
     h->have_init = true;
+    h->init_declared = false;   // (a plain bind never reads device memory: whoever binds declares again)
+    h->static_dirty = true;
+    return BCP_OK;
+}
+
+// Bind-time work: the eleven arrays come to the host, are compared with their entry 0 (init_uniform_pack, bcp_init_uniform.h)
+// and, when every entry agrees, entry 0 becomes the handle's snapshot -- the steps of the shared-geometry kernel then reset from
+// the parameter block instead of loading the arrays (launch_step: kStepInitUniform).
+extern "C" int bcp_declare_uniform_initial_state(bcp_handle* h, int on, void* stream)
+{
+    if (!h) return fail(BCP_E_INVALID, "bcp_declare_uniform_initial_state: null handle");
+    if (!on) {
+        if (h->init_declared) h->static_dirty = true;
+        h->init_declared = false;
+        return BCP_OK;
+    }
+    if (!h->have_init) return fail(BCP_E_STATE, "bcp_declare_uniform_initial_state: no initial state bound");
+    if (h->n_geoms > 0)
+        return fail(BCP_E_STATE, "bcp_declare_uniform_initial_state: the handle has a geometry pool (an initial state per entry)");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    const bool tri = h->params.model == BCP_MODEL_TRICYCLE;
+    const size_t n = (size_t)h->n;
+    const DevState& d = h->init;
+    const double* const src[8] = {d.x, d.y, d.angle, d.v, d.w, tri ? d.steer : nullptr, tri ? d.wheel : nullptr, d.min_dist};
+    std::vector<double> f64[8];
+    std::vector<int32_t> target(n), iter(n);
+    std::vector<uint8_t> collided(n);
+    InitHostArrays a = {};
+    for (int f = 0; f < 8; ++f) {
+        if (!src[f]) continue;
+        f64[f].resize(n);
+        HIP_TRY(hipMemcpyAsync(f64[f].data(), src[f], n * sizeof(double), hipMemcpyDeviceToHost, s));
+        a.f64[f] = f64[f].data();
+    }
+    HIP_TRY(hipMemcpyAsync(target.data(), d.target_idx, n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(iter.data(), d.cur_iter, n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(collided.data(), d.collided, n * sizeof(uint8_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    a.target = target.data();
+    a.iter = iter.data();
+    a.collided = collided.data();
+    InitUniform packed;
+    const InitDifference diff = init_uniform_pack(a, h->n, tri, &packed);
+    if (diff.env >= 0) {
+        if (h->init_declared) h->static_dirty = true;
+        h->init_declared = false;
+        return fail(BCP_E_INVALID, "bcp_declare_uniform_initial_state: env %lld differs from env 0 in %s -- the initial state is not uniform",
+                    (long long)diff.env, init_field_name(diff.field));
+    }
+    h->init_snapshot = packed;
+    h->init_declared = true;
     h->static_dirty = true;
     return BCP_OK;
 }

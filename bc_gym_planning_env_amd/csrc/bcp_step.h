@@ -12,6 +12,7 @@
 #include "bcp_device.h"
 #include "bcp_raster.h"
 #include "bcp_coop.h"
+#include "bcp_init_uniform.h"
 
 using namespace bcp;
 
@@ -97,8 +98,13 @@ struct StepStatic {
     // state arrays; a reset moves it to next_geom[entry].  nullptr: env i uses entry i.
     int32_t* geom_of_env;
     const int32_t* next_geom;
+    // A declared uniform initial state (bcp_declare_uniform_initial_state): the one entry every env is reset to.  Directly in
+    // front of the record, so it is the last of what step_local_kernel stages in LDS; read there behind kStepInitUniform only.
+    alignas(16) InitUniform init_uniform;
     EpisodeRec rec;            // (last: not staged in LDS, see EpisodeRec)
 };
+static_assert(offsetof(StepStatic, init_uniform) % 16 == 0 && offsetof(StepStatic, rec) == offsetof(StepStatic, init_uniform) + sizeof(InitUniform),
+              "the uniform initial state is whole 16-byte pieces of *S, the last ones in front of the record");
 
 // What a wave needs before anything else -- where its state, its path and (kernel 2) its parked poses are -- travels
 // with the kernel arguments: the first vector loads then depend on the argument fetch alone and overlap the (cold, the
@@ -220,6 +226,8 @@ constexpr int kTickLocalTicket = 8;   // step_local_kernel's ticket: not on the 
 
 constexpr uint32_t kStepAdvances = 1u << 24;   // internal flag: this launch is the last kernel of its step
 constexpr uint32_t kStepRecord = 1u << 25;     // internal flag: an episode record is bound (StepStatic::rec)
+constexpr uint32_t kStepInitUniform = 1u << 26;   // internal flag: resets take StepStatic::init_uniform from the LDS copy of *S
+                                                  // (set by launch_step for step_local_kernel's shared-geometry variant alone)
 
 // The step's count of ended envs, by the last party of the step (every slot has been taken): published, counter re-armed
 __device__ __forceinline__ void record_store_count(const EpisodeRec& R)
@@ -1071,6 +1079,26 @@ __device__ __forceinline__ InitAhead fetch_init_ahead(SP S, int64_t k, bool tri)
     return p;
 }
 
+// The same from a declared uniform initial state: the block of the LDS copy of *S (step_local_kernel's shared-geometry variant
+// behind kStepInitUniform) -- a few wide LDS reads in place of eleven loads from memory at the very end of a workgroup.
+template <typename SP>
+__device__ __forceinline__ InitAhead init_ahead_uniform(SP S, bool tri)
+{
+    InitAhead p;
+    p.x = S->init_uniform.x;
+    p.y = S->init_uniform.y;
+    p.th = S->init_uniform.th;
+    p.v = S->init_uniform.v;
+    p.w = S->init_uniform.w;
+    p.steer = tri ? S->init_uniform.steer : 0.0;
+    p.wheel = tri ? S->init_uniform.wheel : 0.0;
+    p.min_dist = S->init_uniform.min_dist;
+    p.target = S->init_uniform.target;
+    p.iter = S->init_uniform.iter;
+    p.collided = S->init_uniform.collided;
+    return p;
+}
+
 // reward-provider outcome for the pose as it is when nothing collides, computed ahead of the collision verdict
 struct ScoredFree {
     double rew, min_dist;
@@ -1201,7 +1229,10 @@ __device__ __forceinline__ int finalize_env_from(const A& a, SP S, int64_t i, Pe
             k = S->next_geom ? as_global(S->next_geom)[g] : g;
             as_global(S->geom_of_env)[i] = (int32_t)k;
         }
-        ahead = fetch_init_ahead(S, k, tri);
+        // (SHARED: a declared uniform initial state is in the LDS copy of *S -- one wave-uniform test of the launch flags, which
+        //  the generic variants never see set)
+        if (SHARED && (a.flags & kStepInitUniform)) ahead = init_ahead_uniform(S, tri);
+        else ahead = fetch_init_ahead(S, k, tri);
     }
     // Episode record (bcp_bind_episode_record), one wave-uniform test of the launch flags when none is bound.  The state the
     // env holds after its last step goes to a slot while the initial-state loads above are in flight.

@@ -56,6 +56,9 @@ static int upload_step_static(bcp_handle* h, hipStream_t s)
     } else {
         memset(&S.rec, 0, sizeof(S.rec));
     }
+    // a declared uniform initial state: the handle's snapshot (the kernels read it behind kStepInitUniform only)
+    memset(&S.init_uniform, 0, sizeof(S.init_uniform));
+    if (h->init_declared) S.init_uniform = h->init_snapshot;
     HIP_TRY(h->dev_static.reserve(1));
     // pageable source: the copy is staged before the call returns, so host_static may change afterwards
     HIP_TRY(hipMemcpyAsync(h->dev_static.get(), &S, sizeof(StepStatic), hipMemcpyHostToDevice, s));
@@ -241,6 +244,10 @@ static int launch_step(bcp_handle* h, const bcp_step_io* io, uint32_t flags, hip
                                                 (S.map.shared && bitmap_words <= kLocalMapWords) ? (int)bitmap_words : 0,
                                                 step_is_plain(h), pairs);
         a.flags |= kStepAdvances;
+        const bool shared = pairs == 4 && !roll && local_step_shared(h, S);
+        // resets from the declared uniform initial state in the LDS copy of *S: the shared-geometry variant alone
+        const bool uniform_reset = shared && h->init_declared && (flags & BCP_STEP_AUTO_RESET);
+        if (uniform_reset) a.flags |= kStepInitUniform;
         a.hot.io_flags = a.flags;   // (the prologue's copies, next to the rest of what it fetches)
         a.hot.io_actions = a.actions;
         a.hot.io_noise_z = a.noise_z;
@@ -252,11 +259,12 @@ static int launch_step(bcp_handle* h, const bcp_step_io* io, uint32_t flags, hip
             HIP_TRY(hipMemsetAsync(h->parked_slots.get(), 0, h->parked_slots.capacity() * sizeof(uint64_t), s));
         }
         a.parked_slots = h->parked_slots.get();
-        const bool shared = pairs == 4 && !roll && local_step_shared(h, S);
         h->last_local_shared = shared ? 1 : 0;
+        h->last_uniform_reset = uniform_reset ? 1 : 0;
         return launch_variant(h, local_step_fn(variant, pairs, roll, shared), grid, block, lds, s, a);
     }
     h->last_local_shared = 0;
+    h->last_uniform_reset = 0;
     if (rollout_steps > 1) return fail(BCP_E_STATE, "launch_step: only the single-launch step form takes several steps per launch");
     if (form == 0) {
         const size_t lds = collision_lds_bytes(h->params.n_verts, h->map.in_lds, h->map.rows, h->map.wpr);
@@ -414,6 +422,12 @@ extern "C" int bcp_step_shared_variant(bcp_handle* h)
 {
     if (!h) return fail(BCP_E_INVALID, "bcp_step_shared_variant: null handle");
     return h->last_local_shared;
+}
+
+extern "C" int bcp_step_uniform_reset(bcp_handle* h)
+{
+    if (!h) return fail(BCP_E_INVALID, "bcp_step_uniform_reset: null handle");
+    return h->last_uniform_reset;
 }
 
 extern "C" int bcp_step_form(bcp_handle* h)

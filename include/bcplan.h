@@ -265,6 +265,19 @@ int bcp_bind_state(bcp_handle *h, const bcp_state *state /*host struct of device
 /* PlanEnv._initial_state (env.py:247): the snapshot reset()/auto-reset restores (one entry per env, or per pool
  * geometry). */
 int bcp_bind_initial_state(bcp_handle *h, const bcp_state *initial /*host struct of device pointers*/);
+/* Declares that every env has the SAME initial state (one shared path: make_initial_state depends on the path and the
+ * parameters only).  on = 1: the eleven bound arrays x .. robot_collided (n entries each) are copied to the host on `stream`,
+ * the stream is synchronised -- bind-time work, not for a captured stream -- and every entry is compared with entry 0 bit for
+ * bit (doubles as 64-bit words: a NaN payload or a -0.0 that differs counts; steering_motor_command and wheel_angle are not
+ * looked at for the diff-drive model).  If all agree the handle keeps entry 0 as a snapshot and is "declared": steps with
+ * BCP_STEP_AUTO_RESET that run the shared-geometry variant of the step kernel (bcp_step_shared_variant) then reset from the
+ * snapshot instead of loading the arrays; every other step reads the arrays as before.  Results are the same either way.
+ * If an entry differs: BCP_E_INVALID, the message names the first env and the field, and the handle is left undeclared.
+ * BCP_E_STATE: no initial state bound, or the handle has a geometry pool.  on = 0 drops the declaration.
+ * The snapshot is a VALUE taken at the call: a caller who later rewrites the arrays in place must declare again, or the
+ * declared steps keep resetting to the old values.  Any later bcp_bind_initial_state drops the declaration (a plain bind
+ * never reads device memory, its arrays may be filled afterwards). */
+int bcp_declare_uniform_initial_state(bcp_handle *h, int on, void *stream);
 /* PlanEnv.reset (env.py:293-303) for every env with mask[i] != 0 (mask NULL = all). */
 int bcp_reset_masked(bcp_handle *h, const uint8_t *mask, void *stream);
 
@@ -1054,6 +1067,9 @@ int bcp_step_form(bcp_handle *h);
 /* 1 when the last step of this handle ran step_local_kernel's shared-geometry variant (BCP_TUNE_LOCAL_SHARED), 0 when it
  * ran anything else or no step has run.  Negative: BCP_E_*. */
 int bcp_step_shared_variant(bcp_handle *h);
+/* 1 when the last step of this handle took its resets from the declared uniform initial state
+ * (bcp_declare_uniform_initial_state: declared, shared-geometry variant, BCP_STEP_AUTO_RESET), 0 otherwise.  Negative: BCP_E_*. */
+int bcp_step_uniform_reset(bcp_handle *h);
 /* Runs `steps` bcp_step() launches back to back on `stream` bracketed by HIP events recorded on that stream and
  * returns the average kernel-launch duration in milliseconds (synchronises).  Used by bench.py for
  * roofline.achieved. */
