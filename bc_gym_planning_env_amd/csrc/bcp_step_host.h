@@ -1,6 +1,6 @@
 // bcp_step_host.h -- the host side of the step: which form a step takes, the device-resident parameter block, the launcher,
 // the methods of Parking and WaitWatchdog, and the entry points built on them (bcp_step, bcp_rollout, the timing calls).
-// The kernels are in bcp_step.h.  Included by bcplan.hip after bcp_field.h; the planners, which step nothing, are in
+// The kernels are in bcp_step.h (behind the bcp_step_*.h it includes), the LDS they get in bcp_step_layout.h.  Included by bcplan.hip after bcp_field.h; the planners, which step nothing, are in
 // bcp_plan_host.h behind it.
 #pragma once
 
@@ -49,7 +49,7 @@ static int upload_step_static(bcp_handle* h, hipStream_t s)
     S.geom_of_env = h->n_geoms > 0 ? h->geom_of_env : nullptr;
     S.next_geom = h->n_geoms > 0 ? h->next_geom : nullptr;
     S.lds_path_doubles =
-        (defer && h->path.shared && h->path.max_len * 5 * sizeof(double) <= 24 * 1024) ? h->path.max_len * 5 : 0;
+        (defer && h->path.shared && h->path.max_len * kWayPointDoubles * sizeof(double) <= kPathLdsBytes) ? h->path.max_len * kWayPointDoubles : 0;
     if (h->have_rec) {
         BCP_TRY(h->parking.record_slots(defer, &h->rec.park));
         S.rec = h->rec;
@@ -152,8 +152,7 @@ static const void* const kPendingFn[4] = {(const void*)step_pending_kernel<false
 // sharded C5, every replica batch.)  BCP_TUNE_LOCAL_SHARED = 0 keeps a handle on the generic variant.
 static bool local_step_shared(const bcp_handle* h, const StepStatic& S)
 {
-    const int64_t bitmap_words = (int64_t)S.map.rows * S.map.wpr;
-    return h->tune.local_shared != 0 && S.map.shared && bitmap_words > 0 && bitmap_words <= kLocalMapWords && S.path.shared &&
+    return h->tune.local_shared != 0 && staged_map_words(S.map.shared != 0, S.map.rows, S.map.wpr) > 0 && S.path.shared &&
            S.lds_path_doubles > 0 && S.geom_of_env == nullptr && S.map.origins == nullptr && S.cull.on && S.cull.step_near != nullptr;
 }
 
@@ -239,10 +238,8 @@ static int launch_step(bcp_handle* h, const bcp_step_io* io, uint32_t flags, hip
         const bool roll = rollout_steps > 1;
         const int pairs = roll ? 4 : local_pairs(h);
         a.rollout_steps = rollout_steps;
-        const int64_t bitmap_words = (int64_t)S.map.rows * S.map.wpr;
-        const size_t lds = local_step_lds_bytes(h->params.n_verts, S.lds_path_doubles,
-                                                (S.map.shared && bitmap_words <= kLocalMapWords) ? (int)bitmap_words : 0,
-                                                step_is_plain(h), pairs);
+        const size_t lds = local_lds_plan(h->params.n_verts, S.lds_path_doubles, staged_map_words(S.map.shared != 0, S.map.rows, S.map.wpr),
+                                          step_is_plain(h), pairs).bytes;
         a.flags |= kStepAdvances;
         const bool shared = pairs == 4 && !roll && local_step_shared(h, S);
         // resets from the declared uniform initial state in the LDS copy of *S: the shared-geometry variant alone
@@ -273,19 +270,16 @@ static int launch_step(bcp_handle* h, const bcp_step_io* io, uint32_t flags, hip
         return BCP_OK;
     }
     // kernel 1 settles every env the distance field decides; kernel 2 rasterises the parked rest
-    const size_t lds1 = ((size_t)h->params.n_verts * 2 + S.lds_path_doubles) * sizeof(double);
-    const size_t lds2 = (size_t)2 * 4 * (S.wide ? 8 : 3) * 64 * sizeof(uint32_t);
     const int waves = 2048;  // a multiple of kShards: 32 teams per shard, so that a shard rarely needs a second round
     const bool second = !first_only && S.dense_threshold >= 0;  // (threshold < 0: everything settled in place)
     if (!second) a.flags |= kStepAdvances;   // kernel 1 is the whole step
     // kernel 1 runs with two wavefronts per 64 envs (mover + scorer, step_fast_pair_kernel)
-    const size_t lds1p = lds1 + ((size_t)6 * kBlock + 8) * sizeof(double) + 2 * kBlock * sizeof(uint32_t);
-    const int rc = launch_variant(h, kFastPairFn[variant], dim3(blocks), dim3(2 * kBlock), lds1p, s, a);
+    const int rc = launch_variant(h, kFastPairFn[variant], dim3(blocks), dim3(2 * kBlock), pair_lds_plan(h->params.n_verts, S.lds_path_doubles).bytes, s, a);
     if (rc != BCP_OK || !second) return rc;
-    return launch_variant(h, kPendingFn[variant], dim3(waves), dim3(kBlock * kPendingWaves), lds2, s, a);
+    return launch_variant(h, kPendingFn[variant], dim3(waves), dim3(kBlock * kPendingWaves), pending_lds_bytes(S.wide != 0), s, a);
 }
 
-// Flags a caller may pass.  The ablation switches of bcp_step.h (timing experiments, results wrong by construction)
+// Flags a caller may pass.  The ablation switches of bcp_diag.h (timing experiments, results wrong by construction)
 // exist only in a -DBCP_DIAG build (tools/); kStepAdvances is internal and never accepted.
 #ifdef BCP_DIAG
 constexpr uint32_t kCallerFlags = BCP_STEP_AUTO_RESET | BCP_STEP_ACTIONS_F32 | kAblateNoCollision | kAblateNoReward |

@@ -1,6 +1,6 @@
 // bcplan.hip -- libbcplan.so: batched PlanEnv.step() for MI355X (gfx950).  C ABI in include/bcplan.h.
 //
-// One translation unit.  The device code is in bcp_device.h, bcp_raster.h, bcp_coop.h and bcp_step.h (the step: robot model ->
+// One translation unit.  The device code is in bcp_device.h, bcp_raster.h, bcp_coop.h and bcp_step.h with the bcp_step_*.h it includes (the step: robot model ->
 // collision classification / exact rasteriser -> rollback -> reward provider -> done -> optional reset -> state write-back),
 // bcp_lookahead.h and bcp_mppi.h (the planners), bcp_ego.h (egocentric views), bcp_sample.h and bcp_aisle.h (world samplers),
 // bcp_inflate.h (costmap inflation), bcp_scan.h (range scans; the walk: bcp_scan_march.h, no HIP in it), bcp_goal.h (goal

@@ -23,9 +23,9 @@ import numpy as np
 import footprints as F
 from util import GOLDEN
 
-# ---- constants restated from csrc/bcp_step.h and csrc/bcp_step_host.h (test_staging_host.py looks them up there) ----------
+# ---- constants restated from csrc/bcp_step_layout.h (test_staging_host.py compares them with what a compiler saw there) ----
 LOCAL_MAP_WORDS = 4096       # kLocalMapWords
-PATH_LDS_BYTES = 24 * 1024   # upload_step_static: a shared path of at most this many bytes is staged
+PATH_LDS_BYTES = 24 * 1024   # kPathLdsBytes: a shared path of at most this many bytes is staged
 WAY_POINT_BYTES = 5 * 8      # x, y, heading, cos, sin
 MAX_STAGED_WAY_POINTS = PATH_LDS_BYTES // WAY_POINT_BYTES   # 614
 SCAN_ITEMS = 1024            # kScanItems

@@ -1,9 +1,12 @@
 """What makes test_gpu_step_staging.py mean something, asserted on its inputs with the oracle alone (no GPU): the worlds of
 tests/staging.py really put lethal cells under colliding footprints in the late words of the bitmap, really walk envs over
 the last way points, into the goal and through resets, and the dense path really overfills the flat scan list of every
-step; and the limits those worlds were built around are still the ones the headers state."""
+step; and the limits those worlds were built around are still the ones the headers state -- read from a program that includes
+csrc/bcp_step_layout.h, not from the headers' text -- with the LDS layouts that header plans for the step kernels."""
+import itertools
 import os
-import re
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
@@ -15,33 +18,139 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIMIT_WORLD_CASES = [n for n in S.STEP_CASES + S.BIND_CASES if n.startswith(("map-", "max-", "bind-"))]
 
 
-def _header(name):
-    with open(os.path.join(ROOT, "bc_gym_planning_env_amd", "csrc", name)) as f:
-        return f.read()
+def _compiler():
+    for cand in ("g++", "/opt/rocm/llvm/bin/clang++", "clang++"):
+        path = shutil.which(cand)
+        if path:
+            return path
+    raise AssertionError("no host C++ compiler found (g++ or ROCm's clang++)")
 
 
-@pytest.mark.parametrize("name,pattern,value", [
-    ("bcp_step.h", r"constexpr int kLocalMapWords\s*=\s*(\d+)\s*;", S.LOCAL_MAP_WORDS),
-    ("bcp_step.h", r"constexpr int kScanItems\s*=\s*(\d+)\s*;", S.SCAN_ITEMS),
-    ("bcp_step.h", r"kStagers = \(kLocalWaves - kLocalPairs\) \* kBlock;\s*// (\d+) / 384 / 192 threads", S.STAGERS),
+# every plan the tests below look at, asked of ONE start of the program
+LOCAL_TUPLES = list(itertools.product((3, 4, 17), (0, 5, 3070), (0, 1, 4095, 4096), (0, 1), (1, 2, 4)))   # n_verts, path doubles, map words, plain, pairs
+PAIR_TUPLES = list(itertools.product((3, 4, 17), (0, 5, 3070)))
+COLLISION_TUPLES = list(itertools.product((3, 4, 17), (0, 1, 4095, 4096)))
+
+
+@pytest.fixture(scope="module")
+def layout(tmp_path_factory):
+    """tests/c_abi/step_layout_main.cpp, which includes csrc/bcp_step_layout.h alone, built with a host compiler under
+    AddressSanitizer and UBSan and run once -> (limits {name: value}, plans {argument: {region: bytes}})"""
+    exe = str(tmp_path_factory.mktemp("step_layout") / "step_layout_main")
+    cxx = _compiler()
+    static_runtime = ["-static-libasan", "-static-libubsan"] if cxx.endswith("g++") else []   # (clang's is static already)
+    cmd = [cxx] + static_runtime + ["-std=c++17", "-Wall", "-Werror", "-g", "-O1", "-ffp-contract=off",
+                                    "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                                    "-I" + os.path.join(ROOT, "bc_gym_planning_env_amd", "csrc"),
+                                    os.path.join(ROOT, "tests", "c_abi", "step_layout_main.cpp"), "-o", exe]
+    built = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=300)
+    assert built.returncode == 0, built.stdout
+    args = (["local:%d,%d,%d,%d,%d" % t for t in LOCAL_TUPLES] + ["pair:%d,%d" % t for t in PAIR_TUPLES] +
+            ["pending:0", "pending:1"] + ["collision:%d,%d" % t for t in COLLISION_TUPLES])
+    ran = subprocess.run([exe] + args, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=120)
+    assert ran.returncode == 0, ran.stdout[-4000:]
+    for word in ("Sanitizer", "runtime error"):
+        assert word not in ran.stdout, ran.stdout[-4000:]
+    lines = ran.stdout.split("\n")
+    assert lines[-2] == "step layout ok"
+    limits = {ln.split(" ")[1]: int(ln.split(" ")[2]) for ln in lines if ln.startswith("limit ")}
+    plans = {ln.split(" ")[0]: {kv.split("=")[0]: int(kv.split("=")[1]) for kv in ln.split(" ")[1:]}
+             for ln in lines if ":" in ln.split(" ")[0]}
+    assert sorted(plans) == sorted(args)
+    return limits, plans
+
+
+@pytest.mark.parametrize("name,value", [
+    ("kLocalMapWords", S.LOCAL_MAP_WORDS),
+    ("kScanItems", S.SCAN_ITEMS),
+    ("local_stagers(4)", S.STAGERS),
     # step_fast_pair_kernel: four doubles per thread of 2 * kBlock = 128 from registers, the loop takes over at 512
-    ("bcp_step.h", r"for \(int u = 0; u < (\d+); \+\+u\) \{\s*const int k = u \* 2 \* kBlock \+ tid;\s*t\[u\] =", 4),
-    ("bcp_step.h", r"for \(int k = (\d+) \+ tid; k < a\.hot\.lds_path_doubles; k \+= 2 \* kBlock\)", S.PAIR_STAGE_DOUBLES),
-    ("bcp_step.h", r"constexpr int kBlock\s*=\s*(\d+)\s*;", 64),
+    ("kPairStageRegs", 4),
+    ("kPairStageDoubles", S.PAIR_STAGE_DOUBLES),
+    ("kBlock", 64),
 ], ids=["map-words", "scan-items", "stagers", "pair-registers", "pair-loop", "block"])
-def test_headers_still_state_the_limits(name, pattern, value):
+def test_headers_still_state_the_limits(layout, name, value):
     """the edges below are derived from these numbers: if one of them moves, a test fails instead of the edges moving away"""
-    found = re.findall(pattern, _header(name))
-    assert found and all(int(v) == value for v in found), (name, pattern, found, value)
+    limits = layout[0]
+    assert limits[name] == value, (name, limits[name], value)
+    assert (limits["local_stagers(4)"], limits["local_stagers(2)"], limits["local_stagers(1)"]) == (768, 384, 192)
+    assert limits["kPairStageDoubles"] == limits["kPairStageRegs"] * 2 * limits["kBlock"]
 
 
-def test_headers_still_stage_24_kb_of_path():
-    body = re.search(r"static int upload_step_static\(.*?\n\}", _header("bcp_step_host.h"), re.S).group(0)
-    found = re.findall(r"h->path\.max_len \* 5 \* sizeof\(double\) <= (\d+) \* (\d+)\)", body)
-    assert found == [("24", "1024")], found
+def test_headers_still_stage_24_kb_of_path(layout):
+    limits = layout[0]
+    assert limits["kPathLdsBytes"] == 24 * 1024 == S.PATH_LDS_BYTES
+    assert limits["kWayPointDoubles"] * 8 == S.WAY_POINT_BYTES
     assert S.MAX_STAGED_WAY_POINTS * S.WAY_POINT_BYTES <= S.PATH_LDS_BYTES < (S.MAX_STAGED_WAY_POINTS + 1) * S.WAY_POINT_BYTES
-    # the launch asks the same question of the bitmap as the kernel and as local_step_shared
-    assert len(re.findall(r"bitmap_words <= kLocalMapWords", _header("bcp_step_host.h"))) == 2
+    # launch, kernel and local_step_shared ask one function whether the bitmap is staged: up to kLocalMapWords, shared maps only
+    assert limits["staged_map_words(1,256,16)"] == 4096 == S.LOCAL_MAP_WORDS
+    assert limits["staged_map_words(1,241,17)"] == 0 and limits["staged_map_words(0,8,8)"] == 0
+
+
+def _regions_hold(plan, order, sizes):
+    """the regions follow one another in `order` (the last name is the end of the allocation); each is at least sizes[region]
+    bytes long, so a region that holds anything begins strictly before the next one"""
+    for name, nxt in zip(order, order[1:]):
+        assert plan[nxt] - plan[name] >= sizes[name], (name, nxt, plan, sizes[name])
+        assert plan[nxt] > plan[name] or sizes[name] == 0, (name, nxt, plan)
+
+
+@pytest.mark.parametrize("pairs", [1, 2, 4])
+@pytest.mark.parametrize("plain", [0, 1])
+def test_the_plan_of_the_single_launch_step(layout, plain, pairs):
+    """local_lds_plan, which sizes step_local_kernel's allocation and carves it up: regions in the kernel's order, each as
+    large as what the kernel stores there, the 16-byte pieces aligned, and as many bytes as the sum the launcher used to add up"""
+    limits, plans = layout
+    block, parked, sparse = limits["kBlock"], limits["parked_pose_bytes"], limits["sparse_lds_words"]
+    chunks, finish = limits["static_chunks"], limits["finish_slot_bytes"]
+    assert finish >= 48 and finish % 16 == 0           # sizeof(FinishWords): five pointers, flags, pad
+    order = ("footprint", "path", "hand", "box", "index", "ctl", "rec", "cells", "map", "stat", "finish", "stash", "bytes")
+    seen = 0
+    for n_verts, path, words, pl, pr in LOCAL_TUPLES:
+        if (pl, pr) != (plain, pairs):
+            continue
+        seen += 1
+        p = plans["local:%d,%d,%d,%d,%d" % (n_verts, path, words, pl, pr)]
+        sizes = {"footprint": 2 * n_verts * 8, "path": path * 8, "hand": pairs * limits["kHandDoubles"] * block * 8, "box": 8 * 8,
+                 "index": 2 * block * 4, "ctl": limits["kCtlWords"] * 4, "rec": pairs * block * parked,
+                 "cells": 4 * pairs * sparse * 4, "map": words * 4, "stat": chunks * 16, "finish": finish,
+                 "stash": 0 if plain else 10 * pairs * block * 8}
+        assert p["footprint"] == 0
+        _regions_hold(p, order, sizes)
+        assert p["rec"] % 16 == 0 and p["stat"] % 16 == 0 and p["finish"] % 16 == 0 and p["stash"] % 8 == 0
+        assert all(p[k] % 8 == 0 for k in ("path", "hand", "box")) and p["index"] % 4 == 0 and p["ctl"] % 4 == 0
+        # the sum local_step_lds_bytes added up before the plan existed
+        b = (2 * n_verts + path + pairs * 8 * 64 + 8) * 8 + 2 * 64 * 4 + 16 * 4
+        b = (b + 15) & ~15
+        b += pairs * 64 * parked + 4 * pairs * sparse * 4 + words * 4
+        b = (b + 15) & ~15
+        b += chunks * 16 + finish + (0 if plain else 10 * pairs * 64 * 8)
+        assert p["bytes"] == b, (p, b)
+    assert seen == 3 * 3 * 4
+    # the flat scan list of a pair (64 results, 64 {lo, first} words, kScanItems bytes) lies in the score part of its hand-off block
+    assert (2 * block + limits["kScanItems"] // 4) * 4 <= 3 * block * 8 and limits["kHandDoubles"] == 8
+
+
+def test_the_plans_of_the_other_step_kernels(layout):
+    """the same for step_fast_pair_kernel, step_pending_kernel and step_kernel, against the sums launch_step and
+    collision_lds_bytes used to hold"""
+    limits, plans = layout
+    sparse = limits["sparse_lds_words"]
+    for n_verts, path in PAIR_TUPLES:
+        p = plans["pair:%d,%d" % (n_verts, path)]
+        sizes = {"footprint": 2 * n_verts * 8, "path": path * 8, "hand_pose": 3 * 64 * 8, "hand_score": 3 * 64 * 8, "box": 8 * 8,
+                 "index": 2 * 64 * 4}
+        assert p["footprint"] == 0
+        _regions_hold(p, ("footprint", "path", "hand_pose", "hand_score", "box", "index", "bytes"), sizes)
+        assert p["bytes"] == (2 * n_verts + path) * 8 + (6 * 64 + 8) * 8 + 2 * 64 * 4
+    assert limits["kPendingWaves"] == 4
+    assert plans["pending:0"]["bytes"] == 2 * 4 * 3 * 64 * 4 and plans["pending:1"]["bytes"] == 2 * 4 * 8 * 64 * 4
+    for n_verts, words in COLLISION_TUPLES:
+        p = plans["collision:%d,%d" % (n_verts, words)]
+        sizes = {"map": words * 4, "qverts": 2 * n_verts * 8, "scratch": 2 * n_verts * 64 * 4, "cells": sparse * 4}
+        assert p["map"] == 0 and p["qverts"] % 8 == 0
+        _regions_hold(p, ("map", "qverts", "scratch", "cells", "bytes"), sizes)
+        assert p["bytes"] == (((words + 1) & ~1) + 4 * n_verts + 2 * n_verts * 64 + sparse) * 4
 
 
 def test_the_edges_are_where_the_cases_stand():

@@ -1,4 +1,4 @@
-"""The C3 step (`c4` as an argument: BASELINE configs[3]) with stages switched off (ablation flags of bcp_step.h: results are wrong by construction, only the
+"""The C3 step (`c4` as an argument: BASELINE configs[3]) with stages switched off (ablation flags of csrc/bcp_diag.h: results are wrong by construction, only the
 timing is of interest).  HIP-event timing of 20 back-to-back steps, 5 repetitions each.  Needs the diagnostic build:
 hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared -std=c++17 -DBCP_DIAG bc_gym_planning_env_amd/csrc/bcplan.hip
       -o tools/libbcplan_diag.so      (BCP_FUSED=0 in the environment: the two-launch step)"""
