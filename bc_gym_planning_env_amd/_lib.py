@@ -18,6 +18,7 @@ TUNE_EXACT_MODE, TUNE_DENSE_THRESHOLD, TUNE_CULL, TUNE_DEFER, TUNE_EDT_LDS, TUNE
 TUNE_LOCAL_PAIRS, TUNE_EGO_LIST_STRIDE, TUNE_NEAR_SHIFT, TUNE_INFLATE_ROUTE, TUNE_GOAL_ROUTE = 8, 9, 10, 11, 12
 TUNE_LOCAL_SHARED = 13
 GOAL_ORTHO, GOAL_DIAG, GOAL_FAR, GOAL_NONE = 12, 17, 65534, 65535
+GOAL_MAX_EXTRA = 4095
 ROUTE_LONG, ROUTE_TOO_CLOSE, ROUTE_NO_ROUTE, ROUTE_STUCK = 1, 2, 4, 8
 SCATTER_SHORT, SCATTER_REVERTED = 1, 2   # BatchedPlanEnv.scatter_obstacles' status bits
 E_NO_DEVICE = -2
@@ -229,6 +230,12 @@ SYMBOLS = {
     "bcp_goal_field_bound": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                        C.c_void_p]),
     "bcp_refresh_goal_fields": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # (extra_of_cost: a HOST uint16 [256]; pass table.ctypes.data of a contiguous numpy array)
+    "bcp_goal_field_cost": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p]),
+    "bcp_goal_field_cost_bound": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p]),
     "bcp_goal_field_sample": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
                                         C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bcp_final_goal_field_sample": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_double,

@@ -771,7 +771,8 @@ class BatchedPlanEnv(Handle):
         reference, so a field nobody holds any more costs nothing."""
         self._goal_followers.append(weakref.ref(fields))
 
-    def goal_field(self, clearance=None, seeds="goal", max_passes=0, follow_refresh=False):
+    def goal_field(self, clearance=None, seeds="goal", max_passes=0, follow_refresh=False, cost_weight=None,
+                   extra_of_cost=None):
         """The geodesic cost-to-go of every bound map to its path's goal (bcp_goal_field, one launch): for each free cell
         the length of the cheapest route through free space to the nearest seed, as a goal_field.GoalField whose sample()
         gives distance to go and route direction at any pose.  clearance: how far in metres a route keeps from every
@@ -780,7 +781,15 @@ class BatchedPlanEnv(Handle):
         every way point (the field is then the distance to the path).  max_passes: 0 = as many as it takes.
         Fields: one for a shared map with a shared path, one per pool entry, one per env for private maps -- and one per env
         for a shared map with private paths, the one map read n_envs times: n_envs * rows * cols * 2 bytes of fields.
-        Only cells == 254 are obstacles, so inflated maps give the same fields.
+        Only cells == 254 are obstacles, so inflated maps give the same fields -- unless the costs are asked for:
+        cost_weight=w (finite, >= 0) weighs the field by the inflation layer's costs (bcp_goal_field_cost with
+        goal_field.cost_table(w): entering a cell of cost c costs the step plus rint(w * 12 * c / 252), so a cell of cost
+        252 counts as 1 + w cells of travel).  Routes then run down the middle of free space where there is room and still
+        squeeze through where there is not; `clearance` stays the hard limit.  Needs inflate_costmaps() first
+        (RuntimeError otherwise).  extra_of_cost: the table itself, 256 integers in [0, _lib.GOAL_MAX_EXTRA] indexed by the
+        map's byte, taken on any map.  Both together: ValueError; either with follow_refresh=True: ValueError.  The
+        GoalField carries the table (extra_of_cost); its values are costs to go in metre-equivalents, and sample(),
+        route(), route_paths(), mppi(goal_field=...) and the planners take it as they take a plain one.
         follow_refresh=True: the fields are built from the handle's own binding with the seeds derived on the device
         (bcp_goal_field_bound: private maps with private paths, seeds="goal" only -- ValueError otherwise; the same
         bytes).  On an endless=True pool the call first completes a refresh in flight (finish_refresh()), and from then
@@ -788,15 +797,17 @@ class BatchedPlanEnv(Handle):
         entries it re-sampled (bcp_refresh_goal_fields): the GoalField stays current for as long as it is alive.  With
         follow_refresh=False an endless=True pool is refused (RuntimeError): a refresh() would leave stale fields."""
         from . import goal_field
-        return goal_field.build(self, clearance, seeds, max_passes, follow_refresh)
+        return goal_field.build(self, clearance, seeds, max_passes, follow_refresh, cost_weight, extra_of_cost)
 
-    def route_paths(self, fields=None, stride=2, max_len=None, clearance=None):
+    def route_paths(self, fields=None, stride=2, max_len=None, clearance=None, cost_weight=None):
         """Replace every entry's path by the route traced down its goal field (bcp_goal_route_bound, one launch): from the
         entry's own start pose, through the centre of every stride-th cell of the cheapest route that keeps `clearance`
         from the walls, to its own goal pose -- a path a robot can follow, where the straight path of a pool world may
         cross a wall.  fields: a goal_field.GoalField of this env with one field per entry, None = built here
-        (self.goal_field(clearance); clearance None = the footprint's inscribed radius).  max_len: the slots a route may
-        take, None = the binding's; a route that needs more is ROUTE_LONG.
+        (self.goal_field(clearance, cost_weight=cost_weight); clearance None = the footprint's inscribed radius;
+        cost_weight as in goal_field(): the route of a weighted field keeps to the middle of free space, and needs
+        inflate_costmaps() first -- scatter_obstacles(), then inflate_costmaps(), then route_paths(cost_weight=w)).
+        max_len: the slots a route may take, None = the binding's; a route that needs more is ROUTE_LONG.
         Entries whose status is 0 get the routed path, its length and the reward provider's initial state on it; every
         other entry keeps what it had (merged on the device).  The paths and the initial state are bound again, path_of(i),
         the per-env views and a device pool's path_points / lens / init follow, and the call ends with reset().  While
@@ -805,7 +816,8 @@ class BatchedPlanEnv(Handle):
         env that holds the same device pool keeps stepping on what it bound (its derived path data and its initial
         states are its own) until it binds the pool again, while the pool's `paths` already show the routes.
         Starts and goals do not change: GoalFields of this env built before the call stay valid, and calling again
-        changes nothing.  clearance only applies when the fields are built here: with `fields` it is a ValueError.
+        changes nothing.  clearance and cost_weight only apply when the fields are built here: with `fields` either is a
+        ValueError.
         Returns the int32 status [entries] (device tensor; _lib.ROUTE_* bits).
         Refused on endless=True pools (refresh() would write straight paths back), on a shared map or path, and on fields
         whose owner or shape is not this env's."""
@@ -816,8 +828,10 @@ class BatchedPlanEnv(Handle):
             raise RuntimeError("route_paths: needs private maps with private paths (a pool, or a map and a path per env)")
         if fields is not None and clearance is not None:
             raise ValueError("route_paths: clearance belongs to the build of the fields; pass one of fields and clearance")
+        if fields is not None and cost_weight is not None:
+            raise ValueError("route_paths: cost_weight belongs to the build of the fields; pass one of fields and cost_weight")
         if fields is None:
-            fields = self.goal_field(clearance)
+            fields = self.goal_field(clearance, cost_weight=cost_weight)
         data, old_pts, old_lens = self._keep["map"], self._keep["path"], self._keep["lens"]
         if fields.owner is not self or tuple(fields.field.shape) != tuple(data.shape):
             raise ValueError("route_paths: fields must be this env's, one per entry: %s expected, got %s"

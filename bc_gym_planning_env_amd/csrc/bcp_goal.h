@@ -25,6 +25,9 @@
 // 0 .. n_maps - 1, and phase 3 takes the entry's one seed from the last way point of its bound path.  Entries that are not
 // worked on keep their slab of `out` and their row of `info`.  The grid never depends on the count: a workgroup without a
 // trip leaves at once.
+// kCost (bcp_goal_field_cost / bcp_goal_field_cost_bound): the same phases; phase 4 adds the relaxed cell's extra
+// (goal_relax_cell_cost), looked up in a table staged in LDS by the map's byte, which phase 1 kept in LDS (kLds) or which is
+// read from `data` again.  The four kernels without kCost are, instruction for instruction, what they were without it.
 #pragma once
 
 #include "bcp_device.h"
@@ -34,6 +37,7 @@
 namespace bcp {
 
 typedef __attribute__((address_space(3))) uint16_t* GoalLdsU16;
+typedef __attribute__((address_space(3))) uint8_t* GoalLdsU8;
 
 struct GoalArgs {
     const uint8_t* data;         // [n_maps][rows][cols], or [rows][cols] when shared
@@ -60,15 +64,30 @@ struct GoalBound {
     int32_t max_len, pad;
 };
 
-// The kernel's argument: GoalArgs as it is, and behind it the bound part for the kBound kernels only -- the others take
-// what they always took.
-template <bool kBound> struct GoalKernelArgs;
-template <> struct GoalKernelArgs<false> {
+// The cost form (bcp_goal_field_cost, bcp_goal_field_cost_bound): the table of extras per map byte, by value -- a launch
+// keeps the table it was made with, and nothing is uploaded.
+struct GoalCost {
+    uint16_t extra[256];
+};
+
+// The kernel's argument: GoalArgs as it is, behind it the bound part for the kBound kernels only and the table for the
+// kCost kernels only -- the others take what they always took.
+template <bool kBound, bool kCost = false> struct GoalKernelArgs;
+template <> struct GoalKernelArgs<false, false> {
     GoalArgs g;
 };
-template <> struct GoalKernelArgs<true> {
+template <> struct GoalKernelArgs<true, false> {
     GoalArgs g;
     GoalBound b;
+};
+template <> struct GoalKernelArgs<false, true> {
+    GoalArgs g;
+    GoalCost c;
+};
+template <> struct GoalKernelArgs<true, true> {
+    GoalArgs g;
+    GoalBound b;
+    GoalCost c;
 };
 
 constexpr int kGoalFixedWords = 128 + 4;   // half-widths [128], pass flags [3], counter
@@ -90,15 +109,21 @@ struct GoalPlaneGet {
     __device__ __forceinline__ uint16_t operator()(int32_t r, int32_t c) const { return p[r * cols + c]; }
 };
 
-// dynamic LDS of the kernel: the fixed words, and on the LDS route both masks and the plane
-__host__ __device__ inline size_t goal_lds_bytes(int rows, int cols, int wpr, bool in_lds)
+// dynamic LDS of the kernel: the fixed words, and on the LDS route both masks and the plane; cost: behind them the table
+// [256] uint16 (on either route) and, on the LDS route, the map's bytes
+__host__ __device__ inline size_t goal_lds_bytes(int rows, int cols, int wpr, bool in_lds, bool cost = false)
 {
-    const size_t fixed = (size_t)kGoalFixedWords * 4;
-    return in_lds ? fixed + (size_t)2 * rows * wpr * 4 + (((size_t)rows * cols * 2 + 3) & ~(size_t)3) : fixed;
+    const size_t fixed = (size_t)kGoalFixedWords * 4, cells = (size_t)rows * cols;
+    const size_t plain = in_lds ? fixed + (size_t)2 * rows * wpr * 4 + ((cells * 2 + 3) & ~(size_t)3) : fixed;
+    return cost ? plain + 512 + (in_lds ? (cells + 3) & ~(size_t)3 : 0) : plain;
 }
 
-template <bool kLds, bool kBound>
-__global__ void __launch_bounds__(1024) goal_field_kernel(const GoalKernelArgs<kBound> ka)
+// kCost: the field weighted by the map's costs (goal_relax_cell_cost).  Phase 1 keeps every byte it reads in a uint8 plane
+// in LDS (kLds; on the global route phase 4 reads the byte from `data`, which nobody writes during the call), the table is
+// staged in LDS once per workgroup, and phase 4 reads one byte and one table entry per cell it relaxes.  Only cells that
+// are open are relaxed, and everything outside the valid shape is closed: the bytes of the padding never reach the table.
+template <bool kLds, bool kBound, bool kCost = false>
+__global__ void __launch_bounds__(1024) goal_field_kernel(const GoalKernelArgs<kBound, kCost> ka)
 {
     const GoalArgs& a = ka.g;
     typedef typename GoalMem<kLds>::Words Words;
@@ -120,6 +145,14 @@ __global__ void __launch_bounds__(1024) goal_field_kernel(const GoalKernelArgs<k
         plane = nullptr;
     }
     for (int dr = tid; dr <= a.reach; dr += nthr) half_width[dr] = (uint32_t)goal_half_width(a.clearance_d2, dr);
+    [[maybe_unused]] GoalLdsU16 extra_of = nullptr;   // kCost: [256], behind the plane (kLds) or the fixed words
+    [[maybe_unused]] GoalLdsU8 bytes = nullptr;       // kCost && kLds: [cells], the map as phase 1 read it
+    if constexpr (kCost) {
+        if constexpr (kLds) extra_of = (GoalLdsU16)((LdsU32)lds_dyn + (goal_lds_bytes(rows, cols, wpr, true) >> 2));
+        else extra_of = (GoalLdsU16)(counter + 1);
+        bytes = (GoalLdsU8)(extra_of + 256);
+        for (int i = tid; i < 256; i += nthr) extra_of[i] = ka.c.extra[i];   // (the first barrier of a trip is ahead of phase 4)
+    }
 
     // trips: the maps 0 .. n_maps - 1, or (kBound) the selection's entries -- *count clamped to [0, n_list], so the loop is
     // bounded by n_list whatever the word holds; an id outside [0, n_maps) is skipped by the whole workgroup
@@ -150,6 +183,12 @@ __global__ void __launch_bounds__(1024) goal_field_kernel(const GoalKernelArgs<k
             const int n_dwords = (cells + head + 3) >> 2;
             for (int j = tid; j < n_dwords; j += nthr) {
                 const uint32_t y = words[j] ^ 0xFEFEFEFEu;   // a zero byte = a lethal cell
+                if constexpr (kCost && kLds) {               // keep the bytes of the map's own cells
+                    for (int b = 0; b < 4; ++b) {
+                        const int p = 4 * j - head + b;
+                        if (p >= 0 && p < cells) bytes[p] = (uint8_t)((y >> (8 * b)) ^ 0xFEu);
+                    }
+                }
                 if (((y - 0x01010101u) & ~y & 0x80808080u) == 0u) continue;
                 for (int b = 0; b < 4; ++b) {
                     const int p = 4 * j - head + b;          // (bytes before and after the map belong to others: skipped)
@@ -221,7 +260,15 @@ __global__ void __launch_bounds__(1024) goal_field_kernel(const GoalKernelArgs<k
                         if ((closed[r * wpr + (c >> 5)] >> (c & 31)) & 1u) continue;
                         const int32_t own = plane[r * cols + c];
                         if (own == 0) continue;
-                        const int32_t now = goal_relax_cell(get, vr, vc, r, c, own);
+                        int32_t now;
+                        if constexpr (kCost) {
+                            int32_t cost;
+                            if constexpr (kLds) cost = bytes[r * cols + c];
+                            else cost = a.data[(a.shared ? 0 : m) * (int64_t)cells + r * cols + c];
+                            now = goal_relax_cell_cost(get, vr, vc, r, c, own, (int32_t)extra_of[cost]);
+                        } else {
+                            now = goal_relax_cell(get, vr, vc, r, c, own);
+                        }
                         if (now != own) {
                             plane[r * cols + c] = (uint16_t)now;
                             lowered = true;

@@ -1,5 +1,6 @@
 // bcp_goal_cell.h -- the goal field's arithmetic (bcp_goal_field, bcp_goal_field_sample; include/bcplan.h): the argument
-// checks, the half-widths of the clearance disc and the widening of one mask word, the pull relaxation of one cell, the field
+// checks, the half-widths of the clearance disc and the widening of one mask word, the pull relaxation of one cell -- plain, and
+// weighted by the map's costs (goal_relax_cell_cost, bcp_goal_field_cost) --, the field
 // at a pose, the seed cell of a bound path (bcp_goal_field_bound), the sampling of one row with its carrot walk, and the
 // route of one row (bcp_goal_route: the walk written out as a path).  Plain C++ with no HIP in it: goal_field_kernel,
 // goal_sample_kernel and goal_route_kernel (bcp_goal.h) and mppi_kernel's terminal read (bcp_mppi.h) call these functions on
@@ -132,6 +133,48 @@ BCP_HD inline int32_t goal_relax_cell(const Get& get, int32_t vr, int32_t vc, in
             best = v[k] + kGoalDiag < best ? v[k] + kGoalDiag : best;
     if (best == nothing) return kGoalNone;
     return best < kGoalFar ? best : kGoalFar;   // (the sums stop at kGoalFar: a longer route reads kGoalFar, never kGoalNone)
+}
+
+// ---- fields weighted by the map's costs (bcp_goal_field_cost, bcp_goal_field_cost_bound) --------------------------------
+// With a table extra_of_cost[256] of uint16, each <= kGoalMaxExtra, and e(c) = extra_of_cost[data[c]]:
+//     v(seed) = 0,   v(c) = min over admissible neighbours n of sat(v(n) + step(n, c) + e(c))   for a free, non-seed cell c
+// The extra belongs to the cell that is entered on the way from the goal, i.e. the cell being relaxed: in the pull form it
+// is one addition behind the minimum over the eight neighbours.  Everything else is the plain field's: obstacles (== 254
+// only), clearance, seeds (value 0 and free whatever stood there: their extra is never charged), the valid shape, the
+// corner rule, the steps, the saturation at kGoalFar, kGoalNone.  An all-zero table gives the plain field bit for bit.
+// The weights stay positive integers and the sum monotone and saturating, so the fixed point is unique and does not depend
+// on the order of evaluation, and every intermediate value is still the cost of an admissible route.
+// e(c) is the same for every neighbour of c, so goal_walk_step's argmin(field + step) is the true successor on a weighted
+// field too: goal_walk_step, goal_sample_row, goal_route_row, goal_value_at and mppi_kernel's terminal read consume a
+// weighted field UNCHANGED.  Below kGoalFar every cell's successor is strictly cheaper (the step is >= 12), so a walk still
+// lowers a uint16 on every trip; on a saturated stretch it ends in kGoalRouteStuck, as on a saturated plain field.
+constexpr int32_t kGoalMaxExtra = 4095;
+
+// The pull relaxation of a weighted field: goal_relax_cell's minimum over the neighbours alone, plus `extra` (the relaxed
+// cell's own, 0 .. kGoalMaxExtra), saturating at kGoalFar; then the smaller of that and the cell's own value.
+template <typename Get>
+BCP_HD inline int32_t goal_relax_cell_cost(const Get& get, int32_t vr, int32_t vc, int32_t r, int32_t c, int32_t own, int32_t extra)
+{
+    const int32_t via = goal_relax_cell(get, vr, vc, r, c, kGoalNone);   // kGoalNone, or <= kGoalFar
+    if (via == kGoalNone) return own;
+    const int32_t now = via + extra < kGoalFar ? via + extra : kGoalFar;
+    return own == kGoalNone || now < own ? now : own;
+}
+
+// what bcp_goal_field_cost refuses on top of goal_field_check_args (those come first, in their order): a NULL table, then
+// the first entry above kGoalMaxExtra -- all 256 are looked at, 254 and 255 too, although a lethal byte is never looked up
+enum GoalCostRefusal { kGoalCostOk = 0, kGoalCostTable = 1, kGoalCostEntry = 2 };
+
+// bad_index: the first offending entry when the answer is kGoalCostEntry
+BCP_HD inline int goal_cost_check_args(const uint16_t* extra_of_cost, int32_t& bad_index)
+{
+    if (!extra_of_cost) return kGoalCostTable;
+    for (int32_t i = 0; i < 256; ++i)
+        if ((int32_t)extra_of_cost[i] > kGoalMaxExtra) {
+            bad_index = i;
+            return kGoalCostEntry;
+        }
+    return kGoalCostOk;
 }
 
 // One step of the carrot walk on a finished field from (r, c): the admissible neighbour k that minimises field + step, ties

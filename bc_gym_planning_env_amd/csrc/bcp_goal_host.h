@@ -1,6 +1,7 @@
 // bcp_goal_host.h -- the host side of the goal field: bcp_goal_field (checks, the choice of where masks and plane live, the
 // launch), bcp_goal_field_bound / bcp_refresh_goal_fields (the same launch on the handle's own binding, for all entries or a
-// device-side list of them), bcp_goal_field_sample / bcp_final_goal_field_sample over the rows of obs_rows() (bcp_ego_host.h),
+// device-side list of them), bcp_goal_field_cost / bcp_goal_field_cost_bound (the two again with a host table of extras per
+// map byte, copied into the launch arguments), bcp_goal_field_sample / bcp_final_goal_field_sample over the rows of obs_rows() (bcp_ego_host.h),
 // bcp_goal_route / bcp_goal_route_bound over the same rows or the binding's entries, and the value
 // check of BCP_TUNE_GOAL_ROUTE.  The refusals are the checks of bcp_goal_cell.h, which the host tests run too; the kernels are
 // in bcp_goal.h.  Included by bcplan.hip after bcp_ego_host.h.
@@ -20,28 +21,52 @@ static int goal_set_route(bcp_handle* h, int32_t value)
     return BCP_OK;
 }
 
-extern "C" int bcp_goal_field(bcp_handle* h, const uint8_t* data, int64_t n_maps, int32_t rows, int32_t cols, int32_t shared,
-                              const int32_t* valid_rows, const int32_t* valid_cols, const int32_t* seeds, int32_t n_seeds,
-                              int32_t clearance_d2, int32_t max_passes, uint16_t* out, int32_t* info, void* stream)
+// The table of a cost call (bcp_goal_field_cost, bcp_goal_field_cost_bound), checked behind everything the plain call
+// refuses (goal_cost_check_args) and copied by value into the launch arguments: no upload, no allocation, no
+// synchronisation, and a captured launch keeps the table it was captured with.
+static int goal_cost_table(const uint16_t* extra_of_cost, GoalCost& c, const char* who)
+{
+    int32_t bad = 0;
+    switch (goal_cost_check_args(extra_of_cost, bad)) {
+    case kGoalCostOk: break;
+    case kGoalCostTable: return fail(BCP_E_INVALID, "%s: null extra_of_cost", who);
+    default: return fail(BCP_E_INVALID, "%s: extra_of_cost[%d] = %d is above %d", who, bad, (int)extra_of_cost[bad], kGoalMaxExtra);
+    }
+    memcpy(c.extra, extra_of_cost, sizeof(c.extra));
+    return BCP_OK;
+}
+
+// bcp_goal_field (cost = false: extra_of_cost is not looked at) and bcp_goal_field_cost
+template <bool kCost>
+static int goal_field_maps(bcp_handle* h, const uint8_t* data, int64_t n_maps, int32_t rows, int32_t cols, int32_t shared,
+                           const int32_t* valid_rows, const int32_t* valid_cols, const int32_t* seeds, int32_t n_seeds,
+                           int32_t clearance_d2, int32_t max_passes, const uint16_t* extra_of_cost, uint16_t* out, int32_t* info,
+                           void* stream, const char* who)
 {
     switch (goal_field_check_args(h != nullptr, n_maps, data != nullptr, seeds != nullptr, out != nullptr, rows, cols, n_seeds,
                                   clearance_d2, max_passes, valid_rows != nullptr, valid_cols != nullptr, shared != 0)) {
     case kGoalOk: break;
-    case kGoalHandle: return fail(BCP_E_INVALID, "bcp_goal_field: null handle");
-    case kGoalMaps: return fail(BCP_E_INVALID, "bcp_goal_field: n_maps %lld is negative", (long long)n_maps);
-    case kGoalShape: return fail(BCP_E_INVALID, "bcp_goal_field: shape %d x %d outside [1, 2048] x [1, 2048]", rows, cols);
-    case kGoalSeeds: return fail(BCP_E_INVALID, "bcp_goal_field: n_seeds %d outside [1, %d]", n_seeds, kGoalMaxSeeds);
-    case kGoalClearance: return fail(BCP_E_INVALID, "bcp_goal_field: clearance_d2 %d outside [0, %d]", clearance_d2, kGoalMaxClearance);
-    case kGoalPasses: return fail(BCP_E_INVALID, "bcp_goal_field: max_passes %d is negative", max_passes);
-    case kGoalValidPair: return fail(BCP_E_INVALID, "bcp_goal_field: valid_rows and valid_cols go together, both or neither");
-    case kGoalValidShared: return fail(BCP_E_INVALID, "bcp_goal_field: a shared map takes no valid shapes");
-    default: return fail(BCP_E_INVALID, "bcp_goal_field: null data / seeds / out");
+    case kGoalHandle: return fail(BCP_E_INVALID, "%s: null handle", who);
+    case kGoalMaps: return fail(BCP_E_INVALID, "%s: n_maps %lld is negative", who, (long long)n_maps);
+    case kGoalShape: return fail(BCP_E_INVALID, "%s: shape %d x %d outside [1, 2048] x [1, 2048]", who, rows, cols);
+    case kGoalSeeds: return fail(BCP_E_INVALID, "%s: n_seeds %d outside [1, %d]", who, n_seeds, kGoalMaxSeeds);
+    case kGoalClearance: return fail(BCP_E_INVALID, "%s: clearance_d2 %d outside [0, %d]", who, clearance_d2, kGoalMaxClearance);
+    case kGoalPasses: return fail(BCP_E_INVALID, "%s: max_passes %d is negative", who, max_passes);
+    case kGoalValidPair: return fail(BCP_E_INVALID, "%s: valid_rows and valid_cols go together, both or neither", who);
+    case kGoalValidShared: return fail(BCP_E_INVALID, "%s: a shared map takes no valid shapes", who);
+    default: return fail(BCP_E_INVALID, "%s: null data / seeds / out", who);
+    }
+    GoalKernelArgs<false, kCost> ka;
+    memset(&ka, 0, sizeof(ka));
+    if constexpr (kCost) {
+        const int rc = goal_cost_table(extra_of_cost, ka.c, who);
+        if (rc != BCP_OK) return rc;
     }
     if (n_maps == 0) return BCP_OK;
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
 
-    GoalArgs a = {};
+    GoalArgs& a = ka.g;
     a.data = data;
     a.valid_rows = valid_rows;
     a.valid_cols = valid_cols;
@@ -58,25 +83,41 @@ extern "C" int bcp_goal_field(bcp_handle* h, const uint8_t* data, int64_t n_maps
     a.reach = goal_isqrt(clearance_d2);
     a.max_passes = max_passes > 0 ? max_passes : rows * cols;
     const int64_t cells = (int64_t)rows * cols;
-    const bool in_lds = goal_lds_bytes(rows, cols, a.wpr, true) <= kMaxDynamicLds && h->tune.goal_route != 2;
+    const bool in_lds = goal_lds_bytes(rows, cols, a.wpr, true, kCost) <= kMaxDynamicLds && h->tune.goal_route != 2;
     // a workgroup's threads: enough cells each to be worth their barriers
     const unsigned threads = cells >= 128 * 128 ? 1024u : 256u;
-    GoalKernelArgs<false> ka = {a};
     if (in_lds) {
         const unsigned grid = (unsigned)std::min<int64_t>(n_maps, 16384);
-        return launch_variant(h, reinterpret_cast<const void*>(goal_field_kernel<true, false>), dim3(grid), dim3(threads),
-                              goal_lds_bytes(rows, cols, a.wpr, true), s, ka);
+        return launch_variant(h, reinterpret_cast<const void*>(goal_field_kernel<true, false, kCost>), dim3(grid), dim3(threads),
+                              goal_lds_bytes(rows, cols, a.wpr, true, kCost), s, ka);
     }
     const int64_t mask_words = (int64_t)2 * rows * a.wpr;
     const int64_t fit = std::max<int64_t>(1, kGoalScratchBytes / (mask_words * (int64_t)sizeof(uint32_t)));
     const int64_t grid = std::min(std::min(n_maps, kGoalGlobalGrid), fit);
     if (h->goal_scratch.reserve((size_t)(grid * mask_words)) != hipSuccess) {
         (void)hipGetLastError();
-        return fail(BCP_E_HIP, "bcp_goal_field: cannot allocate %lld bytes of scratch", (long long)(grid * mask_words * 4));
+        return fail(BCP_E_HIP, "%s: cannot allocate %lld bytes of scratch", who, (long long)(grid * mask_words * 4));
     }
-    ka.g.scratch = h->goal_scratch.get();
-    return launch_variant(h, reinterpret_cast<const void*>(goal_field_kernel<false, false>), dim3((unsigned)grid), dim3(threads),
-                          goal_lds_bytes(rows, cols, a.wpr, false), s, ka);
+    a.scratch = h->goal_scratch.get();
+    return launch_variant(h, reinterpret_cast<const void*>(goal_field_kernel<false, false, kCost>), dim3((unsigned)grid),
+                          dim3(threads), goal_lds_bytes(rows, cols, a.wpr, false, kCost), s, ka);
+}
+
+extern "C" int bcp_goal_field(bcp_handle* h, const uint8_t* data, int64_t n_maps, int32_t rows, int32_t cols, int32_t shared,
+                              const int32_t* valid_rows, const int32_t* valid_cols, const int32_t* seeds, int32_t n_seeds,
+                              int32_t clearance_d2, int32_t max_passes, uint16_t* out, int32_t* info, void* stream)
+{
+    return goal_field_maps<false>(h, data, n_maps, rows, cols, shared, valid_rows, valid_cols, seeds, n_seeds, clearance_d2,
+                                  max_passes, nullptr, out, info, stream, "bcp_goal_field");
+}
+
+extern "C" int bcp_goal_field_cost(bcp_handle* h, const uint8_t* data, int64_t n_maps, int32_t rows, int32_t cols, int32_t shared,
+                                   const int32_t* valid_rows, const int32_t* valid_cols, const int32_t* seeds, int32_t n_seeds,
+                                   int32_t clearance_d2, int32_t max_passes, const uint16_t* extra_of_cost, uint16_t* out,
+                                   int32_t* info, void* stream)
+{
+    return goal_field_maps<true>(h, data, n_maps, rows, cols, shared, valid_rows, valid_cols, seeds, n_seeds, clearance_d2,
+                                 max_passes, extra_of_cost, out, info, stream, "bcp_goal_field_cost");
 }
 
 // ---- fields of the handle's own binding ---------------------------------------------------------------------------
@@ -85,8 +126,10 @@ extern "C" int bcp_goal_field(bcp_handle* h, const uint8_t* data, int64_t n_maps
 // ring's `dirty` and the count its tally[0], as bcp_refresh_mini_worlds used them (bcp_worlds_host.h).
 constexpr int64_t kGoalBoundGrid = 1024;
 
+template <bool kCost>
 static int goal_field_bound(bcp_handle* h, const int32_t* entries, const int32_t* count, int64_t n_list, int32_t clearance_d2,
-                            int32_t max_passes, uint16_t* field, int32_t* info, void* stream, bool refresh_form, const char* who)
+                            int32_t max_passes, const uint16_t* extra_of_cost, uint16_t* field, int32_t* info, void* stream,
+                            bool refresh_form, const char* who)
 {
     const int64_t n_entries = h ? n_slots(h) : 0;
     switch (goal_bound_check_args(h != nullptr, field != nullptr, n_list, n_entries, entries != nullptr, count != nullptr,
@@ -108,6 +151,12 @@ static int goal_field_bound(bcp_handle* h, const int32_t* entries, const int32_t
                                       h->map.rows, h->map.cols);
     default: return fail(BCP_E_STATE, "%s: no refresh pending (between bcp_refresh_mini_worlds and bcp_release_mini_worlds)", who);
     }
+    GoalKernelArgs<true, kCost> ka;
+    memset(&ka, 0, sizeof(ka));
+    if constexpr (kCost) {
+        const int rc = goal_cost_table(extra_of_cost, ka.c, who);
+        if (rc != BCP_OK) return rc;
+    }
     if (refresh_form) {   // the ring's arrays as bcp_plan_mini_worlds laid them out
         const int64_t* first_world = (const int64_t*)h->ring.get();
         const int32_t* counts = (const int32_t*)(first_world + h->n);
@@ -120,8 +169,6 @@ static int goal_field_bound(bcp_handle* h, const int32_t* entries, const int32_t
     hipStream_t s = (hipStream_t)stream;
     const int32_t rows = h->map.rows, cols = h->map.cols;
 
-    GoalKernelArgs<true> ka;
-    memset(&ka, 0, sizeof(ka));
     GoalArgs& a = ka.g;
     a.data = h->map_data;
     a.valid_rows = h->map_valid_rows && h->map_valid_cols ? h->map_valid_rows : nullptr;
@@ -148,12 +195,12 @@ static int goal_field_bound(bcp_handle* h, const int32_t* entries, const int32_t
     b.inv_res = h->map.inv_res;
     b.max_len = h->path.max_len;
     const int64_t cells = (int64_t)rows * cols;
-    const bool in_lds = goal_lds_bytes(rows, cols, a.wpr, true) <= kMaxDynamicLds && h->tune.goal_route != 2;
+    const bool in_lds = goal_lds_bytes(rows, cols, a.wpr, true, kCost) <= kMaxDynamicLds && h->tune.goal_route != 2;
     const unsigned threads = cells >= 128 * 128 ? 1024u : 256u;
     if (in_lds) {
         const unsigned grid = (unsigned)std::min(n_list, kGoalBoundGrid);
-        return launch_variant(h, reinterpret_cast<const void*>(goal_field_kernel<true, true>), dim3(grid), dim3(threads),
-                              goal_lds_bytes(rows, cols, a.wpr, true), s, ka);
+        return launch_variant(h, reinterpret_cast<const void*>(goal_field_kernel<true, true, kCost>), dim3(grid), dim3(threads),
+                              goal_lds_bytes(rows, cols, a.wpr, true, kCost), s, ka);
     }
     const int64_t mask_words = (int64_t)2 * rows * a.wpr;
     const int64_t fit = std::max<int64_t>(1, kGoalScratchBytes / (mask_words * (int64_t)sizeof(uint32_t)));
@@ -163,20 +210,30 @@ static int goal_field_bound(bcp_handle* h, const int32_t* entries, const int32_t
         return fail(BCP_E_HIP, "%s: cannot allocate %lld bytes of scratch", who, (long long)(grid * mask_words * 4));
     }
     a.scratch = h->goal_bound_scratch.get();
-    return launch_variant(h, reinterpret_cast<const void*>(goal_field_kernel<false, true>), dim3((unsigned)grid), dim3(threads),
-                          goal_lds_bytes(rows, cols, a.wpr, false), s, ka);
+    return launch_variant(h, reinterpret_cast<const void*>(goal_field_kernel<false, true, kCost>), dim3((unsigned)grid),
+                          dim3(threads), goal_lds_bytes(rows, cols, a.wpr, false, kCost), s, ka);
 }
 
 extern "C" int bcp_goal_field_bound(bcp_handle* h, const int32_t* entries, const int32_t* count, int64_t n_list,
                                     int32_t clearance_d2, int32_t max_passes, uint16_t* field, int32_t* info, void* stream)
 {
-    return goal_field_bound(h, entries, count, n_list, clearance_d2, max_passes, field, info, stream, false, "bcp_goal_field_bound");
+    return goal_field_bound<false>(h, entries, count, n_list, clearance_d2, max_passes, nullptr, field, info, stream, false,
+                                   "bcp_goal_field_bound");
+}
+
+extern "C" int bcp_goal_field_cost_bound(bcp_handle* h, const int32_t* entries, const int32_t* count, int64_t n_list,
+                                         int32_t clearance_d2, int32_t max_passes, const uint16_t* extra_of_cost,
+                                         uint16_t* field, int32_t* info, void* stream)
+{
+    return goal_field_bound<true>(h, entries, count, n_list, clearance_d2, max_passes, extra_of_cost, field, info, stream, false,
+                                  "bcp_goal_field_cost_bound");
 }
 
 extern "C" int bcp_refresh_goal_fields(bcp_handle* h, int32_t clearance_d2, int32_t max_passes, uint16_t* field, int32_t* info,
                                        void* stream)
 {
-    return goal_field_bound(h, nullptr, nullptr, 0, clearance_d2, max_passes, field, info, stream, true, "bcp_refresh_goal_fields");
+    return goal_field_bound<false>(h, nullptr, nullptr, 0, clearance_d2, max_passes, nullptr, field, info, stream, true,
+                                   "bcp_refresh_goal_fields");
 }
 
 // Whose row reads what (GoalRows, bcp_goal.h), from the handle's map binding and the rows of obs_rows(): the one statement

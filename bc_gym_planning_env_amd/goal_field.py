@@ -3,8 +3,9 @@ launch per build) and what it says at a pose -- distance to go and the direction
 (bcp_goal_field_sample, one tiny launch).  The terminal cost of a sampling planner, the dense shaping term and the
 "direction to goal" feature of a navigation policy.  follow_refresh=True builds the fields from the handle's own binding
 (bcp_goal_field_bound) and, on an endless pool, has every refresh() rebuild the fields of the entries it re-samples
-(bcp_refresh_goal_fields).  The reference has no counterpart; the shape of the wrapper follows
-BatchedRangeScan (range_scan.py)."""
+(bcp_refresh_goal_fields).  cost_weight / extra_of_cost weigh the field by the costs of an inflated map
+(bcp_goal_field_cost): routes then run down the middle of free space where there is room.  The reference has no
+counterpart; the shape of the wrapper follows BatchedRangeScan (range_scan.py)."""
 from collections import OrderedDict
 
 import numpy as np
@@ -21,15 +22,40 @@ def clearance_cells_squared(clearance, resolution):
     return int(np.floor((np.float64(clearance) / np.float64(resolution)) ** 2))
 
 
+def cost_table(cost_weight):
+    """The table of bcp_goal_field_cost for a weight w >= 0: extra[c] = rint(w * 12 * c / 252) for the inflation layer's
+    costs c <= 252, extra[253] = extra[252], extra[254] = extra[255] = 0 -- entering a cell of cost 252 costs 1 + w cells
+    of travel, a cell of cost 0 the bare step.  uint16 [256]; ValueError for a weight that is negative, not finite, or so
+    large that an entry would pass GOAL_MAX_EXTRA (w > 341.25)."""
+    w = np.float64(cost_weight)
+    if not np.isfinite(w) or w < 0:
+        raise ValueError("cost_weight must be finite and >= 0, got %r" % (cost_weight,))
+    extra = np.zeros(256, dtype=np.float64)
+    extra[:253] = np.rint(w * 12.0 * np.arange(253, dtype=np.float64) / 252.0)
+    extra[253] = extra[252]
+    return checked_table(extra, "cost_weight %r" % (cost_weight,))
+
+
+def checked_table(extra_of_cost, what="extra_of_cost"):
+    """-> a contiguous uint16 [256] copy of the table, or ValueError: 256 integers in [0, GOAL_MAX_EXTRA]"""
+    t = np.asarray(extra_of_cost)
+    if t.shape != (256,) or not np.all(np.isfinite(t)) or np.any(t != np.rint(t)) or t.min() < 0 or t.max() > _lib.GOAL_MAX_EXTRA:
+        raise ValueError("%s: the table must hold 256 integers in [0, %d]" % (what, _lib.GOAL_MAX_EXTRA))
+    return np.ascontiguousarray(t, dtype=np.uint16)
+
+
 class GoalField(object):
     """The fields of one owner's map binding (a BatchedPlanEnv, or a NativeOps after set_costmap): `field` uint16
     [entries, rows, cols] on the device (GOAL_NONE = no route; else route length in units of resolution / GOAL_ORTHO),
     `clearance_d2`, and `info` int32 [entries, 2] = (cells with a value, gave_up).  entries is 1 (every row reads field 0)
-    or the owner's entry count (pool entries, else n_envs)."""
+    or the owner's entry count (pool entries, else n_envs).  `extra_of_cost`: None for a plain field, else the uint16 [256]
+    table the field was weighted with (bcp_goal_field_cost); the values are then costs to go, not lengths: metres() and
+    sample()[..., 0] are the cost to go in metre-equivalents (a cell of extra e counts as 1 + e / 12 cells of travel)."""
 
-    def __init__(self, owner, field, clearance_d2, info=None, keep=(), resolution=None):
+    def __init__(self, owner, field, clearance_d2, info=None, keep=(), resolution=None, extra_of_cost=None):
         assert field.dtype == torch.uint16 and field.dim() == 3 and field.is_contiguous()
         self.owner, self.field, self.clearance_d2, self.info = owner, field, int(clearance_d2), info
+        self.extra_of_cost = extra_of_cost
         self.resolution = float(owner.resolution if resolution is None else resolution)
         self.max_passes = 0         # of the build: what a following refresh() rebuilds with (build_bound)
         self._keep = keep           # the inputs of the build, alive until the stream has consumed them
@@ -50,7 +76,7 @@ class GoalField(object):
     def sample(self, poses=None, row_env=None, carrot_cells=8, max_dist=np.inf, want=()):
         """bcp_goal_field_sample: poses None = every env's current pose (the delayed one under pose_delay), or [n, 3]; row i
         belongs to env row_env[i] (int32 [n]), or i % n_envs.  -> out3 float32 [n, 3] = (min(distance to go in metres,
-        max_dist), direction to the carrot in the robot frame), or (out3, *wanted) with want from "cell_value" (int32 [n],
+        max_dist) -- on a weighted field the cost to go in metre-equivalents --, direction to the carrot in the robot frame), or (out3, *wanted) with want from "cell_value" (int32 [n],
         GOAL_NONE for a row without a result) and "carrot" (int32 [n, 2] = (row, col), (-1, -1) likewise).  The carrot is
         the cell reached by at most carrot_cells steps down the field.  Device tensors, no sync; the outputs are cached per
         n (the SCAN_CACHE_ENTRIES most recently used), so a caller that samples every tick allocates nothing."""
@@ -137,7 +163,8 @@ class GoalField(object):
         return (buf["paths"], buf["lens"], buf["status"]) + tuple(buf[w] for w in want)
 
     def metres(self):
-        """float32 [entries, rows, cols]: the fields in metres, inf where there is no route."""
+        """float32 [entries, rows, cols]: the fields in metres -- on a weighted field (extra_of_cost) the cost to go in
+        metre-equivalents --, inf where there is no route."""
         f = self.field.to(torch.int32)
         scale = self.resolution / _lib.GOAL_ORTHO
         return torch.where(f == _lib.GOAL_NONE, torch.full((), float("inf"), device=f.device), f.to(torch.float32) * scale)
@@ -190,8 +217,22 @@ def build_bound(env, d2, max_passes):
     return fields
 
 
-def build(env, clearance=None, seeds="goal", max_passes=0, follow_refresh=False):
+def build(env, clearance=None, seeds="goal", max_passes=0, follow_refresh=False, cost_weight=None, extra_of_cost=None):
     """BatchedPlanEnv.goal_field: see there."""
+    if cost_weight is not None and extra_of_cost is not None:
+        raise ValueError("goal_field: pass one of cost_weight and extra_of_cost")
+    weighted = cost_weight is not None or extra_of_cost is not None
+    if weighted and follow_refresh:
+        raise ValueError("goal_field: cost_weight / extra_of_cost do not go with follow_refresh=True -- the worlds of an "
+                         "endless pool are not inflated, so there are no costs to weigh")
+    table = None
+    if cost_weight is not None:
+        table = cost_table(cost_weight)
+        if not env._inflated:
+            raise RuntimeError("goal_field(cost_weight=...): the costmaps of this env were never inflated, so every cost "
+                               "is 0 or 254 -- call inflate_costmaps() first (an explicit extra_of_cost is taken on any map)")
+    elif extra_of_cost is not None:
+        table = checked_table(extra_of_cost)
     if env.endless and not follow_refresh:
         raise RuntimeError("goal_field: refused on endless=True pools unless follow_refresh=True -- refresh() re-samples "
                            "worlds into the pool, which would leave stale fields")
@@ -217,11 +258,14 @@ def build(env, clearance=None, seeds="goal", max_passes=0, follow_refresh=False)
         assert n == int(data.shape[0])   # (one path for private maps: its way points on every entry's origin)
     field = torch.empty((n, rows, cols), dtype=torch.uint16, device=env.device)
     info = torch.zeros((n, 2), dtype=torch.int32, device=env.device)
-    _lib.check(env._lib.bcp_goal_field(
-        env._h, data.data_ptr(), n, rows, cols, int(env._shared_map and n > 1), vr.data_ptr() if vr is not None else None,
-        vc.data_ptr() if vc is not None else None, s.data_ptr(), int(s.shape[1]), d2, int(max_passes), field.data_ptr(),
-        info.data_ptr(), env._stream()))
-    return GoalField(env, field, d2, info, keep=(s, data, vr, vc))
+    head = (env._h, data.data_ptr(), n, rows, cols, int(env._shared_map and n > 1), vr.data_ptr() if vr is not None else None,
+            vc.data_ptr() if vc is not None else None, s.data_ptr(), int(s.shape[1]), d2, int(max_passes))
+    tail = (field.data_ptr(), info.data_ptr(), env._stream())
+    if table is None:
+        _lib.check(env._lib.bcp_goal_field(*(head + tail)))
+    else:   # (the table is read during the call: a launch carries its own copy)
+        _lib.check(env._lib.bcp_goal_field_cost(*(head + (table.ctypes.data,) + tail)))
+    return GoalField(env, field, d2, info, keep=(s, data, vr, vc), extra_of_cost=table)
 
 
 class BatchedGoalField(BatchedObservationWrapper):

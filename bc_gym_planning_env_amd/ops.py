@@ -213,14 +213,17 @@ class NativeOps(Handle):
         out = out.reshape(d.shape)
         return (out, dist.reshape(d.shape)) if return_distance else out
 
-    def goal_field(self, data, seeds, clearance_d2, valid=None, max_passes=0, want_info=False):
+    def goal_field(self, data, seeds, clearance_d2, valid=None, max_passes=0, want_info=False, extra_of_cost=None):
         """The geodesic cost-to-go of bcp_goal_field for one map [rows, cols] or a batch [n, rows, cols], numpy or torch ->
         uint16 device tensor of the same shape: min(length of the cheapest route through free space to the nearest seed,
         GOAL_FAR) in steps of GOAL_ORTHO / GOAL_DIAG, GOAL_NONE where there is none.  seeds: int32 (row, col) pairs, [S, 2]
         for one map or [n, S, 2] for a batch; one map with seeds [n, S, 2] is shared by n seed sets and gives n fields.
         clearance_d2: a cell is blocked iff an obstacle cell (== 254) lies within that squared distance in cells.
         valid: optional (valid_rows, valid_cols) int32 [n] each, the true shapes of a padded batch.  max_passes: 0 = as
-        many as it takes.  want_info: also int32 [n, 2] = (cells with a value, gave_up)."""
+        many as it takes.  want_info: also int32 [n, 2] = (cells with a value, gave_up).  extra_of_cost: None, or 256
+        integers in [0, GOAL_MAX_EXTRA] indexed by the map's byte (bcp_goal_field_cost): entering a free cell c then costs
+        the step plus extra_of_cost[data[c]], and the values are costs to go; goal_field.cost_table(w) makes the table for
+        an inflated map.  A table of zeros gives the plain field."""
         d = self._device_tensor(data, torch.uint8)
         s = self._device_tensor(seeds, torch.int32)
         maps = d[None] if d.dim() == 2 else d
@@ -234,10 +237,16 @@ class NativeOps(Handle):
             vr, vc = (self._device_tensor(v, torch.int32, (n,)) for v in valid)
         out = torch.empty((n,) + tuple(maps.shape[1:]), dtype=torch.uint16, device=self.device)
         info = torch.zeros((n, 2), dtype=torch.int32, device=self.device) if want_info else None
-        _lib.check(self._lib.bcp_goal_field(
-            self._h, maps.data_ptr(), n, maps.shape[1], maps.shape[2], int(shared),
-            vr.data_ptr() if vr is not None else None, vc.data_ptr() if vc is not None else None, s3.data_ptr(), s3.shape[1],
-            int(clearance_d2), int(max_passes), out.data_ptr(), info.data_ptr() if info is not None else None, self._stream()))
+        head = (self._h, maps.data_ptr(), n, maps.shape[1], maps.shape[2], int(shared),
+                vr.data_ptr() if vr is not None else None, vc.data_ptr() if vc is not None else None, s3.data_ptr(), s3.shape[1],
+                int(clearance_d2), int(max_passes))
+        tail = (out.data_ptr(), info.data_ptr() if info is not None else None, self._stream())
+        if extra_of_cost is None:
+            _lib.check(self._lib.bcp_goal_field(*(head + tail)))
+        else:
+            from .goal_field import checked_table
+            table = checked_table(extra_of_cost)
+            _lib.check(self._lib.bcp_goal_field_cost(*(head + (table.ctypes.data,) + tail)))
         self._alive["goal_field"] = (maps, s3, vr, vc)
         out = out[0] if d.dim() == 2 and s.dim() == 2 else out
         return (out, info) if want_info else out

@@ -910,6 +910,36 @@ int bcp_goal_field_bound(bcp_handle *h, const int32_t *entries /*device [n_list]
 int bcp_refresh_goal_fields(bcp_handle *h, int32_t clearance_d2, int32_t max_passes, uint16_t *field, int32_t *info,
                             void *stream);
 
+/* bcp_goal_field_cost / bcp_goal_field_cost_bound: the same fields, weighted by the map's costs -- what makes a route run
+ * down the middle of free space where there is room and still squeeze through where there is not (the potential of ROS's
+ * navfn, which pays for every cell's cost).  With e(c) = extra_of_cost[data[c]]:
+ *   v(seed) = 0;   v(c) = min over admissible neighbours n of sat(v(n) + step(n, c) + e(c))  for every free, non-seed cell c
+ * The extra belongs to the cell that is ENTERED on the way from the goal.  Everything else is bcp_goal_field's (and
+ * bcp_goal_field_bound's), word for word: obstacles (== 254 only), clearance_d2, seeds (cost 0 and free whatever stood
+ * there; a seed's own extra is never charged), the valid shape (bytes outside it are never looked up), the corner rule,
+ * 12 / 17, the saturation at BCP_GOAL_FAR, BCP_GOAL_NONE, max_passes / gave_up (rows * cols passes still always suffice),
+ * info, the two routes, the scratch they share with their plain counterparts and the stream rules that follow from it.
+ * The result is exact and unique for the same reason, and an all-zero table gives the plain call's bytes.
+ * A weighted field is a goal field for every consumer: e(c) is the same for every neighbour of c, so the neighbour that
+ * minimises field + step is the true successor, and bcp_goal_field_sample, bcp_goal_route*, and bcp_mppi_field read it
+ * unchanged.  Its values are costs to go in units of resolution / 12 "metre-equivalents", not lengths.
+ * extra_of_cost: HOST uint16 [256], indexed by the map's byte, every entry <= BCP_GOAL_MAX_EXTRA.  It is copied by value
+ * into the launch arguments: no upload, no allocation, no host synchronisation, and the caller may overwrite it as soon as
+ * the call returns.  A call can be captured after one ordinary call with the same shapes; a captured call keeps the table
+ * it was captured with.
+ * Refused: everything the plain entry point refuses, in its order, with this entry point's name as prefix; then, with
+ * BCP_E_INVALID, a NULL table; then an entry above BCP_GOAL_MAX_EXTRA (all 256 are checked, 254 and 255 too, although 254
+ * is never looked up).  n_maps == 0 (n_list == 0) succeeds and does nothing -- behind the checks.
+ * There is no refresh form: the worlds of an endless pool are not inflated, so there are no costs to weigh. */
+#define BCP_GOAL_MAX_EXTRA 4095
+int bcp_goal_field_cost(bcp_handle *h, const uint8_t *data, int64_t n_maps, int32_t rows, int32_t cols, int32_t shared,
+                        const int32_t *valid_rows, const int32_t *valid_cols, const int32_t *seeds, int32_t n_seeds,
+                        int32_t clearance_d2, int32_t max_passes, const uint16_t extra_of_cost[256] /*host*/,
+                        uint16_t *out, int32_t *info, void *stream);
+int bcp_goal_field_cost_bound(bcp_handle *h, const int32_t *entries, const int32_t *count, int64_t n_list,
+                              int32_t clearance_d2, int32_t max_passes, const uint16_t extra_of_cost[256] /*host*/,
+                              uint16_t *field, int32_t *info, void *stream);
+
 /* bcp_goal_field_sample: what the fields say at a pose, per row -- distance to go, and the direction of the route.
  * One launch, asynchronous on `stream`, no allocation, no host synchronisation; the launch arguments depend only on the
  * pointers and numbers given, so a call can be captured into a HIP graph after one ordinary call.
