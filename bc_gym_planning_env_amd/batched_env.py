@@ -18,7 +18,7 @@ import torch
 from . import _lib, boxes, host_init, robots
 from .api import Action, Box, CONTINUOUS_REWARD_PURE_PURSUIT, CostMap2D, EnvParams, INDUSTRIAL_TRICYCLE_V1, State
 from .episode_record import EpisodeEnds
-from .geometry import DeviceGeometryPool, chain_layout, stack_costmaps, stack_paths
+from .geometry import DeviceGeometryPool, HostEntries, chain_layout, stack_costmaps, stack_paths
 from .handle import Handle, SCAN_CACHE_ENTRIES, beam_table_cached, cached
 from .planning import Lookahead, Mppi
 from .state import BatchedObservation, BatchedState, EnvView, _EnvViews
@@ -117,13 +117,12 @@ class BatchedPlanEnv(Handle):
         # what only some modes or subclasses change, at its neutral value
         self.endless = False       # BatchedRandomMiniEnv(endless=True)
         self._inflated = False     # inflate_costmaps()
-        self._path_per_env = False  # route_paths() on expanded templates: self._paths then holds a path per env
-        self._map_per_env = False   # scatter_obstacles() on expanded templates: self._costmaps then holds a map per env
         self._goal_followers = []  # weak references to the GoalFields a refresh() keeps current (goal_field(follow_refresh=True))
         self._rollout_buffers, self._lookahead_buffers, self._mppi_buffers = OrderedDict(), OrderedDict(), OrderedDict()
         self._range_scan_buffers = OrderedDict()
 
-        # the geometry, in one of five modes (a shared costmap may go with private paths and the other way round)
+        # the geometry, in one of five modes (a shared costmap may go with private paths and the other way round); the host
+        # copies of either half and which of them is env i's: self._map_host, self._path_host (geometry.HostEntries)
         self._map_storage = (0, 0) if map_storage is None else (int(map_storage[0]), int(map_storage[1]))
         self._template_of_env = None if template_of_env is None else np.asarray(template_of_env, dtype=np.int64)
         self._device_pool = None
@@ -219,29 +218,27 @@ class BatchedPlanEnv(Handle):
 
     def _set_costmaps(self, costmap):
         if isinstance(costmap, CostMap2D) or hasattr(costmap, "get_data") and not isinstance(costmap, (list, tuple)):
-            self._costmaps, self._shared_map = [costmap], True
+            self._map_host, self._shared_map = HostEntries.shared(costmap), True
             data = np.ascontiguousarray(costmap.get_data(), dtype=np.uint8)
-            rows, cols = data.shape
-            origins = np.ascontiguousarray(costmap.get_origin(), dtype=np.float64)
+            self._origin_host = np.ascontiguousarray(costmap.get_origin(), dtype=np.float64)
             self.resolution = float(costmap.get_resolution())
-            data_dev = torch.from_numpy(data).to(self.device)
-            self._keep["map"] = data_dev
-            self._origin_host = origins
-            _lib.check(self._lib.bcp_set_costmaps(self._h, data_dev.data_ptr(), rows, cols, 1, None, None,
-                                                  origins.ctypes.data, 0, self.resolution, self._stream()))
+            self._keep["map"] = torch.from_numpy(data).to(self.device)
+            self._rebind_costmaps()
         else:
             costmaps = list(costmap)
             if len(costmaps) != self.n_envs:
                 raise ValueError("need one costmap per env (%d), got %d" % (self.n_envs, len(costmaps)))
             data, shapes, origins, res = stack_costmaps(costmaps, self._map_storage)
-            self._costmaps = costmaps
+            self._map_host = HostEntries.per_env(costmaps)
             self.set_costmap_tensors(self._device_tensor(data, torch.uint8), self._device_tensor(origins), res,
                                      self._device_tensor(shapes[:, 0], torch.int32),
                                      self._device_tensor(shapes[:, 1], torch.int32))
 
     def _set_from_device_pool(self, dp):
         """A pool whose maps, refined paths and initial states are on the device already: bound where they are."""
-        self._costmaps, self._paths, self._shared_path = dp.costmaps, dp.paths, False
+        # (the lazy sequences read the pool's tensors at every fetch: they follow edits of the pool, also of its attributes)
+        self._map_host, self._path_host = HostEntries.pool_entries(dp.costmaps), HostEntries.pool_entries(dp.paths)
+        self._shared_path = False
         self.set_costmap_tensors(dp.maps, dp.entry_origins(self.device), dp.resolution, dp.valid_rows, dp.valid_cols)
         self._bind_paths(dp.path_points, dp.lens)
 
@@ -249,19 +246,20 @@ class BatchedPlanEnv(Handle):
         """Private costmaps / paths from a few templates: one copy per env, expanded on the device, or -- template_of_env
         None -- the templates themselves, as the entries of a geometry pool."""
         dev = self.device
-        pick = lambda t: t   # noqa: E731
+        pick, entries = (lambda t: t), HostEntries.pool_entries   # noqa: E731
         if template_of_env is not None:
+            entries = functools.partial(HostEntries.templates, template_of_env=template_of_env)
             idx = torch.from_numpy(template_of_env).to(dev)
             assert idx.numel() == self.n_envs and int(idx.max()) < len(costmaps) == len(paths)
             pick = lambda t: t[idx]   # noqa: E731
         data, shapes, origins, res = stack_costmaps(costmaps, self._map_storage)
         shape = pick(torch.from_numpy(shapes).to(dev))
-        self._costmaps = costmaps
+        self._map_host = entries(costmaps)
         self.set_costmap_tensors(pick(torch.from_numpy(data).to(dev)).contiguous(),
                                  pick(torch.from_numpy(origins).to(dev)).contiguous(), res,
                                  shape[:, 0].contiguous(), shape[:, 1].contiguous())
-        points, lens, self._paths = stack_paths(paths, self._refine())
-        self._shared_path = False
+        points, lens, refined = stack_paths(paths, self._refine())
+        self._path_host, self._shared_path = entries(refined), False
         self._bind_paths(pick(torch.from_numpy(points).to(dev)).contiguous(), pick(torch.from_numpy(lens).to(dev)).contiguous())
 
     def _bind_paths(self, points, lens):
@@ -285,6 +283,31 @@ class BatchedPlanEnv(Handle):
             valid_rows.data_ptr() if valid_rows is not None else None,
             valid_cols.data_ptr() if valid_cols is not None else None, origins.data_ptr(), 1, float(resolution),
             self._stream()))
+
+    def _rebind_costmaps(self):
+        """Binds the maps of self._keep["map"] again, with the arguments of the original binding: after an edit of the maps
+        on the device, so that everything the library derives from them is rebuilt."""
+        data = self._keep["map"]
+        if self._shared_map:
+            _lib.check(self._lib.bcp_set_costmaps(self._h, data.data_ptr(), data.shape[0], data.shape[1], 1, None, None,
+                                                  self._origin_host.ctypes.data, 0, float(self.resolution), self._stream()))
+        else:
+            self.set_costmap_tensors(data, self._keep["origins"], self.resolution, self._keep.get("vr"), self._keep.get("vc"))
+
+    def _bound_maps(self):
+        """(maps uint8 [entries, rows, cols], valid_rows, valid_cols, shared): the bound maps as entries, a shared map as one."""
+        if self._shared_map:
+            return self._keep["map"][None], None, None, True
+        return self._keep["map"], self._keep.get("vr"), self._keep.get("vc"), False
+
+    def _bound_origins(self):
+        """float64 device tensor [entries, 2], [1, 2] for a shared map: the origins of the bound maps."""
+        if self._shared_map:
+            return torch.tensor(self._origin_host, device=self.device)[None]
+        return self._keep["origins"]
+
+    _costmaps = property(lambda self: self._map_host.items, doc="the host costmaps as stored (HostEntries.items)")
+    _paths = property(lambda self: self._path_host.items, doc="the host paths, refined, as stored (HostEntries.items)")
 
     @property
     def costmap_tensor(self):
@@ -314,16 +337,11 @@ class BatchedPlanEnv(Handle):
         if self._inflated:
             raise RuntimeError("inflate_costmaps: the costmaps of this env are inflated already")
         radius = robots.inscribed_radius(self.footprint() if footprint is None else footprint)
-        data = self._keep["map"]
-        maps = data[None] if data.dim() == 2 else data
-        vr, vc = (None, None) if self._shared_map else (self._keep.get("vr"), self._keep.get("vc"))
+        maps, vr, vc, _shared = self._bound_maps()
         self._inflate(maps, vr, vc, radius, cost_scaling_factor, maps)
-        if self._shared_map:
-            _lib.check(self._lib.bcp_set_costmaps(self._h, data.data_ptr(), data.shape[0], data.shape[1], 1, None, None,
-                                                  self._origin_host.ctypes.data, 0, float(self.resolution), self._stream()))
-        else:
-            self.set_costmap_tensors(data, self._keep["origins"], self.resolution, vr, vc)
-        # the host copies behind envs[i].get_state().costmap (a device pool hands out copies of its tensors on demand)
+        self._rebind_costmaps()
+        # the host copies behind envs[i].get_state().costmap (a device pool hands out copies of its tensors on demand):
+        # inflated as they are stored, templates once each
         if self._device_pool is None:
             host = list(self._costmaps)
             stack, shapes, _, _ = stack_costmaps(host)
@@ -331,19 +349,20 @@ class BatchedPlanEnv(Handle):
             self._inflate(dev_stack, self._device_tensor(shapes[:, 0], torch.int32),
                           self._device_tensor(shapes[:, 1], torch.int32), radius, cost_scaling_factor, dev_stack)
             inflated = dev_stack.cpu().numpy()
-            self._costmaps = [CostMap2D(inflated[k, :s[0], :s[1]].copy(), c.get_resolution(), c.get_origin())
-                              for k, (c, s) in enumerate(zip(host, shapes))]
+            self._map_host.replace_stored([CostMap2D(inflated[k, :s[0], :s[1]].copy(), c.get_resolution(), c.get_origin())
+                                           for k, (c, s) in enumerate(zip(host, shapes))])
         torch.cuda.current_stream(self.device).synchronize()
         self._inflated = True
 
     def _set_paths(self, path):
         self._shared_path = isinstance(path, np.ndarray) and path.ndim == 2
-        points, lens, self._paths = stack_paths([path] if self._shared_path else path, self._refine())
+        points, lens, refined = stack_paths([path] if self._shared_path else path, self._refine())
+        self._path_host = HostEntries.shared(refined[0]) if self._shared_path else HostEntries.per_env(refined)
         if self._shared_path:
             self._bind_paths(torch.from_numpy(points[0]).to(self.device), None)
         else:
-            if len(self._paths) != self.n_envs:
-                raise ValueError("need one path per env (%d), got %d" % (self.n_envs, len(self._paths)))
+            if len(refined) != self.n_envs:
+                raise ValueError("need one path per env (%d), got %d" % (self.n_envs, len(refined)))
             self._bind_paths(torch.from_numpy(points).to(self.device), torch.from_numpy(lens).to(self.device))
 
     def _make_initial_state(self):
@@ -359,12 +378,7 @@ class BatchedPlanEnv(Handle):
                                 torch.zeros(n, dtype=torch.int32, device=dev), torch.zeros(n, dtype=torch.uint8, device=dev))
         # one initial state per stored path, then per env (per entry with a geometry pool) the one of its path
         per = [self._first_reward_state(p, self.params.reward_provider_params) for p in self._paths]
-        if self._shared_path:
-            of = np.zeros(n, dtype=np.int64)
-        elif self._template_of_env is not None:
-            of = self._template_of_env
-        else:
-            of = np.arange(n)
+        of = np.zeros(n, dtype=np.int64) if self._shared_path else self._path_host.index()
         robot = np.zeros((7, n), dtype=np.float64)
         robot[0:3] = np.stack([p[0] for p in self._paths])[of].T
         md = np.array([m for m, _ in per], dtype=np.float64)[of]
@@ -426,21 +440,14 @@ class BatchedPlanEnv(Handle):
         return cells[:, :dshape[0], :dshape[1]].bool(), t_out
 
     # ------------------------------------------------------------------ per-env lookups
+    def _entry_of(self, i):
+        return None if self.geom_of_env is None else int(self.geom_of_env[i])
+
     def path_of(self, i):
-        if self.geom_of_env is not None:
-            return self._paths[int(self.geom_of_env[i])]
-        if self._template_of_env is not None and not self._path_per_env:
-            return self._paths[self._template_of_env[i]]
-        return self._paths[0] if self._shared_path else self._paths[i]
+        return self._path_host.of_env(i, self._entry_of(i))
 
     def costmap_of(self, i):
-        if self.geom_of_env is not None:
-            return self._costmaps[int(self.geom_of_env[i])]
-        if self._template_of_env is not None and not self._map_per_env:
-            return self._costmaps[self._template_of_env[i]]
-        if self._shared_map or len(self._costmaps) == 1:
-            return self._costmaps[0]
-        return self._costmaps[i]
+        return self._map_host.of_env(i, self._entry_of(i))
 
     def time_of(self, current_iter):
         """Observation.time for iteration counters (device tensor): dt accumulated current_iter times."""
@@ -821,53 +828,8 @@ class BatchedPlanEnv(Handle):
         Returns the int32 status [entries] (device tensor; _lib.ROUTE_* bits).
         Refused on endless=True pools (refresh() would write straight paths back), on a shared map or path, and on fields
         whose owner or shape is not this env's."""
-        if self.endless:
-            raise RuntimeError("route_paths: not supported on endless=True pools -- refresh() re-samples worlds with "
-                               "straight paths into the pool")
-        if self._shared_path or self._shared_map:
-            raise RuntimeError("route_paths: needs private maps with private paths (a pool, or a map and a path per env)")
-        if fields is not None and clearance is not None:
-            raise ValueError("route_paths: clearance belongs to the build of the fields; pass one of fields and clearance")
-        if fields is not None and cost_weight is not None:
-            raise ValueError("route_paths: cost_weight belongs to the build of the fields; pass one of fields and cost_weight")
-        if fields is None:
-            fields = self.goal_field(clearance, cost_weight=cost_weight)
-        data, old_pts, old_lens = self._keep["map"], self._keep["path"], self._keep["lens"]
-        if fields.owner is not self or tuple(fields.field.shape) != tuple(data.shape):
-            raise ValueError("route_paths: fields must be this env's, one per entry: %s expected, got %s"
-                             % (tuple(data.shape), tuple(fields.field.shape)))
-        old_len = int(old_pts.shape[1])
-        max_len = old_len if max_len is None else int(max_len)
-        paths, lens, status, init = fields.route_bound(stride, max_len, want=("init",))
-        status = status.clone()
-        ok = status == 0
-        length = max(max_len, old_len)
-        new_pts = torch.zeros((int(old_pts.shape[0]), length, 3), dtype=torch.float64, device=self.device)
-        new_pts[:, :old_len] = old_pts
-        routed = torch.zeros_like(new_pts)
-        routed[:, :max_len] = paths
-        new_pts = torch.where(ok[:, None, None], routed, new_pts).contiguous()
-        new_lens = torch.where(ok, lens, old_lens).contiguous()
-        if length == old_len:   # nothing grows: the bound tensors themselves (a device pool's own) take the routes
-            new_pts, new_lens = old_pts.copy_(new_pts), old_lens.copy_(new_lens)
-        first = self._initial_state
-        first.min_spat_dist_so_far.copy_(torch.where(ok, init[:, 0], first.min_spat_dist_so_far))
-        first.target_idx.copy_(torch.where(ok, init[:, 1].to(torch.int32), first.target_idx))
-        self._bind_paths(new_pts, new_lens)
-        self._bind(first, self._lib.bcp_bind_initial_state)
-        dp = self._device_pool
-        if dp is not None:
-            dp.path_points, dp.lens = new_pts, new_lens
-            dp.init.copy_(torch.stack([first.min_spat_dist_so_far, first.target_idx.to(torch.float64)], dim=1))
-            self._paths = dp.paths
-        else:   # the host copies behind path_of(i): one per entry (per env where templates were expanded)
-            pts_host, lens_host, ok_host = new_pts.cpu().numpy(), new_lens.cpu().numpy(), ok.cpu().numpy()
-            per_template = self._template_of_env is not None and not self._path_per_env
-            old = [self._paths[int(t)] for t in self._template_of_env] if per_template else list(self._paths)
-            self._paths = [pts_host[k, :lens_host[k]].copy() if ok_host[k] else old[k] for k in range(len(old))]
-            self._path_per_env = self._template_of_env is not None
-        self.reset()
-        return status
+        from . import goal_field
+        return goal_field.route_paths(self, fields, stride, max_len, clearance, cost_weight)
 
     def scatter_obstacles(self, n_boxes, half_size, along=(0.2, 0.8), lateral=1.0, keep_clear=None, n_yaws=16, seed=0,
                           max_attempts=32, ensure_route=True, clearance=None):
@@ -890,53 +852,8 @@ class BatchedPlanEnv(Handle):
         placed.
         Refused on endless=True pools (refresh() would write bare worlds back), on a shared map or path, and on maps that
         are inflated already."""
-        if self.endless:
-            raise RuntimeError("scatter_obstacles: not supported on endless=True pools -- refresh() re-samples bare worlds "
-                               "into the pool")
-        if self._shared_path or self._shared_map:
-            raise RuntimeError("scatter_obstacles: needs private maps with private paths (a pool, or a map and a path per env)")
-        if self._inflated:
-            raise RuntimeError("scatter_obstacles: the costmaps of this env are inflated already -- scatter first, then inflate")
-        data, origins = self._keep["map"], self._keep["origins"]
-        vr, vc = self._keep.get("vr"), self._keep.get("vc")
-        pts, lens = self._keep["path"], self._keep["lens"]
-        n = int(data.shape[0])
-        last = (lens.to(torch.int64) - 1).clamp(min=0)
-        starts = pts[:, 0, :].cpu().numpy()
-        goals = pts[torch.arange(n, device=self.device), last].cpu().numpy()
-        org = origins.cpu().numpy()
-        start_cells, goal_cells = boxes.cells_of(starts, org, self.resolution), boxes.cells_of(goals, org, self.resolution)
-        if keep_clear is None:
-            keep_clear = float(np.linalg.norm(self.footprint(), axis=1).max())
-        d2 = (int(np.ceil(float(keep_clear) / self.resolution)) + 1) ** 2
-        original = data.clone()
-        bx, counts = boxes.scatter_boxes(self, data, origins, self.resolution, boxes.path_frames(starts, goals, lateral),
-                                         boxes.yaw_table(n_yaws), n_boxes, half_size, along,
-                                         boxes.keep_outs([start_cells, goal_cells], d2), (vr, vc), seed, max_attempts)
-        status = (counts < int(n_boxes)).to(torch.int32) * _lib.SCATTER_SHORT
-        if ensure_route:
-            fields = self.goal_field(clearance)
-            sc = torch.from_numpy(start_cells).to(self.device)
-            rows, cols = int(data.shape[1]), int(data.shape[2])
-            inside = (sc[:, 0] >= 0) & (sc[:, 0] < rows) & (sc[:, 1] >= 0) & (sc[:, 1] < cols)
-            # (uint16 planes cannot be indexed: as int16, GOAL_NONE reads -1)
-            at = fields.field.view(torch.int16)[torch.arange(n, device=self.device), sc[:, 0].clamp(0, rows - 1),
-                                                sc[:, 1].clamp(0, cols - 1)]
-            cut = ~inside | (at == _lib.GOAL_NONE - 65536)
-            data.copy_(torch.where(cut[:, None, None], original, data))
-            status = status | cut.to(torch.int32) * _lib.SCATTER_REVERTED
-        self.set_costmap_tensors(data, origins, self.resolution, vr, vc)
-        if self._device_pool is None:   # the host copies behind envs[i].get_state().costmap: one per entry
-            host = data.cpu().numpy()
-            shapes = (np.stack([vr.cpu().numpy(), vc.cpu().numpy()], axis=1) if vr is not None
-                      else np.tile(host.shape[1:], (n, 1)))
-            per_template = self._template_of_env is not None and not self._map_per_env
-            old = [self._costmaps[int(t)] for t in self._template_of_env] if per_template else list(self._costmaps)
-            self._costmaps = [CostMap2D(host[k, :shapes[k][0], :shapes[k][1]].copy(), c.get_resolution(), c.get_origin())
-                              for k, c in enumerate(old)]
-            self._map_per_env = self._template_of_env is not None
-        self.reset()
-        return status, counts, bx
+        return boxes.scatter_obstacles(self, n_boxes, half_size, along, lateral, keep_clear, n_yaws, seed, max_attempts,
+                                       ensure_route, clearance)
 
     def enable_episode_record(self, capacity=None):
         """Keep what every episode end leaves behind (bcp_bind_episode_record): from now on step() returns

@@ -1,6 +1,6 @@
-"""Box obstacles stamped into batches of maps (bcp_scatter_boxes, one launch): the raw call on caller tensors, and what
-BatchedPlanEnv.scatter_obstacles derives from an env's binding before it -- the frame of every entry's path, the keep-outs
-about its start and goal, the table of yaws.  The reference has no counterpart: its obstacle-avoidance scenario
+"""Box obstacles stamped into batches of maps (bcp_scatter_boxes, one launch): the raw call on caller tensors, and
+BatchedPlanEnv.scatter_obstacles with what it derives from an env's binding before the call -- the frame of every entry's
+path, the keep-outs about its start and goal, the table of yaws.  The reference has no counterpart: its obstacle-avoidance scenario
 (rw_randomized_corridor_3_boxes.py) reads maps that exist only as a download."""
 import ctypes as C
 
@@ -8,6 +8,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .api import CostMap2D
 
 
 def yaw_table(n_yaws):
@@ -76,3 +77,52 @@ def scatter_boxes(handle, data, origins, resolution, frame, yaw_cs, n_boxes, hal
         boxes.data_ptr(), counts.data_ptr(), handle._stream()))
     handle._alive["scatter_boxes"] = (data, org, fr, yaw, kp, vr, vc)
     return boxes, counts
+
+
+def scatter_obstacles(env, n_boxes, half_size, along=(0.2, 0.8), lateral=1.0, keep_clear=None, n_yaws=16, seed=0,
+                      max_attempts=32, ensure_route=True, clearance=None):
+    """BatchedPlanEnv.scatter_obstacles: see there."""
+    if env.endless:
+        raise RuntimeError("scatter_obstacles: not supported on endless=True pools -- refresh() re-samples bare worlds "
+                           "into the pool")
+    if env._shared_path or env._shared_map:
+        raise RuntimeError("scatter_obstacles: needs private maps with private paths (a pool, or a map and a path per env)")
+    if env._inflated:
+        raise RuntimeError("scatter_obstacles: the costmaps of this env are inflated already -- scatter first, then inflate")
+    data, vr, vc, _shared = env._bound_maps()
+    origins = env._bound_origins()
+    pts, lens = env._keep["path"], env._keep["lens"]
+    n = int(data.shape[0])
+    last = (lens.to(torch.int64) - 1).clamp(min=0)
+    starts = pts[:, 0, :].cpu().numpy()
+    goals = pts[torch.arange(n, device=env.device), last].cpu().numpy()
+    org = origins.cpu().numpy()
+    start_cells, goal_cells = cells_of(starts, org, env.resolution), cells_of(goals, org, env.resolution)
+    if keep_clear is None:
+        keep_clear = float(np.linalg.norm(env.footprint(), axis=1).max())
+    d2 = (int(np.ceil(float(keep_clear) / env.resolution)) + 1) ** 2
+    original = data.clone()
+    bx, counts = scatter_boxes(env, data, origins, env.resolution, path_frames(starts, goals, lateral), yaw_table(n_yaws),
+                               n_boxes, half_size, along, keep_outs([start_cells, goal_cells], d2), (vr, vc), seed, max_attempts)
+    status = (counts < int(n_boxes)).to(torch.int32) * _lib.SCATTER_SHORT
+    if ensure_route:
+        fields = env.goal_field(clearance)
+        sc = torch.from_numpy(start_cells).to(env.device)
+        rows, cols = int(data.shape[1]), int(data.shape[2])
+        inside = (sc[:, 0] >= 0) & (sc[:, 0] < rows) & (sc[:, 1] >= 0) & (sc[:, 1] < cols)
+        # (uint16 planes cannot be indexed: as int16, GOAL_NONE reads -1)
+        at = fields.field.view(torch.int16)[torch.arange(n, device=env.device), sc[:, 0].clamp(0, rows - 1),
+                                            sc[:, 1].clamp(0, cols - 1)]
+        cut = ~inside | (at == _lib.GOAL_NONE - 65536)
+        data.copy_(torch.where(cut[:, None, None], original, data))
+        status = status | cut.to(torch.int32) * _lib.SCATTER_REVERTED
+    env._rebind_costmaps()
+    if env._device_pool is None:   # the host copies behind envs[i].get_state().costmap: one per entry from now on
+        host_maps, now = env._map_host, data.cpu().numpy()
+        shapes = (np.stack([vr.cpu().numpy(), vc.cpu().numpy()], axis=1) if vr is not None
+                  else np.tile(now.shape[1:], (n, 1)))
+        old = [host_maps.of_entry(k) for k in range(n)]
+        host_maps.replace([CostMap2D(now[k, :shapes[k][0], :shapes[k][1]].copy(), c.get_resolution(), c.get_origin())
+                           for k, c in enumerate(old)])
+    env.reset()
+    return status, counts, bx

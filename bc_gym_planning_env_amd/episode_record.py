@@ -100,8 +100,8 @@ class EpisodeEnds(object):
         out = []
         for j in range(m):
             i, g = int(ids[j]), int(geom[j])
-            st = reference_state(e, e._paths[g] if g >= 0 else e.path_of(i), e._costmaps[g] if g >= 0 else e.costmap_of(i),
-                                 md[j], ti[j], it[j], time[j], col[j],
+            # (the entry the episode ran on, not the one the auto-reset moved the env to)
+            st = reference_state(e, e._path_host.of_env(i, g), e._map_host.of_env(i, g), md[j], ti[j], it[j], time[j], col[j],
                                  ps[:, j].copy() if ps is not None else robot[:3, j].copy(),
                                  rs[:, j] if rs is not None else robot[:, j])
             out.append((i, st, int(reason[i]), float(ret[j]), int(it[j])))

@@ -1,6 +1,6 @@
 """Host side of the geometry BatchedPlanEnv binds: costmaps padded to one shape, paths refined and padded to one
-length, the env -> pool-entry layout of the pool envs, and the pool that already lives on the GPU.  numpy only; torch is
-imported where a device tensor is made."""
+length, the host copies of what is bound (HostEntries), the env -> pool-entry layout of the pool envs, and the pool that
+already lives on the GPU.  numpy only; torch is imported where a device tensor is made."""
 import numpy as np
 
 from .api import CostMap2D
@@ -52,6 +52,59 @@ def pool_or_sample(pool, samplers, sampler, seeds, n_chains, n_envs):
     if seeds is None:
         seeds = range(int(n_chains) if n_chains else min(int(n_envs), 1024))
     return samplers[sampler](list(seeds))
+
+
+class HostEntries(object):
+    """The host copies behind one binding of BatchedPlanEnv -- its costmaps, or its paths -- with the rule from an env, or
+    from a bound entry, to its item.  `items` is a list, or the lazy sequence a DeviceGeometryPool hands out; the bound
+    entries are 1 for a shared item, the pool's entries for a pool, else one per env."""
+
+    def __init__(self, items, n_entries, item_of_entry=None, pool=False):
+        self.items, self.n_entries, self.pool = items, int(n_entries), pool
+        self._item_of_entry = item_of_entry   # int array [n_entries], None = entry k holds items[k]
+
+    @classmethod
+    def shared(cls, item):
+        return cls([item], 1)
+
+    @classmethod
+    def per_env(cls, items):
+        return cls(items, len(items))
+
+    @classmethod
+    def templates(cls, items, template_of_env):
+        """env i holds a private copy of items[template_of_env[i]] (until a replace() gives every env its own item)"""
+        return cls(items, len(template_of_env), np.asarray(template_of_env, dtype=np.int64))
+
+    @classmethod
+    def pool_entries(cls, items):
+        """env i holds items[geom_of_env[i]]; the entry an env is on lives on the device, so of_env() is told"""
+        return cls(items, len(items), pool=True)
+
+    def index(self):
+        """int64 [n_entries]: the item of every bound entry"""
+        return np.arange(self.n_entries) if self._item_of_entry is None else self._item_of_entry
+
+    def of_entry(self, k):
+        return self.items[int(k) if self._item_of_entry is None else int(self._item_of_entry[k])]
+
+    def of_env(self, i, entry=None):
+        """The item of env i; a pool needs `entry`, the pool entry the env is on."""
+        if self.pool:
+            return self.of_entry(entry)
+        return self.of_entry(0 if self.n_entries == 1 else i)
+
+    def replace(self, items):
+        """After an edit of the bound entries: `items`, one per bound entry, are the host copies from now on."""
+        if len(items) != self.n_entries:
+            raise ValueError("need one item per bound entry (%d), got %d" % (self.n_entries, len(items)))
+        self.items, self._item_of_entry = items, None
+
+    def replace_stored(self, items):
+        """After an edit that treats equal entries equally: one new item per stored item, the rule stays."""
+        if len(items) != len(self.items):
+            raise ValueError("need one item per stored item (%d), got %d" % (len(self.items), len(items)))
+        self.items = items
 
 
 class DeviceGeometryPool(object):

@@ -4,7 +4,8 @@ launch per build) and what it says at a pose -- distance to go and the direction
 "direction to goal" feature of a navigation policy.  follow_refresh=True builds the fields from the handle's own binding
 (bcp_goal_field_bound) and, on an endless pool, has every refresh() rebuild the fields of the entries it re-samples
 (bcp_refresh_goal_fields).  cost_weight / extra_of_cost weigh the field by the costs of an inflated map
-(bcp_goal_field_cost): routes then run down the middle of free space where there is room.  The reference has no
+(bcp_goal_field_cost): routes then run down the middle of free space where there is room.  route_paths() makes the routes
+down the fields the env's paths (bcp_goal_route_bound).  The reference has no
 counterpart; the shape of the wrapper follows BatchedRangeScan (range_scan.py)."""
 from collections import OrderedDict
 
@@ -179,8 +180,7 @@ def path_seeds(env, which):
     dev = env.device
     if lens is None:
         pts, lens = pts[None], torch.full((1,), int(pts.shape[0]), dtype=torch.int32, device=dev)
-    origins = (torch.tensor(np.array(env._origin_host, dtype=np.float64), device=dev)[None] if env._shared_map
-               else env._keep["origins"])
+    origins = env._bound_origins()
     inv_res = 1.0 / float(env.resolution)
     cells = torch.round((pts[..., :2] - origins[:, None, :]) * inv_res)       # [fields, L, 2] = (col, row), half to even
     cells = torch.nan_to_num(cells, nan=-1.0).clamp(-1.0, 1e9).to(torch.int32)
@@ -201,8 +201,8 @@ def build_bound(env, d2, max_passes):
     endless env the GoalField is registered with it, and every refresh() rebuilds the fields of the entries it re-samples."""
     if env.endless:
         env.finish_refresh()
-    data = env._keep["map"]
-    if env._shared_map or data.dim() != 3:
+    data, _vr, _vc, shared = env._bound_maps()
+    if shared:
         raise _lib.BcpError("goal_field(follow_refresh=True): needs private maps with private paths (a pool, or a map "
                             "and a path per env); a shared map is served by the default build")
     n, rows, cols = (int(v) for v in data.shape)
@@ -247,18 +247,12 @@ def build(env, clearance=None, seeds="goal", max_passes=0, follow_refresh=False,
     if follow_refresh:
         return build_bound(env, d2, max_passes)
     s = path_seeds(env, seeds)
-    data = env._keep["map"]
-    n = int(s.shape[0])
-    vr = vc = None
-    if env._shared_map:
-        rows, cols = int(data.shape[0]), int(data.shape[1])
-    else:
-        rows, cols = int(data.shape[1]), int(data.shape[2])
-        vr, vc = env._keep.get("vr"), env._keep.get("vc")
-        assert n == int(data.shape[0])   # (one path for private maps: its way points on every entry's origin)
+    data, vr, vc, shared = env._bound_maps()
+    n, rows, cols = int(s.shape[0]), int(data.shape[1]), int(data.shape[2])
+    assert shared or n == int(data.shape[0])   # (one path for private maps: its way points on every entry's origin)
     field = torch.empty((n, rows, cols), dtype=torch.uint16, device=env.device)
     info = torch.zeros((n, 2), dtype=torch.int32, device=env.device)
-    head = (env._h, data.data_ptr(), n, rows, cols, int(env._shared_map and n > 1), vr.data_ptr() if vr is not None else None,
+    head = (env._h, data.data_ptr(), n, rows, cols, int(shared and n > 1), vr.data_ptr() if vr is not None else None,
             vc.data_ptr() if vc is not None else None, s.data_ptr(), int(s.shape[1]), d2, int(max_passes))
     tail = (field.data_ptr(), info.data_ptr(), env._stream())
     if table is None:
@@ -266,6 +260,54 @@ def build(env, clearance=None, seeds="goal", max_passes=0, follow_refresh=False,
     else:   # (the table is read during the call: a launch carries its own copy)
         _lib.check(env._lib.bcp_goal_field_cost(*(head + (table.ctypes.data,) + tail)))
     return GoalField(env, field, d2, info, keep=(s, data, vr, vc), extra_of_cost=table)
+
+
+def route_paths(env, fields=None, stride=2, max_len=None, clearance=None, cost_weight=None):
+    """BatchedPlanEnv.route_paths: see there."""
+    if env.endless:
+        raise RuntimeError("route_paths: not supported on endless=True pools -- refresh() re-samples worlds with "
+                           "straight paths into the pool")
+    if env._shared_path or env._shared_map:
+        raise RuntimeError("route_paths: needs private maps with private paths (a pool, or a map and a path per env)")
+    if fields is not None and clearance is not None:
+        raise ValueError("route_paths: clearance belongs to the build of the fields; pass one of fields and clearance")
+    if fields is not None and cost_weight is not None:
+        raise ValueError("route_paths: cost_weight belongs to the build of the fields; pass one of fields and cost_weight")
+    if fields is None:
+        fields = env.goal_field(clearance, cost_weight=cost_weight)
+    data, old_pts, old_lens = env._keep["map"], env._keep["path"], env._keep["lens"]
+    if fields.owner is not env or tuple(fields.field.shape) != tuple(data.shape):
+        raise ValueError("route_paths: fields must be this env's, one per entry: %s expected, got %s"
+                         % (tuple(data.shape), tuple(fields.field.shape)))
+    old_len = int(old_pts.shape[1])
+    max_len = old_len if max_len is None else int(max_len)
+    paths, lens, status, init = fields.route_bound(stride, max_len, want=("init",))
+    status = status.clone()
+    ok = status == 0
+    length = max(max_len, old_len)
+    new_pts = torch.zeros((int(old_pts.shape[0]), length, 3), dtype=torch.float64, device=env.device)
+    new_pts[:, :old_len] = old_pts
+    routed = torch.zeros_like(new_pts)
+    routed[:, :max_len] = paths
+    new_pts = torch.where(ok[:, None, None], routed, new_pts).contiguous()
+    new_lens = torch.where(ok, lens, old_lens).contiguous()
+    if length == old_len:   # nothing grows: the bound tensors themselves (a device pool's own) take the routes
+        new_pts, new_lens = old_pts.copy_(new_pts), old_lens.copy_(new_lens)
+    first = env._initial_state
+    first.min_spat_dist_so_far.copy_(torch.where(ok, init[:, 0], first.min_spat_dist_so_far))
+    first.target_idx.copy_(torch.where(ok, init[:, 1].to(torch.int32), first.target_idx))
+    env._bind_paths(new_pts, new_lens)
+    env._bind(first, env._lib.bcp_bind_initial_state)
+    dp = env._device_pool
+    if dp is not None:   # (env._paths hands out copies of these on demand)
+        dp.path_points, dp.lens = new_pts, new_lens
+        dp.init.copy_(torch.stack([first.min_spat_dist_so_far, first.target_idx.to(torch.float64)], dim=1))
+    else:   # the host copies behind path_of(i): one per entry from now on
+        host = env._path_host
+        pts_host, lens_host, ok_host = new_pts.cpu().numpy(), new_lens.cpu().numpy(), ok.cpu().numpy()
+        host.replace([pts_host[k, :lens_host[k]].copy() if ok_host[k] else host.of_entry(k) for k in range(host.n_entries)])
+    env.reset()
+    return status
 
 
 class BatchedGoalField(BatchedObservationWrapper):
