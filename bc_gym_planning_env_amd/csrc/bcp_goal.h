@@ -32,6 +32,7 @@
 
 #include "bcp_device.h"
 #include "bcp_goal_cell.h"
+#include "bcp_goal_plan.h"   // goal_lds_bytes, kGoalFixedWords: the LDS the host plans is the LDS the kernel lays out
 #include "bcp_step.h"   // EntrySelect
 
 namespace bcp {
@@ -90,8 +91,6 @@ template <> struct GoalKernelArgs<true, true> {
     GoalCost c;
 };
 
-constexpr int kGoalFixedWords = 128 + 4;   // half-widths [128], pass flags [3], counter
-
 template <bool kLds> struct GoalMem;
 template <> struct GoalMem<true> {
     typedef LdsU32 Words;
@@ -108,15 +107,6 @@ struct GoalPlaneGet {
     int32_t cols;
     __device__ __forceinline__ uint16_t operator()(int32_t r, int32_t c) const { return p[r * cols + c]; }
 };
-
-// dynamic LDS of the kernel: the fixed words, and on the LDS route both masks and the plane; cost: behind them the table
-// [256] uint16 (on either route) and, on the LDS route, the map's bytes
-__host__ __device__ inline size_t goal_lds_bytes(int rows, int cols, int wpr, bool in_lds, bool cost = false)
-{
-    const size_t fixed = (size_t)kGoalFixedWords * 4, cells = (size_t)rows * cols;
-    const size_t plain = in_lds ? fixed + (size_t)2 * rows * wpr * 4 + ((cells * 2 + 3) & ~(size_t)3) : fixed;
-    return cost ? plain + 512 + (in_lds ? (cells + 3) & ~(size_t)3 : 0) : plain;
-}
 
 // kCost: the field weighted by the map's costs (goal_relax_cell_cost).  Phase 1 keeps every byte it reads in a uint8 plane
 // in LDS (kLds; on the global route phase 4 reads the byte from `data`, which nobody writes during the call), the table is

@@ -1,12 +1,14 @@
 // bcp_goal_cell.h -- the goal field's arithmetic (bcp_goal_field, bcp_goal_field_sample; include/bcplan.h): the argument
 // checks, the half-widths of the clearance disc and the widening of one mask word, the pull relaxation of one cell -- plain, and
-// weighted by the map's costs (goal_relax_cell_cost, bcp_goal_field_cost) --, the field
-// at a pose, the seed cell of a bound path (bcp_goal_field_bound), the sampling of one row with its carrot walk, and the
-// route of one row (bcp_goal_route: the walk written out as a path).  Plain C++ with no HIP in it: goal_field_kernel,
-// goal_sample_kernel and goal_route_kernel (bcp_goal.h) and mppi_kernel's terminal read (bcp_mppi.h) call these functions on
-// the device, tests/c_abi/goal_field_main.cpp, tests/c_abi/goal_route_main.cpp and tests/c_abi/mppi_field_main.cpp call the
-// same ones on the host, and there is no other copy of them.  The float64 arithmetic rounds every product, quotient, root and sum on its own
-// (-ffp-contract=off).
+// weighted by the map's costs (goal_relax_cell_cost, bcp_goal_field_cost) --, the field at a pose, the seed cell of a bound
+// path (bcp_goal_field_bound), the sampling of one row with its carrot walk, and the route of one row (bcp_goal_route: the
+// walk written out as a path).  Plain C++ with no HIP in it.  Who calls this, on the device: goal_field_kernel,
+// goal_sample_kernel and goal_route_kernel (bcp_goal.h), and mppi_kernel's terminal read (bcp_mppi.h).  On the host, under
+// sanitizers and through bounds-checked accessors: tests/c_abi/goal_sweep.h (for goal_field_main.cpp and goal_cost_main.cpp),
+// goal_seed_main.cpp, goal_route_main.cpp and mppi_field_main.cpp call the same functions, and there is no other copy of
+// them.  What is NOT here is who works on which word: the loops of goal_field_kernel's phases 2 (the `closed` word) and 3
+// (the seeds) are the kernel's, and goal_sweep.h restates them once around goal_half_width and goal_widen_word.  The float64
+// arithmetic rounds every product, quotient, root and sum on its own (-ffp-contract=off).
 //
 // A field is a uint16 plane [rows][cols]: kGoalNone where no route exists (blocked, outside the valid shape, not connected
 // to a seed), else min(length of the cheapest admissible route to a seed, kGoalFar) with steps of kGoalOrtho to an edge

@@ -3,16 +3,13 @@
 // device-side list of them), bcp_goal_field_cost / bcp_goal_field_cost_bound (the two again with a host table of extras per
 // map byte, copied into the launch arguments), bcp_goal_field_sample / bcp_final_goal_field_sample over the rows of obs_rows() (bcp_ego_host.h),
 // bcp_goal_route / bcp_goal_route_bound over the same rows or the binding's entries, and the value
-// check of BCP_TUNE_GOAL_ROUTE.  The refusals are the checks of bcp_goal_cell.h, which the host tests run too; the kernels are
-// in bcp_goal.h.  Included by bcplan.hip after bcp_ego_host.h.
+// check of BCP_TUNE_GOAL_ROUTE.  The refusals are the checks of bcp_goal_cell.h and the shape of every field launch is
+// plan_goal's (bcp_goal_plan.h), both of which the host tests run too; the kernels are in bcp_goal.h.  Included by
+// bcplan.hip after bcp_ego_host.h.
 // Capture: the launch arguments depend only on what the caller passes and nothing is uploaded, but a field kernel whose
 // dynamic LDS passes 64 KB needs its limit raised on first use (raise_dynamic_lds: not a stream operation), and the global
 // route may grow the scratch: one ordinary call with the same shapes must precede a capture.  The sample call uses no LDS.
 #pragma once
-
-// Global route: two masks per workgroup in scratch, so the grid is what sizes it (as for bcp_inflate_costmaps).
-constexpr int64_t kGoalGlobalGrid = 512;
-constexpr int64_t kGoalScratchBytes = 256ll << 20;
 
 static int goal_set_route(bcp_handle* h, int32_t value)
 {
@@ -34,6 +31,35 @@ static int goal_cost_table(const uint16_t* extra_of_cost, GoalCost& c, const cha
     }
     memcpy(c.extra, extra_of_cost, sizeof(c.extra));
     return BCP_OK;
+}
+
+// The one launch of goal_field_kernel, for every form: the arguments that only depend on the shape and the clearance, the
+// plan (plan_goal, bcp_goal_plan.h: route, threads, grid, LDS, scratch), the scratch the caller hands in -- reserved here,
+// on the global route alone -- and the launch.  trips >= 1: the maps, or the listed entries of the bound form.
+static_assert(kGoalMaxLds == kMaxDynamicLds, "plan_goal decides the route by the library's limit on dynamic LDS");
+
+template <bool kBound, bool kCost>
+static int goal_launch(bcp_handle* h, GoalKernelArgs<kBound, kCost>& ka, int32_t rows, int32_t cols, int32_t clearance_d2,
+                       int32_t max_passes, int64_t trips, DevBuf<uint32_t>& scratch, hipStream_t s, const char* who)
+{
+    GoalArgs& a = ka.g;
+    a.rows = rows;
+    a.cols = cols;
+    a.wpr = (cols + 31) / 32;
+    a.clearance_d2 = clearance_d2;
+    a.reach = goal_isqrt(clearance_d2);
+    a.max_passes = max_passes > 0 ? max_passes : rows * cols;
+    const GoalPlan p = plan_goal(rows, cols, trips, kBound, kCost, h->tune.goal_route == 2);
+    if (!p.in_lds) {
+        if (scratch.reserve((size_t)p.scratch_words) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(BCP_E_HIP, "%s: cannot allocate %lld bytes of scratch", who, (long long)(p.scratch_words * 4));
+        }
+        a.scratch = scratch.get();
+    }
+    const void* fn = p.in_lds ? reinterpret_cast<const void*>(goal_field_kernel<true, kBound, kCost>)
+                              : reinterpret_cast<const void*>(goal_field_kernel<false, kBound, kCost>);
+    return launch_variant(h, fn, dim3((unsigned)p.grid), dim3(p.threads), p.lds_bytes, s, ka);
 }
 
 // bcp_goal_field (cost = false: extra_of_cost is not looked at) and bcp_goal_field_cost
@@ -74,33 +100,9 @@ static int goal_field_maps(bcp_handle* h, const uint8_t* data, int64_t n_maps, i
     a.out = out;
     a.info = info;
     a.n_maps = n_maps;
-    a.rows = rows;
-    a.cols = cols;
-    a.wpr = (cols + 31) / 32;
     a.shared = shared ? 1 : 0;
     a.n_seeds = n_seeds;
-    a.clearance_d2 = clearance_d2;
-    a.reach = goal_isqrt(clearance_d2);
-    a.max_passes = max_passes > 0 ? max_passes : rows * cols;
-    const int64_t cells = (int64_t)rows * cols;
-    const bool in_lds = goal_lds_bytes(rows, cols, a.wpr, true, kCost) <= kMaxDynamicLds && h->tune.goal_route != 2;
-    // a workgroup's threads: enough cells each to be worth their barriers
-    const unsigned threads = cells >= 128 * 128 ? 1024u : 256u;
-    if (in_lds) {
-        const unsigned grid = (unsigned)std::min<int64_t>(n_maps, 16384);
-        return launch_variant(h, reinterpret_cast<const void*>(goal_field_kernel<true, false, kCost>), dim3(grid), dim3(threads),
-                              goal_lds_bytes(rows, cols, a.wpr, true, kCost), s, ka);
-    }
-    const int64_t mask_words = (int64_t)2 * rows * a.wpr;
-    const int64_t fit = std::max<int64_t>(1, kGoalScratchBytes / (mask_words * (int64_t)sizeof(uint32_t)));
-    const int64_t grid = std::min(std::min(n_maps, kGoalGlobalGrid), fit);
-    if (h->goal_scratch.reserve((size_t)(grid * mask_words)) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(BCP_E_HIP, "%s: cannot allocate %lld bytes of scratch", who, (long long)(grid * mask_words * 4));
-    }
-    a.scratch = h->goal_scratch.get();
-    return launch_variant(h, reinterpret_cast<const void*>(goal_field_kernel<false, false, kCost>), dim3((unsigned)grid),
-                          dim3(threads), goal_lds_bytes(rows, cols, a.wpr, false, kCost), s, ka);
+    return goal_launch(h, ka, rows, cols, clearance_d2, max_passes, n_maps, h->goal_scratch, s, who);
 }
 
 extern "C" int bcp_goal_field(bcp_handle* h, const uint8_t* data, int64_t n_maps, int32_t rows, int32_t cols, int32_t shared,
@@ -124,8 +126,6 @@ extern "C" int bcp_goal_field_cost(bcp_handle* h, const uint8_t* data, int64_t n
 // bcp_goal_field_bound and bcp_refresh_goal_fields: the checks (goal_bound_check_args), the arguments from the binding, the
 // route as bcp_goal_field chooses it, and a grid that never depends on the device-side count.  refresh_form: the list is the
 // ring's `dirty` and the count its tally[0], as bcp_refresh_mini_worlds used them (bcp_worlds_host.h).
-constexpr int64_t kGoalBoundGrid = 1024;
-
 template <bool kCost>
 static int goal_field_bound(bcp_handle* h, const int32_t* entries, const int32_t* count, int64_t n_list, int32_t clearance_d2,
                             int32_t max_passes, const uint16_t* extra_of_cost, uint16_t* field, int32_t* info, void* stream,
@@ -167,7 +167,6 @@ static int goal_field_bound(bcp_handle* h, const int32_t* entries, const int32_t
     if (n_list == 0) return BCP_OK;
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
-    const int32_t rows = h->map.rows, cols = h->map.cols;
 
     GoalArgs& a = ka.g;
     a.data = h->map_data;
@@ -176,13 +175,7 @@ static int goal_field_bound(bcp_handle* h, const int32_t* entries, const int32_t
     a.out = field;
     a.info = info;
     a.n_maps = n_entries;
-    a.rows = rows;
-    a.cols = cols;
-    a.wpr = (cols + 31) / 32;
     a.n_seeds = 1;
-    a.clearance_d2 = clearance_d2;
-    a.reach = goal_isqrt(clearance_d2);
-    a.max_passes = max_passes > 0 ? max_passes : rows * cols;
     GoalBound& b = ka.b;
     b.sel.list = entries;
     b.sel.count = entries ? count : nullptr;
@@ -194,24 +187,7 @@ static int goal_field_bound(bcp_handle* h, const int32_t* entries, const int32_t
     b.oy = h->map.oy;
     b.inv_res = h->map.inv_res;
     b.max_len = h->path.max_len;
-    const int64_t cells = (int64_t)rows * cols;
-    const bool in_lds = goal_lds_bytes(rows, cols, a.wpr, true, kCost) <= kMaxDynamicLds && h->tune.goal_route != 2;
-    const unsigned threads = cells >= 128 * 128 ? 1024u : 256u;
-    if (in_lds) {
-        const unsigned grid = (unsigned)std::min(n_list, kGoalBoundGrid);
-        return launch_variant(h, reinterpret_cast<const void*>(goal_field_kernel<true, true, kCost>), dim3(grid), dim3(threads),
-                              goal_lds_bytes(rows, cols, a.wpr, true, kCost), s, ka);
-    }
-    const int64_t mask_words = (int64_t)2 * rows * a.wpr;
-    const int64_t fit = std::max<int64_t>(1, kGoalScratchBytes / (mask_words * (int64_t)sizeof(uint32_t)));
-    const int64_t grid = std::min(std::min(n_list, kGoalGlobalGrid), fit);
-    if (h->goal_bound_scratch.reserve((size_t)(grid * mask_words)) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(BCP_E_HIP, "%s: cannot allocate %lld bytes of scratch", who, (long long)(grid * mask_words * 4));
-    }
-    a.scratch = h->goal_bound_scratch.get();
-    return launch_variant(h, reinterpret_cast<const void*>(goal_field_kernel<false, true, kCost>), dim3((unsigned)grid),
-                          dim3(threads), goal_lds_bytes(rows, cols, a.wpr, false, kCost), s, ka);
+    return goal_launch(h, ka, h->map.rows, h->map.cols, clearance_d2, max_passes, n_list, h->goal_bound_scratch, s, who);
 }
 
 extern "C" int bcp_goal_field_bound(bcp_handle* h, const int32_t* entries, const int32_t* count, int64_t n_list,

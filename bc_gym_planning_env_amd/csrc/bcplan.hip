@@ -4,7 +4,7 @@
 // collision classification / exact rasteriser -> rollback -> reward provider -> done -> optional reset -> state write-back),
 // bcp_lookahead.h and bcp_mppi.h (the planners), bcp_ego.h (egocentric views), bcp_sample.h and bcp_aisle.h (world samplers),
 // bcp_inflate.h (costmap inflation), bcp_scan.h (range scans; the walk: bcp_scan_march.h, no HIP in it), bcp_goal.h (goal
-// fields; a cell's arithmetic: bcp_goal_cell.h, no HIP in it), bcp_boxes.h (box obstacles; the rule: bcp_boxes_cell.h, no HIP
+// fields; a cell's arithmetic: bcp_goal_cell.h, and the plan of a launch: bcp_goal_plan.h, no HIP in either), bcp_boxes.h (box obstacles; the rule: bcp_boxes_cell.h, no HIP
 // in it; bcp_philox.h and bcp_outline.h hold the generator and the edge walk for host and device).  The host side is split by
 // subsystem:
 //   bcp_host.h         errors, the handle and the owners of its state (device buffers are DevBuf, events and streams Owned:
@@ -18,7 +18,10 @@
 //   bcp_worlds_host.h  mini-world and aisle-world entry points
 //   bcp_inflate_host.h bcp_inflate_costmaps (kernel: bcp_inflate.h)
 //   bcp_scan_host.h    bcp_range_scan / bcp_final_range_scan (kernel: bcp_scan.h)
-//   bcp_goal_host.h    bcp_goal_field / bcp_goal_field_sample / bcp_final_goal_field_sample (kernels: bcp_goal.h)
+//   bcp_goal_host.h    goal fields (kernels: bcp_goal.h): bcp_goal_field / bcp_goal_field_cost, their forms on the binding
+//                      bcp_goal_field_bound / bcp_goal_field_cost_bound / bcp_refresh_goal_fields -- one launch path for the
+//                      five, planned by bcp_goal_plan.h --, bcp_goal_field_sample / bcp_final_goal_field_sample, and
+//                      bcp_goal_route / bcp_goal_route_bound
 //   bcp_boxes_host.h   bcp_scatter_boxes (kernel: bcp_boxes.h)
 //   bcp_seams_host.h   bind / reset / broadcast of the state and the operator seams (their small kernels: bcp_seams.h)
 // This file holds create / destroy / seed / pool / tuning / side stream, bcp_set_costmaps with the two reads of the distance

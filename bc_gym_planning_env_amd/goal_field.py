@@ -196,6 +196,20 @@ def path_seeds(env, which):
     return torch.where(beyond[..., None], torch.full((), -1, dtype=torch.int32, device=dev), rc).contiguous()
 
 
+def call_fields(lib, handle, stream, maps, shared, vr, vc, seeds, d2, max_passes, out, info, table=None):
+    """The one call of bcp_goal_field -- or, with a checked table (checked_table, cost_table), bcp_goal_field_cost -- on
+    device tensors: maps uint8 [., rows, cols], seeds int32 [n, S, 2], vr / vc int32 [n] or None, out uint16 [n, rows, cols],
+    info int32 [n, 2] or None.  The table is read during the call: a launch carries its own copy."""
+    head = (handle, maps.data_ptr(), int(seeds.shape[0]), int(maps.shape[1]), int(maps.shape[2]), int(bool(shared)),
+            vr.data_ptr() if vr is not None else None, vc.data_ptr() if vc is not None else None, seeds.data_ptr(),
+            int(seeds.shape[1]), int(d2), int(max_passes))
+    tail = (out.data_ptr(), info.data_ptr() if info is not None else None, stream)
+    if table is None:
+        _lib.check(lib.bcp_goal_field(*(head + tail)))
+    else:
+        _lib.check(lib.bcp_goal_field_cost(*(head + (table.ctypes.data,) + tail)))
+
+
 def build_bound(env, d2, max_passes):
     """The fields of every entry of the env's own binding, seeds derived on the device (bcp_goal_field_bound); on an
     endless env the GoalField is registered with it, and every refresh() rebuilds the fields of the entries it re-samples."""
@@ -252,13 +266,7 @@ def build(env, clearance=None, seeds="goal", max_passes=0, follow_refresh=False,
     assert shared or n == int(data.shape[0])   # (one path for private maps: its way points on every entry's origin)
     field = torch.empty((n, rows, cols), dtype=torch.uint16, device=env.device)
     info = torch.zeros((n, 2), dtype=torch.int32, device=env.device)
-    head = (env._h, data.data_ptr(), n, rows, cols, int(shared and n > 1), vr.data_ptr() if vr is not None else None,
-            vc.data_ptr() if vc is not None else None, s.data_ptr(), int(s.shape[1]), d2, int(max_passes))
-    tail = (field.data_ptr(), info.data_ptr(), env._stream())
-    if table is None:
-        _lib.check(env._lib.bcp_goal_field(*(head + tail)))
-    else:   # (the table is read during the call: a launch carries its own copy)
-        _lib.check(env._lib.bcp_goal_field_cost(*(head + (table.ctypes.data,) + tail)))
+    call_fields(env._lib, env._h, env._stream(), data, shared and n > 1, vr, vc, s, d2, max_passes, field, info, table)
     return GoalField(env, field, d2, info, keep=(s, data, vr, vc), extra_of_cost=table)
 
 

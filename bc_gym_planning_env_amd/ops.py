@@ -237,16 +237,9 @@ class NativeOps(Handle):
             vr, vc = (self._device_tensor(v, torch.int32, (n,)) for v in valid)
         out = torch.empty((n,) + tuple(maps.shape[1:]), dtype=torch.uint16, device=self.device)
         info = torch.zeros((n, 2), dtype=torch.int32, device=self.device) if want_info else None
-        head = (self._h, maps.data_ptr(), n, maps.shape[1], maps.shape[2], int(shared),
-                vr.data_ptr() if vr is not None else None, vc.data_ptr() if vc is not None else None, s3.data_ptr(), s3.shape[1],
-                int(clearance_d2), int(max_passes))
-        tail = (out.data_ptr(), info.data_ptr() if info is not None else None, self._stream())
-        if extra_of_cost is None:
-            _lib.check(self._lib.bcp_goal_field(*(head + tail)))
-        else:
-            from .goal_field import checked_table
-            table = checked_table(extra_of_cost)
-            _lib.check(self._lib.bcp_goal_field_cost(*(head + (table.ctypes.data,) + tail)))
+        from .goal_field import call_fields, checked_table
+        table = checked_table(extra_of_cost) if extra_of_cost is not None else None
+        call_fields(self._lib, self._h, self._stream(), maps, shared, vr, vc, s3, clearance_d2, max_passes, out, info, table)
         self._alive["goal_field"] = (maps, s3, vr, vc)
         out = out[0] if d.dim() == 2 and s.dim() == 2 else out
         return (out, info) if want_info else out

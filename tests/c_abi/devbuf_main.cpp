@@ -7,6 +7,7 @@
 #include <type_traits>
 
 #include "bcp_devbuf.h"
+#include "host_io.h"
 
 static bool g_fail_next = false;
 static int g_live = 0, g_mallocs = 0, g_frees = 0;
@@ -36,14 +37,6 @@ extern "C" hipError_t hipFree(void* ptr)
     return hipSuccess;
 }
 
-static int g_failed = 0;
-#define CHECK(cond)                                                      \
-    do {                                                                 \
-        if (!(cond)) {                                                   \
-            fprintf(stderr, "line %d: %s does not hold\n", __LINE__, #cond); \
-            ++g_failed;                                                  \
-        }                                                                \
-    } while (0)
 
 struct Wide {
     double d[5];

@@ -6,17 +6,10 @@
 #include <initializer_list>
 
 #include "bcp_ego_route.h"
+#include "host_io.h"
 
 using namespace bcp;
 
-static int g_failed = 0;
-#define CHECK(cond)                                                      \
-    do {                                                                 \
-        if (!(cond)) {                                                   \
-            fprintf(stderr, "line %d: %s does not hold\n", __LINE__, #cond); \
-            ++g_failed;                                                  \
-        }                                                                \
-    } while (0)
 
 // what the router is told of the cell lists: they exist and describe the maps; the largest count; the limit in force
 struct EgoLists {

@@ -14,18 +14,10 @@
 #include <vector>
 
 #include "bcp_field_plan.h"
+#include "host_io.h"
 
 using namespace bcp;
 
-static int g_failed = 0;
-#define CHECK(cond)                                                                          \
-    do {                                                                                     \
-        if (!(cond)) {                                                                       \
-            fprintf(stderr, "line %d (%s): %s does not hold\n", __LINE__, g_where, #cond); \
-            ++g_failed;                                                                      \
-        }                                                                                    \
-    } while (0)
-static char g_where[128] = "";
 
 // ---- the zoo ---------------------------------------------------------------------------------------------------
 struct Footprint {

@@ -10,7 +10,7 @@
 //       uint8 data[rows * cols]
 //       int32 seeds[n_seeds][2]              (row, col)
 //       uint16 extra_of_cost[256]
-//     the kernel's phases in sequence; phase 4 as in-place sweeps of goal_relax_cell_cost with the extra of the relaxed
+//     the kernel's phases in sequence (host_goal_sweep, goal_sweep.h); phase 4 as in-place sweeps of goal_relax_cell_cost with the extra of the relaxed
 //     cell's own byte, looked up for open cells only.  Writes uint16 plane[rows * cols] to OUT, prints
 //     "sweeps S gave_up G reached N lookups L" (L: table lookups made)
 //   goal_cost_main walk FILE         FILE (binary): int32 rows, cols, valid_rows, valid_cols, n, 0, 0, 0;
@@ -28,41 +28,10 @@
 #include <vector>
 
 #include "bcp_goal_cell.h"
+#include "goal_sweep.h"
+#include "host_io.h"
 
 using namespace bcp;
-
-struct HostPlane {
-    const std::vector<uint16_t>* cells;
-    int32_t rows, cols;
-    uint16_t operator()(int32_t r, int32_t c) const
-    {
-        if (r < 0 || r >= rows || c < 0 || c >= cols) abort();   // (the index alone could wrap into the plane)
-        return cells->at((size_t)r * cols + c);
-    }
-};
-
-// numpy's (z + pi) % (2 pi) - pi: the remainder takes the divisor's sign
-struct HostNormalizeAngle {
-    double operator()(double z) const
-    {
-        const double pi = 3.14159265358979323846, b = 2.0 * pi;
-        double r = std::fmod(z + pi, b);
-        if (r != 0.0) {
-            if (r < 0.0) r += b;
-        } else {
-            r = 0.0;
-        }
-        return r - pi;
-    }
-};
-
-template <typename T>
-static bool read_n(FILE* f, std::vector<T>& v, size_t n)
-{
-    v.resize(n);
-    v.shrink_to_fit();
-    return n == 0 || fread(v.data(), sizeof(T), n, f) == n;
-}
 
 static int run_relax(const char* path, const char* out_path)
 {
@@ -78,73 +47,17 @@ static int run_relax(const char* path, const char* out_path)
     if (!ok) return 3;
     int32_t bad = 0;
     if (goal_cost_check_args(table.data(), bad) != kGoalCostOk) return 6;
-    const int32_t rows = head[0], cols = head[1], wpr = (cols + 31) / 32, n_seeds = head[4], clearance_d2 = head[5];
+    const int32_t rows = head[0], cols = head[1], n_seeds = head[4], clearance_d2 = head[5];
     const int32_t vr = head[2] < 0 ? 0 : (head[2] > rows ? rows : head[2]), vc = head[3] < 0 ? 0 : (head[3] > cols ? cols : head[3]);
     const int32_t max_passes = head[6] > 0 ? head[6] : rows * cols;
-    const int32_t reach = goal_isqrt(clearance_d2);
-    std::vector<uint32_t> lethal((size_t)rows * wpr, 0u), closed((size_t)rows * wpr, 0u);
-    for (int32_t r = 0; r < vr; ++r)
-        for (int32_t c = 0; c < vc; ++c)
-            if (data[(size_t)r * cols + c] == 254) lethal.at((size_t)r * wpr + (c >> 5)) |= 1u << (c & 31);
-    for (int32_t r = 0; r < rows; ++r) {
-        for (int32_t w = 0; w < wpr; ++w) {
-            const int32_t first = 32 * w;
-            const uint32_t inside = r < vr && vc > first ? (vc - first >= 32 ? ~0u : (1u << (vc - first)) - 1u) : 0u;
-            uint32_t acc = 0u;
-            if (inside) {
-                const int32_t lo = r - reach > 0 ? r - reach : 0, hi = r + reach < vr - 1 ? r + reach : vr - 1;
-                for (int32_t rr = lo; rr <= hi; ++rr) {
-                    const int32_t hw = goal_half_width(clearance_d2, rr > r ? rr - r : r - rr), kw = (hw + 31) >> 5;
-                    const int32_t k0 = w - kw > 0 ? w - kw : 0, k1 = w + kw < wpr - 1 ? w + kw : wpr - 1;
-                    for (int32_t k = k0; k <= k1; ++k) acc |= goal_widen_word(lethal.at((size_t)rr * wpr + k), 32 * (k - w), hw);
-                }
-            }
-            closed.at((size_t)r * wpr + w) = (acc & inside) | ~inside;
-        }
-    }
-    std::vector<uint16_t> plane((size_t)rows * cols, (uint16_t)kGoalNone);
-    for (int32_t s = 0; s < n_seeds; ++s) {
-        const int32_t sr = seeds[(size_t)2 * s], sc = seeds[(size_t)2 * s + 1];
-        if (sr >= 0 && sr < vr && sc >= 0 && sc < vc) {
-            plane.at((size_t)sr * cols + sc) = 0;
-            closed.at((size_t)sr * wpr + (sc >> 5)) &= ~(1u << (sc & 31));
-        }
-    }
-    const HostPlane get = {&plane, rows, cols};
-    int32_t sweeps = 0, gave_up = 0;
-    long long lookups = 0;
-    for (;;) {
-        if (sweeps == max_passes) {
-            gave_up = 1;
-            break;
-        }
-        ++sweeps;
-        bool lowered = false;
-        for (int32_t r = 0; r < vr; ++r) {
-            for (int32_t c = 0; c < vc; ++c) {
-                if ((closed.at((size_t)r * wpr + (c >> 5)) >> (c & 31)) & 1u) continue;
-                const int32_t own = plane[(size_t)r * cols + c];
-                if (own == 0) continue;
-                const int32_t extra = table.at(data.at((size_t)r * cols + c));
-                ++lookups;
-                const int32_t now = goal_relax_cell_cost(get, vr, vc, r, c, own, extra);
-                if (now > own || now < 0 || now > kGoalNone) return 4;   // (values only fall)
-                if (now != own) {
-                    plane[(size_t)r * cols + c] = (uint16_t)now;
-                    lowered = true;
-                }
-            }
-        }
-        if (!lowered) break;
-    }
-    long long reached = 0;
-    for (uint16_t v : plane) reached += v != (uint16_t)kGoalNone;
+    HostSweep sw;
+    if (!host_goal_sweep(rows, cols, vr, vc, data, seeds, n_seeds, clearance_d2, max_passes, &table, sw)) return 4;
     FILE* o = fopen(out_path, "wb");
     if (!o) return 5;
-    const bool wrote = fwrite(plane.data(), sizeof(uint16_t), plane.size(), o) == plane.size();
+    const bool wrote = fwrite(sw.plane.data(), sizeof(uint16_t), sw.plane.size(), o) == sw.plane.size();
     fclose(o);
     if (!wrote) return 5;
-    printf("sweeps %d gave_up %d reached %lld lookups %lld\n", sweeps, gave_up, reached, lookups);
+    printf("sweeps %d gave_up %d reached %lld lookups %lld\n", sw.sweeps, sw.gave_up, sw.reached, sw.lookups);
     return 0;
 }
 
@@ -160,7 +73,7 @@ static int run_walk(const char* path)
     if (!ok) return 3;
     const int32_t rows = head[0], cols = head[1];
     const int32_t vr = head[2] < 0 ? 0 : (head[2] > rows ? rows : head[2]), vc = head[3] < 0 ? 0 : (head[3] > cols ? cols : head[3]);
-    const HostPlane get = {&field, rows, cols};
+    const HostPlane get = {&field, cols, rows, cols};
     for (int32_t i = 0; i < head[4]; ++i) printf("%d\n", goal_walk_step(get, vr, vc, cells[(size_t)2 * i], cells[(size_t)2 * i + 1]));
     return 0;
 }
@@ -177,7 +90,7 @@ static int run_route(const char* path)
     fclose(f);
     if (!ok) return 3;
     const int32_t rows = head[0], cols = head[1], stride = head[2], max_len = head[3];
-    const HostPlane get = {&field, rows, cols};
+    const HostPlane get = {&field, cols, rows, cols};
     std::unique_ptr<double[]> wp(new double[(size_t)max_len * 3]);
     int32_t len = -1;
     double init[2] = {0.0, 0.0};

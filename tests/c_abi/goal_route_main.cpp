@@ -20,40 +20,9 @@
 #include <vector>
 
 #include "bcp_goal_cell.h"
+#include "host_io.h"
 
 using namespace bcp;
-
-struct HostPlane {
-    const std::vector<uint16_t>* cells;
-    int32_t rows, cols;
-    uint16_t operator()(int32_t r, int32_t c) const
-    {
-        if (r < 0 || r >= rows || c < 0 || c >= cols) abort();   // (the index alone could wrap into the plane)
-        return cells->at((size_t)r * cols + c);
-    }
-};
-
-// numpy's (z + pi) % (2 pi) - pi: the remainder takes the divisor's sign
-struct HostNormalizeAngle {
-    double operator()(double z) const
-    {
-        const double pi = 3.14159265358979323846, b = 2.0 * pi;
-        double r = std::fmod(z + pi, b);
-        if (r != 0.0) {
-            if (r < 0.0) r += b;
-        } else {
-            r = 0.0;
-        }
-        return r - pi;
-    }
-};
-
-template <typename T>
-static bool read_n(FILE* f, std::vector<T>& v, size_t n)
-{
-    v.resize(n);
-    return n == 0 || fread(v.data(), sizeof(T), n, f) == n;
-}
 
 static int run_route(const char* path, const char* out_path)
 {
@@ -73,7 +42,7 @@ static int run_route(const char* path, const char* out_path)
     const double ox = nums[0], oy = nums[1], resolution = nums[2], sp = nums[3], ap = nums[4];
     const double inv_res = 1.0 / resolution;   // (as bcp_set_costmaps has it)
     const double lim = 1.7976931348623157e308;
-    const HostPlane get = {&field, rows, cols};
+    const HostPlane get = {&field, cols, rows, cols};
     std::vector<double> all_paths, all_init;
     std::vector<int32_t> lens, status;
     for (int32_t i = 0; i < n_rows; ++i) {

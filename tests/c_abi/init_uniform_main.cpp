@@ -12,14 +12,7 @@
 #include <memory>
 
 #include "bcp_init_uniform.h"
-
-template <typename T>
-static std::unique_ptr<T[]> read_block(FILE* f, int64_t n, bool& ok)
-{
-    std::unique_ptr<T[]> p(new T[(size_t)n]);
-    if (fread(p.get(), sizeof(T), (size_t)n, f) != (size_t)n) ok = false;
-    return p;
-}
+#include "host_io.h"
 
 static int run(const char* path)
 {
@@ -34,9 +27,9 @@ static int run(const char* path)
     const bool tri = head[0] != 0;
     bool ok = true;
     std::unique_ptr<double[]> f64[8];
-    for (int k = 0; k < 8; ++k) f64[k] = read_block<double>(f, n, ok);
-    std::unique_ptr<int32_t[]> target = read_block<int32_t>(f, n, ok), iter = read_block<int32_t>(f, n, ok);
-    std::unique_ptr<uint8_t[]> collided = read_block<uint8_t>(f, n, ok);
+    for (int k = 0; k < 8; ++k) f64[k] = read_block<double>(f, (size_t)n, ok);
+    std::unique_ptr<int32_t[]> target = read_block<int32_t>(f, (size_t)n, ok), iter = read_block<int32_t>(f, (size_t)n, ok);
+    std::unique_ptr<uint8_t[]> collided = read_block<uint8_t>(f, (size_t)n, ok);
     fclose(f);
     if (!ok) return 3;
     bcp::InitHostArrays a = {};

@@ -16,25 +16,9 @@
 #include <vector>
 
 #include "bcp_goal_cell.h"
+#include "host_io.h"
 
 using namespace bcp;
-
-struct HostPlane {
-    const std::vector<uint16_t>* cells;
-    int32_t rows, cols, valid_rows, valid_cols;
-    uint16_t operator()(int32_t r, int32_t c) const
-    {
-        if (r < 0 || r >= valid_rows || c < 0 || c >= valid_cols) abort();   // (the helper reads inside the valid shape only)
-        return cells->at((size_t)r * cols + c);
-    }
-};
-
-template <typename T>
-static bool read_n(FILE* f, std::vector<T>& v, size_t n)
-{
-    v.resize(n);
-    return n == 0 || fread(v.data(), sizeof(T), n, f) == n;
-}
 
 int main(int argc, char** argv)
 {
@@ -54,7 +38,7 @@ int main(int argc, char** argv)
     const double ox = nums[0], oy = nums[1], resolution = nums[2];
     const double inv_res = 1.0 / resolution;   // (as bcp_set_costmaps has it)
     const double lim = 1.7976931348623157e308;
-    const HostPlane get = {&field, rows, cols, vr, vc};
+    const HostPlane get = {&field, cols, vr, vc};   // (the helper reads inside the valid shape only)
     for (int32_t i = 0; i < n_rows; ++i) {
         const double x = poses[(size_t)2 * i], y = poses[(size_t)2 * i + 1];
         const bool finite = x >= -lim && x <= lim && y >= -lim && y <= lim;

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "bcp_scan_march.h"
+#include "host_io.h"
 
 using namespace bcp;
 
@@ -25,13 +26,6 @@ struct HostWords {
     const std::vector<uint32_t>* words;
     uint32_t operator()(int32_t k) const { return words->at((size_t)k); }   // (a walk that left the mask throws)
 };
-
-template <typename T>
-static bool read_n(FILE* f, std::vector<T>& v, size_t n)
-{
-    v.resize(n);
-    return n == 0 || fread(v.data(), sizeof(T), n, f) == n;
-}
 
 static int run_scan(const char* path)
 {

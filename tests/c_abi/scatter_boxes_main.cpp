@@ -11,6 +11,7 @@
 #include <memory>
 
 #include "bcp_boxes_cell.h"
+#include "host_io.h"
 
 using namespace bcp;
 
@@ -18,14 +19,6 @@ static void die(const char* what)
 {
     fprintf(stderr, "scatter_boxes_main: %s\n", what);
     exit(2);
-}
-
-template <typename T>
-static std::unique_ptr<T[]> read_block(FILE* f, size_t n)
-{
-    std::unique_ptr<T[]> p(new T[n]);
-    if (n && fread(p.get(), sizeof(T), n, f) != n) die("short read");
-    return p;
 }
 
 struct HostFill {
@@ -64,14 +57,16 @@ static int run_scatter(const char* in, const char* out)
                            R.h_hi, true, true, true, true) != kScatterOk)
         die("the case is one the library refuses");
     const double inv_res = 1.0 / nums[0];
-    auto valid = read_block<int32_t>(f, (size_t)n * 2);
-    auto origins = read_block<double>(f, (size_t)n * 2);
-    auto frame = read_block<double>(f, (size_t)n * 6);
-    auto keep = read_block<int32_t>(f, (size_t)n * n_keep * 3);
-    auto yaw_cs = read_block<double>(f, (size_t)R.n_yaws * 2);
+    bool ok = true;
+    auto valid = read_block<int32_t>(f, (size_t)n * 2, ok);
+    auto origins = read_block<double>(f, (size_t)n * 2, ok);
+    auto frame = read_block<double>(f, (size_t)n * 6, ok);
+    auto keep = read_block<int32_t>(f, (size_t)n * n_keep * 3, ok);
+    auto yaw_cs = read_block<double>(f, (size_t)R.n_yaws * 2, ok);
     const size_t cells = (size_t)rows * cols;
-    auto data = read_block<uint8_t>(f, (size_t)n * cells);
+    auto data = read_block<uint8_t>(f, (size_t)n * cells, ok);
     fclose(f);
+    if (!ok) die("short read");
     std::unique_ptr<int32_t[]> boxes(new int32_t[(size_t)n * R.n_boxes * kBoxWords]);
     std::unique_ptr<int32_t[]> counts(new int32_t[(size_t)n]);
     for (int32_t i = 0; i < n; ++i) {

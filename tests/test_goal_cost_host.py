@@ -5,12 +5,11 @@ calls the very functions goal_field_kernel<.., kCost> calls; it reads every plan
 the map and the table in heap blocks of exactly their size.  The property the feature is for -- routes that keep to the
 middle of free space -- is tested on the reference alone."""
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import host_program
 import goal_cost_ref as CR
 import goal_field_ref as GR
 import goal_route_ref as RR
@@ -20,35 +19,13 @@ NEW_SYMBOLS = ["bcp_goal_field_cost", "bcp_goal_field_cost_bound"]
 ZERO = np.zeros(256, dtype=np.int64)
 
 
-def _compiler():
-    for cand in ("g++", "/opt/rocm/llvm/bin/clang++", "clang++"):
-        path = shutil.which(cand)
-        if path:
-            return path
-    raise AssertionError("no host C++ compiler found (g++ or ROCm's clang++)")
-
-
 @pytest.fixture(scope="module")
 def program(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("goal_cost") / "goal_cost_main")
-    cxx = _compiler()
-    static_runtime = ["-static-libasan", "-static-libubsan"] if cxx.endswith("g++") else []   # (clang's is static already)
-    cmd = [cxx] + static_runtime + ["-std=c++17", "-Wall", "-Werror", "-g", "-O1", "-ffp-contract=off",
-                                    "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                                    "-I" + os.path.join(ROOT, "bc_gym_planning_env_amd", "csrc"),
-                                    os.path.join(ROOT, "tests", "c_abi", "goal_cost_main.cpp"), "-o", exe]
-    built = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=300)
-    assert built.returncode == 0, built.stdout
-    return exe
+    return host_program.build(tmp_path_factory, "goal_cost_main.cpp")
 
 
 def _run(exe, *args):
-    ran = subprocess.run([exe] + list(args), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=120)
-    assert ran.returncode == 0, ran.stdout[-4000:]
-    assert "goal cost ok" in ran.stdout
-    for word in ("Sanitizer", "runtime error"):
-        assert word not in ran.stdout, ran.stdout[-4000:]
-    return ran.stdout.split("\n")
+    return host_program.run(exe, args, "goal cost ok")
 
 
 def _relax(exe, tmp_path, data, seeds, clearance_d2, table, valid=None, max_passes=0):

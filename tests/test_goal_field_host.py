@@ -4,12 +4,11 @@ restated in numpy / heapq (tests/goal_field_ref.py).  tests/c_abi/goal_field_mai
 no HIP in it -- and calls the very functions goal_field_kernel and goal_sample_kernel call; the program reads every plane
 through a bounds-checked accessor, so a relaxation or a walk that left the map fails here, without a GPU."""
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import host_program
 import goal_field_ref as GR
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -18,35 +17,13 @@ WORLDS = (0, 5, 17)
 CLEARANCES = (0, 151)
 
 
-def _compiler():
-    for cand in ("g++", "/opt/rocm/llvm/bin/clang++", "clang++"):
-        path = shutil.which(cand)
-        if path:
-            return path
-    raise AssertionError("no host C++ compiler found (g++ or ROCm's clang++)")
-
-
 @pytest.fixture(scope="module")
 def program(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("goal_field") / "goal_field_main")
-    cxx = _compiler()
-    static_runtime = ["-static-libasan", "-static-libubsan"] if cxx.endswith("g++") else []   # (clang's is static already)
-    cmd = [cxx] + static_runtime + ["-std=c++17", "-Wall", "-Werror", "-g", "-O1", "-ffp-contract=off",
-                                    "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                                    "-I" + os.path.join(ROOT, "bc_gym_planning_env_amd", "csrc"),
-                                    os.path.join(ROOT, "tests", "c_abi", "goal_field_main.cpp"), "-o", exe]
-    built = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=300)
-    assert built.returncode == 0, built.stdout
-    return exe
+    return host_program.build(tmp_path_factory, "goal_field_main.cpp")
 
 
 def _run(exe, *args):
-    ran = subprocess.run([exe] + list(args), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=120)
-    assert ran.returncode == 0, ran.stdout[-4000:]
-    assert "goal field ok" in ran.stdout
-    for word in ("Sanitizer", "runtime error"):
-        assert word not in ran.stdout, ran.stdout[-4000:]
-    return ran.stdout.split("\n")
+    return host_program.run(exe, args, "goal field ok")
 
 
 def _relax(exe, tmp_path, data, seeds, clearance_d2, valid=None, max_passes=0):

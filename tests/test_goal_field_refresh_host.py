@@ -5,47 +5,24 @@ library and the binding.  tests/c_abi/goal_seed_main.cpp includes the header alo
 form of goal_field_kernel and the entry points call; a conversion of a huge coordinate to an integer would be UBSan's."""
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import host_program
 import goal_field_refresh_ref as RR
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ["bcp_goal_field_bound", "bcp_refresh_goal_fields"]
 
 
-def _compiler():
-    for cand in ("g++", "/opt/rocm/llvm/bin/clang++", "clang++"):
-        path = shutil.which(cand)
-        if path:
-            return path
-    raise AssertionError("no host C++ compiler found (g++ or ROCm's clang++)")
-
-
 @pytest.fixture(scope="module")
 def program(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("goal_seed") / "goal_seed_main")
-    cxx = _compiler()
-    static_runtime = ["-static-libasan", "-static-libubsan"] if cxx.endswith("g++") else []   # (clang's is static already)
-    cmd = [cxx] + static_runtime + ["-std=c++17", "-Wall", "-Werror", "-g", "-O1", "-ffp-contract=off",
-                                    "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                                    "-I" + os.path.join(ROOT, "bc_gym_planning_env_amd", "csrc"),
-                                    os.path.join(ROOT, "tests", "c_abi", "goal_seed_main.cpp"), "-o", exe]
-    built = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=300)
-    assert built.returncode == 0, built.stdout
-    return exe
+    return host_program.build(tmp_path_factory, "goal_seed_main.cpp")
 
 
 def _run(exe, *args):
-    ran = subprocess.run([exe] + list(args), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=120)
-    assert ran.returncode == 0, ran.stdout[-4000:]
-    assert "goal seed ok" in ran.stdout
-    for word in ("Sanitizer", "runtime error"):
-        assert word not in ran.stdout, ran.stdout[-4000:]
-    return ran.stdout.split("\n")
+    return host_program.run(exe, args, "goal seed ok")
 
 
 def _word(v):

@@ -8,12 +8,11 @@ Compared bit for bit: x, y, lens, status, target_idx and the zero tails; within 
 headings and min_spat_dist_so_far -- atan2 and hypot are the host library's here, numpy's there.  Every case is checked to
 lie away from the knife edges of find_last_reached in the reference alone (goal_route_ref.away_from_knife_edges)."""
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import host_program
 import goal_field_ref as GR
 import goal_route_ref as RR
 
@@ -24,35 +23,13 @@ CLEARANCES = (151, 0)
 SP, AP = RR.REWARD_PARAMS.spatial_precision, RR.REWARD_PARAMS.angular_precision
 
 
-def _compiler():
-    for cand in ("g++", "/opt/rocm/llvm/bin/clang++", "clang++"):
-        path = shutil.which(cand)
-        if path:
-            return path
-    raise AssertionError("no host C++ compiler found (g++ or ROCm's clang++)")
-
-
 @pytest.fixture(scope="module")
 def program(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("goal_route") / "goal_route_main")
-    cxx = _compiler()
-    static_runtime = ["-static-libasan", "-static-libubsan"] if cxx.endswith("g++") else []   # (clang's is static already)
-    cmd = [cxx] + static_runtime + ["-std=c++17", "-Wall", "-Werror", "-g", "-O1", "-ffp-contract=off",
-                                    "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                                    "-I" + os.path.join(ROOT, "bc_gym_planning_env_amd", "csrc"),
-                                    os.path.join(ROOT, "tests", "c_abi", "goal_route_main.cpp"), "-o", exe]
-    built = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=300)
-    assert built.returncode == 0, built.stdout
-    return exe
+    return host_program.build(tmp_path_factory, "goal_route_main.cpp")
 
 
 def _run(exe, *args):
-    ran = subprocess.run([exe] + list(args), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=120)
-    assert ran.returncode == 0, ran.stdout[-4000:]
-    assert "goal route ok" in ran.stdout
-    for word in ("Sanitizer", "runtime error"):
-        assert word not in ran.stdout, ran.stdout[-4000:]
-    return ran.stdout.split("\n")
+    return host_program.run(exe, args, "goal route ok")
 
 
 def _route(exe, tmp_path, field, valid, origin, resolution, starts, goals, stride, max_len, pure_pursuit=False, knife=True):

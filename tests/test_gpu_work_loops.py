@@ -63,8 +63,8 @@ def _header(name):
 
 
 @pytest.mark.parametrize("name,pattern,value", [
-    ("bcp_goal_host.h", r"std::min<int64_t>\(n_maps,\s*(\d+)\)", GOAL_LDS_GRID),
-    ("bcp_goal_host.h", r"kGoalGlobalGrid\s*=\s*(\d+)\s*;", GOAL_GLOBAL_GRID),
+    ("bcp_goal_plan.h", r"kGoalLdsGrid\s*=\s*(\d+)\s*;", GOAL_LDS_GRID),
+    ("bcp_goal_plan.h", r"kGoalGlobalGrid\s*=\s*(\d+)\s*;", GOAL_GLOBAL_GRID),
     ("bcp_inflate_host.h", r"std::min<int64_t>\(n_maps,\s*(\d+)\)", INFLATE_LDS_GRID),
     ("bcp_inflate_host.h", r"kInflateGlobalGrid\s*=\s*(\d+)\s*;", INFLATE_GLOBAL_GRID),
     ("bcp_scan_host.h", r"std::min<int64_t>\(chunks,\s*staged\s*\?\s*(\d+)\s*:", SCAN_STAGED_GRID),

@@ -6,12 +6,12 @@ bit, the first differing env and, within it, the first differing field (in bcp_s
 entry 0 packed as StepStatic::init_uniform (eight float64, four int32: 80 bytes).  And the C ABI: the two new symbols are
 declared, exported and typed, and the version did not move."""
 import os
-import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
+
+import host_program
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIELDS = ("x", "y", "angle", "v", "w", "steering_motor_command", "wheel_angle", "min_spat_dist_so_far", "target_idx",
@@ -19,26 +19,9 @@ FIELDS = ("x", "y", "angle", "v", "w", "steering_motor_command", "wheel_angle", 
 STEER, WHEEL = 5, 6
 
 
-def _compiler():
-    for cand in ("g++", "/opt/rocm/llvm/bin/clang++", "clang++"):
-        path = shutil.which(cand)
-        if path:
-            return path
-    raise AssertionError("no host C++ compiler found (g++ or ROCm's clang++)")
-
-
 @pytest.fixture(scope="module")
 def program(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("init_uniform") / "init_uniform_main")
-    cxx = _compiler()
-    static_runtime = ["-static-libasan", "-static-libubsan"] if cxx.endswith("g++") else []   # (clang's is static already)
-    cmd = [cxx] + static_runtime + ["-std=c++17", "-Wall", "-Werror", "-g", "-O1", "-ffp-contract=off",
-                                    "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                                    "-I" + os.path.join(ROOT, "bc_gym_planning_env_amd", "csrc"),
-                                    os.path.join(ROOT, "tests", "c_abi", "init_uniform_main.cpp"), "-o", exe]
-    built = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=300)
-    assert built.returncode == 0, built.stdout
-    return exe
+    return host_program.build(tmp_path_factory, "init_uniform_main.cpp")
 
 
 def uniform(n, seed=0):
@@ -79,11 +62,7 @@ def run_cases(exe, tmp_path, cases):
                 assert a.dtype == dt and a.shape == (n,)
                 f.write(np.ascontiguousarray(a).tobytes())
         paths.append(p)
-    ran = subprocess.run([exe] + paths, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=120)
-    assert ran.returncode == 0, ran.stdout[-4000:]
-    for word in ("Sanitizer", "runtime error"):
-        assert word not in ran.stdout, ran.stdout[-4000:]
-    lines = ran.stdout.split("\n")
+    lines = host_program.run(exe, paths)
     assert lines[len(cases)] == "init uniform ok"
     for k, (arrays, tri) in enumerate(cases):
         (env, field), raw = expected(arrays, tri)

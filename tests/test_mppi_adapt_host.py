@@ -4,13 +4,13 @@ stand-alone program under AddressSanitizer and UBSan (csrc/bcp_mppi_widths.h, no
 CPU oracle alone -- that in the scenarios the GPU tests run the widths move without sitting on their clamps, and that a
 greedy rate does put them there."""
 import os
-import shutil
 import subprocess
 import tempfile
 
 import numpy as np
 import pytest
 
+import host_program
 import lookahead_ref as LR
 import mppi_adapt_ref as AR
 import mppi_ref as MR
@@ -123,31 +123,10 @@ def test_entry_values_go_through_the_clamp():
 
 
 # ---------------------------------------------------------------------------------------------- the checks, sanitized
-def _compiler():
-    for cand in ("g++", "/opt/rocm/llvm/bin/clang++", "clang++"):
-        path = shutil.which(cand)
-        if path:
-            return path
-    raise AssertionError("no host C++ compiler found (g++ or ROCm's clang++)")
-
-
-def test_checks_of_the_struct_under_sanitizers(tmp_path):
+def test_checks_of_the_struct_under_sanitizers(tmp_path_factory):
     """tests/c_abi/mppi_adapt_main.cpp, compiled with -fsanitize=address,undefined and run as its own process: every refusal
     of mppi_adapt_check_args and their order, NaN and +-inf in every field, the clamp and the move"""
-    exe = str(tmp_path / "mppi_adapt_main")
-    cxx = _compiler()
-    static_runtime = ["-static-libasan", "-static-libubsan"] if cxx.endswith("g++") else []   # (clang's is static already)
-    cmd = [cxx] + static_runtime + ["-std=c++17", "-Wall", "-Werror", "-g", "-O1", "-ffp-contract=off",
-                                    "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                                    "-I" + os.path.join(ROOT, "bc_gym_planning_env_amd", "csrc"),
-                                    os.path.join(ROOT, "tests", "c_abi", "mppi_adapt_main.cpp"), "-o", exe]
-    built = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=300)
-    assert built.returncode == 0, built.stdout
-    ran = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=120)
-    assert ran.returncode == 0, ran.stdout[-4000:]
-    assert "mppi adapt ok" in ran.stdout
-    for word in ("Sanitizer", "runtime error"):
-        assert word not in ran.stdout, ran.stdout[-4000:]
+    host_program.run(host_program.build(tmp_path_factory, "mppi_adapt_main.cpp"), (), "mppi adapt ok")
 
 
 # ---------------------------------------------------------------------------------------------- non-vacuity

@@ -3,13 +3,13 @@ score rule on hand-made tables, the one helper that kernel and sampler share (cs
 stand-alone program under AddressSanitizer and UBSan against the numpy restatement, and -- on the restatement and the CPU
 oracle alone -- that a terminal term changes what the refinement does in the scenario the GPU tests run."""
 import os
-import shutil
 import subprocess
 import tempfile
 
 import numpy as np
 import pytest
 
+import host_program
 import goal_field_ref as GR
 import lookahead_ref as LR
 import mppi_field_ref as FR
@@ -98,26 +98,9 @@ def test_a_collided_candidate_carries_both_terms():
 
 
 # ---------------------------------------------------------------------------------------------- the shared helper
-def _compiler():
-    for cand in ("g++", "/opt/rocm/llvm/bin/clang++", "clang++"):
-        path = shutil.which(cand)
-        if path:
-            return path
-    raise AssertionError("no host C++ compiler found (g++ or ROCm's clang++)")
-
-
 @pytest.fixture(scope="module")
 def program(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("mppi_field") / "mppi_field_main")
-    cxx = _compiler()
-    static_runtime = ["-static-libasan", "-static-libubsan"] if cxx.endswith("g++") else []   # (clang's is static already)
-    cmd = [cxx] + static_runtime + ["-std=c++17", "-Wall", "-Werror", "-g", "-O1", "-ffp-contract=off",
-                                    "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                                    "-I" + os.path.join(ROOT, "bc_gym_planning_env_amd", "csrc"),
-                                    os.path.join(ROOT, "tests", "c_abi", "mppi_field_main.cpp"), "-o", exe]
-    built = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=300)
-    assert built.returncode == 0, built.stdout
-    return exe
+    return host_program.build(tmp_path_factory, "mppi_field_main.cpp")
 
 
 def _poses(rng, n, field, valid, origin, res):
@@ -161,12 +144,7 @@ def test_value_at_a_pose_bit_for_bit_under_sanitizers(program, tmp_path):
         f.write(np.array([origin[0], origin[1], res], dtype=np.float64).tobytes())
         f.write(field.tobytes())
         f.write(np.ascontiguousarray(xy).tobytes())
-    ran = subprocess.run([program, path], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=120)
-    assert ran.returncode == 0, ran.stdout[-4000:]
-    assert "mppi field ok" in ran.stdout
-    for word in ("Sanitizer", "runtime error"):
-        assert word not in ran.stdout, ran.stdout[-4000:]
-    lines = [ln.split() for ln in ran.stdout.split("\n")[:len(xy)]]
+    lines = [ln.split() for ln in host_program.run(program, [path], "mppi field ok")[:len(xy)]]
     got_v = np.array([int(ln[0]) for ln in lines], dtype=np.int32)
     got_d = np.array([int(ln[1], 16) for ln in lines], dtype=np.uint64).view(np.float64)
     want_v = FR.values(field[None], [valid], [origin], res, np.zeros(len(xy), np.int64), xy)

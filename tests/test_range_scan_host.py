@@ -4,12 +4,11 @@ as a stand-alone host program under AddressSanitizer and UBSan, bit for bit agai
 the very functions range_scan_kernel calls; the program reads the mask through a bounds-checked accessor, so a walk that
 left the map fails here, without a GPU.  Known answers are checked against both sides."""
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import host_program
 import range_scan_ref as RR
 from util import GOLDEN
 
@@ -17,35 +16,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ["bcp_range_scan", "bcp_final_range_scan"]
 
 
-def _compiler():
-    for cand in ("g++", "/opt/rocm/llvm/bin/clang++", "clang++"):
-        path = shutil.which(cand)
-        if path:
-            return path
-    raise AssertionError("no host C++ compiler found (g++ or ROCm's clang++)")
-
-
 @pytest.fixture(scope="module")
 def program(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("range_scan") / "range_scan_main")
-    cxx = _compiler()
-    static_runtime = ["-static-libasan", "-static-libubsan"] if cxx.endswith("g++") else []   # (clang's is static already)
-    cmd = [cxx] + static_runtime + ["-std=c++17", "-Wall", "-Werror", "-g", "-O1", "-ffp-contract=off",
-                                    "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                                    "-I" + os.path.join(ROOT, "bc_gym_planning_env_amd", "csrc"),
-                                    os.path.join(ROOT, "tests", "c_abi", "range_scan_main.cpp"), "-o", exe]
-    built = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=300)
-    assert built.returncode == 0, built.stdout
-    return exe
+    return host_program.build(tmp_path_factory, "range_scan_main.cpp")
 
 
 def _run(exe, mode, path):
-    ran = subprocess.run([exe, mode, path], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=120)
-    assert ran.returncode == 0, ran.stdout[-4000:]
-    assert "range scan ok" in ran.stdout
-    for word in ("Sanitizer", "runtime error"):
-        assert word not in ran.stdout, ran.stdout[-4000:]
-    return ran.stdout.split("\n")
+    return host_program.run(exe, [mode, path], "range scan ok")
 
 
 def _both(exe, tmp_path, data, valid, origin, resolution, poses, heading_cs, beam_cs, max_range):

@@ -5,46 +5,23 @@ that header alone -- it has no HIP in it -- and calls the very functions scatter
 block of exactly its stated size and every cell is written through a sink that refuses one outside the valid shape, so a
 run that left the map fails here, without a GPU.  Everything is compared byte for byte: maps, boxes and counts."""
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import host_program
 import scatter_boxes_ref as SR
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _compiler():
-    for cand in ("g++", "/opt/rocm/llvm/bin/clang++", "clang++"):
-        path = shutil.which(cand)
-        if path:
-            return path
-    raise AssertionError("no host C++ compiler found (g++ or ROCm's clang++)")
-
-
 @pytest.fixture(scope="module")
 def program(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("scatter_boxes") / "scatter_boxes_main")
-    cxx = _compiler()
-    static_runtime = ["-static-libasan", "-static-libubsan"] if cxx.endswith("g++") else []   # (clang's is static already)
-    cmd = [cxx] + static_runtime + ["-std=c++17", "-Wall", "-Werror", "-g", "-O1", "-ffp-contract=off",
-                                    "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                                    "-I" + os.path.join(ROOT, "bc_gym_planning_env_amd", "csrc"),
-                                    os.path.join(ROOT, "tests", "c_abi", "scatter_boxes_main.cpp"), "-o", exe]
-    built = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=300)
-    assert built.returncode == 0, built.stdout
-    return exe
+    return host_program.build(tmp_path_factory, "scatter_boxes_main.cpp")
 
 
 def _run(exe, *args):
-    ran = subprocess.run([exe] + list(args), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=120)
-    assert ran.returncode == 0, ran.stdout[-4000:]
-    assert "scatter boxes ok" in ran.stdout
-    for word in ("Sanitizer", "runtime error"):
-        assert word not in ran.stdout, ran.stdout[-4000:]
-    return ran.stdout.split("\n")
+    return host_program.run(exe, args, "scatter boxes ok")
 
 
 def _scatter(exe, tmp_path, data, valid, origins, resolution, frame, keep, yaw_cs, n_boxes, max_attempts, seed, along, half_size,

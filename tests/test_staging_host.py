@@ -5,25 +5,16 @@ step; and the limits those worlds were built around are still the ones the heade
 csrc/bcp_step_layout.h, not from the headers' text -- with the LDS layouts that header plans for the step kernels."""
 import itertools
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import host_program
 import footprints as F
 import staging as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIMIT_WORLD_CASES = [n for n in S.STEP_CASES + S.BIND_CASES if n.startswith(("map-", "max-", "bind-"))]
-
-
-def _compiler():
-    for cand in ("g++", "/opt/rocm/llvm/bin/clang++", "clang++"):
-        path = shutil.which(cand)
-        if path:
-            return path
-    raise AssertionError("no host C++ compiler found (g++ or ROCm's clang++)")
 
 
 # every plan the tests below look at, asked of ONE start of the program
@@ -36,22 +27,10 @@ COLLISION_TUPLES = list(itertools.product((3, 4, 17), (0, 1, 4095, 4096)))
 def layout(tmp_path_factory):
     """tests/c_abi/step_layout_main.cpp, which includes csrc/bcp_step_layout.h alone, built with a host compiler under
     AddressSanitizer and UBSan and run once -> (limits {name: value}, plans {argument: {region: bytes}})"""
-    exe = str(tmp_path_factory.mktemp("step_layout") / "step_layout_main")
-    cxx = _compiler()
-    static_runtime = ["-static-libasan", "-static-libubsan"] if cxx.endswith("g++") else []   # (clang's is static already)
-    cmd = [cxx] + static_runtime + ["-std=c++17", "-Wall", "-Werror", "-g", "-O1", "-ffp-contract=off",
-                                    "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                                    "-I" + os.path.join(ROOT, "bc_gym_planning_env_amd", "csrc"),
-                                    os.path.join(ROOT, "tests", "c_abi", "step_layout_main.cpp"), "-o", exe]
-    built = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=300)
-    assert built.returncode == 0, built.stdout
+    exe = host_program.build(tmp_path_factory, "step_layout_main.cpp")
     args = (["local:%d,%d,%d,%d,%d" % t for t in LOCAL_TUPLES] + ["pair:%d,%d" % t for t in PAIR_TUPLES] +
             ["pending:0", "pending:1"] + ["collision:%d,%d" % t for t in COLLISION_TUPLES])
-    ran = subprocess.run([exe] + args, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=120)
-    assert ran.returncode == 0, ran.stdout[-4000:]
-    for word in ("Sanitizer", "runtime error"):
-        assert word not in ran.stdout, ran.stdout[-4000:]
-    lines = ran.stdout.split("\n")
+    lines = host_program.run(exe, args)
     assert lines[-2] == "step layout ok"
     limits = {ln.split(" ")[1]: int(ln.split(" ")[2]) for ln in lines if ln.startswith("limit ")}
     plans = {ln.split(" ")[0]: {kv.split("=")[0]: int(kv.split("=")[1]) for kv in ln.split(" ")[1:]}
