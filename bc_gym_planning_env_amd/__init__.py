@@ -9,18 +9,20 @@ from .api import (Action, Box, ContinuousRewardProviderState, CostMap2D, Diffdri
 __all__ = ["Action", "Box", "ContinuousRewardProviderState", "CostMap2D", "DiffdriveRobotState", "EnvParams",
            "INDUSTRIAL_DIFFDRIVE_V1", "INDUSTRIAL_TRICYCLE_V1", "Observation", "RewardParams", "State",
            "TricycleRobotState", "BatchedPlanEnv", "BatchedRandomAisleTurnEnv", "NativeOps", "Lookahead", "ShootingPlanner",
-           "constant_command_library", "Mppi", "MPPIPlanner", "BatchedRangeScan", "BatchedGoalField", "GoalField"]
+           "constant_command_library", "Mppi", "MPPIPlanner", "Track", "TrackingPlanner", "pursuit_gain_library",
+           "BatchedRangeScan", "BatchedGoalField", "GoalField"]
 
 
 def __getattr__(name):
     # torch is imported lazily so that `import bc_gym_planning_env_amd` stays cheap for host-only users
-    if name in ("BatchedPlanEnv", "BatchedState", "BatchedObservation", "Lookahead", "Mppi"):
+    if name in ("BatchedPlanEnv", "BatchedState", "BatchedObservation", "Lookahead", "Mppi", "Track"):
         from . import batched_env
         return getattr(batched_env, name)
     if name == "BatchedRandomAisleTurnEnv":
         from .aisle_env import BatchedRandomAisleTurnEnv
         return BatchedRandomAisleTurnEnv
-    if name in ("ShootingPlanner", "constant_command_library", "MPPIPlanner"):
+    if name in ("ShootingPlanner", "constant_command_library", "MPPIPlanner", "TrackingPlanner",
+                "pursuit_gain_library"):
         from . import planning
         return getattr(planning, name)
     if name == "BatchedRangeScan":

@@ -125,6 +125,21 @@ class BcpMppiWidths(C.Structure):
     ]
 
 
+class BcpTrackParams(C.Structure):
+    _fields_ = [
+        ("horizon", C.c_int32), ("n_candidates", C.c_int32), ("low", C.c_double * 2), ("high", C.c_double * 2),
+        ("max_curvature", C.c_double),
+    ]
+
+
+class BcpTrackIO(C.Structure):
+    _fields_ = [
+        ("gains", C.c_void_p), ("mask", C.c_void_p), ("actions", C.c_void_p), ("ret", C.c_void_p), ("steps", C.c_void_p),
+        ("reason", C.c_void_p), ("final_pose", C.c_void_p), ("final_target_idx", C.c_void_p), ("err", C.c_void_p),
+        ("trace", C.c_void_p), ("best", C.c_void_p), ("best_plan", C.c_void_p), ("best_action", C.c_void_p),
+    ]
+
+
 class BcpScatterParams(C.Structure):
     """bcp_scatter_params: what bcp_scatter_boxes draws from"""
     _fields_ = [
@@ -162,6 +177,7 @@ SYMBOLS = {
                                  C.c_void_p]),
     "bcp_mppi_adapt": (C.c_int, [_H, C.POINTER(BcpMppiParams), C.POINTER(BcpMppiIO), C.POINTER(BcpMppiWidths),
                                  C.POINTER(BcpMppiTerminal), C.c_uint32, C.c_void_p]),
+    "bcp_track": (C.c_int, [_H, C.POINTER(BcpTrackParams), C.POINTER(BcpTrackIO), C.c_uint32, C.c_void_p]),
     "bcp_expired_waits": (C.c_int, [_H, C.POINTER(C.c_int64), C.c_void_p]),
     "bcp_parked_poses": (C.c_int, [_H, C.POINTER(C.c_int64), C.c_void_p]),
     "bcp_side_stream": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_void_p)]),

@@ -20,12 +20,12 @@ from .api import Action, Box, CONTINUOUS_REWARD_PURE_PURSUIT, CostMap2D, EnvPara
 from .episode_record import EpisodeEnds
 from .geometry import DeviceGeometryPool, HostEntries, chain_layout, stack_costmaps, stack_paths
 from .handle import Handle, SCAN_CACHE_ENTRIES, beam_table_cached, cached
-from .planning import Lookahead, Mppi
+from .planning import Lookahead, Mppi, Track
 from .state import BatchedObservation, BatchedState, EnvView, _EnvViews
 
 # (everything that was ever importable from here still is)
 __all__ = ["BatchedPlanEnv", "DeviceGeometryPool", "BatchedState", "BatchedObservation", "EnvView", "EpisodeEnds",
-           "Lookahead", "Mppi", "beam_table_cached", "SCAN_CACHE_ENTRIES"]
+           "Lookahead", "Mppi", "Track", "beam_table_cached", "SCAN_CACHE_ENTRIES"]
 
 
 def _as_device_actions(actions, n, device):
@@ -119,7 +119,7 @@ class BatchedPlanEnv(Handle):
         self._inflated = False     # inflate_costmaps()
         self._goal_followers = []  # weak references to the GoalFields a refresh() keeps current (goal_field(follow_refresh=True))
         self._rollout_buffers, self._lookahead_buffers, self._mppi_buffers = OrderedDict(), OrderedDict(), OrderedDict()
-        self._range_scan_buffers = OrderedDict()
+        self._range_scan_buffers, self._track_buffers = OrderedDict(), OrderedDict()
 
         # the geometry, in one of five modes (a shared costmap may go with private paths and the other way round); the host
         # copies of either half and which of them is env i's: self._map_host, self._path_host (geometry.HostEntries)
@@ -750,6 +750,73 @@ class BatchedPlanEnv(Handle):
             _lib.check(self._lib.bcp_mppi_field(self._h, C.byref(p), C.byref(io), C.byref(term), flags, self._stream()))
         self._alive["mppi"] = tuple(keep)   # alive until the stream has consumed them
         return Mppi(h, k, it, mean, sigma=widths, **out)
+
+    def default_max_curvature(self):
+        """The curvature clamp track() uses when none is given: what the robot can turn -- tan(max_front_wheel_angle) /
+        front_wheel_from_axis for the tricycle, high[1] / max(low[0], 1e-3) of the action box for the diff-drive."""
+        if self.is_tricycle:
+            p = self._bcp_params
+            return float(np.tan(p.max_front_wheel_angle) / p.front_wheel_from_axis)
+        low, high = np.asarray(self.action_space.low, np.float64), np.asarray(self.action_space.high, np.float64)
+        return float(high[1] / max(low[0], 1e-3))
+
+    def track(self, gains, horizon, max_curvature=None, mask=None, want=(), action_dtype=None):
+        """Roll a pure-pursuit path tracker out for every env under K gain settings over the next `horizon` steps WITHOUT
+        stepping it (bcp_track, nothing of the env changes): every trip's command steers for the first way point at least
+        `reach` ahead at `speed`, through the reference's diff_drive_control_to_tricycle for the tricycle, clipped to the
+        action box; the trips are lookahead()'s (noise-free forward model, stop after the first done step).
+        gains: [K, 2] (speed, reach) shared by all envs, or [N, K, 2] per env; a setting that is not finite, with
+        speed < 0 or reach <= 0 takes no trip (steps 0, zeros) and comes last in `best`.  max_curvature: the clamp of the
+        arc's curvature in 1/m, None: default_max_curvature().  mask: optional [N]; rows of envs with mask 0 keep what the
+        cached buffers held.  want: optional outputs from "final_pose", "final_target_idx", "err", "trace", "best",
+        "best_plan", "best_action" (the last two imply "best").  action_dtype: of best_action, torch.float64 (default) or
+        torch.float32.  Returns a Track of device tensors, no sync; buffers are cached per (H, K).  Delays > 0 and the
+        pure-pursuit reward provider are refused."""
+        gains = self._device_tensor(gains, torch.float64)
+        n, h = self.n_envs, int(horizon)
+        if gains.dim() == 2 and gains.shape[1] == 2:
+            flags = 0
+        elif gains.dim() == 3 and gains.shape[0] == n and gains.shape[2] == 2:
+            flags = _lib.LOOKAHEAD_PER_ENV
+        else:
+            raise ValueError("gains must have shape (K, 2) or (%d, K, 2), got %s" % (n, tuple(gains.shape)))
+        k = int(gains.shape[-2])
+        want = set(want)
+        unknown = want - set(Track.FIELDS[4:])
+        if unknown:
+            raise ValueError("track: unknown outputs %s" % sorted(unknown))
+        if want & {"best_plan", "best_action"}:
+            want.add("best")
+        action_dtype = torch.float64 if action_dtype is None else action_dtype
+        if action_dtype not in (torch.float32, torch.float64):
+            raise ValueError("action_dtype must be torch.float32 or torch.float64")
+        if action_dtype == torch.float32:
+            flags |= _lib.STEP_ACTIONS_F32
+        p = _lib.BcpTrackParams()
+        p.horizon, p.n_candidates = h, k
+        low, high = (np.asarray(b, dtype=np.float64).reshape(2) for b in (self.action_space.low, self.action_space.high))
+        for d in range(2):
+            p.low[d], p.high[d] = low[d], high[d]
+        p.max_curvature = self.default_max_curvature() if max_curvature is None else float(max_curvature)
+        shapes = {"actions": ((n, k, max(h, 0), 2), torch.float64), "ret": ((n, k), torch.float64),
+                  "steps": ((n, k), torch.int32), "reason": ((n, k), torch.uint8), "final_pose": ((n, k, 3), torch.float64),
+                  "final_target_idx": ((n, k), torch.int32), "err": ((n, k), torch.int32),
+                  "trace": ((n, k, max(h, 0), 6), torch.float64), "best": ((n,), torch.int32),
+                  "best_plan": ((n, max(h, 0), 2), torch.float64), "best_action": ((n, 2), action_dtype)}
+        io = _lib.BcpTrackIO()
+        io.gains = gains.data_ptr()
+        keep = [gains]
+        if mask is not None:
+            mask = self._device_tensor(mask, torch.uint8, (n,))
+            io.mask = mask.data_ptr()
+            keep.append(mask)
+        out = self._cached_outputs(self._track_buffers, (h, k), shapes,
+                                   [name for name in Track.FIELDS if name in want or name in Track.REQUIRED])
+        for name, t in out.items():
+            setattr(io, name, t.data_ptr())
+        _lib.check(self._lib.bcp_track(self._h, C.byref(p), C.byref(io), flags, self._stream()))
+        self._alive["track"] = tuple(keep)   # alive until the stream has consumed them
+        return Track(h, k, **out)
 
     def _beam_table(self, beam_angles):
         """The device table [B, 2] of (cos, sin) of the beam angles (beam_table_cached)."""

@@ -2,7 +2,8 @@
 //
 // One translation unit.  The device code is in bcp_device.h, bcp_raster.h, bcp_coop.h and bcp_step.h with the bcp_step_*.h it includes (the step: robot model ->
 // collision classification / exact rasteriser -> rollback -> reward provider -> done -> optional reset -> state write-back),
-// bcp_lookahead.h and bcp_mppi.h (the planners), bcp_ego.h (egocentric views), bcp_sample.h and bcp_aisle.h (world samplers),
+// bcp_lookahead.h, bcp_mppi.h and bcp_track.h (the planners; the tracker's law: bcp_track_law.h, no HIP in it),
+// bcp_ego.h (egocentric views), bcp_sample.h and bcp_aisle.h (world samplers),
 // bcp_inflate.h (costmap inflation), bcp_scan.h (range scans; the walk: bcp_scan_march.h, no HIP in it), bcp_goal.h (goal
 // fields; a cell's arithmetic: bcp_goal_cell.h, and the plan of a launch: bcp_goal_plan.h, no HIP in either), bcp_boxes.h (box obstacles; the rule: bcp_boxes_cell.h, no HIP
 // in it; bcp_philox.h and bcp_outline.h hold the generator and the edge walk for host and device).  The host side is split by
@@ -13,6 +14,7 @@
 //   bcp_field.h        distance field and tiles: kernels, DistanceField, the launchers of what is derived from maps and paths
 //   bcp_step_host.h    step forms, the step's parameter block and launcher, Parking, WaitWatchdog, bcp_step / bcp_rollout
 //   bcp_plan_host.h    the planners: bcp_lookahead / bcp_mppi / bcp_mppi_field / bcp_mppi_adapt
+//   bcp_track_host.h   bcp_track (kernels: bcp_track.h)
 //   bcp_ego_host.h     egocentric costmaps (routed by bcp_ego_route.h, which has no HIP in it), goal-state vectors, the
 //                      episode record and its final observations
 //   bcp_worlds_host.h  mini-world and aisle-world entry points
@@ -47,6 +49,7 @@
 #include "bcp_step.h"
 #include "bcp_lookahead.h"
 #include "bcp_mppi.h"
+#include "bcp_track.h"
 #include "bcp_ego.h"
 #include "bcp_sample.h"
 #include "bcp_aisle.h"
@@ -104,6 +107,7 @@ static void fill_dev_params(bcp_handle* h)
 #include "bcp_field.h"
 #include "bcp_step_host.h"
 #include "bcp_plan_host.h"
+#include "bcp_track_host.h"
 #include "bcp_seams.h"
 #include "bcp_seams_host.h"
 #include "bcp_ego_host.h"

@@ -3,7 +3,9 @@ bc_gym_planning_env/run_the_challange.py), for N envs at once.  Worked examples,
 ShootingPlanner: every tick each env scores a fixed library of candidate plans with the noise-free forward model
 (lookahead()) and takes the first action of the best one (no collision within the horizon first, then the largest return).
 MPPIPlanner: every tick each env refines its own plan by sampling around it (mppi(), one kernel launch) and takes the
-plan's first action; the rest of the plan is the next tick's warm start."""
+plan's first action; the rest of the plan is the next tick's warm start.
+TrackingPlanner: every tick each env rolls a pure-pursuit tracker out under K gain settings (track(), one kernel launch) and
+takes the first command of the best one; its plan can seed MPPIPlanner (nominal=)."""
 import numpy as np
 import torch
 
@@ -51,6 +53,32 @@ class Mppi(object):
         self.mean, self.action, self.sigma = mean, action, sigma
         for name in self.FIELDS:
             setattr(self, name, tensors.get(name))
+
+
+class Track(Lookahead):
+    """What BatchedPlanEnv.track() returns: device tensors over [N, K] gain settings (no sync).  `actions` [N, K, H, 2]
+    float64, the commands the tracker took (after a setting's done step its last command repeated); `ret`, `steps`,
+    `reason` as in Lookahead; optional, None unless asked for: `final_pose`, `final_target_idx`, `err`, `trace`
+    [N, K, H, 6] (x, y, th, wheel angle, target_idx, carrot index as the law read them at step t; zeros after the done
+    step), `best` int32 [N], `best_plan` [N, H, 2] = actions[i, best[i]], `best_action` [N, 2].  The tensors are the env's
+    cached buffers for this (H, K): the next track() with the same shape overwrites them."""
+
+    FIELDS = ("actions", "ret", "steps", "reason", "final_pose", "final_target_idx", "err", "trace", "best", "best_plan",
+              "best_action")
+    REQUIRED = FIELDS[:4]
+
+
+def pursuit_gain_library(action_space, n_speed, reaches):
+    """[n_speed * len(reaches), 2] float64 gain settings (speed, reach) for BatchedPlanEnv.track(): the speeds spread evenly
+    over (0, action_space.high[0]] -- high[0] * (i + 1) / n_speed --, every one with every reach (metres, > 0).
+    Setting k = i_speed * len(reaches) + i_reach."""
+    reaches = np.asarray(reaches, np.float64).reshape(-1)
+    if n_speed < 1 or reaches.size < 1 or not (reaches > 0).all():
+        raise ValueError("n_speed must be at least 1 and reaches positive")
+    top = float(np.asarray(action_space.high, np.float64)[0])
+    speeds = top * (np.arange(n_speed, dtype=np.float64) + 1.0) / n_speed
+    v, r = np.meshgrid(speeds, reaches, indexing="ij")
+    return np.ascontiguousarray(np.stack([v.ravel(), r.ravel()], axis=1))
 
 
 def constant_command_library(action_space, n_v, n_angle, horizon):
@@ -120,6 +148,42 @@ class ShootingPlanner(object):
         return self.library[0, self.last_best]
 
 
+class TrackingPlanner(object):
+    """A pure-pursuit path follower per env on BatchedPlanEnv.track(): every tick the K gain settings of `gains` are rolled
+    out over `horizon` steps of the noise-free forward model, and the env takes the first command of the best one (no
+    collision within the horizon first, then the largest return).
+
+    :param env: a BatchedPlanEnv (or a wrapper that forwards track); delays must be 0, the reward provider the continuous one
+    :param gains: [K, 2] settings (speed, reach) shared by all envs, e.g. pursuit_gain_library(env.action_space, 3,
+        (0.4, 0.8, 1.6)), or [N, K, 2] settings per env
+    :param horizon: steps H of a roll-out
+    :param max_curvature: the clamp of the arc's curvature in 1/m; None: what the robot can turn (BatchedPlanEnv.track)
+    """
+
+    def __init__(self, env, gains, horizon, max_curvature=None):
+        self.env = env
+        base = env
+        while not hasattr(base, "n_envs"):
+            base = base.unwrapped() if callable(base.unwrapped) else base.unwrapped
+        g = gains if isinstance(gains, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(gains, dtype=np.float64))
+        self.base = base   # the BatchedPlanEnv under the wrappers
+        self.gains = g.to(base.device).to(torch.float64).contiguous()
+        self.horizon, self.max_curvature = int(horizon), max_curvature
+        self.last = None   # the Track of the latest act() or plan()
+
+    def act(self, observation=None):
+        """actions [N, 2] (float64 device tensor) for env.step(): step 0 of the best setting.  The observation is not needed
+        (as for ShootingPlanner): the roll-outs start from the env's own state."""
+        self.last = self.env.track(self.gains, self.horizon, self.max_curvature, want=("best", "best_action"))
+        return self.last.best_action
+
+    def plan(self, mask=None):
+        """[N, H, 2] float64: the commands of the best setting over the horizon -- a cached buffer of the env, overwritten by
+        the next call.  mask: optional [N]; rows of envs with mask 0 keep what the buffer held."""
+        self.last = self.env.track(self.gains, self.horizon, self.max_curvature, mask=mask, want=("best", "best_plan"))
+        return self.last.best_plan
+
+
 class MPPIPlanner(object):
     """Model-predictive path integral control per env on BatchedPlanEnv.mppi(): a receding-horizon plan `mean` [N, H, 2]
     (float64, on the device) refined every tick and shifted by one step afterwards.
@@ -142,11 +206,15 @@ class MPPIPlanner(object):
     :param sigma_min, sigma_max: the clamps of the widths, two values each; default sigma / 8 and 2 * sigma
     :param sigma_recover: after the shift every width relaxes towards `sigma` by this share of the difference
 
+    :param nominal: None, or a TrackingPlanner of the same env and horizon: a new plan is then the tracker's best plan
+        (TrackingPlanner.plan()) from the env's state at that moment, not the centre of the box; reset_plans() then
+        launches the tracker for the envs it names
+
     A new plan -- at the start, and for the envs named by reset_plans() -- holds the centre of the action box,
-    (low + high) / 2, at every step, and with adapt_rate `sigma` as its widths."""
+    (low + high) / 2, at every step (or, with `nominal`, the tracker's plan), and with adapt_rate `sigma` as its widths."""
 
     def __init__(self, env, horizon, n_candidates, iterations, sigma, lam, collision_penalty, seed=0, goal_field=None,
-                 terminal_weight=0.0, adapt_rate=None, sigma_min=None, sigma_max=None, sigma_recover=0.0):
+                 terminal_weight=0.0, adapt_rate=None, sigma_min=None, sigma_max=None, sigma_recover=0.0, nominal=None):
         self.env = env
         self.goal_field, self.terminal_weight = goal_field, float(terminal_weight)
         base = env
@@ -167,16 +235,26 @@ class MPPIPlanner(object):
             self.sigma0 = torch.from_numpy(width).to(device)
             self._sigma_call = tuple(width)
             self.sigma = self.sigma0.expand(base.n_envs, self.horizon, 2).contiguous()
+        self.nominal = nominal
+        if nominal is not None:
+            if nominal.base is not base:   # (through whatever wrappers either was given)
+                raise ValueError("nominal follows another env than this planner's")
+            if nominal.horizon != self.horizon:
+                raise ValueError("nominal plans %d steps, this planner %d" % (nominal.horizon, self.horizon))
+            self.mean.copy_(nominal.plan())
         self.draw_index = 0
         self._fresh = True    # nothing to shift yet
         self.last = None      # the Mppi of the latest act()
 
     def reset_plans(self, mask):
         """Call after env.step() with its done mask ([N], non-zero = the env's episode ended and, under auto-reset, it
-        starts anew): those envs' plans go back to the default."""
+        starts anew): those envs' plans go back to the default.  With `nominal` that default is the tracker's plan, and
+        every call launches bcp_track with this mask (a host check of the mask would synchronise): the lanes of envs with
+        mask 0 take no trip, so a call with nothing to reset costs the launch, + 0.02 ms per tick at 4 096 envs."""
         mask = mask if isinstance(mask, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(mask))
         mask = mask.to(self.mean.device) != 0
-        self.mean.copy_(torch.where(mask[:, None, None], self.default, self.mean))
+        fresh = self.default if self.nominal is None else self.nominal.plan(mask=mask.to(torch.uint8))
+        self.mean.copy_(torch.where(mask[:, None, None], fresh, self.mean))
         if self.adapt_rate is not None:
             self.sigma.copy_(torch.where(mask[:, None, None], self.sigma0, self.sigma))
 

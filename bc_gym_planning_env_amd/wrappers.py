@@ -71,6 +71,9 @@ class BatchedObservationWrapper(object):
     def mppi(self, mean, *args, **kw):
         return self.env.mppi(mean, *args, **kw)
 
+    def track(self, gains, horizon, *args, **kw):
+        return self.env.track(gains, horizon, *args, **kw)
+
     def get_state(self):
         return self.env.get_state()
 

@@ -798,6 +798,67 @@ typedef struct bcp_mppi_widths {
 int bcp_mppi_adapt(bcp_handle *h, const bcp_mppi_params *p, const bcp_mppi_io *io, const bcp_mppi_widths *ad,
                    const bcp_mppi_terminal *term /* NULL = no goal field */, uint32_t flags, void *stream);
 
+/* ---- path tracking: K gain settings of a pure-pursuit tracker per env, rolled out through the forward model */
+/* Parameters of bcp_track, passed to the kernel by value. */
+typedef struct bcp_track_params {
+    int32_t horizon, n_candidates;   /* H >= 1, K >= 1 */
+    double  low[2], high[2];         /* the action box (action_space.low / high widened to float64) */
+    double  max_curvature;           /* 1/m, finite, > 0: the clamp of the arc's curvature */
+} bcp_track_params;
+
+/* Host struct of device pointers, caller-owned; N = n_envs, H = horizon, K = n_candidates. */
+typedef struct bcp_track_io {
+    const double *gains;        /* [K][2] (speed, reach), or [N][K][2] with BCP_LOOKAHEAD_PER_ENV */
+    const uint8_t *mask;        /* optional [N]; 0: every output row of the env untouched */
+    double  *actions;           /* [N][K][H][2]: the commands taken; after the done step the last one repeated */
+    double  *ret;               /* [N][K] */
+    int32_t *steps;             /* [N][K] */
+    uint8_t *reason;            /* [N][K] */
+    double  *final_pose;        /* optional [N][K][3] */
+    int32_t *final_target_idx;  /* optional [N][K] */
+    int32_t *err;               /* optional [N][K] */
+    double  *trace;             /* optional [N][K][H][6]: x, y, th, wheel_angle, target_idx, carrot index as the
+                                   law READ them at step t (doubles); rows after the done step zeros */
+    int32_t *best;              /* optional [N] */
+    double  *best_plan;         /* optional [N][H][2] (needs best): actions[i][best[i]] -- the layout of bcp_mppi_io.mean */
+    void    *best_action;       /* optional [N][2] (needs best): float64, or float32 with BCP_STEP_ACTIONS_F32 */
+} bcp_track_io;
+
+/* A feedback controller rolled out through the forward model.  For env i and setting k with gains (speed, reach), a private
+ * copy of env i's state takes up to H trips exactly as bcp_lookahead with noise_z = NULL takes them (the noise-free forward
+ * model, no auto-reset, stop after the first done step, ret added in step order from 0.0; ret, steps, reason, final_pose,
+ * final_target_idx and err mean what they mean in bcp_lookahead_io), but the command of trip t is computed from the state
+ * trip t - 1 left.  All arithmetic is float64, every product, quotient and sum rounded on its own.  With the pose
+ * (x, y, th), the wheel angle wa (0 for the diff-drive), the provider's target_idx, the env's m way points pts and the
+ * lane's previous carrot index c_prev (target_idx before the first trip):
+ *   1. carrot: j0 = min(max(c_prev, target_idx), m - 1); the carrot is the first j >= j0 with dx * dx + dy * dy >=
+ *      reach * reach, dx = pts[j].x - x, dy = pts[j].y - y, or m - 1 if there is none.  It never goes backwards.
+ *   2. robot frame: lx = c * dx + s * dy, ly = -s * dx + c * dy, (c, s) = (cos th, sin th).
+ *   3. curvature: d2 = lx * lx + ly * ly; kappa = d2 < 1e-12 ? 0 : 2 * ly / d2, clamped to [-max_curvature, max_curvature].
+ *   4. desired body motion: v = speed, w = speed * kappa.
+ *   5. command: (v, w) for the diff-drive; for the tricycle diff_drive_control_to_tricycle(v, w, wa, max_front_wheel_angle,
+ *      front_wheel_from_axis) of robot_models/tricycle_model.py:191-231 -- the wheel speed and the wheel angle.
+ *   6. each component clipped to [low[d], high[d]].
+ * The tracker is the reference's "planner helper" put to use; the reference has no counterpart of the roll-out.
+ * best: the setting with the largest key of bcp_lookahead_io.best (free before collided, then ret, lowest k on ties);
+ * best_plan = actions[i][best[i]], best_action = its step 0 (rounded to float32 under the flag): both can be passed on as
+ * they are, best_plan as bcp_mppi_io.mean.
+ * Gains are device data and are not checked on the host: a lane whose speed or reach is not finite, whose speed < 0 or
+ * whose reach <= 0 takes no trip -- steps = 0, reason = 0, ret = 0, zeros in its rows of actions and trace, final_pose /
+ * final_target_idx as the env holds them -- and comes last in the key of `best`, behind every collided setting.
+ * Nothing of the handle changes: no state array, step counter, noise stream or episode record.  Asynchronous on `stream`,
+ * no allocation, no synchronisation; the launch arguments are the caller's pointers and *p by value, so a call can be
+ * captured into a HIP graph after one ordinary call.
+ * Refused with BCP_E_INVALID, nothing written:
+ *   - h, p or io NULL; flag bits other than BCP_STEP_ACTIONS_F32 and BCP_LOOKAHEAD_PER_ENV;
+ *   - control_delay, pose_delay or state_delay > 0;
+ *   - the pure-pursuit reward provider (the law reads target_idx as "the next way point to reach", which only the
+ *     continuous provider keeps);
+ *   - horizon < 1 or n_candidates < 1; max_curvature not finite or not > 0; a non-finite low or high; low[d] > high[d];
+ *   - gains, actions, ret, steps or reason NULL; best_plan or best_action without best;
+ *   - 6 * N * K * H >= 2^62 (the element offsets are 64-bit). */
+int bcp_track(bcp_handle *h, const bcp_track_params *p, const bcp_track_io *io, uint32_t flags, void *stream);
+
 /* ---- costmap inflation ------------------------------------------------------------------------------------ */
 /* inflate_costmap (utilities/costmap_inflation.py:73-92) for n_maps maps in one call: the ROS inflation layer.  Per map
  * `data` [rows][cols] with valid shape (vr, vc) = (valid_rows[m], valid_cols[m]) clamped to [0, rows] x [0, cols], or the
