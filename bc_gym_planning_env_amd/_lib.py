@@ -20,6 +20,7 @@ TUNE_LOCAL_SHARED = 13
 GOAL_ORTHO, GOAL_DIAG, GOAL_FAR, GOAL_NONE = 12, 17, 65534, 65535
 GOAL_MAX_EXTRA = 4095
 ROUTE_LONG, ROUTE_TOO_CLOSE, ROUTE_NO_ROUTE, ROUTE_STUCK = 1, 2, 4, 8
+SMOOTH_BLOCKED = 16   # bcp_smooth_route's status bit beside the ROUTE_* ones
 SCATTER_SHORT, SCATTER_REVERTED = 1, 2   # BatchedPlanEnv.scatter_obstacles' status bits
 E_NO_DEVICE = -2
 OPT_DIFFDRIVE_NOISE = 1
@@ -148,6 +149,11 @@ class BcpScatterParams(C.Structure):
     ]
 
 
+class BcpSmoothParams(C.Structure):
+    """bcp_smooth_params: the pull's reach and the blend of bcp_smooth_route"""
+    _fields_ = [("look", C.c_int32), ("halvings", C.c_int32), ("blend", C.c_double), ("delta", C.c_double)]
+
+
 BcpMppiAdapt = BcpMppiWidths   # (the argument of bcp_mppi_adapt, by the function's name)
 
 
@@ -260,6 +266,9 @@ SYMBOLS = {
                                  C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bcp_goal_route_bound": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bcp_smooth_route": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64,
+                                   C.c_void_p, C.c_int32, C.POINTER(BcpSmoothParams), C.c_int32, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bcp_scatter_boxes": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_double, C.POINTER(BcpScatterParams), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),

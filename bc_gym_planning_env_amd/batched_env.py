@@ -873,7 +873,7 @@ class BatchedPlanEnv(Handle):
         from . import goal_field
         return goal_field.build(self, clearance, seeds, max_passes, follow_refresh, cost_weight, extra_of_cost)
 
-    def route_paths(self, fields=None, stride=2, max_len=None, clearance=None, cost_weight=None):
+    def route_paths(self, fields=None, stride=2, max_len=None, clearance=None, cost_weight=None, smooth=None):
         """Replace every entry's path by the route traced down its goal field (bcp_goal_route_bound, one launch): from the
         entry's own start pose, through the centre of every stride-th cell of the cheapest route that keeps `clearance`
         from the walls, to its own goal pose -- a path a robot can follow, where the straight path of a pool world may
@@ -892,11 +892,16 @@ class BatchedPlanEnv(Handle):
         Starts and goals do not change: GoalFields of this env built before the call stay valid, and calling again
         changes nothing.  clearance and cost_weight only apply when the fields are built here: with `fields` either is a
         ValueError.
+        smooth: None, or a dict of GoalField.smooth's parameters (look, blend, delta, halvings) and route_len (default
+        1024): the route is then traced at stride 1 into a scratch buffer of route_len slots and smoothed
+        (bcp_smooth_route: pulled taut, corners blended, a way point every delta metres) into max_len <= 4096 slots, and
+        `stride` is not used.  An entry keeps its old path unless its route status and its smooth status are both 0,
+        SMOOTH_BLOCKED aside; the returned status is the two OR-ed.
         Returns the int32 status [entries] (device tensor; _lib.ROUTE_* bits).
         Refused on endless=True pools (refresh() would write straight paths back), on a shared map or path, and on fields
         whose owner or shape is not this env's."""
         from . import goal_field
-        return goal_field.route_paths(self, fields, stride, max_len, clearance, cost_weight)
+        return goal_field.route_paths(self, fields, stride, max_len, clearance, cost_weight, smooth)
 
     def scatter_obstacles(self, n_boxes, half_size, along=(0.2, 0.8), lateral=1.0, keep_clear=None, n_yaws=16, seed=0,
                           max_attempts=32, ensure_route=True, clearance=None):

@@ -24,6 +24,7 @@
 //                      bcp_goal_field_bound / bcp_goal_field_cost_bound / bcp_refresh_goal_fields -- one launch path for the
 //                      five, planned by bcp_goal_plan.h --, bcp_goal_field_sample / bcp_final_goal_field_sample, and
 //                      bcp_goal_route / bcp_goal_route_bound
+//   bcp_smooth_host.h  bcp_smooth_route (kernel: bcp_smooth.h; a row's arithmetic: bcp_smooth_cell.h, no HIP in it)
 //   bcp_boxes_host.h   bcp_scatter_boxes (kernel: bcp_boxes.h)
 //   bcp_seams_host.h   bind / reset / broadcast of the state and the operator seams (their small kernels: bcp_seams.h)
 // This file holds create / destroy / seed / pool / tuning / side stream, bcp_set_costmaps with the two reads of the distance
@@ -56,6 +57,7 @@
 #include "bcp_inflate.h"
 #include "bcp_scan.h"
 #include "bcp_goal.h"
+#include "bcp_smooth.h"
 #include "bcp_boxes.h"
 
 using namespace bcp;
@@ -115,6 +117,7 @@ static void fill_dev_params(bcp_handle* h)
 #include "bcp_inflate_host.h"
 #include "bcp_scan_host.h"
 #include "bcp_goal_host.h"
+#include "bcp_smooth_host.h"
 #include "bcp_boxes_host.h"
 
 // ------------------------------------------------------------------------------------------------ host API

@@ -5,7 +5,8 @@ launch per build) and what it says at a pose -- distance to go and the direction
 (bcp_goal_field_bound) and, on an endless pool, has every refresh() rebuild the fields of the entries it re-samples
 (bcp_refresh_goal_fields).  cost_weight / extra_of_cost weigh the field by the costs of an inflated map
 (bcp_goal_field_cost): routes then run down the middle of free space where there is room.  route_paths() makes the routes
-down the fields the env's paths (bcp_goal_route_bound).  The reference has no
+down the fields the env's paths (bcp_goal_route_bound), smooth() / route_paths(smooth=...) pulls them taut and blends their
+corners (bcp_smooth_route).  The reference has no
 counterpart; the shape of the wrapper follows BatchedRangeScan (range_scan.py)."""
 from collections import OrderedDict
 
@@ -62,6 +63,7 @@ class GoalField(object):
         self._keep = keep           # the inputs of the build, alive until the stream has consumed them
         self._buffers = OrderedDict()
         self._route_cache = OrderedDict()   # route() / route_bound(): outputs per (n, max_len)
+        self._smooth_cache = OrderedDict()  # smooth(): outputs per (n, max_len)
 
     def _call(self, final, poses, n, row_env, carrot_cells, max_dist, out3, cell_value, carrot):
         o, f = self.owner, self.field
@@ -161,6 +163,43 @@ class GoalField(object):
                                                buf["paths"].data_ptr(), buf["lens"].data_ptr(),
                                                buf["init"].data_ptr() if "init" in want else None, buf["status"].data_ptr(),
                                                o._stream()))
+        return (buf["paths"], buf["lens"], buf["status"]) + tuple(buf[w] for w in want)
+
+    def smooth(self, paths, lens, row_env=None, entries=False, look=64, blend=0.3, delta=0.05, halvings=2, max_len=None,
+               want=()):
+        """bcp_smooth_route: the way points paths float64 [n, max_len_in, 3] / lens int32 [n] -- a route at stride 1 -- pulled
+        taut over the field (an anchor keeps the farthest of its next `look` way points it sees over passable cells) and
+        every corner blended over `blend` metres of each leg (halved up to `halvings` times where the blend would leave the
+        passable cells), written out every `delta` metres.  Rows as for route(): row i on the map of env row_env[i] (or
+        i % n_envs); entries=True: row m is entry m of the owner's binding, as for route_bound().  max_len: the slots per
+        row, None = max_len_in.  -> (paths float64 [n, max_len, 3] with zeros behind each row's way points, lens int32 [n],
+        status int32 [n]: a mask of _lib.ROUTE_LONG / ROUTE_TOO_CLOSE / ROUTE_NO_ROUTE / SMOOTH_BLOCKED), plus, with want from
+        "init" (float64 [n, 2], as route()'s) and "info" (int32 [n, 4] = vertices kept, corners blended at full size, at a
+        reduced size, left sharp).  Device tensors, no sync; the outputs are cached per (n, max_len)."""
+        o, f = self.owner, self.field
+        unknown = set(want) - {"init", "info"}
+        if unknown:
+            raise ValueError("smooth: unknown outputs %s" % sorted(unknown))
+        paths = o._device_tensor(paths, torch.float64)
+        assert paths.dim() == 3 and paths.shape[2] == 3
+        n, max_len_in = int(paths.shape[0]), int(paths.shape[1])
+        lens = o._device_tensor(lens, torch.int32, (n,))
+        if row_env is not None:
+            row_env = o._device_tensor(row_env, torch.int32, (n,))
+        max_len = max_len_in if max_len is None else int(max_len)
+        buf = cached(self._smooth_cache, (n, min(max(max_len, 1), 4096)), dict, SCAN_CACHE_ENTRIES)
+        shapes = {"paths": ((n, min(max(max_len, 1), 4096), 3), torch.float64), "lens": ((n,), torch.int32),
+                  "status": ((n,), torch.int32), "init": ((n, 2), torch.float64), "info": ((n, 4), torch.int32)}
+        for name in ["paths", "lens", "status"] + list(want):
+            if name not in buf:
+                buf[name] = torch.zeros(shapes[name][0], dtype=shapes[name][1], device=o.device)
+        prm = _lib.BcpSmoothParams(int(look), int(halvings), float(blend), float(delta))
+        _lib.check(o._lib.bcp_smooth_route(o._h, f.data_ptr(), f.shape[0], f.shape[1], f.shape[2], paths.data_ptr(),
+                                           lens.data_ptr(), max_len_in, n, row_env.data_ptr() if row_env is not None else None,
+                                           int(bool(entries)), prm, max_len, buf["paths"].data_ptr(), buf["lens"].data_ptr(),
+                                           buf["init"].data_ptr() if "init" in want else None, buf["status"].data_ptr(),
+                                           buf["info"].data_ptr() if "info" in want else None, o._stream()))
+        o._alive["smooth_route"] = (paths, lens, row_env)
         return (buf["paths"], buf["lens"], buf["status"]) + tuple(buf[w] for w in want)
 
     def metres(self):
@@ -270,7 +309,7 @@ def build(env, clearance=None, seeds="goal", max_passes=0, follow_refresh=False,
     return GoalField(env, field, d2, info, keep=(s, data, vr, vc), extra_of_cost=table)
 
 
-def route_paths(env, fields=None, stride=2, max_len=None, clearance=None, cost_weight=None):
+def route_paths(env, fields=None, stride=2, max_len=None, clearance=None, cost_weight=None, smooth=None):
     """BatchedPlanEnv.route_paths: see there."""
     if env.endless:
         raise RuntimeError("route_paths: not supported on endless=True pools -- refresh() re-samples worlds with "
@@ -289,9 +328,20 @@ def route_paths(env, fields=None, stride=2, max_len=None, clearance=None, cost_w
                          % (tuple(data.shape), tuple(fields.field.shape)))
     old_len = int(old_pts.shape[1])
     max_len = old_len if max_len is None else int(max_len)
-    paths, lens, status, init = fields.route_bound(stride, max_len, want=("init",))
-    status = status.clone()
-    ok = status == 0
+    if smooth is None:
+        paths, lens, status, init = fields.route_bound(stride, max_len, want=("init",))
+        status = status.clone()
+        ok = status == 0
+    else:   # the route at stride 1 into a scratch buffer, and that smoothed: an entry needs both to succeed
+        prm = dict(smooth)
+        route_len = int(prm.pop("route_len", 1024))
+        unknown = set(prm) - {"look", "blend", "delta", "halvings"}
+        if unknown:
+            raise ValueError("route_paths: unknown smooth parameters %s" % sorted(unknown))
+        cells, cell_lens, route_status = fields.route_bound(1, route_len)
+        paths, lens, status, init = fields.smooth(cells, cell_lens, entries=True, max_len=max_len, want=("init",), **prm)
+        status = status | route_status
+        ok = (status & ~_lib.SMOOTH_BLOCKED) == 0
     length = max(max_len, old_len)
     new_pts = torch.zeros((int(old_pts.shape[0]), length, 3), dtype=torch.float64, device=env.device)
     new_pts[:, :old_len] = old_pts

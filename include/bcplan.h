@@ -1101,6 +1101,80 @@ int bcp_goal_route_bound(bcp_handle *h, const uint16_t *field, int32_t rows, int
 #define BCP_ROUTE_NO_ROUTE  4
 #define BCP_ROUTE_STUCK     8
 
+/* bcp_smooth_route: a route's cell chain pulled taut and its corners blended, per row, written as a path that bcp_set_paths
+ * takes.  The stage between bcp_goal_route and a tracker: scatter -> inflate -> field -> route -> smooth -> track / plan.
+ * One launch (one wave per row), asynchronous on `stream`, no allocation, no upload, no host synchronisation; *p is read
+ * during the call and travels by value in the launch arguments, so a call can be captured into a HIP graph after one
+ * ordinary call.  Nothing of the handle changes.
+ * Rows.  rows_are_entries == 0: bcp_goal_route's rows -- row i belongs to env row_env[i], or i % n_envs, stands on the map
+ * entry of its env and reads field 0 (n_fields == 1) or the field of its env's entry; no state needs to be bound.
+ * rows_are_entries != 0: row m is entry m of the binding, as in bcp_goal_route_bound; n and n_fields are the entry count,
+ * row_env is NULL, and the maps are private.
+ * Input: the first m = min(lens_in[i], max_len_in) way points of paths_in[i].
+ * Passable: a cell is passable iff it lies inside its entry's valid shape and field[row][col] != BCP_GOAL_NONE; the field
+ * thereby carries the clearance, and a seed is passable.  The cell of a point (x, y) is bcp_goal_field_sample's: (col, row) =
+ * half-to-even of ((x - ox) * inv_res, (y - oy) * inv_res); a point that is not finite, or whose cell lies outside the valid
+ * shape, has no cell.
+ * clear(a, b), exact in integers, between the CENTRES of cells a and b (a start or goal pose lies within half a cell of its
+ * cell's centre, as with the first leg of bcp_goal_route): with dc = b.col - a.col, dr = b.row - a.row, ax = |dc|, ay = |dr|,
+ * signs sx, sy and counters i = j = 0, while i < ax or j < ay:
+ *   j == ay, or i < ax and j < ay and (2i+1) * ay < (2j+1) * ax:  col += sx, ++i
+ *   i == ax, or i < ax and j < ay and (2i+1) * ay > (2j+1) * ax:  row += sy, ++j
+ *   equality (the segment passes exactly through a cell corner): the edge neighbours (row, col + sx) and (row + sy, col)
+ *   must both be passable -- the field's own corner rule --; then col += sx, row += sy, ++i, ++j
+ * clear is true iff both ends have a cell and a, every cell stepped on (b among them) and every corner's edge neighbours
+ * are passable.  The cells stepped on are exactly those whose open unit square meets the segment, and the walk visits the
+ * same cells and corners from either end.  The products stay below 2^24 for maps up to 2048 x 2048.
+ * Pull: anchors k_0 = 0; k_next = the largest j in (k, min(k + look, m - 1)] with clear(cell[k], cell[j]); if there is none,
+ * k_next = k + 1 and the row's status gets BLOCKED; the pull ends at m - 1.  The vertices V_0 .. V_M are the kept way points
+ * with their input coordinates, bit for bit.
+ * Blend, at every interior vertex V with neighbours P and N (float64, every operation rounded on its own, per coordinate):
+ *   lp = sqrt(dx*dx + dy*dy) with (dx, dy) = P - V, ln likewise for N;  d = blend; if (lp / 3.0 < d) d = lp / 3.0;
+ *   if (ln / 3.0 < d) d = ln / 3.0.  Sizes d, d / 2.0, ... (at most `halvings` halvings) are tried in turn:
+ *   A = V + ((P - V) * (d / lp))      B = V + ((N - V) * (d / ln))      q = pieces(2.0 * d, delta)
+ *   Q_k = ((A * ((1-t)*(1-t))) + (V * ((2.0*t)*(1-t)))) + (B * (t*t)),  t = (double)k / (double)q,  k = 0 .. q -- every
+ *   one of them by this formula, Q_0 and Q_q too
+ *   the size is accepted iff clear(cell(Q_k), cell(Q_k+1)) for every k < q
+ *   pieces(l, s) = max(1, (int)ceil(l / s)); a quotient that is a NaN gives 1, and one above 4096 counts as 4097: a blend
+ *   size of 4097 pieces is refused untested (no row could hold it), a stretch of 4097 makes the row LONG.
+ * If every size is refused, if blend == 0, or if lp or ln is 0, the corner stays sharp: V itself is the one way point there.
+ * Output: way point 0 is V_0 bit for bit, heading included.  Each straight stretch runs from S = the previous corner's B
+ * (its V when sharp; V_0) to E = the next corner's A (its V when sharp; V_M); with l = sqrt over E - S and q = pieces(l,
+ * delta) it writes S + ((E - S) * ((double)i / (double)q)) for i = 1 .. q - 1 and then E itself.  A blended corner's Q_1 ..
+ * Q_q follow its A.  The last way point is V_M bit for bit, heading included; every other heading is bcp_goal_route's:
+ * atan2 to the successor over the written coordinates, or the last input way point's heading where both differences are
+ * zero.  Slots behind a row's way points are written as +0.0.
+ * The way points are counted before anything is written; more than max_len: LONG, lens = 0, every slot zero.
+ * status: [n], bcp_goal_route's bits and one more --
+ *   1 LONG       as above; init = (0, 0), info is still written
+ *   2 TOO_CLOSE  as bcp_goal_route's, evaluated on the written path; init likewise
+ *   4 NO_ROUTE   m < 2, a number among the row's 3 m is not finite, or the row's env or entry is out of range: lens = 0,
+ *                every slot zero, init = (0, 0), info = (0, 0, 0, 0)
+ *   16 BLOCKED   the pull found an anchor that sees none of its successors; the path is still written
+ * init: optional [n][2], as bcp_goal_route's, on the written path (the same function).
+ * info: optional [n][4] = (vertices after the pull, corners blended at full d, corners blended at a reduced d, corners
+ * left sharp).
+ * Refusals, tested in this order.  BCP_E_INVALID: NULL h, field, paths_in, lens_in, paths, lens, status or p; look outside
+ * [1, 4096]; halvings outside [0, 8]; blend NaN, negative or infinite; delta NaN, not > 0 or infinite; max_len_in outside
+ * [2, 4096]; max_len outside [2, 4096]; n <= 0; row_env together with rows_are_entries; with costmaps bound: rows / cols
+ * other than the binding's; n_fields neither 1 nor the entry count (rows_are_entries: not the entry count); n not the entry
+ * count with rows_are_entries.  BCP_E_STATE: no costmaps bound; a shared map with rows_are_entries; paths or lens sharing a
+ * byte with paths_in or lens_in; paths or lens being the arrays given to bcp_set_paths.  Refusals carry the entry point's
+ * name as a prefix, and a refused call writes nothing. */
+typedef struct bcp_smooth_params {
+    int32_t look;       /* way points the pull looks ahead, 1 .. 4096 */
+    int32_t halvings;   /* halved blend sizes tried after the full one, 0 .. 8 */
+    double blend;       /* the blend's length along each leg, metres; 0: every corner stays sharp */
+    double delta;       /* spacing of the written way points, metres */
+} bcp_smooth_params;
+int bcp_smooth_route(bcp_handle *h, const uint16_t *field, int64_t n_fields, int32_t rows, int32_t cols,
+                     const double *paths_in /*[n][max_len_in][3]*/, const int32_t *lens_in /*[n]*/, int32_t max_len_in,
+                     int64_t n, const int32_t *row_env /*or NULL*/, int32_t rows_are_entries,
+                     const bcp_smooth_params *p /*host*/, int32_t max_len,
+                     double *paths /*[n][max_len][3]*/, int32_t *lens, double *init /*optional [n][2]*/,
+                     int32_t *status, int32_t *info /*optional [n][4]*/, void *stream);
+#define BCP_SMOOTH_BLOCKED 16
+
 /* ---- box obstacles ------------------------------------------------------------------------------------ */
 /* bcp_scatter_boxes: rectangular obstacles stamped into every map of a batch, reproducibly.  One launch (one 256-thread
  * workgroup per entry), asynchronous on `stream`, no allocation, no upload, no host synchronisation; the launch arguments
