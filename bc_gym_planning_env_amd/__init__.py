@@ -10,7 +10,7 @@ __all__ = ["Action", "Box", "ContinuousRewardProviderState", "CostMap2D", "Diffd
            "INDUSTRIAL_DIFFDRIVE_V1", "INDUSTRIAL_TRICYCLE_V1", "Observation", "RewardParams", "State",
            "TricycleRobotState", "BatchedPlanEnv", "BatchedRandomAisleTurnEnv", "NativeOps", "Lookahead", "ShootingPlanner",
            "constant_command_library", "Mppi", "MPPIPlanner", "Track", "TrackingPlanner", "pursuit_gain_library",
-           "BatchedRangeScan", "BatchedGoalField", "GoalField"]
+           "BatchedRangeScan", "BatchedGoalField", "GoalField", "SpeedProfile"]
 
 
 def __getattr__(name):
@@ -31,6 +31,9 @@ def __getattr__(name):
     if name in ("BatchedGoalField", "GoalField"):
         from . import goal_field
         return getattr(goal_field, name)
+    if name == "SpeedProfile":
+        from .speed_profile import SpeedProfile
+        return SpeedProfile
     if name == "NativeOps":
         from .ops import NativeOps
         return NativeOps

@@ -21,6 +21,7 @@ GOAL_ORTHO, GOAL_DIAG, GOAL_FAR, GOAL_NONE = 12, 17, 65534, 65535
 GOAL_MAX_EXTRA = 4095
 ROUTE_LONG, ROUTE_TOO_CLOSE, ROUTE_NO_ROUTE, ROUTE_STUCK = 1, 2, 4, 8
 SMOOTH_BLOCKED = 16   # bcp_smooth_route's status bit beside the ROUTE_* ones
+SPEED_NO_PATH = 4     # bcp_path_speed's status of a row without a path
 SCATTER_SHORT, SCATTER_REVERTED = 1, 2   # BatchedPlanEnv.scatter_obstacles' status bits
 E_NO_DEVICE = -2
 OPT_DIFFDRIVE_NOISE = 1
@@ -154,6 +155,17 @@ class BcpSmoothParams(C.Structure):
     _fields_ = [("look", C.c_int32), ("halvings", C.c_int32), ("blend", C.c_double), ("delta", C.c_double)]
 
 
+class BcpSpeedParams(C.Structure):
+    """bcp_speed_params: the limits bcp_path_speed makes a speed profile from"""
+    _fields_ = [("span", C.c_int32)] + [(k, C.c_double) for k in (
+        "v_max", "v_min", "a_lat", "w_max", "a_dec", "a_acc", "v_start", "v_end")]
+
+
+class BcpTrackProfileIO(C.Structure):
+    """bcp_track_profile_io: the speeds bcp_track_profile reads, laid out as the bound paths"""
+    _fields_ = [("speed", C.c_void_p), ("max_len", C.c_int32)]
+
+
 BcpMppiAdapt = BcpMppiWidths   # (the argument of bcp_mppi_adapt, by the function's name)
 
 
@@ -184,6 +196,8 @@ SYMBOLS = {
     "bcp_mppi_adapt": (C.c_int, [_H, C.POINTER(BcpMppiParams), C.POINTER(BcpMppiIO), C.POINTER(BcpMppiWidths),
                                  C.POINTER(BcpMppiTerminal), C.c_uint32, C.c_void_p]),
     "bcp_track": (C.c_int, [_H, C.POINTER(BcpTrackParams), C.POINTER(BcpTrackIO), C.c_uint32, C.c_void_p]),
+    "bcp_track_profile": (C.c_int, [_H, C.POINTER(BcpTrackParams), C.POINTER(BcpTrackIO), C.POINTER(BcpTrackProfileIO),
+                                    C.c_uint32, C.c_void_p]),
     "bcp_expired_waits": (C.c_int, [_H, C.POINTER(C.c_int64), C.c_void_p]),
     "bcp_parked_poses": (C.c_int, [_H, C.POINTER(C.c_int64), C.c_void_p]),
     "bcp_side_stream": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_void_p)]),
@@ -269,6 +283,8 @@ SYMBOLS = {
     "bcp_smooth_route": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64,
                                    C.c_void_p, C.c_int32, C.POINTER(BcpSmoothParams), C.c_int32, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bcp_path_speed": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.POINTER(BcpSpeedParams), C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bcp_scatter_boxes": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_double, C.POINTER(BcpScatterParams), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -74,6 +74,8 @@ class BatchedPlanEnv(Handle):
         acceleration limits, front-column P gain) for a robot of other dimensions than the stock ones
     """
 
+    _path_epoch = 0   # path bindings so far (_bind_paths)
+
     def __init__(self, costmap, path, params=None, n_envs=1, device=0, robot_name=None, noise_parameters='planenv',
                  auto_reset=False, env_id_base=0, seed=0, footprint_scale=1.0, dynamic_model=True,
                  model_front_column_pid=True, template_of_env=None, geom_of_env=None, next_geom=None, map_storage=None,
@@ -263,8 +265,10 @@ class BatchedPlanEnv(Handle):
         self._bind_paths(pick(torch.from_numpy(points).to(dev)).contiguous(), pick(torch.from_numpy(lens).to(dev)).contiguous())
 
     def _bind_paths(self, points, lens):
-        """Device paths [., max_len, 3] of lens [.] points each; lens None: ONE path [len, 3] shared by all envs."""
+        """Device paths [., max_len, 3] of lens [.] points each; lens None: ONE path [len, 3] shared by all envs.  Every
+        binding counts (self._path_epoch): what was derived from an earlier one -- a SpeedProfile -- is stale."""
         self._keep.update(path=points, lens=lens)
+        self._path_epoch += 1
         _lib.check(self._lib.bcp_set_paths(self._h, points.data_ptr(), lens.data_ptr() if lens is not None else None,
                                            int(points.shape[-2]), int(lens is None), self._stream()))
         torch.cuda.current_stream(self.device).synchronize()  # a staging tensor may now be released
@@ -760,7 +764,47 @@ class BatchedPlanEnv(Handle):
         low, high = np.asarray(self.action_space.low, np.float64), np.asarray(self.action_space.high, np.float64)
         return float(high[1] / max(low[0], 1e-3))
 
-    def track(self, gains, horizon, max_curvature=None, mask=None, want=(), action_dtype=None):
+    def speed_profile(self, v_max=None, a_lat=1.0, w_max=1.0, a_dec=1.0, a_acc=1.0, v_start=None, v_end=None, v_min=0.0, span=1,
+                      want=()):
+        """The speed profile of the env's own bound paths (bcp_path_speed on the device copy the env keeps, one launch):
+        Handle.path_speed's parameters, with v_max, v_start and v_end defaulting to action_space.high[0].  Returns a
+        SpeedProfile with speed [entries, max_len] ([max_len] for a shared path) for track(speed_profile=...) and
+        TrackingPlanner(speed_profile=...); it belongs to this binding of the paths -- after route_paths() make a new one.
+        Refused on endless=True pools (refresh() re-samples paths into the pool, which would leave a stale profile), and by
+        the library for paths of more than 4096 slots."""
+        if self.endless:
+            raise RuntimeError("speed_profile: not supported on endless=True pools -- refresh() re-samples paths into the "
+                               "pool, which would leave a stale profile")
+        from . import speed_profile
+        top = float(np.asarray(self.action_space.high, np.float64)[0])
+        v_max = top if v_max is None else v_max
+        prm = speed_profile.speed_params(v_max, a_lat, w_max, a_dec, a_acc, top if v_start is None else v_start,
+                                         top if v_end is None else v_end, v_min, span)
+        paths, lens = self._keep["path"], self._keep["lens"]
+        if lens is None:   # the shared path: one row
+            paths = paths[None]
+            lens = torch.full((1,), int(paths.shape[1]), dtype=torch.int32, device=self.device)
+        out = speed_profile.path_speed(self, paths, lens, prm, want, owner=self, epoch=self._path_epoch)
+        if self._keep["lens"] is None:
+            out.speed, out.kappa, out.v_limit = (None if t is None else t[0] for t in (out.speed, out.kappa, out.v_limit))
+        return out
+
+    def _checked_profile(self, profile):
+        """The speeds of a SpeedProfile track() may read: made for the paths bound now, one row per bound path."""
+        if profile.owner is not None and (profile.owner is not self or profile.epoch != self._path_epoch):
+            raise ValueError("track: the speed profile was made for another env or an earlier binding of the paths (binding "
+                             "%s, now %d) -- make a new one with speed_profile()" % (profile.epoch, self._path_epoch))
+        bound = self._keep["path"]
+        shape = (int(bound.shape[-2]),) if self._keep["lens"] is None else (int(bound.shape[0]), int(bound.shape[1]))
+        if profile.max_len != shape[-1]:
+            raise ValueError("track: the speed profile has max_len %d, the bound paths %d" % (profile.max_len, shape[-1]))
+        speed = profile.speed
+        if tuple(speed.shape) != shape or speed.dtype != torch.float64 or speed.device != self.device or not speed.is_contiguous():
+            raise ValueError("track: the speed profile must be a contiguous float64 tensor %s on %s, got %s"
+                             % (shape, self.device, tuple(speed.shape)))
+        return speed
+
+    def track(self, gains, horizon, max_curvature=None, mask=None, want=(), action_dtype=None, speed_profile=None):
         """Roll a pure-pursuit path tracker out for every env under K gain settings over the next `horizon` steps WITHOUT
         stepping it (bcp_track, nothing of the env changes): every trip's command steers for the first way point at least
         `reach` ahead at `speed`, through the reference's diff_drive_control_to_tricycle for the tricycle, clipped to the
@@ -770,8 +814,13 @@ class BatchedPlanEnv(Handle):
         arc's curvature in 1/m, None: default_max_curvature().  mask: optional [N]; rows of envs with mask 0 keep what the
         cached buffers held.  want: optional outputs from "final_pose", "final_target_idx", "err", "trace", "best",
         "best_plan", "best_action" (the last two imply "best").  action_dtype: of best_action, torch.float64 (default) or
-        torch.float32.  Returns a Track of device tensors, no sync; buffers are cached per (H, K).  Delays > 0 and the
-        pure-pursuit reward provider are refused."""
+        torch.float32.  speed_profile: None, or a SpeedProfile of the paths bound now (speed_profile()): every command's
+        speed is then the gain's capped by the profile at the way point the robot heads for and at the carrot
+        (bcp_track_profile); one made for an earlier binding of the paths or with another max_len is a ValueError.  A
+        SpeedProfile built by hand or by path_speed() (owner None) is checked for its shape alone: it is the caller's to
+        renew after route_paths().
+        Returns a Track of device tensors, no sync; buffers are cached per (H, K).  Delays > 0 and the pure-pursuit reward
+        provider are refused."""
         gains = self._device_tensor(gains, torch.float64)
         n, h = self.n_envs, int(horizon)
         if gains.dim() == 2 and gains.shape[1] == 2:
@@ -814,7 +863,14 @@ class BatchedPlanEnv(Handle):
                                    [name for name in Track.FIELDS if name in want or name in Track.REQUIRED])
         for name, t in out.items():
             setattr(io, name, t.data_ptr())
-        _lib.check(self._lib.bcp_track(self._h, C.byref(p), C.byref(io), flags, self._stream()))
+        if speed_profile is None:
+            _lib.check(self._lib.bcp_track(self._h, C.byref(p), C.byref(io), flags, self._stream()))
+        else:
+            prof = _lib.BcpTrackProfileIO()
+            speed = self._checked_profile(speed_profile)
+            prof.speed, prof.max_len = speed.data_ptr(), int(speed.shape[-1])
+            keep.append(speed)
+            _lib.check(self._lib.bcp_track_profile(self._h, C.byref(p), C.byref(io), C.byref(prof), flags, self._stream()))
         self._alive["track"] = tuple(keep)   # alive until the stream has consumed them
         return Track(h, k, **out)
 

@@ -29,6 +29,7 @@ struct TrackArgs {
     int32_t horizon, k;
     uint32_t flags;            // BCP_STEP_ACTIONS_F32 | BCP_LOOKAHEAD_PER_ENV
     double low[2], high[2], max_curvature;
+    const double* profile;     // bcp_track_profile: [max_len] or [entries][max_len] speeds laid out as the bound paths; else nullptr
 };
 
 // the device's side of the law's Math parameter (bcp_track_law.h)
@@ -50,6 +51,9 @@ __device__ __forceinline__ void track_gains_of(const TrackArgs& a, int64_t c, in
 // Every lane stays in the trip loop until the whole wave is through.  The carrot scan is the one data-dependent loop: a
 // lane runs it only while it is active, over the way-point records of its env (the lanes of an env read the same lines);
 // the wave rejoins before plan_trip, which every lane calls.
+// PROFILE: step 4 of the law reads a.profile, the row of the slot g that plan_load resolves for the env (bcp_track_profile);
+// without it the kernel is bcp_track's, a.profile not read.
+template <bool PROFILE>
 __global__ void __launch_bounds__(kBlock) track_kernel(const TrackArgs a)
 {
     const StepStatic* S = a.S;
@@ -73,6 +77,8 @@ __global__ void __launch_bounds__(kBlock) track_kernel(const TrackArgs a)
     track_gains_of(a, c, k, speed, reach);
     const bool tricycle = P.model == BCP_MODEL_TRICYCLE;
     const DeviceTrackMath math;
+    GlobalPtr<const double> profile(nullptr);
+    if constexpr (PROFILE) profile = as_global(a.profile) + (S->path.shared ? 0 : g * (int64_t)S->path.max_len);
 
     double ret = 0.0, cmd0 = 0.0, cmd1 = 0.0;
     int steps = 0, reason = 0, errs = 0;
@@ -86,9 +92,13 @@ __global__ void __launch_bounds__(kBlock) track_kernel(const TrackArgs a)
         if (__ballot(!finished) == 0) break;   // wave-uniform
         const bool active = !finished;
         if (active) {
-            const bcp::TrackCommand cmd =
-                bcp::track_law(as_global(pts), m, st.r.p.x, st.r.p.y, st.r.p.th, st.r.wheel, st.target, carrot, speed, reach,
-                               a.max_curvature, tricycle, P.max_wheel_angle, P.L, a.low, a.high, math);
+            bcp::TrackCommand cmd;
+            if constexpr (PROFILE)
+                cmd = bcp::track_law_profile(as_global(pts), profile, m, st.r.p.x, st.r.p.y, st.r.p.th, st.r.wheel, st.target, carrot,
+                                             speed, reach, a.max_curvature, tricycle, P.max_wheel_angle, P.L, a.low, a.high, math);
+            else
+                cmd = bcp::track_law(as_global(pts), m, st.r.p.x, st.r.p.y, st.r.p.th, st.r.wheel, st.target, carrot, speed, reach,
+                                     a.max_curvature, tricycle, P.max_wheel_angle, P.L, a.low, a.high, math);
             if (a.trace) {   // the state as the law read it
                 const GlobalPtr<double> q = trace_row + 6 * t;
                 q[0] = st.r.p.x;

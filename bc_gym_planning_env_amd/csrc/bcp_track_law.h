@@ -124,6 +124,44 @@ BCP_HD inline TrackCommand track_law(Points pts, int m, double x, double y, doub
     return out;
 }
 
+// The cap a speed profile puts on a lane's speed: the smaller of the profile at the way point the robot is heading for,
+// min(target_idx, m - 1), and at the carrot -- numpy's minimum, a NaN if either is one.  profile[j]: way point j's speed.
+template <typename Profile>
+BCP_HD inline double track_speed_cap(Profile profile, int m, int target_idx, int carrot)
+{
+    int at = target_idx < m - 1 ? target_idx : m - 1;
+    if (at < 0) at = 0;
+    const double a = profile[at], b = profile[carrot];
+    if (a != a) return a;
+    if (b != b) return b;
+    return b < a ? b : a;
+}
+
+// the gain's speed under a cap: a cap that is NaN or negative leaves it as it is
+BCP_HD inline double track_capped_speed(double speed, double cap) { return (cap >= 0.0 && cap < speed) ? cap : speed; }
+
+// track_law with step 4 reading a speed profile (bcp_track_profile): v = the gain's speed capped by track_speed_cap, w = v *
+// kappa.  Everything else is track_law's, statement by statement; a profile of speeds >= the gain's gives its bits.
+template <typename Points, typename Profile, typename Math>
+BCP_HD inline TrackCommand track_law_profile(Points pts, Profile profile, int m, double x, double y, double th, double wheel_angle,
+                                             int target_idx, int c_prev, double speed, double reach, double max_curvature,
+                                             bool tricycle, double max_wheel_angle, double L, const double low[2],
+                                             const double high[2], const Math& math)
+{
+    TrackCommand out;
+    double dx, dy, c, s, lx, ly;
+    out.carrot = track_carrot(pts, m, x, y, reach, c_prev, target_idx, dx, dy);
+    math.cos_sin(th, c, s);
+    track_robot_frame(c, s, dx, dy, lx, ly);
+    const double kappa = track_curvature(lx, ly, max_curvature);
+    const double v = track_capped_speed(speed, track_speed_cap(profile, m, target_idx, out.carrot)), w = v * kappa;
+    double a0 = v, a1 = w;
+    if (tricycle) track_diff_drive_to_tricycle(v, w, wheel_angle, max_wheel_angle, L, math, a0, a1);
+    out.cmd0 = track_clip(a0, low[0], high[0]);
+    out.cmd1 = track_clip(a1, low[1], high[1]);
+    return out;
+}
+
 // what bcp_track refuses with BCP_E_INVALID after the handle's own checks, in the order it looks
 enum TrackRefusal { kTrackOk = 0, kTrackShape = 1, kTrackCurvature = 2, kTrackBoxFinite = 3, kTrackBoxOrder = 4, kTrackNull = 5,
                     kTrackBest = 6, kTrackLarge = 7 };

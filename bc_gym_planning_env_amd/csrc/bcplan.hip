@@ -14,7 +14,7 @@
 //   bcp_field.h        distance field and tiles: kernels, DistanceField, the launchers of what is derived from maps and paths
 //   bcp_step_host.h    step forms, the step's parameter block and launcher, Parking, WaitWatchdog, bcp_step / bcp_rollout
 //   bcp_plan_host.h    the planners: bcp_lookahead / bcp_mppi / bcp_mppi_field / bcp_mppi_adapt
-//   bcp_track_host.h   bcp_track (kernels: bcp_track.h)
+//   bcp_track_host.h   bcp_track / bcp_track_profile (kernels: bcp_track.h)
 //   bcp_ego_host.h     egocentric costmaps (routed by bcp_ego_route.h, which has no HIP in it), goal-state vectors, the
 //                      episode record and its final observations
 //   bcp_worlds_host.h  mini-world and aisle-world entry points
@@ -25,6 +25,7 @@
 //                      five, planned by bcp_goal_plan.h --, bcp_goal_field_sample / bcp_final_goal_field_sample, and
 //                      bcp_goal_route / bcp_goal_route_bound
 //   bcp_smooth_host.h  bcp_smooth_route (kernel: bcp_smooth.h; a row's arithmetic: bcp_smooth_cell.h, no HIP in it)
+//   bcp_speed_host.h   bcp_path_speed (kernel: bcp_speed.h; a way point's arithmetic and the passes: bcp_speed_cell.h, no HIP in it)
 //   bcp_boxes_host.h   bcp_scatter_boxes (kernel: bcp_boxes.h)
 //   bcp_seams_host.h   bind / reset / broadcast of the state and the operator seams (their small kernels: bcp_seams.h)
 // This file holds create / destroy / seed / pool / tuning / side stream, bcp_set_costmaps with the two reads of the distance
@@ -58,6 +59,7 @@
 #include "bcp_scan.h"
 #include "bcp_goal.h"
 #include "bcp_smooth.h"
+#include "bcp_speed.h"
 #include "bcp_boxes.h"
 
 using namespace bcp;
@@ -118,6 +120,7 @@ static void fill_dev_params(bcp_handle* h)
 #include "bcp_scan_host.h"
 #include "bcp_goal_host.h"
 #include "bcp_smooth_host.h"
+#include "bcp_speed_host.h"
 #include "bcp_boxes_host.h"
 
 // ------------------------------------------------------------------------------------------------ host API

@@ -110,6 +110,20 @@ class Handle(object):
         self._alive["range_scan"] = (table, poses)
         return out["ranges"] if not want else (out["ranges"],) + tuple(out[w] for w in want)
 
+    def path_speed(self, paths, lens, v_max, a_lat, w_max, a_dec, a_acc, v_start=None, v_end=None, v_min=0.0, span=1, want=()):
+        """A speed per way point of any paths (bcp_path_speed, one launch, nothing of the handle changes): paths float64
+        [n, max_len, 3] with lens [n] way points each, e.g. what GoalField.route() or GoalField.smooth() return.  No faster
+        than v_max, than sqrt(a_lat / kappa) and than w_max / kappa at a way point of curvature kappa (the Menger curvature
+        of the way points `span` before and behind), no slower than v_min for curvature's sake; at most v_start / v_end
+        (None: v_max) at the two ends; braking with at most a_dec and accelerating with at most a_acc along the path.
+        want: optional outputs from "kappa" and "v_limit".  Returns a speed_profile.SpeedProfile of device tensors, no sync."""
+        from . import speed_profile
+        p = self._device_tensor(paths, torch.float64)
+        assert p.dim() == 3 and p.shape[2] == 3
+        return speed_profile.path_speed(self, p, self._device_tensor(lens, torch.int32, (int(p.shape[0]),)),
+                                        speed_profile.speed_params(v_max, a_lat, w_max, a_dec, a_acc, v_start, v_end, v_min, span),
+                                        want)
+
     def close(self):
         if self._h:
             self._lib.bcp_destroy(self._h)

@@ -158,9 +158,12 @@ class TrackingPlanner(object):
         (0.4, 0.8, 1.6)), or [N, K, 2] settings per env
     :param horizon: steps H of a roll-out
     :param max_curvature: the clamp of the arc's curvature in 1/m; None: what the robot can turn (BatchedPlanEnv.track)
+    :param speed_profile: None, or a SpeedProfile of the env's bound paths (env.speed_profile()): every setting's speed is
+        capped by it, so the tracker slows for corners (bcp_track_profile); also settable later as self.speed_profile, e.g.
+        after route_paths(), which makes an earlier profile stale
     """
 
-    def __init__(self, env, gains, horizon, max_curvature=None):
+    def __init__(self, env, gains, horizon, max_curvature=None, speed_profile=None):
         self.env = env
         base = env
         while not hasattr(base, "n_envs"):
@@ -168,19 +171,24 @@ class TrackingPlanner(object):
         g = gains if isinstance(gains, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(gains, dtype=np.float64))
         self.base = base   # the BatchedPlanEnv under the wrappers
         self.gains = g.to(base.device).to(torch.float64).contiguous()
-        self.horizon, self.max_curvature = int(horizon), max_curvature
+        self.horizon, self.max_curvature, self.speed_profile = int(horizon), max_curvature, speed_profile
         self.last = None   # the Track of the latest act() or plan()
+
+    def _extra(self):
+        """(speed_profile=None is the call as it always was, also through wrappers that know no such keyword)"""
+        return {} if self.speed_profile is None else dict(speed_profile=self.speed_profile)
 
     def act(self, observation=None):
         """actions [N, 2] (float64 device tensor) for env.step(): step 0 of the best setting.  The observation is not needed
         (as for ShootingPlanner): the roll-outs start from the env's own state."""
-        self.last = self.env.track(self.gains, self.horizon, self.max_curvature, want=("best", "best_action"))
+        self.last = self.env.track(self.gains, self.horizon, self.max_curvature, want=("best", "best_action"), **self._extra())
         return self.last.best_action
 
     def plan(self, mask=None):
         """[N, H, 2] float64: the commands of the best setting over the horizon -- a cached buffer of the env, overwritten by
         the next call.  mask: optional [N]; rows of envs with mask 0 keep what the buffer held."""
-        self.last = self.env.track(self.gains, self.horizon, self.max_curvature, mask=mask, want=("best", "best_plan"))
+        self.last = self.env.track(self.gains, self.horizon, self.max_curvature, mask=mask, want=("best", "best_plan"),
+                                   **self._extra())
         return self.last.best_plan
 
 

@@ -74,6 +74,12 @@ class BatchedObservationWrapper(object):
     def track(self, gains, horizon, *args, **kw):
         return self.env.track(gains, horizon, *args, **kw)
 
+    def speed_profile(self, *args, **kw):
+        return self.env.speed_profile(*args, **kw)
+
+    def path_speed(self, paths, lens, *args, **kw):
+        return self.env.path_speed(paths, lens, *args, **kw)
+
     def get_state(self):
         return self.env.get_state()
 

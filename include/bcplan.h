@@ -1175,6 +1175,66 @@ int bcp_smooth_route(bcp_handle *h, const uint16_t *field, int64_t n_fields, int
                      int32_t *status, int32_t *info /*optional [n][4]*/, void *stream);
 #define BCP_SMOOTH_BLOCKED 16
 
+/* ---- speed profile: a speed per way point that slows for curvature, and the tracker that follows it ------------ */
+/* bcp_path_speed: for every row of `paths` a speed per way point -- no faster than the curvature there allows, braking in
+ * time for what lies ahead and accelerating no harder than allowed.  One launch (one wave per row), asynchronous on
+ * `stream`; nothing is allocated or uploaded, nothing synchronises with the host, *p travels by value in the launch
+ * arguments (a call can be captured into a HIP graph after one ordinary call), and nothing of the handle changes: no
+ * binding is needed, the handle names the device.  The reference has no counterpart (its path_velocity measures a speed).
+ * All arithmetic is float64, every product, quotient, root and sum rounded on its own.
+ * Row i has m = min(lens[i], max_len) way points P_0 .. P_{m-1} (x, y of [n][max_len][3]; the heading is not read).
+ *   Curvature kappa[j], the Menger curvature of a triple: a = max(j - span, 0), b = min(j + span, m - 1); kappa[j] = 0 if
+ *     a == j or b == j; otherwise with A = P_j - P_a, B = P_b - P_j, C = P_b - P_a: la = sqrt(Ax*Ax + Ay*Ay), lb, lc likewise,
+ *     den = (la * lb) * lc, cr = |Ax*By - Ay*Bx|, kappa = den < 1e-18 ? 0 : (2.0 * cr) / den.
+ *   Limit u_lim[j], a squared speed: u = v_max * v_max; if kappa > 0: t = a_lat / kappa, if (t < u) u = t; s = w_max / kappa,
+ *     s2 = s * s, if (s2 < u) u = s2; then f = v_min * v_min, if (u < f) u = f; at j == 0 u = min(u, v_start * v_start); at
+ *     j == m - 1 u = min(u, v_end * v_end) (both when m == 1).
+ *   Passes, with ds_j = sqrt(dx*dx + dy*dy) from P_j to P_{j+1}, cd_j = (2.0 * a_dec) * ds_j, ca_j = (2.0 * a_acc) * ds_j:
+ *     backward ub[m-1] = u_lim[m-1], ub[j] = min(u_lim[j], ub[j+1] + cd_j); forward uf[0] = ub[0], uf[j] = min(ub[j],
+ *     uf[j-1] + ca_{j-1}); speed[j] = sqrt(uf[j]).
+ * kappa and v_limit (= sqrt(u_lim)) are these values bit for bit.  The sequential recurrence DEFINES speed; a pass is a
+ * scan of f_j(u) = min(A_j, u + c_j) with the combine (A1, c1) o (A2, c2) = (min(A1, A2 + c1), c1 + c2), and the device
+ * associates the sums of the c's in a tree.  Every term is non-negative, so speed is within relative 2 (m + 1) * 2^-52 of
+ * the recurrence's value.
+ * status[i]: 0, or BCP_SPEED_NO_PATH when lens[i] < 1 or an x or y among the row's first m is not finite; then every slot
+ * of the row in speed, kappa and v_limit is +0.0.  Slots behind m are always written as +0.0.
+ * Refused with BCP_E_INVALID in this order, nothing written, the message prefixed "bcp_path_speed": h, paths, lens, p,
+ * speed or status NULL; max_len outside [1, 4096]; n outside [1, 2^31 - 1]; span outside [1, 64]; v_max, a_lat, w_max,
+ * a_dec, a_acc (in this order) not finite or not > 0; v_min, v_start, v_end (in this order) not finite or negative;
+ * v_min > v_max; speed, kappa or v_limit sharing a byte with paths. */
+typedef struct bcp_speed_params {
+    int32_t span;       /* way points between a triple's points, 1 .. 64 */
+    double v_max;       /* m/s: the speed of a straight stretch */
+    double v_min;       /* m/s: curvature alone never asks for less (the end clamps may) */
+    double a_lat;       /* m/s^2: v^2 * kappa stays below it */
+    double w_max;       /* rad/s: v * kappa stays below it */
+    double a_dec;       /* m/s^2: braking along the path */
+    double a_acc;       /* m/s^2: acceleration along the path */
+    double v_start;     /* m/s: at most this at way point 0 */
+    double v_end;       /* m/s: at most this at way point m - 1 */
+} bcp_speed_params;
+#define BCP_SPEED_NO_PATH 4
+int bcp_path_speed(bcp_handle *h, const double *paths /*[n][max_len][3]*/, const int32_t *lens /*[n]*/,
+                   int32_t max_len, int64_t n, const bcp_speed_params *p /*host*/,
+                   double *speed /*[n][max_len]*/, double *kappa /*optional*/, double *v_limit /*optional, sqrt(u_lim)*/,
+                   int32_t *status /*[n]*/, void *stream);
+
+/* bcp_track_profile: bcp_track whose speed follows a profile.  `speed` is laid out as the paths given to bcp_set_paths:
+ * [max_len] for a shared path, else [entries][max_len]; a lane reads the row of the slot its env stands on (geom_of_env[i],
+ * or i).  Everything bcp_track specifies holds except step 4 of its law, with m the env's way points and `carrot` step 1's:
+ *   cap = min(speed_row[min(target_idx, m - 1)], speed_row[carrot])   (a NaN if either is one)
+ *   v = the gain's speed; if (cap >= 0 && cap < v) v = cap            (a NaN or negative cap leaves the gain's speed)
+ *   w = v * kappa, kappa the pursuit arc's curvature of step 3.
+ * A profile of speeds at or above every gain's speed gives bcp_track's outputs bit for bit.  Refused with BCP_E_INVALID:
+ * prof or prof->speed NULL; prof->max_len other than the bound paths' max_len; then everything bcp_track refuses, in its
+ * order (BCP_E_STATE where nothing is bound).  The messages carry "bcp_track_profile" as a prefix. */
+typedef struct bcp_track_profile_io {
+    const double *speed;   /* device: a speed per way point slot of the bound paths */
+    int32_t max_len;       /* the slots of a row: the bound paths' max_len */
+} bcp_track_profile_io;
+int bcp_track_profile(bcp_handle *h, const bcp_track_params *p, const bcp_track_io *io,
+                      const bcp_track_profile_io *prof, uint32_t flags, void *stream);
+
 /* ---- box obstacles ------------------------------------------------------------------------------------ */
 /* bcp_scatter_boxes: rectangular obstacles stamped into every map of a batch, reproducibly.  One launch (one 256-thread
  * workgroup per entry), asynchronous on `stream`, no allocation, no upload, no host synchronisation; the launch arguments
